@@ -2,6 +2,7 @@
 """bench.py -- Newton-step throughput of the batched FOM / ROM hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config fom|pod_galerkin|pod_lspg|quadratic|ann|decoder_bf16]
+                  [--dump-outputs DIR]
 
 Default = BASELINE.json configs[1], the configuration the metric is quoted on: B = 1024 (mu1, mu2) samples per GPU,
 N = 1024 nodes, fp64, 500 implicit-Euler steps at dt = 0.025 (dt = 0.05 diverges at N = 1024 in the reference itself,
@@ -71,7 +72,12 @@ def parse_args(argv=None):
                          "driver's default command line, none once a workload flag is given; small = 96 samples x 12 steps "
                          "(the contract test)")
     ap.add_argument("--other-steps", type=int, default=3, help="timed passes of each other_configs entry")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one returned as DIR/<name>.npy (float64, at most "
+                         "64 MB in all: per-sample arrays too large for that are cut to a fixed, seeded sample subset)")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     # the driver's own line (no workload flag given): configs[1] as the headline + one short run of every other config
     args.default_workload = (args.config == "fom" and args.batch is None and args.n is None and args.dt is None
                              and args.time_steps == 500)
@@ -228,6 +234,13 @@ class Workload:
 
     def units(self, res):
         return int(res.iters.sum().item())
+
+    def outputs(self, res):
+        """What a caller of the timed path receives from one pass: name -> list of tensors along the sample axis."""
+        out = {"hist": [res.hist], "iters": [res.iters], "flags": [res.flags]}
+        if hasattr(res, "info"):
+            out["info"] = [res.info]
+        return out
 
     def status(self, res):
         from burgers_hip import lib
@@ -439,12 +452,16 @@ class DecoderWorkload(Workload):
         assert self.dec.plan is not None, "the committed decoder must take the one-kernel form (bg_decode_mlp_bf16)"
         self.mu1d, self.mu2d = torch.as_tensor(self.mu1, device=self.dev), torch.as_tensor(self.mu2, device=self.dev)
         self.chunk = 1024                                  # samples per contraction: the fp64 result block is 2.1 GB
+        self.chunks = []
 
     def one_pass(self):
-        last = None
+        self.chunks = []                                   # the previous pass's blocks go before this pass allocates
         for lo in range(0, self.args.batch, self.chunk):
-            last = self.dec.predict(self.mu1d[lo:lo + self.chunk], self.mu2d[lo:lo + self.chunk])
-        return last
+            self.chunks.append(self.dec.predict(self.mu1d[lo:lo + self.chunk], self.mu2d[lo:lo + self.chunk]))
+        return self.chunks[-1]
+
+    def outputs(self, res):
+        return {"U": self.chunks}                          # (B, N, Nt) float64, one block per chunk of samples
 
     def units(self, res):
         return self.args.batch * self.Nt
@@ -654,6 +671,43 @@ def allgather_svd_ms(w, res, dist_mod, backend):
             "backend": backend}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(w, res, out_dir, rank, world):
+    """--dump-outputs: the arrays the last timed pass returned, as float64 .npy files.  Arrays of at most 1/8 of this
+    rank's share of DUMP_BYTES are written whole; the rest are cut to one fixed, seeded subset of samples (same rows in
+    every one of them, listed in sample_index.npy), as many samples as the remaining budget holds."""
+    import numpy as np
+    import torch
+    budget = DUMP_BYTES // world - 4096 * 8                 # headroom for the .npy headers
+    outs = w.outputs(res)
+    B = sum(t.shape[0] for t in next(iter(outs.values())))
+    per_sample = {k: v[0][0].numel() * 8 for k, v in outs.items()}
+    whole = [k for k in outs if B * per_sample[k] <= budget // 8]
+    cut = [k for k in outs if k not in whole]
+    left = budget - sum(B * per_sample[k] for k in whole)
+    k_rows = min(B, left // max(1, sum(per_sample[k] for k in cut)))
+    if cut and k_rows < 1:
+        raise SystemExit("--dump-outputs: one sample of the output does not fit the dump budget")
+    idx = np.arange(B) if k_rows >= B else np.sort(np.random.default_rng(SEED).choice(B, int(k_rows), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+
+    def rows(blocks, sel):
+        parts, lo = [], 0
+        for t in blocks:
+            s = sel[(sel >= lo) & (sel < lo + t.shape[0])] - lo
+            parts.append(t[torch.as_tensor(s, device=t.device)].to(torch.float64).cpu())
+            lo += t.shape[0]
+        return torch.cat(parts).numpy()
+
+    for k in outs:
+        np.save(os.path.join(out_dir, k + tag + ".npy"), rows(outs[k], np.arange(B) if k in whole else idx))
+    if cut:
+        np.save(os.path.join(out_dir, "sample_index" + tag + ".npy"), (idx + rank * B).astype(np.float64))
+
+
 def timed_passes(w, warmup, steps, barrier):
     """``warmup`` untimed passes, then exactly ``steps`` passes bracketed by barrier + synchronize on both sides.
     Returns (last result, wall seconds of the timed region, per-pass ms by HIP events on the launch stream)."""
@@ -756,6 +810,8 @@ def _run_rank(args, real_stdout):
         torch.cuda.synchronize(dev)
 
     res, elapsed, pass_ms = timed_passes(w, args.warmup, args.steps, barrier)
+    if args.dump_outputs:
+        dump_outputs(w, res, args.dump_outputs, rank, world)
 
     units = w.units(res)                                     # units in one pass, this rank
     el = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)

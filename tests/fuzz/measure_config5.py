@@ -1,5 +1,5 @@
 import sys, os
-REPO="/root/repo"; sys.path[:0]=[REPO, os.path.join(REPO,"1d-burgers-equation-roms_amd")]
+REPO=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path[:0]=[REPO, os.path.join(REPO,"1d-burgers-equation-roms_amd")]
 import numpy as np, torch, copy
 from burgers_hip import rom, decoder
 from oracle import burgers_ref as br

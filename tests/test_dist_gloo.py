@@ -103,23 +103,29 @@ def test_pod_truncation_and_file_contracts(tmp_path):
     assert np.load(pu).flags["C_CONTIGUOUS"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/FEM/fem_training_data"),
-                    reason="reference checkout not present (build container only)")
 def test_pod_basis_reproduces_committed_modes():
-    """The 9 committed training snapshots -> the committed 40-mode basis and quadratic Phi."""
+    """The 9 training snapshots -> the committed 40-mode basis and quadratic Phi.  The snapshots (3 x 3 mu grid,
+    dt 0.05, 500 steps) are regenerated with the C oracle, pinned to the committed snapshot columns here."""
+    from conftest import load_golden
     from burgers_hip import pod
-    d = "/root/reference/FEM/fem_training_data"
-    files = [f for f in os.listdir(d) if f.endswith(".npy") and f.startswith("fem_simulation_")]
-    S = torch.from_numpy(np.hstack([np.load(os.path.join(d, f)) for f in files]))
+    from oracle import burgers_ref_c as bc
+    mu1 = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2 = np.tile(np.linspace(0.015, 0.03, 3), 3)
+    h, _ = bc.fom_run(np.linspace(0, 100, 512), np.ones(512), mu1, mu2, 0.05, 500)
+    gf = load_golden("committed_fom_n512.npz")
+    for b, key in ((0, "4.250_0.0150"), (8, "5.500_0.0300")):
+        assert np.linalg.norm(h[b].T[:, gf["cols"]] - gf["U_" + key]) < 1e-10 * np.linalg.norm(gf["U_" + key])
+    S = torch.from_numpy(np.hstack([h[b].T for b in range(9)]))
+    g = load_golden("committed_pod_r40.npz")
     U, s, _ = pod.pod_basis(S, epsilon_squared=1e-3)
-    ref = np.load("/root/reference/POD/modes/U_modes_tol_1e-03.npy")
+    ref = g["Phi"]
     assert U.shape == ref.shape == (512, 40)
     Ua = pod.align_signs(U, torch.from_numpy(ref)).numpy()
     assert np.abs(Ua - ref).max() < 1e-10
-    Phi, H, q = pod.build_quadratic_manifold(S, 21, alpha=1e-2)
-    Phi_ref = np.load("/root/reference/Quadratic_manifold/Phi.npy")
+    q = load_golden("committed_quadratic_n21.npz")
+    Phi, H, _ = pod.build_quadratic_manifold(S, 21, alpha=1e-2)
+    Phi_ref = q["Phi"]
     assert np.abs(pod.align_signs(Phi, torch.from_numpy(Phi_ref)).numpy() - Phi_ref).max() < 1e-9
-    H_ref = np.ascontiguousarray(np.load("/root/reference/Quadratic_manifold/H.npy"))
+    H_ref = np.ascontiguousarray(q["H"])
     sg = np.sign((Phi.numpy() * Phi_ref).sum(0))
     I, J = np.triu_indices(21)
     assert np.linalg.norm(H.numpy() * (sg[I] * sg[J]) - H_ref) < 1e-8 * np.linalg.norm(H_ref)

@@ -1,6 +1,7 @@
 import os, sys, time
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "1d-burgers-equation-roms_amd"))
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "1d-burgers-equation-roms_amd"))
+sys.path.insert(0, REPO)
 import numpy as np, torch
 from burgers_hip import rom, fom, pod
 N = 512; X = np.linspace(0, 100, N)
