@@ -18,6 +18,7 @@ class FomResult:
     hist: torch.Tensor     # (B, nsteps+1, N) float64, time-major per sample
     iters: torch.Tensor    # (B, nsteps) int32, Picard iterations per step
     flags: torch.Tensor    # (B,) int32, BG_FLAG_* bits
+    path: str | None = None  # ROM results: the C entry point of a device-side loop, "host" or "library"
 
     def snapshots(self):
         """(B, N, nsteps+1) C-contiguous: the reference's per-sample (N, nT+1) layout."""

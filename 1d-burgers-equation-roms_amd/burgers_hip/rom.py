@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import weakref
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -91,15 +92,13 @@ def rom_reduce(c, W, U, G, proj, supg, active, Ar, br, wtu=None, colmajor=False,
         with torch.cuda.device(c.device):
             rc = c.L.bg_rom_reduce_indexed(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(W), stride, _lib.ptr(w_index),
                                            _lib.ptr(U), _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E, opts,
-                                           _lib.ptr(active) if active is not None else None, _lib.ptr(Ar), _lib.ptr(br),
-                                           _lib.ptr(wtu) if wtu is not None else None, c.stream())
+                                           _lib.ptr(active), _lib.ptr(Ar), _lib.ptr(br), _lib.ptr(wtu), c.stream())
         _lib.check(rc, "bg_rom_reduce_indexed")
         return
     with torch.cuda.device(c.device):
         rc = c.L.bg_rom_reduce(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(W), stride, _lib.ptr(U), _lib.ptr(G),
                                _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E, opts,
-                               _lib.ptr(active) if active is not None else None, _lib.ptr(Ar), _lib.ptr(br),
-                               _lib.ptr(wtu) if wtu is not None else None, c.stream())
+                               _lib.ptr(active), _lib.ptr(Ar), _lib.ptr(br), _lib.ptr(wtu), c.stream())
     if rc == _lib.BG_ERR_UNSUPPORTED_R:
         raise NotImplementedError(f"ROM kernels cover r <= {c.L.bg_rom_max_r()} (got {r})")
     _lib.check(rc, "bg_rom_reduce")
@@ -134,8 +133,7 @@ def lu_solve(A, b, sign=1.0, active=None, x=None, info=None):
     x = torch.empty((B, n), dtype=torch.float64, device=device) if x is None else x
     info = torch.zeros((B,), dtype=torch.int32, device=device) if info is None else info
     with torch.cuda.device(device):
-        rc = L.bg_lu_solve(n, B, _lib.ptr(A), _lib.ptr(b), float(sign),
-                           _lib.ptr(active) if active is not None else None, _lib.ptr(x), _lib.ptr(info),
+        rc = L.bg_lu_solve(n, B, _lib.ptr(A), _lib.ptr(b), float(sign), _lib.ptr(active), _lib.ptr(x), _lib.ptr(info),
                            _lib.stream_ptr(device))
     if rc == _lib.BG_ERR_UNSUPPORTED_R:
         raise NotImplementedError("bg_lu_solve covers n <= 64")
@@ -149,8 +147,8 @@ def rom_reduce_lifted(c, Phi, q, U, G, proj, supg, active, Ar, br, wtu, extra_op
     with torch.cuda.device(c.device):
         rc = c.L.bg_rom_reduce_lifted(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(Phi), _lib.ptr(q), _lib.ptr(U),
                                       _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E,
-                                      (1 if supg else 0) | c.mesh_opt | extra_opts, _lib.ptr(active) if active is not None else None, _lib.ptr(Ar), _lib.ptr(br),
-                                      _lib.ptr(wtu) if wtu is not None else None, c.stream())
+                                      (1 if supg else 0) | c.mesh_opt | extra_opts, _lib.ptr(active), _lib.ptr(Ar),
+                                      _lib.ptr(br), _lib.ptr(wtu), c.stream())
     if rc == _lib.BG_ERR_UNSUPPORTED_R:
         raise NotImplementedError(f"ROM kernels cover r <= {c.L.bg_rom_max_r()} (got {r})")
     _lib.check(rc, "bg_rom_reduce_lifted")
@@ -159,7 +157,7 @@ def rom_reduce_lifted(c, Phi, q, U, G, proj, supg, active, Ar, br, wtu, extra_op
 def rom_lift(c, Phi, q, U, active=None):
     with torch.cuda.device(c.device):
         rc = c.L.bg_rom_lift(c.N, c.B, Phi.shape[1], _lib.ptr(c.X), _lib.ptr(Phi), _lib.ptr(q),
-                             _lib.ptr(active) if active is not None else None, _lib.ptr(U), c.stream())
+                             _lib.ptr(active), _lib.ptr(U), c.stream())
     _lib.check(rc, "bg_rom_lift")
 
 
@@ -221,7 +219,7 @@ class _IterState:
             self.counter[0].zero_()         # row 1 (singular systems) keeps accumulating until read
         with torch.cuda.device(c.device):
             rc = c.L.bg_lu_solve_update(q.shape[1], c.B, _lib.ptr(Ar), _lib.ptr(br), mode,
-                                        _lib.ptr(wtu) if wtu is not None else None, _lib.ptr(q), _lib.ptr(self.dq),
+                                        _lib.ptr(wtu), _lib.ptr(q), _lib.ptr(self.dq),
                                         float(tol), int(max_it), _lib.ptr(self.active), _lib.ptr(self.k),
                                         _lib.ptr(self.flags), _lib.ptr(self.counter), _lib.ptr(self.info), c.stream())
         if rc == _lib.BG_ERR_UNSUPPORTED_R:
@@ -251,33 +249,47 @@ def _workspace(c, r):
 
 
 # --------------------------------------------------------------------------- POD
-def pod_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0, balance=True):
-    """``pod_prom_burgers`` for a batch with the whole time loop on the device (bg_rom_run): one workgroup per
-    sample, no host in the loop.  Covers N <= 512 and r <= bg_rom_run_max_r()."""
+def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, group, balance, launch, keep=()):
+    """What the four device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run) share: the
+    batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
+    FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
+    entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
+    flags, info, order, stream.  Nothing is synchronised: ``res.info`` is checked lazily by the caller, and the operands
+    live in ``res._keep`` (inputs first, then ``keep``) as long as the result, since the launch is asynchronous."""
     L = _lib.load()
-    device = _lib.require_device(device)
-    opts = _lib.mesh_options(check_mesh(X), supg=True) | options
-    Xd = _as_dev(X, device)
+    opts = _lib.mesh_options(Xh, supg=supg) | options
+    Xd = _as_dev(Xh, device)
     N = Xd.numel()
-    Phid = _as_dev(Phi, device)
-    if Phid.dim() != 2 or Phid.shape[0] != N:
-        raise ValueError("Phi must have one row per mesh node")
-    r = Phid.shape[1]
     u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
     B = mu1d.numel()
     hist = torch.empty((B, nsteps + 1, N), dtype=torch.float64, device=device)
     iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
     flags = torch.zeros((B,), dtype=torch.int32, device=device)
     info = torch.zeros((B,), dtype=torch.int32, device=device)
-    order = sample_order(mu1d, 2 * _cu_count(device)) if balance else None
+    order = sample_order(mu1d, grid, group) if balance else None
+    outputs = (_lib.ptr(hist), _lib.ptr(iters), _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order), _lib.stream_ptr(device))
     with torch.cuda.device(device):
-        rc = L.bg_rom_run(N, B, r, int(nsteps), proj, _lib.ptr(Xd), _lib.ptr(Phid), _lib.ptr(u0d), _lib.ptr(mu1d),
-                          _lib.ptr(mu2d), float(dt), float(E), float(tol), int(max_it), int(opts), _lib.ptr(hist),
-                          _lib.ptr(iters), _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order), _lib.stream_ptr(device))
-    _lib.check(rc, "bg_rom_run")
-    res = FomResult(hist, iters, flags)
-    res.info = info              # checked lazily by the facade (a readback would synchronise)
+        rc = launch(getattr(L, entry), N, B, _lib.ptr(Xd), (_lib.ptr(u0d), _lib.ptr(mu1d), _lib.ptr(mu2d)), int(opts), outputs)
+    _lib.check(rc, entry)
+    res = FomResult(hist, iters, flags, path=entry)
+    res.info = info
+    res._keep = (Xd, u0d, mu1d, mu2d) + tuple(keep)
     return res
+
+
+def pod_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0, balance=True):
+    """``pod_prom_burgers`` for a batch with the whole time loop on the device (bg_rom_run): one workgroup per
+    sample, no host in the loop.  Covers N <= 512 and r <= bg_rom_run_max_r()."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    Phid = _as_dev(Phi, device)
+    if Phid.dim() != 2 or Phid.shape[0] != len(Xh):
+        raise ValueError("Phi must have one row per mesh node")
+    r = Phid.shape[1]
+    return _device_loop("bg_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+                        lambda f, N, B, x, inputs, opts, outputs: f(
+                            N, B, r, int(nsteps), proj, x, _lib.ptr(Phid), *inputs, float(dt), float(E), float(tol),
+                            int(max_it), opts, *outputs), keep=(Phid,))
 
 
 def sample_order(mu1d, grid, group=1):
@@ -310,48 +322,50 @@ def _cu_count(device):
     return torch.cuda.get_device_properties(device).multi_processor_count
 
 
-def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, max_it=20, device=None, PhiP=None, options=0,
+class WidePodPlan:
+    """The operand bg_rom_run_wide reads, built once per basis on the device (include/burgers_hip.h): the padded copy
+    PhiP [NPAD + 2][96] of ``Phi`` (row i at index i + 1, zero rows and columns around it), kept together with the basis
+    it was built from, which the pivoting redo of pod_prom_run_wide uses."""
+
+    def __init__(self, Phi, device):
+        L = _lib.load()
+        self.Phi = _as_dev(Phi, device)
+        if self.Phi.dim() != 2 or self.Phi.shape[1] > L.bg_rom_run_wide_max_r():
+            raise ValueError(f"Phi must be (N, r) with r <= {L.bg_rom_run_wide_max_r()}")
+        self.N, self.r = self.Phi.shape
+        NPAD = (self.N + 63) // 64 * 64
+        self.PhiP = torch.zeros((NPAD + 2, 96), dtype=torch.float64, device=self.Phi.device)
+        self.PhiP[1:self.N + 1, :self.r] = self.Phi
+        if self.PhiP.numel() != L.bg_rom_run_wide_phi_elems(self.N):
+            raise ValueError(f"bg_rom_run_wide does not cover N = {self.N}")
+
+
+def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0,
                       balance=True):
     """``pod_prom_burgers`` for bases of 41 .. 96 modes with the whole time loop on the device (bg_rom_run_wide): the basis
     streams through LDS, the reduced system's accumulators are spread over the four waves of the sample's workgroup.
     Samples whose elimination would have needed a row exchange come back marked and are redone through the library
-    path (LU with partial pivoting).  ``PhiP``: the padded basis copy of a previous call (``res.PhiP``) to reuse."""
-    L = _lib.load()
+    path (LU with partial pivoting); finding them reads ``info`` back, so unlike the other device-side loops this wrapper
+    synchronises the host.  ``Phi``: the basis, or a WidePodPlan of it to reuse across calls (``res.plan``; ``res.PhiP`` is
+    its padded copy)."""
     device = _lib.require_device(device)
-    opts = _lib.mesh_options(check_mesh(X), supg=True) | options
-    Xd = _as_dev(X, device)
-    N = Xd.numel()
-    Phid = _as_dev(Phi, device)
-    if Phid.dim() != 2 or Phid.shape[0] != N:
-        raise ValueError("Phi must have one row per mesh node")
-    r = Phid.shape[1]
-    if PhiP is None:
-        NPAD = (N + 63) // 64 * 64
-        PhiP = torch.zeros((NPAD + 2, 96), dtype=torch.float64, device=device)
-        PhiP[1:N + 1, :r] = Phid
-    assert PhiP.numel() == L.bg_rom_run_wide_phi_elems(N)
-    u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
-    B = mu1d.numel()
-    hist = torch.empty((B, nsteps + 1, N), dtype=torch.float64, device=device)
-    iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
-    flags = torch.zeros((B,), dtype=torch.int32, device=device)
-    info = torch.zeros((B,), dtype=torch.int32, device=device)
-    order = sample_order(mu1d, _cu_count(device)) if balance else None
-    with torch.cuda.device(device):
-        rc = L.bg_rom_run_wide(N, B, r, int(nsteps), proj, _lib.ptr(Xd), _lib.ptr(PhiP), _lib.ptr(u0d), _lib.ptr(mu1d),
-                               _lib.ptr(mu2d), float(dt), float(E), float(tol), int(max_it), int(opts), _lib.ptr(hist),
-                               _lib.ptr(iters), _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order), _lib.stream_ptr(device))
-    _lib.check(rc, "bg_rom_run_wide")
-    redo = (info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
+    Xh = check_mesh(X)
+    plan = Phi if isinstance(Phi, WidePodPlan) else WidePodPlan(Phi, device)
+    if plan.N != len(Xh) or plan.Phi.device != device:
+        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
+    res = _device_loop("bg_rom_run_wide", Xh, u0, mu1, mu2, nsteps, device, True, options, _cu_count(device), 1, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
+                           float(tol), int(max_it), opts, *outputs), keep=(plan,))
+    _, u0d, mu1d, mu2d = res._keep[:4]
+    redo = (res.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
     if redo.numel():                                     # rare: np.linalg.solve would have exchanged rows
-        rr = _pod_prom_run_library(Xd, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, Phid, proj, E, tol, max_it, device)
-        hist[redo], iters[redo], flags[redo] = rr.hist, rr.iters, rr.flags
-        info[redo] = 0
-    res = FomResult(hist, iters, flags)
-    res.info = info
+        rr = _pod_prom_run_library(Xh, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, plan.Phi, proj, E, tol, max_it, device)
+        res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
+        res.info[redo] = 0
     res.redone = int(redo.numel())
-    res.PhiP = PhiP
-    res._keep = (Xd, u0d, mu1d, mu2d)
+    res.plan = plan
+    res.PhiP = plan.PhiP                                 # the padded copy the kernel read (what wide results carried before)
     return res
 
 
@@ -406,7 +420,7 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
         iters[:, n] = st.k
         hist[:, n + 1] = U0
     flags |= st.flags
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="host")
 
 
 def _batched_solve(A, b, considered):
@@ -474,7 +488,7 @@ def _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it
         flags |= (k >= max_it).to(torch.int32) * _lib.BG_FLAG_HIT_CAP
         iters[:, n] = k
         hist[:, n + 1] = U0
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="library")
 
 
 # ------------------------------------------------------------ quadratic manifold
@@ -537,30 +551,15 @@ def quadratic_run_fused(X, u0, mu1, mu2, dt, nsteps, plan, proj, E=0.0, newton_t
                         balance=True):
     """``pod_quadratic_manifold`` for a batch with the whole time loop on the device (bg_quad_rom_run): four samples
     per workgroup, no host in the loop; the reduced solve pivots like np.linalg.solve."""
-    L = _lib.load()
     device = _lib.require_device(device)
-    opts = _lib.mesh_options(check_mesh(X), supg=False)
-    Xd = _as_dev(X, device)
-    N = Xd.numel()
-    if N != plan.N:
+    Xh = check_mesh(X)
+    if len(Xh) != plan.N:
         raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
-    u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
-    B = mu1d.numel()
-    hist = torch.empty((B, nsteps + 1, N), dtype=torch.float64, device=device)
-    iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
-    flags = torch.zeros((B,), dtype=torch.int32, device=device)
-    info = torch.zeros((B,), dtype=torch.int32, device=device)
-    order = sample_order(mu1d, _cu_count(device), group=4) if balance else None
-    with torch.cuda.device(device):
-        rc = L.bg_quad_rom_run(N, B, plan.n, int(nsteps), proj, _lib.ptr(Xd), _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif),
-                               _lib.ptr(plan.H3f), _lib.ptr(u0d), _lib.ptr(mu1d), _lib.ptr(mu2d), float(dt), float(E),
-                               float(newton_tol), int(newton_itmax), int(opts), _lib.ptr(hist), _lib.ptr(iters),
-                               _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order), _lib.stream_ptr(device))
-    _lib.check(rc, "bg_quad_rom_run")
-    res = FomResult(hist, iters, flags)
-    res.info = info              # checked lazily by the caller (a readback would synchronise)
-    res._keep = (plan, Xd, u0d, mu1d, mu2d)
-    return res
+    return _device_loop("bg_quad_rom_run", Xh, u0, mu1, mu2, nsteps, device, False, 0, _cu_count(device), 4, balance,
+                        lambda f, N, B, x, inputs, opts, outputs: f(
+                            N, B, plan.n, int(nsteps), proj, x, _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif),
+                            _lib.ptr(plan.H3f), *inputs, float(dt), float(E), float(newton_tol), int(newton_itmax), opts,
+                            *outputs), keep=(plan,))
 
 
 def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0, newton_tol=1e-6,
@@ -640,7 +639,7 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
         hist[:, m + 1] = u
         Un = u
     flags |= st.flags                                        # HIT_CAP = "Newton did not converge" (:1171)
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="host")
 
 
 # ----------------------------------------------------------------------- POD-ANN
@@ -749,7 +748,7 @@ class AnnEvaluator:
             for wt, bias, kind, alpha in plan:
                 z = torch.matmul(x, wt)                                       # (B, 1+n, h): one GEMM
                 with torch.cuda.device(device):
-                    _lib.check(L.bg_mlp_act_jvp(B, 1 + n, wt.shape[1], _lib.ptr(z), _lib.ptr(bias) if bias is not None else None,
+                    _lib.check(L.bg_mlp_act_jvp(B, 1 + n, wt.shape[1], _lib.ptr(z), _lib.ptr(bias),
                                                 kind, alpha, _lib.stream_ptr(device)), "bg_mlp_act_jvp")
                 x = z
             self.qs_out.copy_(x[:, 0, :])
@@ -842,8 +841,9 @@ class _ClosureTangent:
 
 
 def _ann_fused_plan(model, n, nbar, N, dtype, device):
-    """The closure as bg_ann_rom_run wants it, or None when the device-side loop does not apply (not a plain fp32
-    MLP the evaluator recognises, or beyond bg_ann_rom_limits)."""
+    """The closure as bg_ann_rom_run wants it (``args``: its part of the argument list; ``keep``: the device copies
+    those pointers refer to), or None when the device-side loop does not apply (not a plain fp32 MLP the evaluator
+    recognises, or beyond bg_ann_rom_limits)."""
     import ctypes
     import torch.nn as nn
     if dtype != torch.float32 or N > 512:
@@ -867,25 +867,22 @@ def _ann_fused_plan(model, n, nbar, N, dtype, device):
            for lin, _ in ann.layers]
     biases = [None if lin.bias is None else lin.bias.detach().to(**f32).contiguous() for lin, _ in ann.layers]
     nl = len(wts)
-    return dict(
-        keep=(wts, biases), nl=nl,
-        widths=(ctypes.c_int * (nl + 1))(*widths),
-        wt=(ctypes.c_void_p * nl)(*[w.data_ptr() for w in wts]),
-        bias=(ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in biases]),
-        acts=(ctypes.c_int * nl)(*[kinds[type(act)] for _, act in ann.layers]),
-        alphas=(ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in ann.layers]))
+    return SimpleNamespace(keep=(wts, biases), args=(
+        nl, (ctypes.c_int * (nl + 1))(*widths),
+        (ctypes.c_void_p * nl)(*[w.data_ptr() for w in wts]),
+        (ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in biases]),
+        (ctypes.c_int * nl)(*[kinds[type(act)] for _, act in ann.layers]),
+        (ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in ann.layers])))
 
 
 def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, tol=1e-6, max_it=50, device=None,
                       options=0, plan=None, balance=True):
     """``pod_ann_prom`` for a batch with the whole time loop on the device (bg_ann_rom_run): one workgroup per sample,
     the closure MLP evaluated in-kernel in float32, the reduced solve with partial pivoting.  Returns None when the model
-    is outside what that kernel covers."""
-    L = _lib.load()
+    is outside what that kernel covers.  ``plan``: an _ann_fused_plan of the model to reuse across calls."""
     device = _lib.require_device(device)
-    opts = _lib.mesh_options(check_mesh(X), supg=True) | options
-    Xd = _as_dev(X, device)
-    N = Xd.numel()
+    Xh = check_mesh(X)
+    N = len(Xh)
     Up, Us = _as_dev(U_p, device), _as_dev(U_s, device)
     if Up.dim() != 2 or Us.dim() != 2 or Up.shape[0] != N or Us.shape[0] != N:
         raise ValueError("U_p and U_s must have one row per mesh node")
@@ -897,24 +894,10 @@ def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0,
     UT = torch.zeros((-(-(n + nbar) // 8) * 8, N), dtype=torch.float64, device=device)     # [U_p^T; U_s^T; zero rows]
     UT[:n] = Up.t()
     UT[n:n + nbar] = Us.t()
-    u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
-    B = mu1d.numel()
-    hist = torch.empty((B, nsteps + 1, N), dtype=torch.float64, device=device)
-    iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
-    flags = torch.zeros((B,), dtype=torch.int32, device=device)
-    info = torch.zeros((B,), dtype=torch.int32, device=device)
-    order = sample_order(mu1d, 2 * _cu_count(device)) if balance else None
-    with torch.cuda.device(device):
-        rc = L.bg_ann_rom_run(N, B, n, nbar, int(nsteps), proj, _lib.ptr(Xd), _lib.ptr(UT), _lib.ptr(u0d),
-                              _lib.ptr(mu1d), _lib.ptr(mu2d), plan["nl"], plan["widths"], plan["wt"], plan["bias"],
-                              plan["acts"], plan["alphas"], float(dt), float(E), float(tol), int(max_it), int(opts),
-                              _lib.ptr(hist), _lib.ptr(iters), _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order),
-                              _lib.stream_ptr(device))
-    _lib.check(rc, "bg_ann_rom_run")
-    res = FomResult(hist, iters, flags)
-    res.info = info
-    res._keep = (plan, UT, Xd, u0d, mu1d, mu2d)      # the launch is asynchronous: its operands live as long as the result
-    return res
+    return _device_loop("bg_ann_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+                        lambda f, N, B, x, inputs, opts, outputs: f(
+                            N, B, n, nbar, int(nsteps), proj, x, _lib.ptr(UT), *inputs, *plan.args, float(dt), float(E),
+                            float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
 
 
 def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG", E=0.0, tol=1e-6, max_it=50,
@@ -962,7 +945,7 @@ def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG",
         flags |= st.flags
     finally:
         ann.release()               # also on an exception (SingularReducedSystem): never leave the graph to the collector
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="host")
 
 
 # ----------------------------------------------------------------------- POD-RBF
@@ -1054,7 +1037,7 @@ def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_mi
         iters[:, nt] = st.k
         hist[:, nt + 1] = U0
     flags |= st.flags
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="host")
 
 
 # --------------------------------------------------------------------- local POD
@@ -1112,4 +1095,4 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
         iters[:, n] = st.k
         hist[:, n + 1] = U0
     flags |= st.flags
-    return FomResult(hist, iters, flags)
+    return FomResult(hist, iters, flags, path="host")

@@ -63,7 +63,7 @@ for case in range(n_cases):
     b = rom.pod_ann_run(X, np.ones(N), mu1, mu2, 0.05, nT, U_p, U_s, model, projection=proj, E=E, fused=False)
     torch.cuda.synchronize()
     tag = f"case {case}: N={N} n={n} nbar={nbar} hidden={hidden} {act.__name__} bias={bias} {proj} E={E} B={B}"
-    if not hasattr(f, "info"):
+    if f.path != "bg_ann_rom_run":
         print("NOT FUSED", tag); bad += 1; continue
     ok = ((f.flags == 0) & (b.flags == 0)).cpu().numpy()
     fi, bi = f.iters.cpu().numpy(), b.iters.cpu().numpy()

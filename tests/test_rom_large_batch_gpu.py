@@ -359,7 +359,7 @@ def test_config4_quadratic_r40_k820(hip, quad_r40):
         h2, it2, fl2 = _chunked(lambda lo, hi: rom.quadratic_run(X, np.ones(512), mu1[lo:hi], mu2[lo:hi], 0.05, nT, Phi, H,
                                                                  projection=proj), B)
         torch.cuda.synchronize()
-        assert hasattr(res, "info")                            # the device-side loop
+        assert res.path == "bg_quad_rom_run"                   # the device-side loop
         assert torch.equal(res.iters, it2) and torch.equal(res.flags, fl2) and torch.equal(res.hist, h2), proj
         # LSPG (the reference's default, :1081) converges on every sample.  Galerkin with 40 quadratic modes does
         # not: most samples run into the 25-iteration cap ("Newton did not converge", :1171) and a non-convergent

@@ -25,7 +25,7 @@ def test_wide_committed_r96_and_oracle(hip):
     for tag, proj in (("galerkin", "Galerkin"), ("lspg", "LSPG")):
         res = rom.pod_prom_run(X, np.ones(512), [4.75, 5.3], [0.02, 0.018], 0.05, 8, g["Phi"], projection=proj)
         torch.cuda.synchronize()
-        assert hasattr(res, "PhiP") and res.redone == 0            # the device-side loop ran, nothing handed back
+        assert res.path == "bg_rom_run_wide" and res.redone == 0            # the device-side loop ran, nothing handed back
         assert rel_l2(res.hist[0].cpu().numpy().T, g["first9_" + tag]) < TOL
         U, ito = br.pod_prom_burgers(X, 0.05, 8, np.ones(512), 5.3, 0.0, 0.018, g["Phi"], projection=proj, return_iters=True)
         assert rel_l2(res.hist[1].cpu().numpy().T, U) < TOL and np.array_equal(res.iters[1].cpu().numpy(), ito)
@@ -49,7 +49,7 @@ def test_wide_vs_library_path_and_oracle(hip, N, r, B, nT):
         f = rom.pod_prom_run(X, np.ones(N), mu1, mu2, 0.05, nT, Phi, projection=proj, E=0.002)
         b = rom.pod_prom_run(X, np.ones(N), mu1[:4], mu2[:4], 0.05, nT, Phi, projection=proj, E=0.002, fused=False)
         torch.cuda.synchronize()
-        assert hasattr(f, "PhiP") and not hasattr(b, "PhiP")
+        assert f.path == "bg_rom_run_wide" and b.path == ("host" if r <= hip.load().bg_rom_max_r() else "library")
         assert torch.equal(f.iters[:4], b.iters) and rel_l2(f.hist[:4].cpu().numpy(), b.hist.cpu().numpy()) < 1e-11, proj
         for s in (0, B - 1):
             U, ito = br.pod_prom_burgers(X, 0.05, nT, np.ones(N), mu1[s], 0.002, mu2[s], Phi, projection=proj, return_iters=True)
@@ -75,3 +75,35 @@ def test_wide_results_do_not_depend_on_the_batch_and_pivoting_fallback(hip):
     torch.cuda.synchronize()
     assert forced.redone == 5 and bool((forced.info == 0).all())
     assert torch.equal(forced.iters, full.iters[:5]) and rel_l2(forced.hist.cpu().numpy(), full.hist[:5].cpu().numpy()) < 1e-11
+
+
+def test_wide_plan_reuse_and_checks(hip, monkeypatch):
+    """A WidePodPlan built once gives bitwise the result of passing the basis itself; a plan for another mesh size and a
+    basis wider than bg_rom_run_wide_max_r() are refused with ValueError before anything is launched."""
+    from burgers_hip import rom
+    g = load_golden("committed_pod_r96.npz")
+    X, _ = mesh(512)
+    mu1, mu2 = [4.6, 5.4, 4.9], [0.021, 0.016, 0.027]
+    plan = rom.WidePodPlan(g["Phi"], torch.device("cuda", torch.cuda.current_device()))
+    direct = rom.pod_prom_run_wide(X, np.ones(512), mu1, mu2, 0.05, 4, g["Phi"], rom.PROJ["lspg"])
+    first = rom.pod_prom_run_wide(X, np.ones(512), mu1, mu2, 0.05, 4, plan, rom.PROJ["lspg"])
+    again = rom.pod_prom_run_wide(X, np.ones(512), mu1, mu2, 0.05, 4, first.plan, rom.PROJ["lspg"])
+    torch.cuda.synchronize()
+    assert first.plan is plan and again.plan is plan
+    for res in (first, again):
+        assert res.path == "bg_rom_run_wide"
+        for k in ("hist", "iters", "flags", "info"):
+            assert torch.equal(getattr(res, k), getattr(direct, k)), k
+
+    def no_launch(*a, **k):
+        raise AssertionError("launched")
+    monkeypatch.setattr(rom, "_device_loop", no_launch)
+    X4, _ = mesh(448)
+    with pytest.raises(ValueError):
+        rom.pod_prom_run_wide(X4, np.ones(448), mu1, mu2, 0.05, 2, plan, rom.PROJ["lspg"])
+    wide = np.concatenate([g["Phi"], g["Phi"][:, :1]], axis=1)          # one column beyond the kernel
+    assert wide.shape[1] == hip.load().bg_rom_run_wide_max_r() + 1
+    with pytest.raises(ValueError):
+        rom.WidePodPlan(wide, "cuda")
+    with pytest.raises(ValueError):
+        rom.pod_prom_run_wide(X, np.ones(512), mu1, mu2, 0.05, 2, wide, rom.PROJ["lspg"])

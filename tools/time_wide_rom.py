@@ -30,4 +30,4 @@ for proj in ("Galerkin", "LSPG"):
               f"; total {np.median(it[:, :6].sum(1)) * 1.024 / npass:.1f} k")
         continue
     print(f"{'library path' if a.library else 'bg_rom_run_wide'} {proj} r={a.r} B={a.batch} steps={a.steps}: {ms:.1f} ms, {its} sample-iterations, "
-          f"{its / ms * 1e3:.3g} sample-Newton-steps/s" + (f", handed back {res.redone}" if hasattr(res, 'redone') else ""))
+          f"{its / ms * 1e3:.3g} sample-Newton-steps/s" + (f", handed back {res.redone}" if res.path == "bg_rom_run_wide" else ""))
