@@ -45,24 +45,49 @@ def _round_robin(m):
     return torch.from_numpy(steps)
 
 
-def jacobi_svd(R, tol=1e-15, max_sweeps=40):
+def _require_finite(A, who):
+    """The reference's np.linalg.svd raises LinAlgError on NaN / Inf input; a NaN row would otherwise pass the
+    kernel's skip test and come back as a NaN mode."""
+    if not bool(torch.isfinite(A).all()):
+        raise np.linalg.LinAlgError(f"{who}: the matrix holds NaN or Inf")
+
+
+def jacobi_svd(R, tol=1e-15, max_sweeps=80, info=None):
     """SVD of a square device matrix by one-sided Jacobi on the HIP kernel bg_jacobi_sweep.
     Returns U, s, Vh with R = U diag(s) Vh, s descending.  The rotations act on the ROWS of R, i.e.
-    on the columns of R^T: R^T J = W with orthogonal columns  =>  R = J (W^T): left vectors J, right W/|W|."""
+    on the columns of R^T: R^T J = W with orthogonal columns  =>  R = J (W^T): left vectors J, right W/|W|.
+
+    Before every sweep, rows whose squared norm is at or below (eps |R|_F)^2 are set to zero: they hold rounding
+    noise of the input, which rotations against the large rows keep regenerating above the relative tol, so a
+    rank-deficient core otherwise rotates forever (N x 808 bench gather: ~4800 rotations in every sweep).  Their
+    singular values come back 0 and their rows of Vh zero; the kernel skips every pair holding a zero row.  A
+    floor of m eps |R|_F would also converge but moves the modes near sigma/sigma_1 = 1e-7 by 4e-7 (measured).
+    Graded cores of condition 1e10 need up to ~46 sweeps at m = 512..777.  A sweep that still rotates at
+    max_sweeps raises RuntimeError; NaN / Inf input raises LinAlgError.  ``info`` (a dict) receives the sweep
+    count."""
     from . import lib as _lib
     L = _lib.load()
+    _require_finite(R, "jacobi_svd")
     m = R.shape[0]
     G = R.contiguous().clone()
     Jt = torch.eye(m, dtype=torch.float64, device=R.device)
     pairs = _round_robin(m).to(R.device)
     rot = torch.zeros((1,), dtype=torch.int32, device=R.device)
+    floor = (torch.finfo(torch.float64).eps * torch.linalg.matrix_norm(G)) ** 2
+    n_rot = sweep = 0
     with torch.cuda.device(R.device):
-        for _ in range(max_sweeps):
+        for sweep in range(1, max_sweeps + 1):
+            G.masked_fill_((G * G).sum(1, keepdim=True) <= floor, 0.0)
             rot.zero_()
             _lib.check(L.bg_jacobi_sweep(m, m, _lib.ptr(G), _lib.ptr(Jt), _lib.ptr(pairs), pairs.shape[0], pairs.shape[1],
                                          float(tol), _lib.ptr(rot), _lib.stream_ptr(R.device)), "bg_jacobi_sweep")
-            if int(rot.item()) == 0:
+            n_rot = int(rot.item())
+            if n_rot == 0:
                 break
+    if n_rot:
+        raise RuntimeError(f"jacobi_svd: not converged after {max_sweeps} sweeps (m = {m}, {n_rot} rotations in the last)")
+    if info is not None:
+        info["sweeps"] = sweep
     s = torch.linalg.vector_norm(G, dim=1)
     order = torch.argsort(s, descending=True)
     s, G, Jt = s[order], G[order], Jt[order]
@@ -70,21 +95,28 @@ def jacobi_svd(R, tol=1e-15, max_sweeps=40):
     return Jt.t().contiguous(), s, Vh
 
 
-def thin_svd(A):
+def thin_svd(A, info=None):
     """U, s, Vh of a wide matrix A (m x M), M >> m (snapshot matrices are N x B (nT+1)), on A's device.
 
     A^T = Q R by Householder QR (O(M m^2), rocSOLVER), then the SVD of the m x m core by one-sided Jacobi
     (bg_jacobi_sweep), and A = R^T Q^T = Vr s (Q Ur)^T.  rocSOLVER's own SVD is a Jacobi eigensolver on the
     Gram matrix: measured absolute accuracy 1e-9 sigma_max (tools/time_pod.py), which loses the singular
-    triplets a 1e-6 energy tolerance still keeps.  On CPU tensors (tests, fixtures) LAPACK does the lot."""
+    triplets a 1e-6 energy tolerance still keeps.  A tall A (m > M) works on A^T.  On CPU tensors (tests,
+    fixtures) LAPACK does the lot.
+
+    Triplets at the rounding level of the input, sigma <= eps |A|_F, come back as sigma = 0 with a zero column of U
+    (wide A) or zero row of Vh (tall A), see jacobi_svd; every larger triplet is kept.  A device A holding NaN or
+    Inf raises LinAlgError, as np.linalg.svd does; a core that does not converge raises RuntimeError.  ``info``
+    (a dict) receives the Jacobi sweep count."""
     m, M = A.shape
     if not A.is_cuda:
         return torch.linalg.svd(A, full_matrices=False)
     if m > M:                                                     # tall: work on the transpose
-        V, s, Uh = thin_svd(A.t())
+        V, s, Uh = thin_svd(A.t(), info)
         return Uh.t().contiguous(), s, V.t().contiguous()
+    _require_finite(A, "thin_svd")
     Q, R = torch.linalg.qr(A.t(), mode="reduced")                # (M, m), (m, m)
-    Ur, s, VrT = jacobi_svd(R)
+    Ur, s, VrT = jacobi_svd(R, info=info)
     return VrT.t().contiguous(), s, (Q @ Ur).t()
 
 
@@ -116,8 +148,9 @@ def compute_H(Q, E, alpha):
     The reference writes the minimiser through the thin SVD of Q, H = (Uq diag(s^2/(s^2+alpha^2))) (Vq^T E^T / s)^T.
     The same minimiser is the least-squares solution of [Q^T; alpha I] H^T = [E^T; 0], solved here by Householder
     QR and a triangular solve on the device: backward stable at condition sigma_max/alpha, where the device SVD
-    (see thin_svd) returned H with 2e-3 relative error.  Agrees with the SVD formula to 1e-11 and with the
-    committed H.npy to 1e-10 (tests)."""
+    (see thin_svd) returned H with 2e-3 relative error.  Measured on the 9-sample training fit (N = 512, n = 21):
+    agrees with the SVD formula to 3e-11 on CPU tensors (LAPACK QR) but to 1.9e-8 on the device, from the same Phi
+    and snapshots, and with the committed H.npy to 1.9e-8 on the device (tests/test_offline_builders_gpu.py)."""
     k = Q.shape[0]
     A = torch.cat([Q.t(), alpha * torch.eye(k, dtype=Q.dtype, device=Q.device)], 0)      # (Ns + k, k)
     B = torch.cat([E.t(), torch.zeros((k, E.shape[0]), dtype=Q.dtype, device=Q.device)], 0)

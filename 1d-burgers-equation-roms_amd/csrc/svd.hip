@@ -9,7 +9,9 @@
 //
 // Layout: G [m][ld] row-major, the m ROWS are the vectors being orthogonalised (rows of R = columns of R^T);
 // J [m][ld] receives the same rotations starting from the identity.  One launch = one step of a round-robin
-// ordering: m/2 disjoint row pairs, one 256-thread workgroup per pair.
+// ordering: m/2 disjoint row pairs, one 256-thread workgroup per pair.  The caller zeroes the rows at the
+// rounding level (|g|^2 <= (eps |R|_F)^2) before each sweep and raises when a sweep still rotates at its
+// sweep limit (burgers_hip/pod.py jacobi_svd).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,7 +46,10 @@ __global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G
     const double alpha = (s_part[0][0] + s_part[0][1]) + (s_part[0][2] + s_part[0][3]);
     const double beta = (s_part[1][0] + s_part[1][1]) + (s_part[1][2] + s_part[1][3]);
     const double gamma = (s_part[2][0] + s_part[2][1]) + (s_part[2][2] + s_part[2][3]);
-    if (!(fabs(gamma) > tol * sqrt(alpha * beta))) return;          // already orthogonal (or a zero / NaN row)
+    // already orthogonal, or a zero row: the caller (burgers_hip/pod.py jacobi_svd) zeroes every row with
+    // |g|^2 <= (eps |R|_F)^2 before each sweep, since rows at the rounding level never meet the relative tol;
+    // NaN input is refused there too (a NaN row would pass this test and come back as a NaN mode)
+    if (!(fabs(gamma) > tol * sqrt(alpha * beta))) return;
     const double zeta = (beta - alpha) / (2.0 * gamma);
     const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
     const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
