@@ -250,7 +250,7 @@ def _workspace(c, r):
 
 # --------------------------------------------------------------------------- POD
 def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, group, balance, launch, keep=()):
-    """What the four device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run) share: the
+    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run, bg_rbf_rom_run) share: the
     batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
     FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
     entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
@@ -1003,13 +1003,84 @@ class RbfClosure:
         return self.jacobian_t(qp).transpose(1, 2)                     # (B, nbar, n) view
 
 
+class RbfFusedPlan:
+    """The operand copies bg_rbf_rom_run reads, built once per closure and basis on the device (include/burgers_hip.h):
+    UT = [U_p^T; U_s^T] with row stride 512, the centres transposed, the output-scaled weights Wd and the bias padded to
+    128 columns, x_min and dx (the closure's own scaling, RbfClosure).  ``ok`` is False when the closure or the mesh is
+    beyond bg_rbf_rom_limits (N > 512, n > 20, nbar > 128 or too many centres)."""
+
+    def __init__(self, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device):
+        import ctypes
+        L = _lib.load()
+        self.Up, self.Us = _as_dev(U_p, device), _as_dev(U_s, device)
+        if self.Up.dim() != 2 or self.Us.dim() != 2 or self.Up.shape[0] != self.Us.shape[0]:
+            raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
+        self.N, self.n = self.Up.shape
+        self.nbar = self.Us.shape[1]
+        rbf = RbfClosure(X_train, W, epsilon, kernel, x_min, x_max, y_min, y_max, device)
+        if rbf.n != self.n or rbf.Wd.shape[1] != self.nbar:
+            raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
+        self.Ns, self.kind, self.eps = rbf.Ns, rbf.kind, rbf.eps
+        lim = [ctypes.c_int() for _ in range(3)]
+        L.bg_rbf_rom_limits(*[ctypes.byref(v) for v in lim])
+        max_n, max_nbar, max_ns = (v.value for v in lim)
+        self.ok = self.N <= 512 and self.n <= max_n and self.nbar <= max_nbar and self.Ns <= max_ns
+        if not self.ok:
+            return
+        f64 = dict(dtype=torch.float64, device=device)
+        self.UT = torch.zeros((self.n + self.nbar, 512), **f64)
+        self.UT[:self.n, :self.N] = self.Up.t()
+        self.UT[self.n:, :self.N] = self.Us.t()
+        self.XtT, self.x_min, self.dx = rbf.XtT, rbf.x_min.contiguous(), rbf.dx.contiguous()
+        self.Wd = torch.zeros((self.Ns, 128), **f64)
+        self.Wd[:, :self.nbar] = rbf.Wd
+        self.bias = torch.zeros((128,), **f64)
+        self.bias[:self.nbar] = rbf.bias
+
+
+def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                      projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None,
+                      plan=None, balance=True, options=0):
+    """``pod_rbf_prom`` for a batch with the whole time loop on the device (bg_rbf_rom_run): one workgroup per sample,
+    the closure evaluated in-kernel in fp64, the reduced solve with partial pivoting.  Returns None when the closure is
+    outside bg_rbf_rom_limits.  ``plan``: an RbfFusedPlan of the same closure and basis to reuse across calls
+    (``res.plan``); the closure arguments are then not read again, U_p only for its shape."""
+    p = projection.lower()
+    if p not in PROJ:
+        raise ValueError("projection must be 'LSPG' or 'Galerkin'.")
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    if plan is None:
+        plan = RbfFusedPlan(U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device)
+    Up = U_p if isinstance(U_p, torch.Tensor) else np.asarray(U_p)
+    if plan.N != len(Xh) or tuple(Up.shape) != (plan.N, plan.n) or plan.Up.device != device:
+        raise ValueError("the plan must be built for this mesh and U_p (and live on the device of the call)")
+    if not plan.ok:
+        return None
+    res = _device_loop("bg_rbf_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.n, plan.nbar, plan.Ns, int(nsteps), PROJ[p], plan.kind, x, _lib.ptr(plan.UT),
+                           _lib.ptr(plan.XtT), _lib.ptr(plan.Wd), _lib.ptr(plan.bias), _lib.ptr(plan.x_min),
+                           _lib.ptr(plan.dx), float(plan.eps), *inputs, float(dt), float(E), float(tol_newton),
+                           int(max_newton), opts, *outputs), keep=(plan,))
+    res.plan = plan
+    return res
+
+
 def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
-                projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None):
-    """Batched ``pod_rbf_prom`` (FEM/fem_burgers.py:1278-1398)."""
+                projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None, fused=False):
+    """Batched ``pod_rbf_prom`` (FEM/fem_burgers.py:1278-1398).  Default: the batched iteration driven from the host.
+    ``fused``: the device-side time loop bg_rbf_rom_run (pod_rbf_run_fused) when the closure is within bg_rbf_rom_limits,
+    otherwise the host-driven iteration as well."""
     p = projection.lower()
     if p not in PROJ:
         raise ValueError("projection must be 'LSPG' or 'Galerkin'.")
     proj = PROJ[p]
+    if fused:
+        res = pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                                projection, kernel, E, tol_newton, max_newton, device)
+        if res is not None:
+            return check_singular(res)
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     rbf = RbfClosure(X_train, W, epsilon, kernel, x_min, x_max, y_min, y_max, c.device)
     Up, Us = _as_dev(U_p, c.device), _as_dev(U_s, c.device)

@@ -370,6 +370,37 @@ int bg_ann_rom_run(int N, int B, int n, int nbar, int nsteps, int projection, co
                    const float *alphas, double dt, double E, double tol, int max_it, int options, double *hist,
                    int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * bg_rbf_rom_run -- batched replacement of FEMBurgers.pod_rbf_prom, the WHOLE time loop on the device
+ *   reference: FEM/fem_burgers.py:1278-1398 (loop), the scaled RBF closure :160-260 (interpolate_with_rbf_scaled
+ *   :225-236, compute_rbf_jacobian_full :238-260).
+ *   One workgroup owns one sample for all time steps and Gauss-Newton iterations (csrc/rom_rbf_fused.hip).  Per iteration:
+ *   q_p = U_p^T u, recomputed from the current iterate (:1352); the closure Jacobian at q_p; the tangent
+ *   W = U_p + U_s J (:1361); assembly with SUPG and the projection; the n x n solve with partial pivoting (:1365);
+ *   q_new = q_p + dq with err = |dq| / |q_new|, or |dq| when |q_new| = 0 (:1366-1390); the closure value at q_new and the
+ *   decode u = U_p q_new + U_s f(q_new) (:1378-1381).  All fp64.
+ *   The closure, with xs = 2 (q - x_min) / dx - 1, r2_i = |xs - Xt_i|^2 (kind BG_RBF_GAUSSIAN: phi = exp(-eps^2 r2),
+ *   BG_RBF_IMQ: phi = (1 + eps^2 r2)^(-1/2)):  f(q) = phi(q) Wd + bias, J = d f / d q (the forms of bg_rbf_eval).
+ *   Operand copies, built once per closure and basis by the caller (burgers_hip/rom.py::RbfFusedPlan):
+ *     UT     [n + nbar][512], 16-byte aligned: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, zero columns from N
+ *     XtT    [n][Ns]     the centres X_train transposed (centre index fastest)
+ *     Wd     [Ns][128], 16-byte aligned: W diag(dy / 2), zero columns from nbar (dy = y_max - y_min, entries below 1e-15 -> 1)
+ *     bias   [128]       dy / 2 + y_min, zero from nbar
+ *     x_min  [n], dx [n] x_max - x_min with entries below 1e-15 replaced by 1
+ *   Limits (bg_rbf_rom_limits): N <= 512 (BG_ERR_UNSUPPORTED_N), n <= 20, nbar <= 128, Ns <= 65536 (BG_ERR_UNSUPPORTED_R);
+ *   the centres stream through LDS in tiles.  N < 3, n, nbar, Ns < 1, an unknown kind or a null operand: BG_ERR_BAD_ARG.
+ *   u0, mu1, mu2, hist, iters, flags, info, order: as bg_rom_run (order entries outside [0, B) are skipped); flags:
+ *   BG_FLAG_HIT_CAP when an iteration count reaches max_it, BG_FLAG_NONFINITE for a non-finite error; info: 0, or k + 1
+ *   when the reduced system met an exactly zero pivot at elimination step k (the sample stops there).
+ *   options: BG_OPT_SUPG (pod_rbf_prom has it) | BG_OPT_NONUNIFORM.
+ * --------------------------------------------------------------------------------- */
+int bg_rbf_rom_limits(int *max_n, int *max_nbar, int *max_ns);
+int bg_rbf_rom_run(int N, int B, int n, int nbar, int Ns, int nsteps, int projection, int kind, const double *x,
+                   const double *UT, const double *XtT, const double *Wd, const double *bias, const double *x_min,
+                   const double *dx, double eps, const double *u0, const double *mu1, const double *mu2, double dt,
+                   double E, double tol, int max_it, int options, double *hist, int32_t *iters, int32_t *flags,
+                   int32_t *info, const int32_t *order, void *stream);
+
 /* bg_decode_modes_bf16 -- the contraction of the non-intrusive POD-ANN decoder (bf16 tier of BASELINE config 5)
  *   reference: `Uhat = U_modes @ Qhat.T`, Non-Instrusive/predict_pod_ann.py:73-80, for a batch of (mu1, mu2) samples
  *   out[b][i][t] = sum_k Um[i][k] * Q[b * Nt + t][k]: bf16 operands, float32 accumulate, each result written once as
