@@ -135,6 +135,11 @@ _SIGNATURES = {
     "bg_rbf_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_double_p] * 7 + [ctypes.c_double, c_double_p, c_double_p,
                                       c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                       ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_local_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
+    "bg_local_rom_run": (ctypes.c_int, [ctypes.c_int] * 7 + [c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
+                                        c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p,
+                                        c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -250,8 +250,8 @@ def _workspace(c, r):
 
 # --------------------------------------------------------------------------- POD
 def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, group, balance, launch, keep=()):
-    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run, bg_rbf_rom_run) share: the
-    batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
+    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run, bg_rbf_rom_run,
+    bg_local_rom_run) share: the batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
     FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
     entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
     flags, info, order, stream.  Nothing is synchronised: ``res.info`` is checked lazily by the caller, and the operands
@@ -1112,15 +1112,106 @@ def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_mi
 
 
 # --------------------------------------------------------------------- local POD
+class LocalPodPlan:
+    """The operands bg_local_rom_run reads, built once per clustering on the device (include/burgers_hip.h): the local
+    bases zero-padded into one stack [C][N][rmax] in centre order (slot = centre index), their widths (int32), UgT =
+    U_global[:, :m]^T contiguous, and the centres [C][m].  Shapes that cannot be right raise ValueError; ``ok`` is False
+    (with ``reason``) when the clustering is valid but the device loop does not cover it -- beyond bg_local_rom_limits,
+    N > 512, or a centre 0 .. C-1 without a basis -- and the caller then takes the host path."""
+
+    def __init__(self, centres, local_bases, U_global, m, N, device):
+        import ctypes
+        L = _lib.load()
+        self.N, self.m = int(N), int(m)
+        self.centres = _as_dev(centres, device)
+        if self.centres.dim() != 2 or self.centres.shape[1] != self.m:
+            raise ValueError(f"centres must be (C, m) with m = {self.m}")
+        self.C = self.centres.shape[0]
+        Ug = _as_dev(U_global, device)
+        if Ug.dim() != 2 or Ug.shape[0] != self.N or Ug.shape[1] < self.m:
+            raise ValueError(f"U_global must be (N, >= m) with N = {self.N}, m = {self.m}")
+        for k, b in local_bases.items():
+            if len(np.shape(b)) != 2 or np.shape(b)[0] != self.N:
+                raise ValueError(f"local basis {k} must have one row per mesh node (N = {self.N})")
+        lim = [ctypes.c_int() for _ in range(3)]
+        L.bg_local_rom_limits(*[ctypes.byref(v) for v in lim])
+        max_r, max_m, max_c = (v.value for v in lim)
+        self.widths_host = [int(np.shape(local_bases[c])[1]) if c in local_bases else 0 for c in range(self.C)]
+        self.rmax = max(self.widths_host)
+        missing = [c for c in range(self.C) if c not in local_bases]
+        if missing:
+            self.reason = f"centre {missing[0]} has no local basis"
+        elif self.N > 512:
+            self.reason = f"N = {self.N} > 512"
+        elif self.rmax > max_r or self.m > max_m or self.C > max_c:
+            self.reason = (f"beyond bg_local_rom_limits: widths {self.rmax} (<= {max_r}), m {self.m} (<= {max_m}), "
+                           f"{self.C} centres (<= {max_c})")
+        elif min(self.widths_host) < 1:
+            self.reason = "a local basis has no columns"
+        else:
+            self.reason = None
+        self.ok = self.reason is None
+        if not self.ok:
+            return
+        self.stack = torch.zeros((self.C, self.N, self.rmax), dtype=torch.float64, device=self.centres.device)
+        for c, w_ in enumerate(self.widths_host):
+            self.stack[c, :, :w_] = _as_dev(local_bases[c], device)
+        self.widths = torch.as_tensor(self.widths_host, dtype=torch.int32, device=self.centres.device)
+        self.UgT = Ug[:, :self.m].t().contiguous()
+
+
+def local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
+                         projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, plan=None, balance=True,
+                         options=0):
+    """``local_prom_burgers`` for a batch with the whole time loop on the device (bg_local_rom_run): one workgroup per
+    sample, the nearest-centre pick at every step start, the cluster's basis reloaded into registers only when it
+    changes.  Returns None when the clustering is outside what the kernel covers (LocalPodPlan.ok).  ``res.clusters``:
+    (B, nsteps) int32, the centre index of every sample and step.  ``plan``: a LocalPodPlan of the same clustering to
+    reuse across calls (``res.plan``); centres, bases and U_global are then not read again."""
+    if projection not in ("Galerkin", "LSPG"):
+        raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
+    proj = PROJ[projection.lower()]
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    if plan is None:
+        plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(Xh), device)
+    if plan.N != len(Xh) or plan.m != int(num_global_modes) or plan.centres.device != device:
+        raise ValueError("the plan must be built for this mesh and num_global_modes (and live on the device of the call)")
+    if not plan.ok:
+        return None
+    out = {}
+
+    def launch(f, N, B, x, inputs, opts, outputs):
+        out["clusters"] = torch.zeros((B, int(nsteps)), dtype=torch.int32, device=device)
+        return f(N, B, plan.C, plan.rmax, plan.m, int(nsteps), proj, x, _lib.ptr(plan.stack), _lib.ptr(plan.widths),
+                 _lib.ptr(plan.UgT), _lib.ptr(plan.centres), *inputs, float(dt), float(E), float(tol), int(max_it), opts,
+                 *outputs[:4], _lib.ptr(out["clusters"]), *outputs[4:])
+
+    res = _device_loop("bg_local_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1,
+                       balance, launch, keep=(plan,))
+    res.plan = plan
+    res.clusters = out["clusters"]
+    return res
+
+
 def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
-                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None):
+                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, fused=False):
     """Batched ``local_prom_burgers`` (FEM/fem_burgers.py:979-1079): each sample picks, once per time
     step, the local basis of the cluster whose centre is nearest to ``U_global[:, :m]^T u^n``
     (= ``kmeans.predict``), then iterates like ``pod_prom_burgers`` in that basis.  The bases are
     zero-padded to a common width and travel as per-sample W; padded reduced unknowns get a unit
-    diagonal so that their correction is exactly zero."""
+    diagonal so that their correction is exactly zero.  ``res.clusters``: (B, nsteps) int32, the
+    centre index of every sample and step.
+    ``fused``: the device-side time loop bg_local_rom_run (local_prom_run_fused) where it covers the clustering
+    (N <= 512, widths <= 40, m and C <= 64, a basis for every centre); otherwise, and by default, the host-driven
+    iteration."""
     if projection not in ("Galerkin", "LSPG"):
         raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
+    if fused:
+        res = local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
+                                   projection, E, tol, max_it, device)
+        if res is not None:
+            return check_singular(res)
     proj = PROJ[projection.lower()]
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     ids = sorted(local_bases.keys())
@@ -1138,6 +1229,7 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
     stackT = stack.transpose(1, 2).contiguous()                              # (C, rmax, N)
     rows = torch.arange(c.B, device=c.device)
     hist, iters, flags = _alloc_hist(c, nsteps)
+    clusters = torch.zeros((c.B, nsteps), dtype=torch.int32, device=c.device)
     Ar, br, wtu, G = _workspace(c, rmax)
     st = _IterState(c, rmax)
     q = torch.zeros((c.B, rmax), dtype=torch.float64, device=c.device)
@@ -1149,6 +1241,7 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
         slot = slot_of[cid]
         if bool((slot < 0).any()):
             raise KeyError("a predicted cluster has no local basis")
+        clusters[:, n] = cid
         slot32 = slot.to(torch.int32)                                         # basis of each sample (:1013)
         pad = (col[None, :] >= width_t[slot][:, None]).to(torch.float64)      # 1 on padded reduced unknowns
         st.begin_step()
@@ -1166,4 +1259,6 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
         iters[:, n] = st.k
         hist[:, n + 1] = U0
     flags |= st.flags
-    return FomResult(hist, iters, flags, path="host")
+    res = FomResult(hist, iters, flags, path="host")
+    res.clusters = clusters
+    return res

@@ -20,6 +20,10 @@
 // and factors it while the others are still applying panel p (look-ahead): one barrier per panel.  Every update is an
 // FMA over all 64 lanes, so the multipliers are formed for the rows ABOVE the pivot too (Gauss-Jordan) at no extra
 // instruction: the elimination ends with a diagonal system and the 40 dependent steps of a back substitution vanish.
+//
+// Local POD (bg_local_rom_run, reference :979-1079) is the same kernel with LOCAL = true: the nearest-centre pick at every
+// step start and a reload of the basis when the cluster changes (see the kernel).  Those instantiations are compiled in
+// rom_local_fused.hip, which includes this file with BG_ROM_FUSED_LOCAL_TU defined.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,14 +51,32 @@ struct RomRunArgs {
     int N, B, r, nsteps, max_it, supg, nonuniform, force_pivoted;
 };
 
+// Local POD (bg_local_rom_run): the POD kernel with one basis per time step, picked from the stack by the nearest centre.
+// Phi is unused and r is set per step; the POD instantiations keep RomRunArgs, so their argument layout is unchanged.
+struct LocalRunArgs : RomRunArgs {
+    const double* bases;      // [C][N][rmax], zero beyond each width
+    const int32_t* widths;    // [C], 1 .. rmax
+    const double* UgT;        // [m][N]: U_global[:, :m] transposed
+    const double* centres;    // [C][m]
+    int32_t* clusters;        // [B][nsteps] or null
+    int C, rmax, m;
+};
+template <bool LOCAL> struct RunArgsOf { using type = RomRunArgs; };
+template <> struct RunArgsOf<true> { using type = LocalRunArgs; };
+
 // Two workgroups per CU (round 3): the fp64 MFMAs of a wave do not overlap with its own vector-ALU work
 // (tools/mfma_valu_bench.hip), but the matrix pipe and the VALU of a SIMD serve different waves at the same time, so a
 // second resident sample fills the phases in which the first one solves, lifts or waits at a barrier.  What that takes
 // is LDS <= 80 KB per workgroup (was 135 KB): the per-thread halo table (40 KB) became register traffic between
 // neighbouring lanes (HaloLanes), and the four per-wave partial systems (56 KB) two that wave pairs share (NRED = 2).
 // The repair kernel (PIV) keeps one workgroup per CU: its one-wave pivoted solve holds a 41-double row per lane.
-template <int S, int NB, int PROJ, bool PIV>
-__global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs a)
+// LOCAL (local POD, reference :979-1079): at the start of every time step the sample's cluster is the nearest centre to
+// q_g = U_g^T u^n; when it differs from the cluster whose basis the workgroup holds, the fragments and the edge table are
+// reloaded from the stack, and r becomes that cluster's width.  The rest is the POD body: the solves put a unit diagonal on
+// the unknowns at and beyond r (what the host path does to the padded columns), and q = Phi^T u + dq is right after a
+// switch, when u^n is not in the new span.
+template <int S, int NB, int PROJ, bool PIV, bool LOCAL = false>
+__global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename RunArgsOf<LOCAL>::type a)
 {
     constexpr int NPAD = 64 * S;
     constexpr int RW = 4 * NB;                   // padded reduced dimension
@@ -89,6 +111,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
     __shared__ double s_x[RW];                   // solution of the pivoted fallback
     __shared__ int s_bad[4];
     __shared__ int s_info;
+    __shared__ double s_qg[LOCAL ? 64 : 1];      // local POD: U_g^T u^n of the current time step
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction
@@ -98,7 +121,9 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
     const int rowbase = owner * S;
 
     // ---- basis fragments: loaded once per workgroup, kept in registers for every sample ------------------------
+    // (local POD: loaded at the first time step of a workgroup and whenever the cluster changes, below)
     double frag[NB][S];                          // Phi[rowbase + s][4 c + t]
+    if constexpr (!LOCAL) {
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
         const int col = 4 * c + t;
@@ -122,6 +147,14 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
             }
         }
     }
+    } else {
+#pragma unroll
+        for (int c = 0; c < NB; ++c)
+#pragma unroll
+            for (int s = 0; s < S; ++s) frag[c][s] = 0.0;
+    }
+    int loaded = -1;                             // local POD: the cluster whose basis is in frag / s_edge (kept across samples)
+    int r_step = r;                              // local POD: the width of the current step's cluster (POD: r)
     if (tid < 4) s_u[tid < 2 ? tid : NPAD + tid] = 0.0;      // halos [0], [1], [NPAD+2], [NPAD+3]
 
     // Issue priority (round 3).  Two workgroups share every SIMD, and the matrix instruction holds the issue port for 16
@@ -179,6 +212,66 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
         int flags = 0, info_out = 0;
         bool aborted = false;                    // fast kernel: the multiplier guard tripped, the repair kernel redoes this sample
         for (int step = 0; step < a.nsteps && info_out == 0 && !aborted; ++step) {
+            if constexpr (LOCAL) {
+                // ---- q_g = U_g^T u^n (:1011): wave w takes the columns j = w (mod 4), lanes stride the rows ------------
+                for (int j = w; j < a.m; j += 4) {
+                    double p = 0.0;
+#pragma unroll 4                                 // (loads in flight together: each one is an L2 round trip)
+                    for (int i = lane; i < N; i += 64) p = __builtin_fma(a.UgT[(size_t)j * N + i], s_u[i + 2], p);
+                    p = wave_sum(p);
+                    if (lane == 0) s_qg[j] = p;
+                }
+                __syncthreads();                 // s_qg complete; also every read of s_edge of the previous step is done
+                // ---- kmeans.predict (:1012): lane c holds |q_g - centre_c|^2 (summed in j order), then the FIRST index of
+                // the minimum over the wave (a NaN distance counts as the smallest, as in np.argmin).  Every wave computes
+                // it: the cluster is workgroup-uniform without a broadcast.
+                double d = __builtin_inf();
+                int ci = lane;
+                if (lane < a.C) {
+                    d = 0.0;
+#pragma unroll 4
+                    for (int j = 0; j < a.m; ++j) {
+                        const double e = s_qg[j] - a.centres[(size_t)lane * a.m + j];
+                        d = __builtin_fma(e, e, d);
+                    }
+                }
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const double od = __shfl_xor(d, off);
+                    const int oc = __shfl_xor(ci, off);
+                    const bool take = (od != od) ? (d == d || oc < ci) : (od < d || (od == d && oc < ci));
+                    d = take ? od : d;
+                    ci = take ? oc : ci;
+                }
+                const int cl = __builtin_amdgcn_readfirstlane(ci);
+                const int rc = a.widths[cl] < a.rmax ? a.widths[cl] : a.rmax;     // (clamped: the stack rows are rmax wide)
+                if (cl != loaded) {              // workgroup-uniform: reload the fragments and the edge table (:1013)
+                    // as the POD kernel loads Phi, from the cluster's block of the stack (row stride rmax)
+                    const double* P = a.bases + (size_t)cl * N * a.rmax;
+                    const int ld = a.rmax;
+#pragma unroll
+                    for (int c = 0; c < NB; ++c) {
+                        const int col = 4 * c + t;
+#pragma unroll
+                        for (int s = 0; s < S; ++s) {
+                            const int i = rowbase + s;
+                            frag[c][s] = (i < N && col < rc) ? P[(size_t)i * ld + col] : 0.0;
+                        }
+                        if ((lane >> 2) == 0 || (lane >> 2) == 15) {      // the halo rows of this wave (see above)
+                            const int side = (lane >> 2) == 0 ? 0 : 1;
+#pragma unroll
+                            for (int d = 0; d < 2; ++d) {
+                                const int ie = side == 0 ? rowbase - 1 - d : rowbase + S + d;
+                                s_edge[side][d][c][w][t] = (ie >= 0 && ie < N && col < rc) ? P[(size_t)ie * ld + col] : 0.0;
+                            }
+                        }
+                    }
+                    loaded = cl;
+                    __syncthreads();             // s_edge rewritten before the projection reads it
+                }
+                r_step = rc;
+                if (tid == 0 && a.clusters) a.clusters[(size_t)smp * a.nsteps + step] = cl;
+            }
             // ---- g = M u^n + dt F (`M @ U[:, n] + At*F`, :746); rows are revisited by the same thread below ------
             for (int i = tid; i < NPAD; i += 256) {
                 double g = 0.0;
@@ -208,6 +301,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
                 // (a few integer instructions) instead: scratch 160 -> 76 bytes (Galerkin), 280 -> 140 (LSPG).
                 int tid_i = tid;
                 asm volatile("" : "+v"(tid_i));
+                const int rr = LOCAL ? r_step : r;
                 const int lane = tid_i & 63, t = lane & 3, rowbase = (16 * w + (lane >> 2)) * S;
                 const HaloLanes<NB> halo{s_edge, w, t, lane};
                 // ---- assembly: A(u_k), R(u_k) per row into LDS ----------------------------------------------------
@@ -275,22 +369,22 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
                 if constexpr (PIV) {
                     if (tid == 0) s_info = 0;
                     __syncthreads();
-                    if (w == 0) pivoted_solve<NB, GAL, NRED>(s_red, s_x, &s_info, lane, r);
+                    if (w == 0) pivoted_solve<NB, GAL, NRED>(s_red, s_x, &s_info, lane, rr);
                     __syncthreads();
                     xout = (lane < RW) ? s_x[lane] : 0.0;
                     if (s_info != 0 && info_out == 0) info_out = s_info;
                 } else {
                     bool tripped;
-                    xout = coop_gj_solve<NB, GAL, !skip(2), NRED>(s_red, s_m, s_diag, s_y, s_bad, w, lane, r, tripped);
+                    xout = coop_gj_solve<NB, GAL, !skip(2), NRED>(s_red, s_m, s_diag, s_y, s_bad, w, lane, rr, tripped);
 
                     if (!kTiming && tripped) aborted = true;
                 }
                 lap(2);
                 // ---- q = Phi^T u_k + dq, err = |dq| / |q|  (:770-776) ---------------------------------------------
                 double wtu = 0.0;
-                if (lane < r) wtu = entry(lane, RW + 1);        // Phi^T u: the second column of the extra block (both forms)
-                const double dq = (lane < r) ? xout : 0.0;
-                const double qn = (lane < r) ? wtu + dq : 0.0;
+                if (lane < rr) wtu = entry(lane, RW + 1);       // Phi^T u: the second column of the extra block (both forms)
+                const double dq = (lane < rr) ? xout : 0.0;
+                const double qn = (lane < rr) ? wtu + dq : 0.0;
                 double nd, nq;
                 wave_sum2(dq * dq, qn * qn, nd, nq);
                 nd = sqrt(nd); nq = sqrt(nq);
@@ -342,29 +436,60 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(RomRunArgs 
     }
 }
 
-template <int S, int NB>
-void launch_fused(int projection, int grid, hipStream_t st, const RomRunArgs& a)
+template <int S, int NB, bool LOCAL>
+void launch_fused(int projection, int grid, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
 {
     if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_GALERKIN, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_GALERKIN, false, LOCAL>), dim3(grid), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_LSPG, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_LSPG, false, LOCAL>), dim3(grid), dim3(256), 0, st, a);
 }
 
 // The repair kernel: samples the fast kernel gave up on (info = BG_INFO_NEEDS_PIVOTING), redone from u0 with the
 // partial-pivoting solve.  One shape covers every N <= 512 and r <= 40 (zero padding); it is not a hot path.
-void launch_repair(int projection, int grid, hipStream_t st, const RomRunArgs& a)
+template <bool LOCAL>
+void launch_repair(int projection, int grid, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
 {
     if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_GALERKIN, true>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_GALERKIN, true, LOCAL>), dim3(grid), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_LSPG, true>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_LSPG, true, LOCAL>), dim3(grid), dim3(256), 0, st, a);
+}
+
+// Both entry points: the fast kernel of the instantiation that covers N and r (2 workgroups per CU), then the repair
+// kernel (1 per CU).  r: the (widest) basis width.
+template <bool LOCAL>
+int launch_run(int N, int B, int r, int projection, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
+{
+    const int cus = device_cu_count();
+    const int grid = B < 2 * cus ? B : 2 * cus;              // two resident workgroups per CU
+    const int grid_repair = B < cus ? B : cus;
+    const int nb = r <= 8 ? 2 : (r <= 24 ? 6 : 10);
+    const int s4 = N <= 256 ? 4 : 8;
+    if (!a.force_pivoted) {
+        switch (s4 * 100 + nb) {
+#ifndef BG_FUSED_ONLY_810                 // (experiments compile the headline instantiation alone)
+            case 402: launch_fused<4, 2, LOCAL>(projection, grid, st, a); break;
+            case 406: launch_fused<4, 6, LOCAL>(projection, grid, st, a); break;
+            case 410: launch_fused<4, 10, LOCAL>(projection, grid, st, a); break;
+            case 802: launch_fused<8, 2, LOCAL>(projection, grid, st, a); break;
+            case 806: launch_fused<8, 6, LOCAL>(projection, grid, st, a); break;
+#endif
+            case 810: launch_fused<8, 10, LOCAL>(projection, grid, st, a); break;
+            default: return BG_ERR_UNSUPPORTED_R;
+        }
+        const int rc = check_launch();
+        if (rc != BG_OK) return rc;
+    }
+    if (kAblate < 0) launch_repair<LOCAL>(projection, grid_repair, st, a);     // every workgroup leaves at once unless a sample is flagged
+    return check_launch();
 }
 
 }  // namespace
 
 extern "C" {
 
+#ifndef BG_ROM_FUSED_LOCAL_TU
 int bg_rom_run_max_r(void) { return 40; }
 
 int bg_rom_run(int N, int B, int r, int nsteps, int projection, const double* x, const double* Phi, const double* u0,
@@ -382,29 +507,42 @@ int bg_rom_run(int N, int B, int r, int nsteps, int projection, const double* x,
     a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.r = r; a.nsteps = nsteps; a.max_it = max_it;
     a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
     a.force_pivoted = (options & BG_OPT_FORCE_PIVOTED) ? 1 : 0;
-    const int cus = device_cu_count();
-    const int grid = B < 2 * cus ? B : 2 * cus;              // two resident workgroups per CU
-    const int grid_repair = B < cus ? B : cus;
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = r <= 8 ? 2 : (r <= 24 ? 6 : 10);
-    const int s4 = N <= 256 ? 4 : 8;
-    if (!a.force_pivoted) {
-        switch (s4 * 100 + nb) {
-#ifndef BG_FUSED_ONLY_810                 // (experiments compile the headline instantiation alone)
-            case 402: launch_fused<4, 2>(projection, grid, st, a); break;
-            case 406: launch_fused<4, 6>(projection, grid, st, a); break;
-            case 410: launch_fused<4, 10>(projection, grid, st, a); break;
-            case 802: launch_fused<8, 2>(projection, grid, st, a); break;
-            case 806: launch_fused<8, 6>(projection, grid, st, a); break;
-#endif
-            case 810: launch_fused<8, 10>(projection, grid, st, a); break;
-            default: return BG_ERR_UNSUPPORTED_R;
-        }
-        const int rc = check_launch();
-        if (rc != BG_OK) return rc;
-    }
-    if (kAblate < 0) launch_repair(projection, grid_repair, st, a);     // every workgroup leaves at once unless a sample is flagged
-    return check_launch();
+    return launch_run<false>(N, B, r, projection, (hipStream_t)stream, a);
 }
+
+#else  // rom_local_fused.hip
+
+int bg_local_rom_limits(int* max_r, int* max_m, int* max_clusters)
+{
+    if (max_r) *max_r = 40;
+    if (max_m) *max_m = 64;
+    if (max_clusters) *max_clusters = 64;        // one lane per centre in the nearest-centre pick
+    return BG_OK;
+}
+
+int bg_local_rom_run(int N, int B, int C, int rmax, int m, int nsteps, int projection, const double* x,
+                     const double* bases, const int32_t* widths, const double* UgT, const double* centres,
+                     const double* u0, const double* mu1, const double* mu2, double dt, double E, double tol, int max_it,
+                     int options, double* hist, int32_t* iters, int32_t* flags, int32_t* info, int32_t* clusters,
+                     const int32_t* order, void* stream)
+{
+    if (N < 2 || B < 0 || C < 1 || rmax < 1 || m < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
+    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
+    if (N > 512) return BG_ERR_UNSUPPORTED_N;
+    if (rmax > 40 || m > 64 || C > 64) return BG_ERR_UNSUPPORTED_R;
+    if (B == 0) return BG_OK;
+    if (!x || !bases || !widths || !UgT || !centres || !u0 || !mu1 || !mu2 || !hist || !flags || !info ||
+        (nsteps > 0 && !iters))
+        return BG_ERR_BAD_ARG;
+    LocalRunArgs a;
+    a.x = x; a.Phi = nullptr; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags;
+    a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.r = rmax; a.nsteps = nsteps;
+    a.max_it = max_it; a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
+    a.force_pivoted = (options & BG_OPT_FORCE_PIVOTED) ? 1 : 0;
+    a.bases = bases; a.widths = widths; a.UgT = UgT; a.centres = centres; a.clusters = clusters;
+    a.C = C; a.rmax = rmax; a.m = m;
+    return launch_run<true>(N, B, rmax, projection, (hipStream_t)stream, a);
+}
+#endif
 
 }  // extern "C"

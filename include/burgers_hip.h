@@ -401,6 +401,31 @@ int bg_rbf_rom_run(int N, int B, int n, int nbar, int Ns, int nsteps, int projec
                    double E, double tol, int max_it, int options, double *hist, int32_t *iters, int32_t *flags,
                    int32_t *info, const int32_t *order, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * bg_local_rom_run -- batched replacement of FEMBurgers.local_prom_burgers, the WHOLE time loop on the device
+ *   reference: FEM/fem_burgers.py:979-1079.  bg_rom_run with one basis per time step (csrc/rom_fused.hip, the LOCAL
+ *   variant of the same kernel): at the start of every step the sample's cluster is c = argmin_c |q_g - centres[c]|^2
+ *   with q_g = U_g^T u^n (kmeans.predict, :1011-1012; the distance summed in j order, the first index of the minimum);
+ *   the step then iterates like pod_prom_burgers in that cluster's basis of width widths[c] (:1013-1060).  A workgroup
+ *   reloads its register-resident basis only when the cluster changes (kept across the samples it works on).
+ *   bases    [C][N][rmax] row-major: cluster c's basis in columns 0 .. widths[c]-1, zeros beyond
+ *   widths   [C] int32, 1 .. rmax
+ *   UgT      [m][N]: U_global[:, :m] transposed (m = num_global_modes)
+ *   centres  [C][m] (the KMeans cluster_centers_)
+ *   clusters [B][nsteps] int32 or NULL: the cluster of every sample and step
+ *   Limits (bg_local_rom_limits): N <= 512 (BG_ERR_UNSUPPORTED_N), rmax <= 40, m <= 64, C <= 64 (BG_ERR_UNSUPPORTED_R).
+ *   N < 2, B, nsteps < 0, C, rmax, m, max_it < 1, dt <= 0 or a null operand with B > 0: BG_ERR_BAD_ARG.
+ *   u0, mu1, mu2, hist, iters, flags, info, order: as bg_rom_run, including the repair kernel that redoes a sample whose
+ *   pivot-free elimination met a multiplier above 1 (it takes the same cluster path).
+ *   options: BG_OPT_SUPG (local_prom_burgers has it) | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED.
+ * --------------------------------------------------------------------------------- */
+int bg_local_rom_limits(int *max_r, int *max_m, int *max_clusters);
+int bg_local_rom_run(int N, int B, int C, int rmax, int m, int nsteps, int projection, const double *x,
+                     const double *bases, const int32_t *widths, const double *UgT, const double *centres,
+                     const double *u0, const double *mu1, const double *mu2, double dt, double E, double tol,
+                     int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
+                     int32_t *clusters, const int32_t *order, void *stream);
+
 /* bg_decode_modes_bf16 -- the contraction of the non-intrusive POD-ANN decoder (bf16 tier of BASELINE config 5)
  *   reference: `Uhat = U_modes @ Qhat.T`, Non-Instrusive/predict_pod_ann.py:73-80, for a batch of (mu1, mu2) samples
  *   out[b][i][t] = sum_k Um[i][k] * Q[b * Nt + t][k]: bf16 operands, float32 accumulate, each result written once as
