@@ -2,7 +2,7 @@
 """bench.py -- Newton-step throughput of the batched FOM / ROM hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config fom|pod_galerkin|pod_lspg|quadratic|ann|decoder_bf16]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 Default = BASELINE.json configs[1], the configuration the metric is quoted on: B = 1024 (mu1, mu2) samples per GPU,
 N = 1024 nodes, fp64, 500 implicit-Euler steps at dt = 0.025 (dt = 0.05 diverges at N = 1024 in the reference itself,
@@ -10,6 +10,11 @@ BASELINE.md section 2), u0 = 1, E = 0, mu ~ U[4.25,5.5] x U[0.015,0.03], rng see
 are BASELINE.json configs[2..4]: each prints the same driver-contract line with its own roofline.
 One bench "step" = one full pass of the workload (all time steps, every inner iteration of every sample of this rank).
 Unit: the sample-Newton-step, one (sample, inner iteration) pair = one assembly + one solve (+ projection for the ROMs).
+
+A plain run does only what the headline needs: set up, warm up, time the passes, dump the outputs if asked, print the
+line (headline, roofline from the timed passes, non-finite / capped sample counts).  --full adds everything else: the
+parity of a sample subset against the CPU restatement, the CPU baseline legs, the other_configs runs of the default
+line and, with more than one GPU, the timed all-gather + SVD.
 
 Multi-GPU: `python bench.py --gpus N` starts its own N rank processes (rank i -> device i, RCCL) BEFORE the parent makes
 any GPU call; the driver's `python -m torch.distributed.run ... bench.py --gpus N` form (RANK in the environment) runs
@@ -62,14 +67,17 @@ def parse_args(argv=None):
     ap.add_argument("--n", type=int, default=None, help="mesh nodes (default 1024 for fom, 512 for the ROMs)")
     ap.add_argument("--time-steps", type=int, default=500)
     ap.add_argument("--dt", type=float, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU-reference parity, CPU baseline, other_configs, "
+                         "multi-GPU all-gather + SVD timing (the options below apply to --full runs only)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each CPU-baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (the driver's contract): --batch samples PER GPU; strong: --batch is the GLOBAL sweep, split "
                          "evenly over the ranks (each rank's share may then take the low-latency workgroup-per-sample kernel)")
     ap.add_argument("--other-configs", choices=("auto", "full", "small", "none"), default="auto",
-                    help="1-GPU fom run: append short runs of BASELINE configs[2..4] as other_configs.  auto = full for the "
-                         "driver's default command line, none once a workload flag is given; small = 96 samples x 12 steps "
+                    help="1-GPU fom run with --full: append short runs of BASELINE configs[2..4] as other_configs.  auto = "
+                         "full for the default workload, none once a workload flag is given; small = 96 samples x 12 steps "
                          "(the contract test)")
     ap.add_argument("--other-steps", type=int, default=3, help="timed passes of each other_configs entry")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -78,11 +86,13 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be at least 1")
-    # the driver's own line (no workload flag given): configs[1] as the headline + one short run of every other config
+    if args.other_configs in ("full", "small") and not args.full:
+        ap.error("--other-configs %s needs --full" % args.other_configs)
+    # --full with no workload flag: configs[1] as the headline + one short run of every other config
     args.default_workload = (args.config == "fom" and args.batch is None and args.n is None and args.dt is None
                              and args.time_steps == 500)
     if args.other_configs == "auto":
-        args.other_configs = "full" if args.default_workload else "none"
+        args.other_configs = "full" if args.full and args.default_workload else "none"
     rom = args.config != "fom"
     if args.steps is None:
         args.steps = 3 if rom else 10
@@ -728,8 +738,8 @@ def timed_passes(w, warmup, steps, barrier):
 
 
 def other_config_entries(args, dev, barrier):
-    """The default 1-GPU run also measures BASELINE configs[2..4]: each --config workload at its own
-    full size for a few passes, same timing protocol as the headline, parity of a sample subset against the CPU
+    """The default 1-GPU --full run also measures BASELINE configs[2..4]: each --config workload at its
+    own full size for a few passes, same timing protocol as the headline, parity of a sample subset against the CPU
     restatement outside the timed region.  One compact entry each; the full line of a config is `--config NAME`."""
     import gc
     import numpy as np
@@ -821,7 +831,7 @@ def _run_rank(args, real_stdout):
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     elapsed, total_units = float(el.item()), float(tot.item())
     gather = None
-    if dist is not None and args.config == "fom":
+    if args.full and dist is not None and args.config == "fom":
         gather = allgather_svd_ms(w, res, dist, backend)
 
     others = None
@@ -832,7 +842,9 @@ def _run_rank(args, real_stdout):
     if rank == 0:
         value = total_units * args.steps / elapsed
         metric, workload = w.describe()
-        par, cpu = cpu_leg(w, res, timed=(args.gpus == 1 and not args.no_cpu_baseline))
+        par, cpu = {}, None
+        if args.full:
+            par, cpu = cpu_leg(w, res, timed=(args.gpus == 1 and not args.no_cpu_baseline))
         line = {"metric": metric, "value": value, "unit": w.unit, "n_gpus": args.gpus, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
                 "scaling": args.scaling, "vs_baseline": None, "dtype": w.dtype, "data": "synthetic",

@@ -31,7 +31,7 @@ def _run(cmd, env=None, timeout=900):
 
 def test_bench_json_contract(hip):
     d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
-              "--time-steps", "20", "--cpu-seconds", "1"])
+              "--time-steps", "20", "--cpu-seconds", "1", "--full"])
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64"
     r = d["roofline"]
     assert r["bound"] == "fp64_valu" and r["unit"] == "TFLOP/s" and r["peak"] == 78.6
@@ -46,7 +46,7 @@ def test_bench_json_contract(hip):
 def test_bench_rom_configs(hip, config, batch):
     """BASELINE configs[2..4] through the same contract: MFMA roofline, parity against the oracle outside the timed region."""
     d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--config", config, "--steps", "1", "--warmup", "1", "--batch",
-              str(batch), "--time-steps", "12", "--cpu-seconds", "1"])
+              str(batch), "--time-steps", "12", "--cpu-seconds", "1", "--full"])
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["peak"] == 78.6
     assert d["roofline"]["measured_ceiling_of_the_instruction_used"]["TFLOP/s"] == 62.0
     assert d["rel_l2_vs_cpu_ref"] < d["parity_tolerance"] and d["nonfinite_samples"] == 0
@@ -56,9 +56,9 @@ def test_bench_rom_configs(hip, config, batch):
 
 
 def test_bench_default_line_carries_the_other_configs(hip):
-    """The driver's default command line also measures configs[2..4] (other_configs): here at the small size."""
+    """The default command line with --full also measures configs[2..4] (other_configs): here at the small size."""
     d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "64",
-              "--time-steps", "20", "--no-cpu-baseline", "--other-configs", "small", "--other-steps", "1"])
+              "--time-steps", "20", "--no-cpu-baseline", "--other-configs", "small", "--other-steps", "1", "--full"])
     oc = d["other_configs"]
     assert [e["config"]["name"] for e in oc] == ["pod_galerkin", "pod_lspg", "quadratic", "ann", "decoder_bf16", "pod_r96_galerkin",
                                                    "pod_r96_lspg"]
@@ -70,9 +70,20 @@ def test_bench_default_line_carries_the_other_configs(hip):
             assert e["iters_match_cpu_ref"] is True
 
 
+def test_bench_plain_line_is_lean(hip):
+    """Without --full the default workload's line carries the headline, its roofline and the sample status, and nothing
+    that needs runs of its own: no other_configs, no CPU baseline, no parity against the CPU restatement."""
+    d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1"])
+    assert d["n_gpus"] == 1 and d["steps"] == 1 and d["warmup"] == 1 and d["dtype"] == "f64"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["global_batch"] == 1024
+    assert d["nonfinite_samples"] == 0 and d["roofline"]["bound"] == "fp64_valu"
+    for k in ("other_configs", "cpu_baseline", "rel_l2_vs_cpu_ref", "iters_match_cpu_ref", "allgather_svd"):
+        assert k not in d, k
+
+
 def test_bench_decoder_bf16(hip):
     d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "decoder_bf16", "--steps", "1", "--warmup", "1",
-              "--batch", "300", "--time-steps", "100"])
+              "--batch", "300", "--time-steps", "100", "--full"])
     assert d["dtype"] == "bf16" and d["roofline"]["bound"] == "hbm" and d["rel_l2_vs_cpu_ref"] < d["parity_tolerance"]
 
 
@@ -81,7 +92,7 @@ def test_bench_starts_its_own_ranks(hip):
     the GPU (gloo rehearsal on this box's one GPU: RCCL refuses two ranks per device), relays one JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64",
-              "--time-steps", "20"], env=env)
+              "--time-steps", "20", "--full"], env=env)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 128 and "cpu_baseline" not in d
     assert d["rel_l2_vs_cpu_ref"] < 1e-10 and d["iters_match_cpu_ref"] is True
     assert d["allgather_svd_ms"] > 0 and d["allgather_svd"]["snapshots"] == 2 * 8 * 5

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 evidence in one GPU call, condensed ON the box into gpurun_out/r03_profiles/ (copy its files into profiles/):
-#   1. rocprofv3 --kernel-trace --stats of the DEFAULT bench.py command (FOM headline + the other_configs runs)
+#   1. rocprofv3 --kernel-trace --stats of the default `bench.py --full` command (FOM headline + the other_configs runs)
 #   2. per ROM config (short passes): one SQ pass (matrix-pipe / VALU activity), one FETCH_SIZE pass, one WRITE_SIZE pass
 #      (counters in their own passes, no trace domains besides --kernel-trace: MI355X_MICROARCH, rocprofv3 PMC slots)
 set -e
@@ -11,7 +11,7 @@ W=/tmp/r03_prof
 rm -rf $W; mkdir -p $O $W
 cd /tmp
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_LDS"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $W/kt -- python $R/bench.py --no-cpu-baseline > $W/kt.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $W/kt -- python $R/bench.py --full --no-cpu-baseline > $W/kt.log 2>&1
 f=$(ls $W/kt/*/*kernel_stats.csv | head -1)
 python3 - "$f" "$O/r03_default_bench_kernel_stats.csv" <<'PY'
 import csv, sys
