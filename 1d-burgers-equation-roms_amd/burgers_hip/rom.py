@@ -369,6 +369,64 @@ def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, m
     return res
 
 
+class BlockedPodPlan:
+    """What bg_rom_run_blocked reads and writes besides the batch, built once per basis on the device
+    (include/burgers_hip.h): the padded copy PhiP [NPAD + 2][RP] of ``Phi`` (row i at index i + 1, zero rows and columns
+    around it), the workspace of ``slots`` slots (one per workgroup; default: one per compute unit, the kernel's LDS
+    admits one workgroup per CU) and the basis itself, which the pivoting redo of pod_prom_run_blocked uses."""
+
+    def __init__(self, Phi, device, slots=None):
+        L = _lib.load()
+        shape = tuple(np.shape(Phi))
+        if len(shape) != 2:
+            raise ValueError("Phi must be (N, r)")
+        N, r = shape
+        if r < 1 or r > L.bg_rom_run_blocked_max_r():
+            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {L.bg_rom_run_blocked_max_r()}")
+        if N < 3 or N > 512:
+            raise ValueError(f"bg_rom_run_blocked covers 3 <= N <= 512, not N = {N}")
+        device = _lib.require_device(device)
+        self.Phi = _as_dev(Phi, device)
+        self.N, self.r = N, r
+        self.slots = int(slots) if slots is not None else _cu_count(device)
+        if self.slots < 1:
+            raise ValueError("slots must be positive")
+        RP = (r + 15) // 16 * 16
+        NPAD = (N + 7) // 8 * 8
+        self.PhiP = torch.zeros((NPAD + 2, RP), dtype=torch.float64, device=self.Phi.device)
+        self.PhiP[1:N + 1, :r] = self.Phi
+        assert self.PhiP.numel() == L.bg_rom_run_blocked_phi_elems(N, r)
+        self.work = torch.empty((self.slots, L.bg_rom_run_blocked_work_elems(N, r)), dtype=torch.float64,
+                                device=self.Phi.device)
+
+
+def pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                         options=0, balance=True):
+    """``pod_prom_burgers`` for bases of up to 256 modes with the whole time loop on the device (bg_rom_run_blocked): the
+    reduced system lives in a per-workgroup workspace slot, projected and eliminated tile by tile on the matrix cores.
+    Samples whose elimination would have needed a row exchange come back marked and are redone through the library
+    path, as in pod_prom_run_wide (so this wrapper synchronises the host).  ``Phi_or_plan``: the basis, or a
+    BlockedPodPlan of it to reuse across calls (``res.plan``)."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    plan = Phi_or_plan if isinstance(Phi_or_plan, BlockedPodPlan) else BlockedPodPlan(Phi_or_plan, device)
+    if plan.N != len(Xh) or plan.Phi.device != device:
+        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
+    res = _device_loop("bg_rom_run_blocked", Xh, u0, mu1, mu2, nsteps, device, True, options, plan.slots, 1, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
+                           float(tol), int(max_it), opts, _lib.ptr(plan.work), plan.slots, *outputs), keep=(plan,))
+    _, u0d, mu1d, mu2d = res._keep[:4]
+    redo = (res.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
+    if redo.numel():                                     # np.linalg.solve would have exchanged rows
+        rr = _pod_prom_run_library(Xh, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, plan.Phi, proj, E, tol, max_it, device)
+        res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
+        res.info[redo] = 0
+    res.redone = int(redo.numel())
+    res.plan = plan
+    return res
+
+
 def check_singular(res):
     """np.linalg.solve raises LinAlgError('Singular matrix') at :767; the device loop records it per sample."""
     info = getattr(res, "info", None)
@@ -378,15 +436,19 @@ def check_singular(res):
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
-                 device=None, fused=True):
+                 device=None, fused=True, blocked=False):
     """Batched ``pod_prom_burgers``; ``projection`` is case-sensitive like the reference (:754-764).
     ``fused`` (default): the device-side time loop bg_rom_run where it applies (N <= 512, r <= 40); otherwise, or
-    with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host."""
+    with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host.
+    ``blocked`` (opt-in, with ``fused``): bases of bg_rom_run_wide_max_r() < r <= bg_rom_run_blocked_max_r() on
+    N <= 512 take the device-side loop bg_rom_run_blocked instead of the library path."""
     if projection not in ("Galerkin", "LSPG"):
         raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
     proj = PROJ[projection.lower()]
     L = _lib.load()
     r_in, n_in = np.shape(Phi)[1], np.shape(Phi)[0]
+    if blocked and fused and L.bg_rom_run_wide_max_r() < r_in <= L.bg_rom_run_blocked_max_r() and n_in <= 512:
+        return check_singular(pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     if fused and L.bg_rom_run_max_r() < r_in <= L.bg_rom_run_wide_max_r() and n_in <= 512:
         return check_singular(pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     if r_in > L.bg_rom_max_r() or n_in > L.bg_rom_max_n():

@@ -264,6 +264,33 @@ int bg_rom_run_wide(int N, int B, int r, int nsteps, int projection, const doubl
                     int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
                     const int32_t *order, void *stream);
 
+/* bg_rom_run_blocked -- bg_rom_run_wide for the thesis' finest bases, r <= 256 (bg_rom_run_blocked_max_r), N <= 512
+ *   reference: FEM/fem_burgers.py:709-785 with POD/modes/U_modes_tol_1e-05.npy (r = 160) and _1e-06.npy (r = 227).
+ *   Opt-in: the facade routes r > bg_rom_run_wide_max_r() here only when asked (burgers_hip/rom.py, blocked=True).
+ *   Same arguments, outputs and semantics as bg_rom_run_wide except:
+ *   PhiP   [NPAD + 2][RP], NPAD = N rounded up to 8, RP = r rounded up to 16 (bg_rom_run_blocked_phi_elems(N, r) doubles):
+ *          Phi row i at row index i + 1, zero rows around and beyond the mesh, zero columns beyond r;
+ *   work   `slots` slots of bg_rom_run_blocked_work_elems(N, r) doubles, one per workgroup (contents need no
+ *          initialisation and are garbage afterwards).  A slot holds the padded reduced system [RP][RP + 16]: Ar, then
+ *          -br and 15 zero columns; the blocked elimination runs in place there.  Workgroup k of G = min(B, slots)
+ *          takes the slots k, k + G, ... of `order` and only ever touches slot k of `work`.
+ *   order  [B] or NULL; entries outside [0, B) are skipped.
+ *   info   0; k + 1 when the pivot of column k is exactly zero together with the rest of its column (LAPACK's info);
+ *          BG_INFO_NEEDS_PIVOTING for a sample whose pivot-free elimination met a multiplier above 1 below the diagonal
+ *          (np.linalg.solve would have exchanged rows): the caller redoes it with a pivoting solve.
+ *   Errors: N < 3, r < 1, B or nsteps < 0, max_it < 1, dt <= 0 or a null operand with B > 0: BG_ERR_BAD_ARG;
+ *   N > 512: BG_ERR_UNSUPPORTED_N; r > 256: BG_ERR_UNSUPPORTED_R; work NULL or slots < 1 with B > 0: BG_ERR_WORKSPACE;
+ *   an unknown projection: BG_ERR_PROJECTION; B = 0: BG_OK with nothing launched.
+ *   One workgroup of four waves per slot, 16x16x4 fp64 matrix instructions for the projection and the elimination
+ *   (csrc/rom_blocked.hip).  options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED (every sample handed back). */
+int bg_rom_run_blocked_max_r(void);
+long long bg_rom_run_blocked_phi_elems(int N, int r);
+long long bg_rom_run_blocked_work_elems(int N, int r);
+int bg_rom_run_blocked(int N, int B, int r, int nsteps, int projection, const double *x, const double *PhiP,
+                       const double *u0, const double *mu1, const double *mu2, double dt, double E, double tol,
+                       int max_it, int options, double *work, int slots, double *hist, int32_t *iters,
+                       int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
 /* =================================================================================
  * bg_fd_run -- batched replacement of FDBurgers.fom_burgers_newton (analytical Jacobian)
  *   reference: FD/fd_burgers.py:59-107 (time + Newton loops), residual :28-35, Jacobian :37-44,
