@@ -99,6 +99,12 @@ _SIGNATURES = {
     "bg_rom_run_blocked": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 5 + [ctypes.c_double] * 3 +
                            [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p,
                             c_int_p, ctypes.c_void_p]),
+    "bg_rom_run_long_max_n": (ctypes.c_int, []),
+    "bg_rom_run_long_max_r": (ctypes.c_int, []),
+    "bg_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
+    "bg_rom_run_long_phi_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "bg_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 5 + [ctypes.c_double] * 3 +
+                        [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
     "bg_rom_lift": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                    c_int_p, c_double_p, ctypes.c_void_p]),
     "bg_quad_features": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_double_p, ctypes.c_void_p]),

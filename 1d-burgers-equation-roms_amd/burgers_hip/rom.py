@@ -427,6 +427,49 @@ def pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, 
     return res
 
 
+class LongPodPlan:
+    """The operand bg_rom_run_long reads, built once per basis on the device (include/burgers_hip.h): the padded copy
+    PhiP [NPAD + 2][40] of ``Phi`` (row i at index i + 1, NPAD = N rounded up to 64, zero rows and columns around it)."""
+
+    def __init__(self, Phi, device):
+        L = _lib.load()
+        shape = tuple(np.shape(Phi))
+        if len(shape) != 2:
+            raise ValueError("Phi must be (N, r)")
+        N, r = shape
+        if r < 1 or r > L.bg_rom_run_long_max_r():
+            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {L.bg_rom_run_long_max_r()}")
+        if N < 3 or N > L.bg_rom_run_long_max_n():
+            raise ValueError(f"bg_rom_run_long covers 3 <= N <= {L.bg_rom_run_long_max_n()}, not N = {N}")
+        device = _lib.require_device(device)
+        self.Phi = _as_dev(Phi, device)
+        self.N, self.r = N, r
+        elems = L.bg_rom_run_long_phi_elems(N, r)
+        self.PhiP = torch.zeros(((N + 63) // 64 * 64 + 2, 40), dtype=torch.float64, device=self.Phi.device)
+        if self.PhiP.numel() != elems:
+            raise ValueError(f"bg_rom_run_long does not cover N = {N}, r = {r}")
+        self.PhiP[1:N + 1, :r] = self.Phi
+
+
+def pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0,
+                      balance=True):
+    """``pod_prom_burgers`` for meshes of up to bg_rom_run_long_max_n() = 1024 nodes and bases of up to 40 modes with the
+    whole time loop on the device (bg_rom_run_long): the basis streams through LDS, the pivoting repair runs inside the
+    call, nothing is synchronised.  ``Phi_or_plan``: the basis, or a LongPodPlan of it to reuse across calls (``res.plan``)."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    plan = Phi_or_plan if isinstance(Phi_or_plan, LongPodPlan) else LongPodPlan(Phi_or_plan, device)
+    if plan.N != len(Xh) or plan.Phi.device != device:
+        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
+    grid = _lib.load().bg_rom_run_long_workgroups_per_cu() * _cu_count(device)
+    res = _device_loop("bg_rom_run_long", Xh, u0, mu1, mu2, nsteps, device, True, options, grid, 1, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
+                           float(tol), int(max_it), opts, *outputs), keep=(plan,))
+    res.plan = plan
+    return res
+
+
 def check_singular(res):
     """np.linalg.solve raises LinAlgError('Singular matrix') at :767; the device loop records it per sample."""
     info = getattr(res, "info", None)
@@ -436,17 +479,21 @@ def check_singular(res):
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
-                 device=None, fused=True, blocked=False):
+                 device=None, fused=True, blocked=False, long_mesh=False):
     """Batched ``pod_prom_burgers``; ``projection`` is case-sensitive like the reference (:754-764).
     ``fused`` (default): the device-side time loop bg_rom_run where it applies (N <= 512, r <= 40); otherwise, or
     with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host.
     ``blocked`` (opt-in, with ``fused``): bases of bg_rom_run_wide_max_r() < r <= bg_rom_run_blocked_max_r() on
-    N <= 512 take the device-side loop bg_rom_run_blocked instead of the library path."""
+    N <= 512 take the device-side loop bg_rom_run_blocked instead of the library path.
+    ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_max_n() with r <= bg_rom_run_long_max_r()
+    take the device-side loop bg_rom_run_long instead of the library path."""
     if projection not in ("Galerkin", "LSPG"):
         raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
     proj = PROJ[projection.lower()]
     L = _lib.load()
     r_in, n_in = np.shape(Phi)[1], np.shape(Phi)[0]
+    if long_mesh and fused and 512 < n_in <= L.bg_rom_run_long_max_n() and r_in <= L.bg_rom_run_long_max_r():
+        return check_singular(pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     if blocked and fused and L.bg_rom_run_wide_max_r() < r_in <= L.bg_rom_run_blocked_max_r() and n_in <= 512:
         return check_singular(pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     if fused and L.bg_rom_run_max_r() < r_in <= L.bg_rom_run_wide_max_r() and n_in <= 512:

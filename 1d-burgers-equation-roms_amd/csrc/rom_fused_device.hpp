@@ -329,16 +329,11 @@ __device__ __forceinline__ double red_sum(const double (*__restrict__ s_red)[RW]
     else return s_red[0][rr][cc] + s_red[1][rr][cc];
 }
 
-template <int NB, bool GAL, int NRED = 4>
-__device__ __forceinline__ void pivoted_solve(const double (*__restrict__ s_red)[4 * NB][4 * NB + 4],
-                                              double* __restrict__ s_x, int* __restrict__ s_info, int lane, int r)
+// `entry(i, j)`: (Ar | br)[i][j], j <= RW, wherever the caller keeps the system (rom_long.hip parks it whole)
+template <int NB, class Entry>
+__device__ __forceinline__ void pivoted_solve_of(const Entry& entry, double* __restrict__ s_x, int* __restrict__ s_info, int lane, int r)
 {
     constexpr int RW = 4 * NB;
-    auto entry = [&](int i, int j) -> double {
-        int rr = i, cc = j;
-        if (!GAL && j < RW && (i >> 2) > (j >> 2)) { rr = j; cc = i; }
-        return red_sum<NRED, RW>(s_red, rr, cc);
-    };
     double row[RW + 1];
 #pragma unroll
     for (int j = 0; j < RW; ++j) row[j] = (lane < r && j < r) ? entry(lane, j) : ((lane == j) ? 1.0 : 0.0);
@@ -349,26 +344,34 @@ __device__ __forceinline__ void pivoted_solve(const double (*__restrict__ s_red)
     if (lane == 0) *s_info = info;
 }
 
+template <int NB, bool GAL, int NRED = 4>
+__device__ __forceinline__ void pivoted_solve(const double (*__restrict__ s_red)[4 * NB][4 * NB + 4],
+                                              double* __restrict__ s_x, int* __restrict__ s_info, int lane, int r)
+{
+    constexpr int RW = 4 * NB;
+    auto entry = [&](int i, int j) -> double {
+        int rr = i, cc = j;
+        if (!GAL && j < RW && (i >> 2) > (j >> 2)) { rr = j; cc = i; }
+        return red_sum<NRED, RW>(s_red, rr, cc);
+    };
+    pivoted_solve_of<NB>(entry, s_x, s_info, lane, r);
+}
+
 // ---- the reduced solve of one iteration by all four waves (see rom_fused.hip's header) ---------------------------
 // In: the four per-wave partial systems s_red (+ mirror for LSPG); r = live unknowns (the rest is identity padding).
 // Out: x_k in lane k of EVERY wave (identical values); tripped = a multiplier above 1 or a zero pivot was seen (then x is
 // not to be used).  Contains workgroup barriers: all 256 threads call it.  ELIM = false compiles the panels out (timing).
-template <int NB, bool GAL, bool ELIM = true, int NRED = 4>
-__device__ __forceinline__ double coop_gj_solve(const double (*__restrict__ s_red)[4 * NB][4 * NB + 4],
-                                                double (*__restrict__ s_m)[4][64], double* __restrict__ s_diag,
-                                                double* __restrict__ s_y, int* __restrict__ s_bad, int w, int lane, int r,
-                                                bool& tripped)
+// coop_gj_solve_of: the same with the system behind `entry(i, j)` = (Ar | br)[i][j], j <= RW (rom_long.hip parks it whole).
+template <int NB, bool ELIM = true, class Entry>
+__device__ __forceinline__ double coop_gj_solve_of(const Entry& entry, double (*__restrict__ s_m)[4][64], double* __restrict__ s_diag,
+                                                   double* __restrict__ s_y, int* __restrict__ s_bad, int w, int lane, int r,
+                                                   bool& tripped)
 {
     constexpr int RW = 4 * NB;
     constexpr int NSLOT = LuRegs<NB>::NSLOT;
     // `lane` is made opaque here: the per-lane LDS addresses and mirror selects of the load below are loop invariants, and
     // left to itself the optimiser hoists them out of the time loop and keeps (or spills) two dozen registers for them
     asm volatile("" : "+v"(lane));
-    auto entry = [&](int i, int j) -> double {               // (Ar | br)[i][j], j <= RW
-        int rr = i, cc = j;
-        if (!GAL && j < RW && (i >> 2) > (j >> 2)) { rr = j; cc = i; }   // LSPG: mirror the lower blocks
-        return red_sum<NRED, RW>(s_red, rr, cc);
-    };
     LuRegs<NB> lu;
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) {
@@ -432,6 +435,21 @@ __device__ __forceinline__ double coop_gj_solve(const double (*__restrict__ s_re
     __syncthreads();
     tripped = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) != 0;                  // workgroup-uniform
     return (lane < RW) ? s_y[lane] * rcp(s_diag[lane]) : 0.0;
+}
+
+template <int NB, bool GAL, bool ELIM = true, int NRED = 4>
+__device__ __forceinline__ double coop_gj_solve(const double (*__restrict__ s_red)[4 * NB][4 * NB + 4],
+                                                double (*__restrict__ s_m)[4][64], double* __restrict__ s_diag,
+                                                double* __restrict__ s_y, int* __restrict__ s_bad, int w, int lane, int r,
+                                                bool& tripped)
+{
+    constexpr int RW = 4 * NB;
+    auto entry = [&](int i, int j) -> double {               // (Ar | br)[i][j], j <= RW
+        int rr = i, cc = j;
+        if (!GAL && j < RW && (i >> 2) > (j >> 2)) { rr = j; cc = i; }   // LSPG: mirror the lower blocks
+        return red_sum<NRED, RW>(s_red, rr, cc);
+    };
+    return coop_gj_solve_of<NB, ELIM>(entry, s_m, s_diag, s_y, s_bad, w, lane, r, tripped);
 }
 
 }  // namespace fused

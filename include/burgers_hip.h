@@ -291,6 +291,33 @@ int bg_rom_run_blocked(int N, int B, int r, int nsteps, int projection, const do
                        int max_it, int options, double *work, int slots, double *hist, int32_t *iters,
                        int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_rom_run_long -- bg_rom_run for long meshes: 3 <= N <= 1024 (bg_rom_run_long_max_n; meant for N > 512, where bg_rom_run
+ *   ends), r <= 40 (bg_rom_run_long_max_r).  reference: FEM/fem_burgers.py:709-785.
+ *   Opt-in: the facade routes N > 512 here only when asked (burgers_hip/rom.py, long_mesh=True).
+ *   Same arguments, outputs and semantics as bg_rom_run except:
+ *   PhiP   [NPAD + 2][40], NPAD = N rounded up to 64 (bg_rom_run_long_phi_elems(N, r) doubles, 16-byte aligned; 0 for an
+ *          N or r the kernel does not cover): Phi row i at row index i + 1, zero rows around and beyond the mesh, zero
+ *          columns beyond r -- built once per basis by the caller;
+ *   order  [B] or NULL; entries outside [0, B) are skipped.
+ *   info   0, or k + 1 when the reduced matrix of a sample is exactly singular at elimination step k.  Pivoting is repaired
+ *          inside the call as in bg_rom_run: a sample whose pivot-free elimination meets a multiplier above 1 below the
+ *          diagonal or a zero pivot is marked BG_INFO_NEEDS_PIVOTING by the first kernel and redone from u0 by a second
+ *          kernel of the same call with the pivot search of bg_lu_solve, so the caller never sees that value.
+ *   Errors: N < 3, r < 1, B or nsteps < 0, max_it < 1, dt <= 0, a null operand or output with B > 0, PhiP not 16-byte
+ *   aligned: BG_ERR_BAD_ARG; N > 1024: BG_ERR_UNSUPPORTED_N; r > 40: BG_ERR_UNSUPPORTED_R; an unknown projection:
+ *   BG_ERR_PROJECTION; B = 0: BG_OK with nothing launched.
+ *   The basis streams through LDS 64 mesh rows at a time, the accumulators of the reduced system are dealt to the four
+ *   waves (csrc/rom_long.hip); workgroup k of G = min(B, bg_rom_run_long_workgroups_per_cu() CUs) takes the slots k, k + G, ...
+ *   options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED (tests: every sample through the second kernel). */
+int bg_rom_run_long_max_n(void);
+int bg_rom_run_long_max_r(void);
+int bg_rom_run_long_workgroups_per_cu(void);
+long long bg_rom_run_long_phi_elems(int N, int r);
+int bg_rom_run_long(int N, int B, int r, int nsteps, int projection, const double *x, const double *PhiP,
+                    const double *u0, const double *mu1, const double *mu2, double dt, double E, double tol,
+                    int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
+                    const int32_t *order, void *stream);
+
 /* =================================================================================
  * bg_fd_run -- batched replacement of FDBurgers.fom_burgers_newton (analytical Jacobian)
  *   reference: FD/fd_burgers.py:59-107 (time + Newton loops), residual :28-35, Jacobian :37-44,
