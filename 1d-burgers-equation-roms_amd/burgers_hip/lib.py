@@ -88,6 +88,14 @@ _SIGNATURES = {
                                        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p,
                                        c_int_p, ctypes.c_void_p]),
+    "bg_quad_rom_run_long_max_n": (ctypes.c_int, []),
+    "bg_quad_rom_run_long_max_r": (ctypes.c_int, []),
+    "bg_quad_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
+    "bg_quad_rom_run_long_phit_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_quad_rom_run_long_phif_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_quad_rom_run_long_h3f_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_quad_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 7 + [ctypes.c_double] * 3 +
+                             [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
     "bg_rom_run_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_rom_run_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,

@@ -250,8 +250,8 @@ def _workspace(c, r):
 
 # --------------------------------------------------------------------------- POD
 def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, group, balance, launch, keep=()):
-    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_ann_rom_run, bg_rbf_rom_run,
-    bg_local_rom_run) share: the batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
+    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_quad_rom_run_long, bg_ann_rom_run,
+    bg_rbf_rom_run, bg_local_rom_run) share: the batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
     FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
     entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
     flags, info, order, stream.  Nothing is synchronised: ``res.info`` is checked lazily by the caller, and the operands
@@ -621,6 +621,31 @@ def quad_tangent_tensor(Phid, Hd):
     return (Hd[:, idx] * fac).contiguous()
 
 
+def _quad_operand_copies(Phid, Hd):
+    """PhiT, Phif, H3f of bg_quad_rom_run and bg_quad_rom_run_long (layouts: include/burgers_hip.h) from Phi (N, n) and
+    H (N, n(n+1)/2) on the device, n <= 40."""
+    device = Phid.device
+    N, n = Phid.shape
+    f64 = dict(dtype=torch.float64, device=device)
+    NG, NPAD = (N + 3) // 4, (N + 63) // 64 * 64
+    PhiT = torch.zeros((40, NPAD), **f64)
+    PhiT[:n, :N] = Phid.t()
+    Pp = torch.zeros((4 * NG, 40), **f64)
+    Pp[:N, :n] = Phid
+    # accumulator seeds of the tangent tiles: (rg, blk, c, i) -> [rg][c][4 i + blk]
+    Phif = Pp.reshape(NG, 4, 10, 4).permute(0, 2, 3, 1).contiguous()
+    H3p = torch.zeros((4 * NG, 40, 40), **f64)
+    H3p[:N, :n, :n] = quad_tangent_tensor(Phid, Hd)
+    # H3 of a mesh row is symmetric: only its upper 4 x 4 blocks (a <= b, row-major) travel.  Block (a, b), lane 16 k + 4 blk + i
+    # = H3[4 rg + blk][4 a + i][4 b + k]; two blocks per 16-byte slot: [rg][slot (28)][lane][2] (block 55 = zero padding)
+    Hb = H3p.reshape(NG, 4, 10, 4, 10, 4).permute(0, 2, 4, 5, 1, 3)           # (rg, a, b, k, blk, i)
+    A_, B_ = np.triu_indices(10)
+    Hu = Hb[:, torch.as_tensor(A_, device=device), torch.as_tensor(B_, device=device)].reshape(NG, 55, 64)
+    Hu = torch.cat([Hu, torch.zeros((NG, 1, 64), **f64)], 1)
+    H3f = Hu.reshape(NG, 28, 2, 64).permute(0, 1, 3, 2).contiguous()
+    return PhiT, Phif, H3f
+
+
 class QuadFusedPlan:
     """The operand copies bg_quad_rom_run reads, built once per (Phi, H) on the device (include/burgers_hip.h):
     Phi^T zero padded, the accumulator seeds of the tangent tiles, and H3 in the A-operand order of the matrix
@@ -636,23 +661,7 @@ class QuadFusedPlan:
         self.ok = N <= 512 and n <= L.bg_quad_rom_max_n()
         if not self.ok:
             return
-        f64 = dict(dtype=torch.float64, device=device)
-        NG, NPAD = (N + 3) // 4, (N + 63) // 64 * 64
-        self.PhiT = torch.zeros((40, NPAD), **f64)
-        self.PhiT[:n, :N] = self.Phi.t()
-        Pp = torch.zeros((4 * NG, 40), **f64)
-        Pp[:N, :n] = self.Phi
-        # accumulator seeds of the tangent tiles: (rg, blk, c, i) -> [rg][c][4 i + blk]
-        self.Phif = Pp.reshape(NG, 4, 10, 4).permute(0, 2, 3, 1).contiguous()
-        H3p = torch.zeros((4 * NG, 40, 40), **f64)
-        H3p[:N, :n, :n] = quad_tangent_tensor(self.Phi, self.H)
-        # H3 of a mesh row is symmetric: only its upper 4 x 4 blocks (a <= b, row-major) travel.  Block (a, b), lane 16 k + 4 blk + i
-        # = H3[4 rg + blk][4 a + i][4 b + k]; two blocks per 16-byte slot: [rg][slot (28)][lane][2] (block 55 = zero padding)
-        Hb = H3p.reshape(NG, 4, 10, 4, 10, 4).permute(0, 2, 4, 5, 1, 3)           # (rg, a, b, k, blk, i)
-        A_, B_ = np.triu_indices(10)
-        Hu = Hb[:, torch.as_tensor(A_, device=device), torch.as_tensor(B_, device=device)].reshape(NG, 55, 64)
-        Hu = torch.cat([Hu, torch.zeros((NG, 1, 64), **f64)], 1)
-        self.H3f = Hu.reshape(NG, 28, 2, 64).permute(0, 1, 3, 2).contiguous()
+        self.PhiT, self.Phif, self.H3f = _quad_operand_copies(self.Phi, self.H)
         assert self.H3f.numel() == L.bg_quad_rom_h3f_elems(N) and self.Phif.numel() == L.bg_quad_rom_phif_elems(N)
 
 
@@ -671,16 +680,73 @@ def quadratic_run_fused(X, u0, mu1, mu2, dt, nsteps, plan, proj, E=0.0, newton_t
                             *outputs), keep=(plan,))
 
 
+class QuadLongPlan:
+    """The operand copies bg_quad_rom_run_long reads, built once per (Phi, H) on the device (include/burgers_hip.h; the
+    layouts of QuadFusedPlan).  Covers 512 < N <= bg_quad_rom_run_long_max_n() and n <= bg_quad_rom_run_long_max_r();
+    anything else raises ValueError."""
+
+    def __init__(self, Phi, H, device):
+        L = _lib.load()
+        shape, hshape = tuple(np.shape(Phi)), tuple(np.shape(H))
+        if len(shape) != 2:
+            raise ValueError("Phi must be (N, n)")
+        N, n = shape
+        if n < 1 or n > L.bg_quad_rom_run_long_max_r():
+            raise ValueError(f"Phi must be (N, n) with 1 <= n <= {L.bg_quad_rom_run_long_max_r()}")
+        if N <= 512 or N > L.bg_quad_rom_run_long_max_n():
+            raise ValueError(f"bg_quad_rom_run_long covers 512 < N <= {L.bg_quad_rom_run_long_max_n()}, not N = {N}")
+        if hshape != (N, n * (n + 1) // 2):
+            raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
+        device = _lib.require_device(device)
+        self.Phi, self.H = _as_dev(Phi, device), _as_dev(np.ascontiguousarray(H) if isinstance(H, np.ndarray) else H, device)
+        self.N, self.n = N, n
+        self.PhiT, self.Phif, self.H3f = _quad_operand_copies(self.Phi, self.H)
+        if (self.PhiT.numel(), self.Phif.numel(), self.H3f.numel()) != (
+                L.bg_quad_rom_run_long_phit_elems(N), L.bg_quad_rom_run_long_phif_elems(N), L.bg_quad_rom_run_long_h3f_elems(N)):
+            raise ValueError(f"bg_quad_rom_run_long does not cover N = {N}, n = {n}")
+
+
+def quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_H_or_plan, proj, E=0.0, newton_tol=1e-6, newton_itmax=25,
+                       device=None, balance=True):
+    """``pod_quadratic_manifold`` for meshes of 513 .. bg_quad_rom_run_long_max_n() = 1024 nodes and n <= 40 with the
+    whole time loop on the device (bg_quad_rom_run_long): four samples per workgroup, nothing is synchronised.
+    ``Phi_H_or_plan``: the pair (Phi, H), or a QuadLongPlan of it to reuse across calls (``res.plan``)."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    plan = Phi_H_or_plan if isinstance(Phi_H_or_plan, QuadLongPlan) else QuadLongPlan(*Phi_H_or_plan, device)
+    if plan.N != len(Xh) or plan.Phi.device != device:
+        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
+    grid = _lib.load().bg_quad_rom_run_long_workgroups_per_cu() * _cu_count(device)
+    res = _device_loop("bg_quad_rom_run_long", Xh, u0, mu1, mu2, nsteps, device, False, 0, grid, 4, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.n, int(nsteps), proj, x, _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif),
+                           _lib.ptr(plan.H3f), *inputs, float(dt), float(E), float(newton_tol), int(newton_itmax), opts,
+                           *outputs), keep=(plan,))
+    res.plan = plan
+    return res
+
+
 def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0, newton_tol=1e-6,
-                  newton_itmax=25, device=None, fused=True, plan=None):
+                  newton_itmax=25, device=None, fused=True, plan=None, long_mesh=False):
     """Batched ``pod_quadratic_manifold`` (no SUPG term in this variant, :1142).  ``fused`` (default): the device-side
     time loop bg_quad_rom_run where it applies (N <= 512, n <= 40); otherwise, or with ``fused=False``, the batched
     iteration (bg_quad_tangent -> bg_rom_reduce_frag -> bg_lu_solve_update -> decode GEMM) driven from the host.
-    ``plan``: a QuadFusedPlan of (Phi, H) to reuse across calls."""
+    ``plan``: a QuadFusedPlan of (Phi, H) to reuse across calls.
+    ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_quad_rom_run_long_max_n() with n <=
+    bg_quad_rom_run_long_max_r() take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration
+    (``plan`` may then be a QuadLongPlan)."""
     p = projection.lower()
     if p not in PROJ:
         raise ValueError("projection must be 'Galerkin' or 'LSPG'")
     proj = PROJ[p]
+    if long_mesh and fused:
+        L = _lib.load()
+        n_in, r_in = np.shape(Phi)[0], np.shape(Phi)[1]
+        if 512 < n_in <= L.bg_quad_rom_run_long_max_n() and r_in <= L.bg_quad_rom_run_long_max_r():
+            what = plan if isinstance(plan, QuadLongPlan) else (Phi, H)
+            return check_singular(quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, what, proj, E, newton_tol, newton_itmax, device))
+    if isinstance(plan, QuadLongPlan):
+        plan = None
     if fused:
         dev = _lib.require_device(device)
         if plan is None:

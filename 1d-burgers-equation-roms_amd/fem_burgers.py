@@ -110,12 +110,14 @@ class FEMBurgers:
 
     # ---------------------------------------------------------------- quadratic manifold
     def pod_quadratic_manifold(self, At, nTimeSteps, u0, uxa, E, mu2, Phi, H, projection="LSPG",
-                               newton_tol=1e-6, newton_itmax=25):
-        """Quadratic-manifold PROM (reference :1081-1175); ``uxa`` is the left Dirichlet value."""
+                               newton_tol=1e-6, newton_itmax=25, long_mesh=False):
+        """Quadratic-manifold PROM (reference :1081-1175); ``uxa`` is the left Dirichlet value.  ``long_mesh``: meshes of
+        513 .. 1024 nodes with n <= 40 take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration."""
         batched = self._batched(uxa, mu2, u0)
         res = _rom.quadratic_run(self.X, np.asarray(u0, dtype=np.float64), uxa, mu2, At, int(nTimeSteps),
                                  np.asarray(Phi, dtype=np.float64), np.asarray(H, dtype=np.float64),
-                                 projection=projection, E=E, newton_tol=newton_tol, newton_itmax=newton_itmax)
+                                 projection=projection, E=E, newton_tol=newton_tol, newton_itmax=newton_itmax,
+                                 long_mesh=long_mesh)
         if self.verbose and (res.flags != 0).any():
             print("  Warning: Newton did not converge")
         return self._finish(res, batched)

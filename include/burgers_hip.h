@@ -392,6 +392,36 @@ int bg_quad_rom_run(int N, int B, int n, int nsteps, int projection, const doubl
                     int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * bg_quad_rom_run_long -- bg_quad_rom_run for meshes of 513 <= N <= bg_quad_rom_run_long_max_n() (1024) nodes,
+ *   n <= bg_quad_rom_run_long_max_r() (40) (csrc/quad_long.hip).  Same argument list, operand meaning, mathematics and
+ *   outputs as bg_quad_rom_run; the per-node arrays g = M u^n + dt F and dt F live in the registers of the wave that
+ *   owns the sample instead of LDS.  N <= 512 is REFUSED with BG_ERR_UNSUPPORTED_N (bg_quad_rom_run covers it), as is
+ *   N > 1024.  Operand copies, built once per basis by the caller (zero padded; the layouts of bg_quad_rom_run):
+ *     PhiT [40][NPAD]               Phi^T, NPAD = N rounded up to 64; 16-byte aligned
+ *     Phif [NG][10][16]             Phi[4 rg + blk][4 c + i] at [rg][c][4 i + blk], NG = ceil(N / 4)
+ *     H3f  [NG][28][64][2]          the upper 4 x 4 blocks of the symmetric tangent tensor in A-operand order, exactly as
+ *                                   documented for bg_quad_rom_run; 16-byte aligned
+ *     sizes: bg_quad_rom_run_long_phit_elems(N), _phif_elems(N), _h3f_elems(N) doubles (0 for an N that is not covered).
+ *   order: wave w of workgroup slot g works on sample order[4 g + w]; entries outside [0, B) are skipped (their rows of
+ *   hist, iters, flags, info are not written).  A sample's result does not depend on the samples that share its
+ *   workgroup or launch.  The launch uses min(ceil(B / 4), CUs * bg_quad_rom_run_long_workgroups_per_cu()) workgroups.
+ *   Checked before any launch: N < 3, B < 0, n < 1, nsteps < 0, max_it < 1, dt <= 0: BG_ERR_BAD_ARG; an unknown
+ *   projection: BG_ERR_PROJECTION; N outside 513 .. 1024: BG_ERR_UNSUPPORTED_N; n > 40: BG_ERR_UNSUPPORTED_R; B = 0: BG_OK
+ *   (pointers may be null); a null operand or output with B > 0, or a misaligned PhiT / H3f: BG_ERR_BAD_ARG.
+ *   options: BG_OPT_NONUNIFORM.
+ * --------------------------------------------------------------------------------- */
+int bg_quad_rom_run_long_max_n(void);
+int bg_quad_rom_run_long_max_r(void);
+int bg_quad_rom_run_long_workgroups_per_cu(void);
+long long bg_quad_rom_run_long_phit_elems(int N);
+long long bg_quad_rom_run_long_phif_elems(int N);
+long long bg_quad_rom_run_long_h3f_elems(int N);
+int bg_quad_rom_run_long(int N, int B, int n, int nsteps, int projection, const double *x, const double *PhiT,
+                         const double *Phif, const double *H3f, const double *u0, const double *mu1, const double *mu2,
+                         double dt, double E, double tol, int max_it, int options, double *hist, int32_t *iters,
+                         int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * bg_ann_rom_run -- batched replacement of FEMBurgers.pod_ann_prom, the WHOLE time loop on the device
  *   reference: FEM/fem_burgers.py:1177-1251 (loop), compute_ann_jacobian :1254-1275, model POD-ANN/pod_ann.py:38-56.
  *   One workgroup owns one sample for all time steps and Gauss-Newton iterations: assembly, fp64-MFMA projection of the
