@@ -1,6 +1,6 @@
-// rom_device.hpp -- device pieces shared by the batched ROM kernels (rom.hip) and the fused ROM
-// time-stepper (rom_fused.hip): one row of the Picard assembly, and the pivoted r x r solve of one
-// wavefront.  reference: FEM/fem_burgers.py:730-776 (pod_prom_burgers inner body).
+// rom_device.hpp -- device pieces shared by the batched ROM kernels (rom.hip) and the device-side ROM
+// time loops (rom_*.hip, quad_device.hpp): one row of the Picard assembly, the nodal forcing loads of
+// one mesh node, and the pivoted r x r solve of one wavefront.  reference: FEM/fem_burgers.py:730-776 (pod_prom_burgers inner body).
 #pragma once
 #include "fom_device.hpp"
 
@@ -50,6 +50,31 @@ __device__ __forceinline__ void rom_assemble_row(int i, int N, double um, double
         }
     }
     R = -rhs;
+}
+
+// Nodal loads of the forcing term at node i < N of one sample (compute_forcing_vector :427-461, f_gp of :556-558):
+// frPrev = right-node load of the element (i-1, i), fl = left-node load of the element (i, i+1), hf = h_e (f(gp1) + f(gp2))
+// of the element (i, i+1); each 0 where the mesh has no such element.  F_i = frPrev + fl; the time loops keep dt F and,
+// where the assembly has the SUPG term, hf.
+__device__ __forceinline__ void rom_nodal_forcing(const double* x, int i, int N, double mu2, double h, int nonuniform,
+                                                  double& frPrev, double& fl, double& hf)
+{
+    frPrev = 0.0; fl = 0.0; hf = 0.0;
+    if (i > 0) {
+        const double xl = x[i - 1], xr = x[i];
+        const double he = nonuniform ? xr - xl : h;
+        const double f1 = 0.02 * exp(mu2 * (GP_A * xl + GP_B * xr));
+        const double f2 = 0.02 * exp(mu2 * (GP_B * xl + GP_A * xr));
+        frPrev = (f1 * GP_B + f2 * GP_A) * (0.5 * he);
+    }
+    if (i < N - 1) {
+        const double xl = x[i], xr = x[i + 1];
+        const double he = nonuniform ? xr - xl : h;
+        const double f1 = 0.02 * exp(mu2 * (GP_A * xl + GP_B * xr));
+        const double f2 = 0.02 * exp(mu2 * (GP_B * xl + GP_A * xr));
+        fl = (f1 * GP_A + f2 * GP_B) * (0.5 * he);
+        hf = he * (f1 + f2);
+    }
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int srclane)

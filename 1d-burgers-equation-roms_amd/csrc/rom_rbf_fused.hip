@@ -167,21 +167,7 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
             const int i = tid + 256 * ii;
             double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
             if (i < N) {
-                if (i > 0) {
-                    const double xl = a.x[i - 1], xr = a.x[i];
-                    const double he = a.nonuniform ? xr - xl : h;
-                    const double f1 = 0.02 * exp(mu2 * (GP_A * xl + GP_B * xr));
-                    const double f2 = 0.02 * exp(mu2 * (GP_B * xl + GP_A * xr));
-                    frPrev = (f1 * GP_B + f2 * GP_A) * (0.5 * he);
-                }
-                if (i < N - 1) {
-                    const double xl = a.x[i], xr = a.x[i + 1];
-                    const double he = a.nonuniform ? xr - xl : h;
-                    const double f1 = 0.02 * exp(mu2 * (GP_A * xl + GP_B * xr));
-                    const double f2 = 0.02 * exp(mu2 * (GP_B * xl + GP_A * xr));
-                    fl = (f1 * GP_A + f2 * GP_B) * (0.5 * he);
-                    hf = he * (f1 + f2);
-                }
+                rom_nodal_forcing(a.x, i, N, mu2, h, a.nonuniform, frPrev, fl, hf);
                 u = a.u0[(size_t)smp * N + i];
                 hist[i] = u;
             }
