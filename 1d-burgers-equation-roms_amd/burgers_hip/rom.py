@@ -322,6 +322,28 @@ def _cu_count(device):
     return torch.cuda.get_device_properties(device).multi_processor_count
 
 
+def _padded_basis(Phi, N, r, row_multiple, cols):
+    """The padded copy of the device basis ``Phi`` the streaming POD loops read: Phi at row offset 1 in a zero matrix of
+    (N rounded up to ``row_multiple``) + 2 rows by ``cols`` columns."""
+    NPAD = (N + row_multiple - 1) // row_multiple * row_multiple
+    PhiP = torch.zeros((NPAD + 2, cols), dtype=torch.float64, device=Phi.device)
+    PhiP[1:N + 1, :r] = Phi
+    return PhiP
+
+
+def _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device):
+    """Redo the samples a device loop marked BG_INFO_NEEDS_PIVOTING (np.linalg.solve would have exchanged rows: rare)
+    through the library path, LU with partial pivoting.  Reads ``info`` back, so it synchronises the host."""
+    _, u0d, mu1d, mu2d = res._keep[:4]
+    redo = (res.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
+    if redo.numel():
+        rr = _pod_prom_run_library(Xh, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, plan.Phi, proj, E, tol, max_it, device)
+        res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
+        res.info[redo] = 0
+    res.redone = int(redo.numel())
+    res.plan = plan
+
+
 class WidePodPlan:
     """The operand bg_rom_run_wide reads, built once per basis on the device (include/burgers_hip.h): the padded copy
     PhiP [NPAD + 2][96] of ``Phi`` (row i at index i + 1, zero rows and columns around it), kept together with the basis
@@ -333,9 +355,7 @@ class WidePodPlan:
         if self.Phi.dim() != 2 or self.Phi.shape[1] > L.bg_rom_run_wide_max_r():
             raise ValueError(f"Phi must be (N, r) with r <= {L.bg_rom_run_wide_max_r()}")
         self.N, self.r = self.Phi.shape
-        NPAD = (self.N + 63) // 64 * 64
-        self.PhiP = torch.zeros((NPAD + 2, 96), dtype=torch.float64, device=self.Phi.device)
-        self.PhiP[1:self.N + 1, :self.r] = self.Phi
+        self.PhiP = _padded_basis(self.Phi, self.N, self.r, 64, 96)
         if self.PhiP.numel() != L.bg_rom_run_wide_phi_elems(self.N):
             raise ValueError(f"bg_rom_run_wide does not cover N = {self.N}")
 
@@ -357,14 +377,7 @@ def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, m
                        lambda f, N, B, x, inputs, opts, outputs: f(
                            N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
                            float(tol), int(max_it), opts, *outputs), keep=(plan,))
-    _, u0d, mu1d, mu2d = res._keep[:4]
-    redo = (res.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
-    if redo.numel():                                     # rare: np.linalg.solve would have exchanged rows
-        rr = _pod_prom_run_library(Xh, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, plan.Phi, proj, E, tol, max_it, device)
-        res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
-        res.info[redo] = 0
-    res.redone = int(redo.numel())
-    res.plan = plan
+    _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device)
     res.PhiP = plan.PhiP                                 # the padded copy the kernel read (what wide results carried before)
     return res
 
@@ -391,10 +404,7 @@ class BlockedPodPlan:
         self.slots = int(slots) if slots is not None else _cu_count(device)
         if self.slots < 1:
             raise ValueError("slots must be positive")
-        RP = (r + 15) // 16 * 16
-        NPAD = (N + 7) // 8 * 8
-        self.PhiP = torch.zeros((NPAD + 2, RP), dtype=torch.float64, device=self.Phi.device)
-        self.PhiP[1:N + 1, :r] = self.Phi
+        self.PhiP = _padded_basis(self.Phi, N, r, 8, (r + 15) // 16 * 16)
         assert self.PhiP.numel() == L.bg_rom_run_blocked_phi_elems(N, r)
         self.work = torch.empty((self.slots, L.bg_rom_run_blocked_work_elems(N, r)), dtype=torch.float64,
                                 device=self.Phi.device)
@@ -416,14 +426,7 @@ def pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, 
                        lambda f, N, B, x, inputs, opts, outputs: f(
                            N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
                            float(tol), int(max_it), opts, _lib.ptr(plan.work), plan.slots, *outputs), keep=(plan,))
-    _, u0d, mu1d, mu2d = res._keep[:4]
-    redo = (res.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
-    if redo.numel():                                     # np.linalg.solve would have exchanged rows
-        rr = _pod_prom_run_library(Xh, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, plan.Phi, proj, E, tol, max_it, device)
-        res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
-        res.info[redo] = 0
-    res.redone = int(redo.numel())
-    res.plan = plan
+    _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device)
     return res
 
 
@@ -444,11 +447,9 @@ class LongPodPlan:
         device = _lib.require_device(device)
         self.Phi = _as_dev(Phi, device)
         self.N, self.r = N, r
-        elems = L.bg_rom_run_long_phi_elems(N, r)
-        self.PhiP = torch.zeros(((N + 63) // 64 * 64 + 2, 40), dtype=torch.float64, device=self.Phi.device)
-        if self.PhiP.numel() != elems:
+        self.PhiP = _padded_basis(self.Phi, N, r, 64, 40)
+        if self.PhiP.numel() != L.bg_rom_run_long_phi_elems(N, r):
             raise ValueError(f"bg_rom_run_long does not cover N = {N}, r = {r}")
-        self.PhiP[1:N + 1, :r] = self.Phi
 
 
 def pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0,

@@ -252,20 +252,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                     const double um = s_u[w][i + 1], u0 = s_u[w][i + 2], ur = s_u[w][i + 3];
                     uu[m] = u0;
                     double g = 0.0;
-                    if (i < N) {
-                        if (a.nonuniform) {
-                            double v = 0.0;
-                            if (i > 0) v = (a.x[i] - a.x[i - 1]) / 6.0 * __builtin_fma(2.0, u0, um);
-                            if (i < N - 1) v = __builtin_fma((a.x[i + 1] - a.x[i]) / 6.0, __builtin_fma(2.0, u0, ur), v);
-                            g = v + nodes.fdt(w, i, m);
-                        } else {
-                            double acc;
-                            if (i == 0) acc = __builtin_fma(2.0, u0, ur);
-                            else if (i == N - 1) acc = __builtin_fma(2.0, u0, um);
-                            else acc = __builtin_fma(4.0, u0, um) + ur;
-                            g = __builtin_fma(h / 6.0, acc, nodes.fdt(w, i, m));
-                        }
-                    }
+                    if (i < N) g = rom_mass_rhs_node(a.x, i, N, um, u0, ur, nodes.fdt(w, i, m), h, a.nonuniform);
                     nodes.set_g(w, i, m, g);
                 }
                 for (int c0 = 0; c0 < QN; c0 += 4) {

@@ -536,19 +536,8 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                     const int i = tid + 256 * ii;
                     double g = 0.0;
                     if (i < N) {
-                        const double um = s_u[i + 1], uc = s_u[i + 2], ur = s_u[i + 3];
-                        if (a.nonuniform) {
-                            double v = 0.0;
-                            if (i > 0) v = (a.x[i] - a.x[i - 1]) / 6.0 * __builtin_fma(2.0, uc, um);
-                            if (i < N - 1) v = __builtin_fma((a.x[i + 1] - a.x[i]) / 6.0, __builtin_fma(2.0, uc, ur), v);
-                            g = v + fdt[ii];
-                        } else {
-                            double acc;
-                            if (i == 0) acc = __builtin_fma(2.0, uc, ur);
-                            else if (i == N - 1) acc = __builtin_fma(2.0, uc, um);
-                            else acc = __builtin_fma(4.0, uc, um) + ur;
-                            g = __builtin_fma(h / 6.0, acc, fdt[ii]);
-                        }
+                        const double uc = s_u[i + 2];
+                        g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], uc, s_u[i + 3], fdt[ii], h, a.nonuniform);
 #pragma unroll
                         for (int c = 0; c < ANN_MAX_N; ++c)
                             if (c < n) part[c] = __builtin_fma(a.UT[(size_t)c * N + i], uc, part[c]);

@@ -156,21 +156,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
             // ---- g = M u^n + dt F (`M @ U[:, n] + At*F`, :746) -------------------------------------------------------------
             for (int i = tid; i < BNMAX; i += 256) {
                 double g = 0.0;
-                if (i < N) {
-                    const double um = s_u[i + 1], u0 = s_u[i + 2], ur = s_u[i + 3];
-                    if (a.nonuniform) {
-                        double v = 0.0;
-                        if (i > 0) v = (a.x[i] - a.x[i - 1]) / 6.0 * __builtin_fma(2.0, u0, um);
-                        if (i < N - 1) v = __builtin_fma((a.x[i + 1] - a.x[i]) / 6.0, __builtin_fma(2.0, u0, ur), v);
-                        g = v + s_fdt[i];
-                    } else {
-                        double acc;
-                        if (i == 0) acc = __builtin_fma(2.0, u0, ur);
-                        else if (i == N - 1) acc = __builtin_fma(2.0, u0, um);
-                        else acc = __builtin_fma(4.0, u0, um) + ur;
-                        g = __builtin_fma(h / 6.0, acc, s_fdt[i]);
-                    }
-                }
+                if (i < N) g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], s_u[i + 2], s_u[i + 3], s_fdt[i], h, a.nonuniform);
                 s_g[i] = g;
             }
             __syncthreads();

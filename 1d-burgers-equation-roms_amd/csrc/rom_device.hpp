@@ -1,6 +1,6 @@
 // rom_device.hpp -- device pieces shared by the batched ROM kernels (rom.hip) and the device-side ROM
-// time loops (rom_*.hip, quad_device.hpp): one row of the Picard assembly, the nodal forcing loads of
-// one mesh node, and the pivoted r x r solve of one wavefront.  reference: FEM/fem_burgers.py:730-776 (pod_prom_burgers inner body).
+// time loops (rom_*.hip, rom_stream_device.hpp, quad_device.hpp): one row of the Picard assembly, the nodal forcing loads
+// and the right-hand side M u^n + dt F of one mesh node, and the pivoted r x r solve of one wavefront.  reference: FEM/fem_burgers.py:730-776 (pod_prom_burgers inner body).
 #pragma once
 #include "fom_device.hpp"
 
@@ -75,6 +75,24 @@ __device__ __forceinline__ void rom_nodal_forcing(const double* x, int i, int N,
         fl = (f1 * GP_A + f2 * GP_B) * (0.5 * he);
         hf = he * (f1 + f2);
     }
+}
+
+// g_i = (M u^n + dt F)_i at node i < N of one sample (`M @ U[:, n] + At*F`, :746): the row of the consistent mass matrix
+// applied to um, u0, ur = u[i-1], u[i], u[i+1] plus fdt_i = dt F_i.  Uniform meshes use the closed form h / 6 (1, 4, 1).
+__device__ __forceinline__ double rom_mass_rhs_node(const double* x, int i, int N, double um, double u0, double ur,
+                                                    double fdt_i, double h, int nonuniform)
+{
+    if (nonuniform) {
+        double v = 0.0;
+        if (i > 0) v = (x[i] - x[i - 1]) / 6.0 * __builtin_fma(2.0, u0, um);
+        if (i < N - 1) v = __builtin_fma((x[i + 1] - x[i]) / 6.0, __builtin_fma(2.0, u0, ur), v);
+        return v + fdt_i;
+    }
+    double acc;
+    if (i == 0) acc = __builtin_fma(2.0, u0, ur);
+    else if (i == N - 1) acc = __builtin_fma(2.0, u0, um);
+    else acc = __builtin_fma(4.0, u0, um) + ur;
+    return __builtin_fma(h / 6.0, acc, fdt_i);
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int srclane)

@@ -253,7 +253,8 @@ int bg_rom_run(int N, int B, int r, int nsteps, int projection, const double *x,
  *          row index i + 1, zero rows around and beyond the mesh, zero columns beyond r -- built once per basis by the caller;
  *   info   0, k + 1 for an exactly singular reduced system, or BG_INFO_NEEDS_PIVOTING for a sample whose pivot-free
  *          elimination met a multiplier above 1: the caller redoes that sample with a pivoting solve (there is no second
- *          kernel here; burgers_hip/rom.py sends it through the library path).
+ *          kernel here; burgers_hip/rom.py sends it through the library path);
+ *   order  [B] or NULL; entries outside [0, B) are skipped.
  *   The basis streams through LDS 64 mesh rows at a time, the accumulators of the reduced system are dealt to the four
  *   waves (csrc/rom_wide.hip).  options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED (tests: every sample is
  *   handed back as if its elimination had needed a row exchange). */
