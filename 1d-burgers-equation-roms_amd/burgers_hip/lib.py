@@ -160,6 +160,12 @@ _SIGNATURES = {
                                         c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p,
                                         c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_local_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
+    "bg_local_rom_run_long_bases_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "bg_local_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 7 + [c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p,
+                                             c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -1293,9 +1293,12 @@ class LocalPodPlan:
     bases zero-padded into one stack [C][N][rmax] in centre order (slot = centre index), their widths (int32), UgT =
     U_global[:, :m]^T contiguous, and the centres [C][m].  Shapes that cannot be right raise ValueError; ``ok`` is False
     (with ``reason``) when the clustering is valid but the device loop does not cover it -- beyond bg_local_rom_limits,
-    N > 512, or a centre 0 .. C-1 without a basis -- and the caller then takes the host path."""
+    N > 512, or a centre 0 .. C-1 without a basis -- and the caller then takes the host path.
+    ``long_mesh``: the operands of bg_local_rom_run_long instead, for 3 <= N <= 1024 (bg_local_rom_run_long_limits): the
+    stack is [C][NPAD + 2][40], every block the padded copy of its basis that bg_rom_run_long reads (row i at index i + 1,
+    NPAD = N rounded up to 64, zero rows and columns around it)."""
 
-    def __init__(self, centres, local_bases, U_global, m, N, device):
+    def __init__(self, centres, local_bases, U_global, m, N, device, long_mesh=False):
         import ctypes
         L = _lib.load()
         self.N, self.m = int(N), int(m)
@@ -1309,18 +1312,24 @@ class LocalPodPlan:
         for k, b in local_bases.items():
             if len(np.shape(b)) != 2 or np.shape(b)[0] != self.N:
                 raise ValueError(f"local basis {k} must have one row per mesh node (N = {self.N})")
-        lim = [ctypes.c_int() for _ in range(3)]
-        L.bg_local_rom_limits(*[ctypes.byref(v) for v in lim])
-        max_r, max_m, max_c = (v.value for v in lim)
+        self.long_mesh = bool(long_mesh)
+        lim = [ctypes.c_int() for _ in range(4 if self.long_mesh else 3)]
+        if self.long_mesh:
+            L.bg_local_rom_run_long_limits(*[ctypes.byref(v) for v in lim])
+            max_n, max_r, max_m, max_c = (v.value for v in lim)
+        else:
+            L.bg_local_rom_limits(*[ctypes.byref(v) for v in lim])
+            max_n, (max_r, max_m, max_c) = 512, (v.value for v in lim)
+        limits = "bg_local_rom_run_long_limits" if self.long_mesh else "bg_local_rom_limits"
         self.widths_host = [int(np.shape(local_bases[c])[1]) if c in local_bases else 0 for c in range(self.C)]
         self.rmax = max(self.widths_host)
         missing = [c for c in range(self.C) if c not in local_bases]
         if missing:
             self.reason = f"centre {missing[0]} has no local basis"
-        elif self.N > 512:
-            self.reason = f"N = {self.N} > 512"
+        elif self.N > max_n or (self.long_mesh and self.N < 3):
+            self.reason = f"N = {self.N} > {max_n}" if self.N > max_n else f"N = {self.N} < 3"
         elif self.rmax > max_r or self.m > max_m or self.C > max_c:
-            self.reason = (f"beyond bg_local_rom_limits: widths {self.rmax} (<= {max_r}), m {self.m} (<= {max_m}), "
+            self.reason = (f"beyond {limits}: widths {self.rmax} (<= {max_r}), m {self.m} (<= {max_m}), "
                            f"{self.C} centres (<= {max_c})")
         elif min(self.widths_host) < 1:
             self.reason = "a local basis has no columns"
@@ -1329,30 +1338,35 @@ class LocalPodPlan:
         self.ok = self.reason is None
         if not self.ok:
             return
-        self.stack = torch.zeros((self.C, self.N, self.rmax), dtype=torch.float64, device=self.centres.device)
-        for c, w_ in enumerate(self.widths_host):
-            self.stack[c, :, :w_] = _as_dev(local_bases[c], device)
+        if self.long_mesh:
+            self.stack = torch.stack([_padded_basis(_as_dev(local_bases[c], device), self.N, w_, 64, max_r)
+                                      for c, w_ in enumerate(self.widths_host)])
+            if self.stack.numel() != L.bg_local_rom_run_long_bases_elems(self.N, self.C):
+                raise ValueError(f"bg_local_rom_run_long does not cover N = {self.N}, C = {self.C}")
+        else:
+            self.stack = torch.zeros((self.C, self.N, self.rmax), dtype=torch.float64, device=self.centres.device)
+            for c, w_ in enumerate(self.widths_host):
+                self.stack[c, :, :w_] = _as_dev(local_bases[c], device)
         self.widths = torch.as_tensor(self.widths_host, dtype=torch.int32, device=self.centres.device)
         self.UgT = Ug[:, :self.m].t().contiguous()
 
 
-def local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
-                         projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, plan=None, balance=True,
-                         options=0):
-    """``local_prom_burgers`` for a batch with the whole time loop on the device (bg_local_rom_run): one workgroup per
-    sample, the nearest-centre pick at every step start, the cluster's basis reloaded into registers only when it
-    changes.  Returns None when the clustering is outside what the kernel covers (LocalPodPlan.ok).  ``res.clusters``:
-    (B, nsteps) int32, the centre index of every sample and step.  ``plan``: a LocalPodPlan of the same clustering to
-    reuse across calls (``res.plan``); centres, bases and U_global are then not read again."""
+def _local_device_loop(entry, grid, long_mesh, X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global,
+                       num_global_modes, projection, E, tol, max_it, device, plan, balance, options):
+    """What local_prom_run_fused (bg_local_rom_run) and local_prom_run_long (bg_local_rom_run_long) share: the plan and
+    its checks, the launch with the ``clusters`` output, the result.  ``grid(device)``: the persistent workgroups.
+    Returns None when the plan's clustering is outside what the entry point covers."""
     if projection not in ("Galerkin", "LSPG"):
         raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
     proj = PROJ[projection.lower()]
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     if plan is None:
-        plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(Xh), device)
-    if plan.N != len(Xh) or plan.m != int(num_global_modes) or plan.centres.device != device:
-        raise ValueError("the plan must be built for this mesh and num_global_modes (and live on the device of the call)")
+        plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(Xh), device, long_mesh=long_mesh)
+    if (plan.N != len(Xh) or plan.m != int(num_global_modes) or plan.centres.device != device
+            or plan.long_mesh != bool(long_mesh)):
+        raise ValueError("the plan must be built for this mesh, num_global_modes and entry point (and live on the device "
+                         "of the call)")
     if not plan.ok:
         return None
     out = {}
@@ -1363,15 +1377,45 @@ def local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_gl
                  _lib.ptr(plan.UgT), _lib.ptr(plan.centres), *inputs, float(dt), float(E), float(tol), int(max_it), opts,
                  *outputs[:4], _lib.ptr(out["clusters"]), *outputs[4:])
 
-    res = _device_loop("bg_local_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1,
-                       balance, launch, keep=(plan,))
+    res = _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, True, options, grid(device), 1, balance, launch, keep=(plan,))
     res.plan = plan
     res.clusters = out["clusters"]
     return res
 
 
+def local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
+                         projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, plan=None, balance=True,
+                         options=0):
+    """``local_prom_burgers`` for a batch with the whole time loop on the device (bg_local_rom_run): one workgroup per
+    sample, the nearest-centre pick at every step start, the cluster's basis reloaded into registers only when it
+    changes.  Returns None when the clustering is outside what the kernel covers (LocalPodPlan.ok).  ``res.clusters``:
+    (B, nsteps) int32, the centre index of every sample and step.  ``plan``: a LocalPodPlan of the same clustering to
+    reuse across calls (``res.plan``); centres, bases and U_global are then not read again."""
+    return _local_device_loop("bg_local_rom_run", lambda d: 2 * _cu_count(d), False, X, u0, mu1, mu2, dt, nsteps, centers,
+                              local_bases, U_global, num_global_modes, projection, E, tol, max_it, device, plan, balance,
+                              options)
+
+
+def local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
+                        projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, plan=None, balance=True,
+                        options=0):
+    """``local_prom_burgers`` for meshes of up to 1024 nodes (bg_local_rom_run_long_limits; widths <= 40, m and C <= 64)
+    with the whole time loop on the device (bg_local_rom_run_long): the picked cluster's basis streams through LDS, the
+    pivoting repair runs inside the call, nothing is synchronised.  Raises ValueError when the clustering is outside the
+    limits.  ``res.clusters`` and ``plan`` (a LocalPodPlan built with ``long_mesh=True``; ``res.plan``) as in
+    local_prom_run_fused."""
+    device = _lib.require_device(device)
+    if plan is None:
+        plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(check_mesh(X)), device, long_mesh=True)
+    if not plan.ok:
+        raise ValueError(f"bg_local_rom_run_long does not cover this clustering: {plan.reason}")
+    grid = lambda d: _lib.load().bg_rom_run_long_workgroups_per_cu() * _cu_count(d)
+    return _local_device_loop("bg_local_rom_run_long", grid, True, X, u0, mu1, mu2, dt, nsteps, None, None, None,
+                              num_global_modes, projection, E, tol, max_it, device, plan, balance, options)
+
+
 def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
-                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, fused=False):
+                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, fused=False, long_mesh=False):
     """Batched ``local_prom_burgers`` (FEM/fem_burgers.py:979-1079): each sample picks, once per time
     step, the local basis of the cluster whose centre is nearest to ``U_global[:, :m]^T u^n``
     (= ``kmeans.predict``), then iterates like ``pod_prom_burgers`` in that basis.  The bases are
@@ -1380,9 +1424,17 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
     centre index of every sample and step.
     ``fused``: the device-side time loop bg_local_rom_run (local_prom_run_fused) where it covers the clustering
     (N <= 512, widths <= 40, m and C <= 64, a basis for every centre); otherwise, and by default, the host-driven
-    iteration."""
+    iteration.
+    ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= 1024 whose clustering is inside
+    bg_local_rom_run_long_limits take the device-side loop bg_local_rom_run_long instead of the host-driven iteration."""
     if projection not in ("Galerkin", "LSPG"):
         raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
+    if fused and long_mesh and np.shape(X)[0] > 512:
+        dev = _lib.require_device(device)
+        plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(check_mesh(X)), dev, long_mesh=True)
+        if plan.ok:
+            return check_singular(local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, None, None, None, num_global_modes,
+                                                      projection, E, tol, max_it, dev, plan=plan))
     if fused:
         res = local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
                                    projection, E, tol, max_it, device)

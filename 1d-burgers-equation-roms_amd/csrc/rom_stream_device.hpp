@@ -1,6 +1,7 @@
 // rom_stream_device.hpp -- the whole POD-PROM time loop of one sample on one compute unit with the basis STREAMED through
-// LDS: the one source of bg_rom_run_wide (rom_wide.hip, 40 < r <= 96, N <= 512) and bg_rom_run_long (rom_long.hip, r <= 40,
-// 513 <= N <= 1024).  reference: FEMBurgers.pod_prom_burgers, FEM/fem_burgers.py:709-785.
+// LDS: the one source of bg_rom_run_wide (rom_wide.hip, 40 < r <= 96, N <= 512), bg_rom_run_long (rom_long.hip, r <= 40,
+// 513 <= N <= 1024) and bg_local_rom_run_long (rom_local_long.hip, local POD on the same meshes).
+// reference: FEMBurgers.pod_prom_burgers, FEM/fem_burgers.py:709-785; local_prom_burgers, :979-1079.
 //
 // bg_rom_run (rom_fused.hip) keeps the basis in registers.  Here it streams through LDS, 64 mesh rows at a time (one pass over
 // the padded copy PhiP per Picard iteration, L2-resident), and what stays in registers are the ACCUMULATORS of the reduced
@@ -14,7 +15,7 @@
 // Then the reduced system is parked in LDS over the dead slabs and solved (the kernel's own step), q = Phi^T u + dq, the
 // stopping test, and after the last iteration one lift-only sweep for U[:, n+1] = Phi q (:779).
 //
-// What the two kernels do not share is stated once per kernel in a description K (WidePod, LongPod in the .hip files):
+// What the kernels do not share is stated once per kernel in a description K (WidePod, LongPod, LongLocal in the .hip files):
 //   K::NB                        4-column blocks of the padded reduced dimension R = 4 NB: column NB t + c <-> (lane index t, block c)
 //   K::PS, K::SW                 doubles per row of the LDS slabs and of the parked system Ar | br | Phi^T u (16-byte aligned rows)
 //   K::NMAX                      mesh rows held: the length of u, g, h_f, dt F in LDS and of every per-node loop
@@ -22,7 +23,11 @@
 //   K::mirror_lspg               LSPG parks the lower block pairs too; otherwise the solve reads them through a symmetric accessor
 //   K::has_repair                a second instantiation PIV redoes the samples marked BG_INFO_NEEDS_PIVOTING (and only those)
 //   K::timing                    diagnostic build: shader clocks per phase in place of the iteration counts (see the end of the body)
-//   K::solve_update<GAL, PIV, W> solve(Ar, -br) of the parked system by all four waves, q = Phi^T u + dq into L.q, |dq|^2 and |q|^2
+//   K::solve_update<GAL, PIV, W> solve(Ar, -br) of the parked system (r live unknowns) by all four waves, q = Phi^T u + dq into L.q,
+//                                |dq|^2 and |q|^2
+//   K::Args                      the kernel's argument struct: StreamRunArgs, or LocalStreamRunArgs when K::local
+//   K::local                     local POD: at the top of every time step the nearest centre to U_g^T u^n picks the step's basis
+//                                (a block of the stack PhiP [C][NPAD + 2][R]) and its width; the sweep streams that block
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +64,16 @@ struct StreamRunArgs {
     int N, NPAD, B, r, nsteps, max_it, supg, nonuniform, force_pivoted;
 };
 
+// Local POD (K::local): one basis per time step, picked from the stack by the nearest centre.  PhiP is the stack
+// [C][NPAD + 2][R], every block laid out like the POD operand with zero columns beyond its width; r the widest width.
+struct LocalStreamRunArgs : StreamRunArgs {
+    const int32_t* widths;    // [C], 1 .. r
+    const double* UgT;        // [m][N]: U_global[:, :m] transposed
+    const double* centres;    // [C][m]
+    int32_t* clusters;        // [B][nsteps] or null
+    int C, m;
+};
+
 struct StreamLds {
     double* slab;           // two slab buffers; later the parked system
     double* u;              // [NMAX + 4]: u at offset 2, zero halo on each side
@@ -67,7 +82,50 @@ struct StreamLds {
     double* q;              // [R]
     double* m; double* diag; double* y; double* x;      // the solve's own arrays: multipliers of two panels, diagonal, y (and x)
     int* bad;               // guard of each wave (and the info of a pivoted solve)
+    double* qg;             // K::local: [64], U_g^T u^n of the current time step
 };
+
+// Local POD, the start of a time step (reference :1011-1012), with the arithmetic of rom_fused_kernel<..., LOCAL>
+// (rom_fused.hip) written again: called from there, these two functions changed the SGPR spills of every local instantiation
+// (and the VGPR count of two), and those kernels are meant to stay what they are.
+// local_global_coords: q_g = U_g^T u^n into s_qg[0 .. m) -- wave w of the workgroup's four takes the columns j = w (mod 4),
+// lanes stride the rows; s_u2 = u^n at node 0; the caller puts a workgroup barrier behind it.
+__device__ __forceinline__ void local_global_coords(const double* UgT, const double* s_u2, int N, int m, int w, int lane, double* s_qg)
+{
+    for (int j = w; j < m; j += 4) {
+        double p = 0.0;
+#pragma unroll 4                                 // (loads in flight together: each one is an L2 round trip)
+        for (int i = lane; i < N; i += 64) p = __builtin_fma(UgT[(size_t)j * N + i], s_u2[i], p);
+        p = wave_sum(p);
+        if (lane == 0) s_qg[j] = p;
+    }
+}
+
+// kmeans.predict (:1012): lane c holds |q_g - centre_c|^2 (summed in j order), then the FIRST index of the minimum over the
+// wave (a NaN distance counts as the smallest, as in np.argmin).  Every wave computes it: the cluster is workgroup-uniform
+// without a broadcast.  C <= 64.
+__device__ __forceinline__ int local_nearest_centre(const double* s_qg, const double* centres, int C, int m, int lane)
+{
+    double d = __builtin_inf();
+    int ci = lane;
+    if (lane < C) {
+        d = 0.0;
+#pragma unroll 4
+        for (int j = 0; j < m; ++j) {
+            const double e = s_qg[j] - centres[(size_t)lane * m + j];
+            d = __builtin_fma(e, e, d);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double od = __shfl_xor(d, off);
+        const int oc = __shfl_xor(ci, off);
+        const bool take = (od != od) ? (d == d || oc < ci) : (od < d || (od == d && oc < ci));
+        d = take ? od : d;
+        ci = take ? oc : ci;
+    }
+    return __builtin_amdgcn_readfirstlane(ci);
+}
 
 template <class K, bool GAL>
 struct StreamItems {
@@ -157,7 +215,7 @@ __device__ __forceinline__ void stream_park(const double (&acc)[StreamItems<K, G
 // registers.  A `switch (w)` around the matrix instructions of each row step instead cost 340 accumulator moves per
 // 87 instructions (first version of the wide kernel: 6.5e5 sample-steps/s).  All four copies execute the same sequence of barriers.
 template <class K, bool GAL, bool PIV, int W>
-__device__ __forceinline__ void rom_stream_body(const StreamRunArgs& a, const StreamLds& L)
+__device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const StreamLds& L)
 {
     static_assert(!PIV || K::has_repair, "this kernel has no repair instantiation");
     constexpr int NB = K::NB, R = 4 * NB, PS = K::PS, NMAX = K::NMAX, SLAB = StreamDims<K>::SLAB, CHUNKS = StreamDims<K>::CHUNKS;
@@ -213,11 +271,17 @@ __device__ __forceinline__ void rom_stream_body(const StreamRunArgs& a, const St
                 tick = now;
             }
         };
+        // K::local: the step's basis and width are the picked cluster's (wave-uniform: the DMA source base stays in scalar
+        // registers); otherwise the arguments are read where they are used, as before there was a pick
+        const double* PhiL = nullptr;
+        int r_local = 0;
+        auto step_basis = [&]() -> const double* { if constexpr (K::local) return PhiL; else return a.PhiP; };
+        auto step_width = [&]() -> int { if constexpr (K::local) return r_local; else return a.r; };
         // LDS DMA of slab `slab` (mesh rows [r0 - 1, r0 + 64] = rows r0 .. r0 + 65 of PhiP) into buffer `buf`: wave w moves the
         // 1-KB pieces w, w + 4, ...; a lane's 16 bytes land at piece base + 16 lane, i.e. LDS row o / (8 PS), byte o % (8 PS) of it
         // (the 16 bytes of row padding are filled from a valid dummy address)
         auto slab_dma = [&](int slab, int buf) {
-            const char* src = reinterpret_cast<const char*>(a.PhiP + (size_t)slab * SRS * R);
+            const char* src = reinterpret_cast<const char*>(step_basis() + (size_t)slab * SRS * R);
             const int ln = tid & 63;
             for (int j = w; j < CHUNKS; j += 4) {
                 const int o = 1024 * j + 16 * ln;
@@ -235,7 +299,17 @@ __device__ __forceinline__ void rom_stream_body(const StreamRunArgs& a, const St
                 if (i < N) g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], s_u[i + 2], s_u[i + 3], s_fdt[i], h, a.nonuniform);
                 s_g[i] = g;
             }
+            if constexpr (K::local)                            // q_g = U_g^T u^n (:1011); s_u is not written before the barrier
+                local_global_coords(a.UgT, s_u + 2, N, a.m, w, tid & 63, L.qg);
             __syncthreads();
+            if constexpr (K::local) {
+                // kmeans.predict (:1012), (:1013): the nearest centre's block of the stack and its width serve this step.  No
+                // DMA is in flight here, and the streaming sweep re-reads the basis on every pass: a switch costs nothing more.
+                const int cl = local_nearest_centre(L.qg, a.centres, a.C, a.m, tid & 63);
+                PhiL = a.PhiP + (size_t)cl * (size_t)(a.NPAD + 2) * R;
+                r_local = a.widths[cl] < a.r ? a.widths[cl] : a.r;      // (clamped: the blocks are R wide, a.r <= R)
+                if (tid == 0 && a.clusters) a.clusters[(size_t)smp * a.nsteps + step] = cl;
+            }
             int k = 0;
             bool proj = true;
             while (true) {
@@ -330,7 +404,7 @@ __device__ __forceinline__ void rom_stream_body(const StreamRunArgs& a, const St
                 lap(3);
                 // ---- solve(Ar, -br) (:767), q = Phi^T u_k + dq, err = |dq| / |q|  (:770-776) -------------------------------------
                 double nd, nq;
-                K::template solve_update<GAL, PIV, W>(a, L, lane, aborted, info_out, nd, nq, [&] { lap(4); });
+                K::template solve_update<GAL, PIV, W>(a, L, step_width(), lane, aborted, info_out, nd, nq, [&] { lap(4); });
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;
@@ -359,7 +433,7 @@ __device__ __forceinline__ void rom_stream_body(const StreamRunArgs& a, const St
 
 // The four-way branch on the wave at the top of a kernel.
 template <class K, bool GAL, bool PIV>
-__device__ __forceinline__ void rom_stream_waves(const StreamRunArgs& a, const StreamLds& L)
+__device__ __forceinline__ void rom_stream_waves(const typename K::Args& a, const StreamLds& L)
 {
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {       // wave-uniform by construction
         case 0: rom_stream_body<K, GAL, PIV, 0>(a, L); break;

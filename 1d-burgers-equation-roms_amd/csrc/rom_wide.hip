@@ -190,6 +190,8 @@ __device__ __attribute__((noinline)) void wide_solve(const lds_double_t* S, lds_
 }
 
 struct WidePod {
+    using Args = StreamRunArgs;
+    static constexpr bool local = false;
     static constexpr int NB = WNB, PS = WPS, SW = WPS, NMAX = WNMAX;
     static constexpr bool cf_by_mesh_row = true;        // lo, di, up, R of all 512 mesh rows stay in LDS
     static constexpr bool mirror_lspg = false;          // wide_solve reads the lower blocks by symmetry
@@ -203,11 +205,10 @@ struct WidePod {
     // solve(Ar, -br) (:767): guarded pivot-free Gauss-Jordan, two row tiles, panels of four columns; two values of dq and q per lane.
     // BG_OPT_FORCE_PIVOTED (tests): every sample is handed back to the caller after its first solve.
     template <bool GAL, bool PIV, int W, class Lap>
-    static __device__ __forceinline__ void solve_update(const StreamRunArgs& a, const StreamLds& L, int lane, bool& aborted, int&,
+    static __device__ __forceinline__ void solve_update(const StreamRunArgs& a, const StreamLds& L, int r, int lane, bool& aborted, int&,
                                                         double& nd, double& nq, const Lap& solved)
     {
         const double* S = L.slab;
-        const int r = a.r;
         const double wtu0 = (lane < r) ? S[lane * WPS + WR + 1] : 0.0;                     // Phi^T u, rows 0 .. 63
         const double wtu1 = (64 + lane < r) ? S[(64 + lane) * WPS + WR + 1] : 0.0;         // rows 64 .. 95
         wide_solve<GAL>((lds_double_t*)S, (lds_double_t*)L.m, (lds_double_t*)L.diag, (lds_double_t*)L.y, (lds_int_t*)L.bad, W, lane, r);

@@ -147,13 +147,14 @@ class FEMBurgers:
 
     # ------------------------------------------------------------------------- local POD
     def local_prom_burgers(self, At, nTimeSteps, u0, mu1, E, mu2, kmeans, local_bases, U_global,
-                           num_global_modes, projection="Galerkin", fused=False):
+                           num_global_modes, projection="Galerkin", fused=False, long_mesh=False):
         """Local (clustered) POD PROM (reference :979-1079).  ``kmeans`` is the fitted
         scikit-learn KMeans of the reference (only ``cluster_centers_`` is used: ``predict`` is the
         nearest centre), ``local_bases`` a dict cluster id -> (N, r_c) basis.  ``fused``: the whole time loop
-        on the device (bg_local_rom_run) where it covers the clustering; the default is the host-driven iteration."""
+        on the device (bg_local_rom_run) where it covers the clustering; the default is the host-driven iteration.
+        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_local_rom_run_long."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.local_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                   np.asarray(kmeans.cluster_centers_, dtype=np.float64), local_bases, U_global,
-                                  int(num_global_modes), projection=projection, E=E, fused=fused)
+                                  int(num_global_modes), projection=projection, E=E, fused=fused, long_mesh=long_mesh)
         return self._finish(res, batched)

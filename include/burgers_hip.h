@@ -511,6 +511,33 @@ int bg_local_rom_run(int N, int B, int C, int rmax, int m, int nsteps, int proje
                      int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
                      int32_t *clusters, const int32_t *order, void *stream);
 
+/* bg_local_rom_run_long -- bg_local_rom_run for long meshes: 3 <= N <= 1024 (meant for N > 512, where bg_local_rom_run
+ *   ends), widths <= 40, m <= 64, C <= 64 (bg_local_rom_run_long_limits).  reference: FEM/fem_burgers.py:979-1079.
+ *   Opt-in: the facade routes N > 512 here only when asked (burgers_hip/rom.py, fused=True, long_mesh=True).
+ *   The loop of bg_rom_run_long (csrc/rom_local_long.hip: the basis streams through LDS) with the cluster pick of
+ *   bg_local_rom_run at the start of every step, in the same arithmetic; the step's sweeps stream the picked cluster's
+ *   block of the stack, and the solve gives the unknowns at and beyond widths[c] a zero correction.
+ *   Same arguments, outputs and semantics as bg_local_rom_run except:
+ *   bases  [C][NPAD + 2][40], NPAD = N rounded up to 64 (bg_local_rom_run_long_bases_elems(N, C) doubles, 16-byte
+ *          aligned; 0 for an N or C the kernel does not cover): block c is cluster c's basis laid out like
+ *          bg_rom_run_long's PhiP -- basis row i at row index i + 1, zero rows around and beyond the mesh, zero columns
+ *          beyond widths[c] -- built once per clustering by the caller;
+ *   rmax   the widest width (widths[c] is clamped to it);
+ *   order  [B] or NULL; entries outside [0, B) are skipped.
+ *   Errors: N < 3, B or nsteps < 0, C, rmax, m, max_it < 1, dt <= 0, a null operand or output with B > 0, bases not
+ *   16-byte aligned: BG_ERR_BAD_ARG; N > 1024: BG_ERR_UNSUPPORTED_N; rmax > 40, m > 64, C > 64: BG_ERR_UNSUPPORTED_R; an
+ *   unknown projection: BG_ERR_PROJECTION; B = 0: BG_OK with nothing launched.
+ *   info, the repair kernel inside the call (it takes the same cluster path) and the workgroups per CU
+ *   (bg_rom_run_long_workgroups_per_cu) are as in bg_rom_run_long.
+ *   options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED (tests: every sample through the second kernel). */
+int bg_local_rom_run_long_limits(int *max_n, int *max_r, int *max_m, int *max_clusters);
+long long bg_local_rom_run_long_bases_elems(int N, int C);
+int bg_local_rom_run_long(int N, int B, int C, int rmax, int m, int nsteps, int projection, const double *x,
+                          const double *bases, const int32_t *widths, const double *UgT, const double *centres,
+                          const double *u0, const double *mu1, const double *mu2, double dt, double E, double tol,
+                          int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
+                          int32_t *clusters, const int32_t *order, void *stream);
+
 /* bg_decode_modes_bf16 -- the contraction of the non-intrusive POD-ANN decoder (bf16 tier of BASELINE config 5)
  *   reference: `Uhat = U_modes @ Qhat.T`, Non-Instrusive/predict_pod_ann.py:73-80, for a batch of (mu1, mu2) samples
  *   out[b][i][t] = sum_k Um[i][k] * Q[b * Nt + t][k]: bf16 operands, float32 accumulate, each result written once as
