@@ -34,6 +34,23 @@ BG_COUNTER_SLOTS, BG_COUNTER_STRIDE = 16, 32
 BG_RBF_GAUSSIAN, BG_RBF_IMQ = 0, 1
 BG_INFO_NEEDS_PIVOTING = -1
 
+# Fragments of the argument list the device-side time loops share (include/burgers_hip.h), in the order _loop puts them
+_LOOP_BATCH = [c_double_p] * 3                                              # u0, mu1, mu2
+_LOOP_STEP = [ctypes.c_double] * 3 + [ctypes.c_int] * 2                      # dt, E, tol, max_it, options
+_LOOP_OUT = [c_double_p] + [c_int_p] * 4 + [ctypes.c_void_p]                 # hist, iters, flags, info, order, stream
+_LOOP_OUT_CLUSTERS = [c_double_p] + [c_int_p] * 5 + [ctypes.c_void_p]        # ... info, clusters, order, stream
+_ANN_MLP = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]   # layers, widths, wt, bias, acts, alphas: HOST arrays
+_LOCAL_OPERANDS = [c_double_p, c_int_p, c_double_p, c_double_p]              # stack, widths, UgT, centres
+
+
+def _loop(ints, operands, after_batch=(), workspace=(), out=_LOOP_OUT):
+    """(restype, argtypes) of a device-side time loop: ``ints`` leading ints, x, ``operands``, the batch, ``after_batch``
+    (bg_ann_rom_run's MLP), the step, ``workspace`` (bg_rom_run_blocked's work, slots), the outputs."""
+    return (ctypes.c_int, [ctypes.c_int] * ints + [c_double_p] + list(operands) + _LOOP_BATCH + list(after_batch) +
+            _LOOP_STEP + list(workspace) + out)
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "bg_abi_version": (ctypes.c_int, []),
@@ -78,41 +95,30 @@ _SIGNATURES = {
                                             c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_int_p,
                                             c_double_p, c_double_p, c_double_p, ctypes.c_void_p]),
     "bg_rom_run_max_r": (ctypes.c_int, []),
-    "bg_rom_run": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
-                                  c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                  ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_rom_run": _loop(5, [c_double_p]),
     "bg_quad_rom_max_n": (ctypes.c_int, []),
     "bg_quad_rom_h3f_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_quad_rom_phif_elems": (ctypes.c_longlong, [ctypes.c_int]),
-    "bg_quad_rom_run": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
-                                       c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
-                                       ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p,
-                                       c_int_p, ctypes.c_void_p]),
+    "bg_quad_rom_run": _loop(5, [c_double_p] * 3),
     "bg_quad_rom_run_long_max_n": (ctypes.c_int, []),
     "bg_quad_rom_run_long_max_r": (ctypes.c_int, []),
     "bg_quad_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
     "bg_quad_rom_run_long_phit_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_quad_rom_run_long_phif_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_quad_rom_run_long_h3f_elems": (ctypes.c_longlong, [ctypes.c_int]),
-    "bg_quad_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 7 + [ctypes.c_double] * 3 +
-                             [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_quad_rom_run_long": _loop(5, [c_double_p] * 3),
     "bg_rom_run_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),
-    "bg_rom_run_wide": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
-                                       c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                       ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_rom_run_wide": _loop(5, [c_double_p]),
     "bg_rom_run_blocked_max_r": (ctypes.c_int, []),
     "bg_rom_run_blocked_phi_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_rom_run_blocked_work_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
-    "bg_rom_run_blocked": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 5 + [ctypes.c_double] * 3 +
-                           [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p,
-                            c_int_p, ctypes.c_void_p]),
+    "bg_rom_run_blocked": _loop(5, [c_double_p], workspace=[c_double_p, ctypes.c_int]),
     "bg_rom_run_long_max_n": (ctypes.c_int, []),
     "bg_rom_run_long_max_r": (ctypes.c_int, []),
     "bg_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
     "bg_rom_run_long_phi_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
-    "bg_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 5 + [c_double_p] * 5 + [ctypes.c_double] * 3 +
-                        [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_rom_run_long": _loop(5, [c_double_p]),
     "bg_rom_lift": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                    c_int_p, c_double_p, ctypes.c_void_p]),
     "bg_quad_features": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_double_p, ctypes.c_void_p]),
@@ -144,28 +150,14 @@ _SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_float), c_double_p, ctypes.c_void_p]),
     "bg_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
-    # widths / acts (int[]), wt / bias (void*[]) and alphas (float[]) are HOST arrays built by the caller
-    "bg_ann_rom_run": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int,
-                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p),
-                                      ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
-                                      ctypes.POINTER(ctypes.c_float), ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                      ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_ann_rom_run": _loop(6, [c_double_p], after_batch=_ANN_MLP),
     "bg_rbf_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
-    "bg_rbf_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_double_p] * 7 + [ctypes.c_double, c_double_p, c_double_p,
-                                      c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                      ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_rbf_rom_run": _loop(8, [c_double_p] * 6 + [ctypes.c_double]),
     "bg_local_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
-    "bg_local_rom_run": (ctypes.c_int, [ctypes.c_int] * 7 + [c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
-                                        c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
-                                        ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p,
-                                        c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_local_rom_run": _loop(7, _LOCAL_OPERANDS, out=_LOOP_OUT_CLUSTERS),
     "bg_local_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
     "bg_local_rom_run_long_bases_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
-    "bg_local_rom_run_long": (ctypes.c_int, [ctypes.c_int] * 7 + [c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
-                                             c_double_p, c_double_p, c_double_p, ctypes.c_double, ctypes.c_double,
-                                             ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p,
-                                             c_int_p, c_int_p, c_int_p, ctypes.c_void_p]),
+    "bg_local_rom_run_long": _loop(7, _LOCAL_OPERANDS, out=_LOOP_OUT_CLUSTERS),
 }
 
 _lib = None
@@ -215,6 +207,13 @@ def declared_symbols():
 def check(code, where):
     if code != BG_OK:
         raise BurgersHipError(code, where)
+
+
+def limits(name, count):
+    """The ``count`` ints a ``*_limits`` entry point reports through its out-parameters.  Needs no device."""
+    out = [ctypes.c_int() for _ in range(count)]
+    check(getattr(load(), name)(*[ctypes.byref(v) for v in out]), name)
+    return tuple(v.value for v in out)
 
 
 def require_device(device=None):

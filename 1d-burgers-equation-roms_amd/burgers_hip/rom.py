@@ -15,15 +15,56 @@ from __future__ import annotations
 import weakref
 from dataclasses import dataclass
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 import torch
+import torch.nn as nn
 
 from . import lib as _lib
 from .fom import FomResult, _as_dev, check_mesh
 from .fom import batch_inputs as _batch_inputs
 
 PROJ = {"galerkin": _lib.BG_PROJ_GALERKIN, "lspg": _lib.BG_PROJ_LSPG}
+_ACT_KINDS = {type(None): _lib.BG_ACT_NONE, nn.ELU: _lib.BG_ACT_ELU, nn.ReLU: _lib.BG_ACT_RELU, nn.Tanh: _lib.BG_ACT_TANH}
+_NOT_AVAILABLE = "Projection method '{}' is not available. Please use 'Galerkin' or 'LSPG'."
+
+
+def _projection(projection, message, exact=False):
+    """The BG_PROJ_* code of ``projection`` or ValueError(``message``); ``exact``: spelt as the reference does (:754-764)."""
+    if (projection not in ("Galerkin", "LSPG")) if exact else (projection.lower() not in PROJ):
+        raise ValueError(message.format(projection))
+    return PROJ[projection.lower()]
+
+
+class _Route(NamedTuple):
+    """One device-side time loop as the host sees it.  ``wg_per_cu``, ``max_n`` and ``max_r`` are ints or the names of the
+    library's int() symbols that report them (_limit); the closure and local loops report theirs through ``*_limits``."""
+    entry: str
+    wg_per_cu: object        # persistent workgroups per compute unit
+    max_r: object = None     # widest basis
+    min_n: int = 2           # min_n <= N <= max_n: the meshes the entry point covers
+    max_n: object = 512
+    group: int = 1           # samples per slot of ``order``
+    supg: bool = True
+    redo: bool = False       # the wrapper redoes BG_INFO_NEEDS_PIVOTING samples on the host
+
+
+_ROUTES = {r.entry: r for r in (
+    _Route("bg_rom_run", 2, "bg_rom_run_max_r"),
+    _Route("bg_rom_run_wide", 1, "bg_rom_run_wide_max_r", redo=True),
+    _Route("bg_rom_run_blocked", 1, "bg_rom_run_blocked_max_r", min_n=3, redo=True),
+    _Route("bg_rom_run_long", "bg_rom_run_long_workgroups_per_cu", "bg_rom_run_long_max_r", 3, "bg_rom_run_long_max_n"),
+    _Route("bg_quad_rom_run", 1, "bg_quad_rom_max_n", group=4, supg=False),
+    _Route("bg_quad_rom_run_long", "bg_quad_rom_run_long_workgroups_per_cu", "bg_quad_rom_run_long_max_r", 513,
+           "bg_quad_rom_run_long_max_n", group=4, supg=False),
+    _Route("bg_ann_rom_run", 2), _Route("bg_rbf_rom_run", 2), _Route("bg_local_rom_run", 2),
+    _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
+)}
+
+
+def _limit(v):
+    return v if isinstance(v, int) else getattr(_lib.load(), v)()
 
 
 class SingularReducedSystem(np.linalg.LinAlgError):
@@ -241,23 +282,35 @@ def _alloc_hist(c, nsteps):
     return hist, iters, flags
 
 
-def _workspace(c, r):
-    """Reduced system Ar | br, W^T u and the per-step right-hand side G = M u^n + dt F."""
-    f64 = dict(dtype=torch.float64, device=c.device)
-    return (torch.zeros((c.B, r, r), **f64), torch.zeros((c.B, r), **f64), torch.zeros((c.B, r), **f64),
-            torch.empty((c.B, c.N), **f64))
+def _host_loop(c, nsteps, n, step):
+    """The frame of the host-driven loops for ``n`` reduced unknowns; ``step(k, U, st, Ar, br, wtu, G)`` iterates time
+    step k from the state U (B, N), with G = M u^n + dt F and all samples active, and returns the new state."""
+    hist, iters, flags = _alloc_hist(c, nsteps)
+    f64 = dict(dtype=torch.float64, device=c.device)     # the reduced system Ar | br, W^T u and G = M u^n + dt F
+    Ar, br, wtu = torch.zeros((c.B, n, n), **f64), torch.zeros((c.B, n), **f64), torch.zeros((c.B, n), **f64)
+    G = torch.empty((c.B, c.N), **f64)
+    st = _IterState(c, n)
+    U = c.u0.clone()
+    for k in range(nsteps):
+        _mass_rhs(c, U, G)
+        st.begin_step()
+        U = step(k, U, st, Ar, br, wtu, G)
+        iters[:, k] = st.k
+        hist[:, k + 1] = U
+    flags |= st.flags
+    return FomResult(hist, iters, flags, path="host")
 
 
 # --------------------------------------------------------------------------- POD
-def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, group, balance, launch, keep=()):
-    """What the device-side time loops (bg_rom_run, bg_rom_run_wide, bg_quad_rom_run, bg_quad_rom_run_long, bg_ann_rom_run,
-    bg_rbf_rom_run, bg_local_rom_run) share: the batched inputs, the outputs, the sample order over ``grid`` slots (``group`` samples per slot), the launch and its
+def _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance, launch, keep=(), slots=None):
+    """What the device-side time loops (_ROUTES) share: the batched inputs, the outputs, the sample order over the grid
+    (``slots``, or the route's workgroups per CU on every compute unit; ``route.group`` samples per slot), the launch and its
     FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
     entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
     flags, info, order, stream.  Nothing is synchronised: ``res.info`` is checked lazily by the caller, and the operands
     live in ``res._keep`` (inputs first, then ``keep``) as long as the result, since the launch is asynchronous."""
-    L = _lib.load()
-    opts = _lib.mesh_options(Xh, supg=supg) | options
+    grid = slots if slots is not None else _limit(route.wg_per_cu) * _cu_count(device)
+    opts = _lib.mesh_options(Xh, supg=route.supg) | options
     Xd = _as_dev(Xh, device)
     N = Xd.numel()
     u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
@@ -266,12 +319,12 @@ def _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, supg, options, grid, g
     iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
     flags = torch.zeros((B,), dtype=torch.int32, device=device)
     info = torch.zeros((B,), dtype=torch.int32, device=device)
-    order = sample_order(mu1d, grid, group) if balance else None
+    order = sample_order(mu1d, grid, route.group) if balance else None
     outputs = (_lib.ptr(hist), _lib.ptr(iters), _lib.ptr(flags), _lib.ptr(info), _lib.ptr(order), _lib.stream_ptr(device))
     with torch.cuda.device(device):
-        rc = launch(getattr(L, entry), N, B, _lib.ptr(Xd), (_lib.ptr(u0d), _lib.ptr(mu1d), _lib.ptr(mu2d)), int(opts), outputs)
-    _lib.check(rc, entry)
-    res = FomResult(hist, iters, flags, path=entry)
+        rc = launch(getattr(_lib.load(), route.entry), N, B, _lib.ptr(Xd), (_lib.ptr(u0d), _lib.ptr(mu1d), _lib.ptr(mu2d)), int(opts), outputs)
+    _lib.check(rc, route.entry)
+    res = FomResult(hist, iters, flags, path=route.entry)
     res.info = info
     res._keep = (Xd, u0d, mu1d, mu2d) + tuple(keep)
     return res
@@ -286,7 +339,7 @@ def pod_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, 
     if Phid.dim() != 2 or Phid.shape[0] != len(Xh):
         raise ValueError("Phi must have one row per mesh node")
     r = Phid.shape[1]
-    return _device_loop("bg_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+    return _device_loop(_ROUTES["bg_rom_run"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
                         lambda f, N, B, x, inputs, opts, outputs: f(
                             N, B, r, int(nsteps), proj, x, _lib.ptr(Phid), *inputs, float(dt), float(E), float(tol),
                             int(max_it), opts, *outputs), keep=(Phid,))
@@ -341,23 +394,62 @@ def _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device):
         res.hist[redo], res.iters[redo], res.flags[redo] = rr.hist, rr.iters, rr.flags
         res.info[redo] = 0
     res.redone = int(redo.numel())
+
+
+class _PaddedPodPlan:
+    """What the three streaming POD loops read, built once per basis on the device: the basis and its padded copy PhiP
+    (_padded_basis: ``cols(r)`` columns), checked against the entry's own count ``elems(N, r)``.  What the shape alone
+    decides is refused before the device is touched; every refusal is a ValueError."""
+    slots = work = None           # BlockedPodPlan: its workgroups and their workspace, one slot each
+
+    def __init__(self, route, Phi, device, row_multiple, cols, elems):
+        shape = tuple(np.shape(Phi))
+        if len(shape) != 2:
+            raise ValueError("Phi must be (N, r)")
+        N, r = shape
+        max_r, max_n = _limit(route.max_r), _limit(route.max_n)
+        if r < 1 or r > max_r:
+            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {max_r}")
+        if N < route.min_n or N > max_n:
+            raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {max_n}, not N = {N}")
+        device = _lib.require_device(device)
+        self.Phi = _as_dev(Phi, device)
+        self.N, self.r = N, r
+        self.PhiP = _padded_basis(self.Phi, N, r, row_multiple, cols(r))
+        if self.PhiP.numel() != elems(N, r):
+            raise ValueError(f"{route.entry} does not cover N = {N}, r = {r}")
+
+
+def _check_plan(plan, Xh, device):
+    if plan.N != len(Xh) or plan.Phi.device != device:
+        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
+
+
+def _run_pod_route(route, plan_type, X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E, tol, max_it, device, options, balance):
+    """pod_prom_run_wide, _blocked and _long: the plan (or the basis to build one from), the launch, the redo on the host."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    plan = Phi_or_plan if isinstance(Phi_or_plan, plan_type) else plan_type(Phi_or_plan, device)
+    _check_plan(plan, Xh, device)
+    work = () if plan.slots is None else (_lib.ptr(plan.work), plan.slots)
+    res = _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
+                           float(tol), int(max_it), opts, *work, *outputs), keep=(plan,), slots=plan.slots)
+    if route.redo:
+        _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device)
     res.plan = plan
+    return res
 
 
-class WidePodPlan:
+class WidePodPlan(_PaddedPodPlan):
     """The operand bg_rom_run_wide reads, built once per basis on the device (include/burgers_hip.h): the padded copy
     PhiP [NPAD + 2][96] of ``Phi`` (row i at index i + 1, zero rows and columns around it), kept together with the basis
     it was built from, which the pivoting redo of pod_prom_run_wide uses."""
 
     def __init__(self, Phi, device):
-        L = _lib.load()
-        self.Phi = _as_dev(Phi, device)
-        if self.Phi.dim() != 2 or self.Phi.shape[1] > L.bg_rom_run_wide_max_r():
-            raise ValueError(f"Phi must be (N, r) with r <= {L.bg_rom_run_wide_max_r()}")
-        self.N, self.r = self.Phi.shape
-        self.PhiP = _padded_basis(self.Phi, self.N, self.r, 64, 96)
-        if self.PhiP.numel() != L.bg_rom_run_wide_phi_elems(self.N):
-            raise ValueError(f"bg_rom_run_wide does not cover N = {self.N}")
+        super().__init__(_ROUTES["bg_rom_run_wide"], Phi, device, 64, lambda r: 96,
+                         lambda N, r: _lib.load().bg_rom_run_wide_phi_elems(N))
 
 
 def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0,
@@ -368,46 +460,26 @@ def pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E=0.0, tol=1e-6, m
     path (LU with partial pivoting); finding them reads ``info`` back, so unlike the other device-side loops this wrapper
     synchronises the host.  ``Phi``: the basis, or a WidePodPlan of it to reuse across calls (``res.plan``; ``res.PhiP`` is
     its padded copy)."""
-    device = _lib.require_device(device)
-    Xh = check_mesh(X)
-    plan = Phi if isinstance(Phi, WidePodPlan) else WidePodPlan(Phi, device)
-    if plan.N != len(Xh) or plan.Phi.device != device:
-        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
-    res = _device_loop("bg_rom_run_wide", Xh, u0, mu1, mu2, nsteps, device, True, options, _cu_count(device), 1, balance,
-                       lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
-                           float(tol), int(max_it), opts, *outputs), keep=(plan,))
-    _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device)
-    res.PhiP = plan.PhiP                                 # the padded copy the kernel read (what wide results carried before)
+    res = _run_pod_route(_ROUTES["bg_rom_run_wide"], WidePodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it,
+                         device, options, balance)
+    res.PhiP = res.plan.PhiP                             # the padded copy the kernel read (what wide results carried before)
     return res
 
 
-class BlockedPodPlan:
+class BlockedPodPlan(_PaddedPodPlan):
     """What bg_rom_run_blocked reads and writes besides the batch, built once per basis on the device
     (include/burgers_hip.h): the padded copy PhiP [NPAD + 2][RP] of ``Phi`` (row i at index i + 1, zero rows and columns
     around it), the workspace of ``slots`` slots (one per workgroup; default: one per compute unit, the kernel's LDS
     admits one workgroup per CU) and the basis itself, which the pivoting redo of pod_prom_run_blocked uses."""
 
     def __init__(self, Phi, device, slots=None):
-        L = _lib.load()
-        shape = tuple(np.shape(Phi))
-        if len(shape) != 2:
-            raise ValueError("Phi must be (N, r)")
-        N, r = shape
-        if r < 1 or r > L.bg_rom_run_blocked_max_r():
-            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {L.bg_rom_run_blocked_max_r()}")
-        if N < 3 or N > 512:
-            raise ValueError(f"bg_rom_run_blocked covers 3 <= N <= 512, not N = {N}")
-        device = _lib.require_device(device)
-        self.Phi = _as_dev(Phi, device)
-        self.N, self.r = N, r
-        self.slots = int(slots) if slots is not None else _cu_count(device)
+        super().__init__(_ROUTES["bg_rom_run_blocked"], Phi, device, 8, lambda r: (r + 15) // 16 * 16,
+                         _lib.load().bg_rom_run_blocked_phi_elems)
+        self.slots = int(slots) if slots is not None else _cu_count(self.Phi.device)
         if self.slots < 1:
             raise ValueError("slots must be positive")
-        self.PhiP = _padded_basis(self.Phi, N, r, 8, (r + 15) // 16 * 16)
-        assert self.PhiP.numel() == L.bg_rom_run_blocked_phi_elems(N, r)
-        self.work = torch.empty((self.slots, L.bg_rom_run_blocked_work_elems(N, r)), dtype=torch.float64,
-                                device=self.Phi.device)
+        self.work = torch.empty((self.slots, _lib.load().bg_rom_run_blocked_work_elems(self.N, self.r)),
+                                dtype=torch.float64, device=self.Phi.device)
 
 
 def pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
@@ -417,39 +489,16 @@ def pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, 
     Samples whose elimination would have needed a row exchange come back marked and are redone through the library
     path, as in pod_prom_run_wide (so this wrapper synchronises the host).  ``Phi_or_plan``: the basis, or a
     BlockedPodPlan of it to reuse across calls (``res.plan``)."""
-    device = _lib.require_device(device)
-    Xh = check_mesh(X)
-    plan = Phi_or_plan if isinstance(Phi_or_plan, BlockedPodPlan) else BlockedPodPlan(Phi_or_plan, device)
-    if plan.N != len(Xh) or plan.Phi.device != device:
-        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
-    res = _device_loop("bg_rom_run_blocked", Xh, u0, mu1, mu2, nsteps, device, True, options, plan.slots, 1, balance,
-                       lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
-                           float(tol), int(max_it), opts, _lib.ptr(plan.work), plan.slots, *outputs), keep=(plan,))
-    _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device)
-    return res
+    return _run_pod_route(_ROUTES["bg_rom_run_blocked"], BlockedPodPlan, X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E,
+                          tol, max_it, device, options, balance)
 
 
-class LongPodPlan:
+class LongPodPlan(_PaddedPodPlan):
     """The operand bg_rom_run_long reads, built once per basis on the device (include/burgers_hip.h): the padded copy
     PhiP [NPAD + 2][40] of ``Phi`` (row i at index i + 1, NPAD = N rounded up to 64, zero rows and columns around it)."""
 
     def __init__(self, Phi, device):
-        L = _lib.load()
-        shape = tuple(np.shape(Phi))
-        if len(shape) != 2:
-            raise ValueError("Phi must be (N, r)")
-        N, r = shape
-        if r < 1 or r > L.bg_rom_run_long_max_r():
-            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {L.bg_rom_run_long_max_r()}")
-        if N < 3 or N > L.bg_rom_run_long_max_n():
-            raise ValueError(f"bg_rom_run_long covers 3 <= N <= {L.bg_rom_run_long_max_n()}, not N = {N}")
-        device = _lib.require_device(device)
-        self.Phi = _as_dev(Phi, device)
-        self.N, self.r = N, r
-        self.PhiP = _padded_basis(self.Phi, N, r, 64, 40)
-        if self.PhiP.numel() != L.bg_rom_run_long_phi_elems(N, r):
-            raise ValueError(f"bg_rom_run_long does not cover N = {N}, r = {r}")
+        super().__init__(_ROUTES["bg_rom_run_long"], Phi, device, 64, lambda r: 40, _lib.load().bg_rom_run_long_phi_elems)
 
 
 def pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None, options=0,
@@ -457,18 +506,8 @@ def pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol
     """``pod_prom_burgers`` for meshes of up to bg_rom_run_long_max_n() = 1024 nodes and bases of up to 40 modes with the
     whole time loop on the device (bg_rom_run_long): the basis streams through LDS, the pivoting repair runs inside the
     call, nothing is synchronised.  ``Phi_or_plan``: the basis, or a LongPodPlan of it to reuse across calls (``res.plan``)."""
-    device = _lib.require_device(device)
-    Xh = check_mesh(X)
-    plan = Phi_or_plan if isinstance(Phi_or_plan, LongPodPlan) else LongPodPlan(Phi_or_plan, device)
-    if plan.N != len(Xh) or plan.Phi.device != device:
-        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
-    grid = _lib.load().bg_rom_run_long_workgroups_per_cu() * _cu_count(device)
-    res = _device_loop("bg_rom_run_long", Xh, u0, mu1, mu2, nsteps, device, True, options, grid, 1, balance,
-                       lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.r, int(nsteps), proj, x, _lib.ptr(plan.PhiP), *inputs, float(dt), float(E),
-                           float(tol), int(max_it), opts, *outputs), keep=(plan,))
-    res.plan = plan
-    return res
+    return _run_pod_route(_ROUTES["bg_rom_run_long"], LongPodPlan, X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E, tol,
+                          max_it, device, options, balance)
 
 
 def check_singular(res):
@@ -477,6 +516,23 @@ def check_singular(res):
     if info is not None and bool(info.ne(0).any()):
         raise SingularReducedSystem("Singular matrix")
     return res
+
+
+def _pod_route(N, r, fused=True, blocked=False, long_mesh=False):
+    """Which way pod_prom_run takes an (N, r) basis, by the library's limits alone: a device loop's entry point, "library"
+    or "host"; the first test that applies wins (the table in DESIGN.md, "Host side of the device-side loops")."""
+    run, wide, blk, long = (_ROUTES["bg_rom_run" + k] for k in ("", "_wide", "_blocked", "_long"))
+    if long_mesh and fused and run.max_n < N <= _limit(long.max_n) and r <= _limit(long.max_r):
+        return long.entry
+    if blocked and fused and _limit(wide.max_r) < r <= _limit(blk.max_r) and N <= blk.max_n:
+        return blk.entry
+    if fused and _limit(run.max_r) < r <= _limit(wide.max_r) and N <= wide.max_n:
+        return wide.entry
+    if r > _limit("bg_rom_max_r") or N > _limit("bg_rom_max_n"):
+        return "library"
+    if fused and r <= _limit(run.max_r):
+        return run.entry
+    return "host"
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
@@ -488,35 +544,22 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
     N <= 512 take the device-side loop bg_rom_run_blocked instead of the library path.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_max_n() with r <= bg_rom_run_long_max_r()
     take the device-side loop bg_rom_run_long instead of the library path."""
-    if projection not in ("Galerkin", "LSPG"):
-        raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
-    proj = PROJ[projection.lower()]
-    L = _lib.load()
-    r_in, n_in = np.shape(Phi)[1], np.shape(Phi)[0]
-    if long_mesh and fused and 512 < n_in <= L.bg_rom_run_long_max_n() and r_in <= L.bg_rom_run_long_max_r():
-        return check_singular(pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
-    if blocked and fused and L.bg_rom_run_wide_max_r() < r_in <= L.bg_rom_run_blocked_max_r() and n_in <= 512:
-        return check_singular(pod_prom_run_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
-    if fused and L.bg_rom_run_max_r() < r_in <= L.bg_rom_run_wide_max_r() and n_in <= 512:
-        return check_singular(pod_prom_run_wide(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
-    if r_in > L.bg_rom_max_r() or n_in > L.bg_rom_max_n():
+    proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh)
+    if route == "library":
         return _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device)
-    if fused and r_in <= L.bg_rom_run_max_r():
-        return check_singular(pod_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
+    if route != "host":
+        run = {"bg_rom_run": pod_prom_run_fused, "bg_rom_run_wide": pod_prom_run_wide,
+               "bg_rom_run_blocked": pod_prom_run_blocked, "bg_rom_run_long": pod_prom_run_long}[route]
+        return check_singular(run(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     Phid = _as_dev(Phi, c.device)
     if Phid.shape[0] != c.N:
         raise ValueError("Phi must have one row per mesh node")
     r = Phid.shape[1]
-    PhiT = Phid.t().contiguous()
-    hist, iters, flags = _alloc_hist(c, nsteps)
-    Ar, br, wtu, G = _workspace(c, r)
-    st = _IterState(c, r)
     q = torch.zeros((c.B, r), dtype=torch.float64, device=c.device)
-    U0 = c.u0.clone()
-    for n in range(nsteps):
-        _mass_rhs(c, U0, G)
-        st.begin_step()
+
+    def step(n, U0, st, Ar, br, wtu, G):
         first = n == 0                      # u0 is not in span(Phi): the very first assembly reads it from HBM
         while True:
             if first:
@@ -527,10 +570,9 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
             if st.solve_update(1, Ar, br, wtu, q, tol, max_it) == 0:     # q = Phi^T U0 + dq (:767-776)
                 break
         rom_lift(c, Phid, q, U0)            # U[:, n+1] = Phi q                            (:779)
-        iters[:, n] = st.k
-        hist[:, n + 1] = U0
-    flags |= st.flags
-    return FomResult(hist, iters, flags, path="host")
+        return U0
+
+    return _host_loop(c, nsteps, r, step)
 
 
 def _batched_solve(A, b, considered):
@@ -647,23 +689,38 @@ def _quad_operand_copies(Phid, Hd):
     return PhiT, Phif, H3f
 
 
-class QuadFusedPlan:
+class _QuadPlan:
+    """What QuadFusedPlan and QuadLongPlan share: the H-shape check (before the device is touched), (Phi, H) on the device
+    and, for a basis the loop covers (``covers(N, n)``, which may raise instead; ``ok``), _quad_operand_copies."""
+
+    def __init__(self, Phi, H, device, covers):
+        N, n = self.N, self.n = tuple(np.shape(Phi))
+        self.ok = covers(N, n)
+        if tuple(np.shape(H)) != (N, n * (n + 1) // 2):
+            raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
+        device = _lib.require_device(device)
+        self.Phi, self.H = _as_dev(Phi, device), _as_dev(np.ascontiguousarray(H) if isinstance(H, np.ndarray) else H, device)
+        if self.ok:
+            self.PhiT, self.Phif, self.H3f = _quad_operand_copies(self.Phi, self.H)
+
+
+def _run_quad_route(route, Xh, plan, u0, mu1, mu2, dt, nsteps, proj, E, newton_tol, newton_itmax, device, balance):
+    return _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, 0, balance,
+                        lambda f, N, B, x, inputs, opts, outputs: f(
+                            N, B, plan.n, int(nsteps), proj, x, _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif), _lib.ptr(plan.H3f),
+                            *inputs, float(dt), float(E), float(newton_tol), int(newton_itmax), opts, *outputs), keep=(plan,))
+
+
+class QuadFusedPlan(_QuadPlan):
     """The operand copies bg_quad_rom_run reads, built once per (Phi, H) on the device (include/burgers_hip.h):
     Phi^T zero padded, the accumulator seeds of the tangent tiles, and H3 in the A-operand order of the matrix
     instruction.  None-like (``ok`` False) when the basis is beyond the kernel (N > 512 or n > 40)."""
 
     def __init__(self, Phi, H, device):
         L = _lib.load()
-        self.Phi, self.H = _as_dev(Phi, device), _as_dev(np.ascontiguousarray(H) if isinstance(H, np.ndarray) else H, device)
-        N, n = self.Phi.shape
-        self.N, self.n = N, n
-        if self.H.shape != (N, n * (n + 1) // 2):
-            raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
-        self.ok = N <= 512 and n <= L.bg_quad_rom_max_n()
-        if not self.ok:
-            return
-        self.PhiT, self.Phif, self.H3f = _quad_operand_copies(self.Phi, self.H)
-        assert self.H3f.numel() == L.bg_quad_rom_h3f_elems(N) and self.Phif.numel() == L.bg_quad_rom_phif_elems(N)
+        super().__init__(Phi, H, device, lambda N, n: _quad_route(N, n) == "bg_quad_rom_run")
+        assert not self.ok or (self.H3f.numel() == L.bg_quad_rom_h3f_elems(self.N)
+                               and self.Phif.numel() == L.bg_quad_rom_phif_elems(self.N))
 
 
 def quadratic_run_fused(X, u0, mu1, mu2, dt, nsteps, plan, proj, E=0.0, newton_tol=1e-6, newton_itmax=25, device=None,
@@ -674,34 +731,28 @@ def quadratic_run_fused(X, u0, mu1, mu2, dt, nsteps, plan, proj, E=0.0, newton_t
     Xh = check_mesh(X)
     if len(Xh) != plan.N:
         raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
-    return _device_loop("bg_quad_rom_run", Xh, u0, mu1, mu2, nsteps, device, False, 0, _cu_count(device), 4, balance,
-                        lambda f, N, B, x, inputs, opts, outputs: f(
-                            N, B, plan.n, int(nsteps), proj, x, _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif),
-                            _lib.ptr(plan.H3f), *inputs, float(dt), float(E), float(newton_tol), int(newton_itmax), opts,
-                            *outputs), keep=(plan,))
+    return _run_quad_route(_ROUTES["bg_quad_rom_run"], Xh, plan, u0, mu1, mu2, dt, nsteps, proj, E, newton_tol, newton_itmax,
+                           device, balance)
 
 
-class QuadLongPlan:
+class QuadLongPlan(_QuadPlan):
     """The operand copies bg_quad_rom_run_long reads, built once per (Phi, H) on the device (include/burgers_hip.h; the
     layouts of QuadFusedPlan).  Covers 512 < N <= bg_quad_rom_run_long_max_n() and n <= bg_quad_rom_run_long_max_r();
     anything else raises ValueError."""
 
     def __init__(self, Phi, H, device):
         L = _lib.load()
-        shape, hshape = tuple(np.shape(Phi)), tuple(np.shape(H))
-        if len(shape) != 2:
+        if len(np.shape(Phi)) != 2:
             raise ValueError("Phi must be (N, n)")
-        N, n = shape
-        if n < 1 or n > L.bg_quad_rom_run_long_max_r():
-            raise ValueError(f"Phi must be (N, n) with 1 <= n <= {L.bg_quad_rom_run_long_max_r()}")
-        if N <= 512 or N > L.bg_quad_rom_run_long_max_n():
-            raise ValueError(f"bg_quad_rom_run_long covers 512 < N <= {L.bg_quad_rom_run_long_max_n()}, not N = {N}")
-        if hshape != (N, n * (n + 1) // 2):
-            raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
-        device = _lib.require_device(device)
-        self.Phi, self.H = _as_dev(Phi, device), _as_dev(np.ascontiguousarray(H) if isinstance(H, np.ndarray) else H, device)
-        self.N, self.n = N, n
-        self.PhiT, self.Phif, self.H3f = _quad_operand_copies(self.Phi, self.H)
+
+        def covers(N, n):
+            if n < 1 or n > L.bg_quad_rom_run_long_max_r():
+                raise ValueError(f"Phi must be (N, n) with 1 <= n <= {L.bg_quad_rom_run_long_max_r()}")
+            if N <= 512 or N > L.bg_quad_rom_run_long_max_n():
+                raise ValueError(f"bg_quad_rom_run_long covers 512 < N <= {L.bg_quad_rom_run_long_max_n()}, not N = {N}")
+            return True
+        super().__init__(Phi, H, device, covers)
+        N, n = self.N, self.n
         if (self.PhiT.numel(), self.Phif.numel(), self.H3f.numel()) != (
                 L.bg_quad_rom_run_long_phit_elems(N), L.bg_quad_rom_run_long_phif_elems(N), L.bg_quad_rom_run_long_h3f_elems(N)):
             raise ValueError(f"bg_quad_rom_run_long does not cover N = {N}, n = {n}")
@@ -715,16 +766,21 @@ def quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_H_or_plan, proj, E=0.0, 
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     plan = Phi_H_or_plan if isinstance(Phi_H_or_plan, QuadLongPlan) else QuadLongPlan(*Phi_H_or_plan, device)
-    if plan.N != len(Xh) or plan.Phi.device != device:
-        raise ValueError("Phi must have one row per mesh node (and a plan must live on the device of the call)")
-    grid = _lib.load().bg_quad_rom_run_long_workgroups_per_cu() * _cu_count(device)
-    res = _device_loop("bg_quad_rom_run_long", Xh, u0, mu1, mu2, nsteps, device, False, 0, grid, 4, balance,
-                       lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.n, int(nsteps), proj, x, _lib.ptr(plan.PhiT), _lib.ptr(plan.Phif),
-                           _lib.ptr(plan.H3f), *inputs, float(dt), float(E), float(newton_tol), int(newton_itmax), opts,
-                           *outputs), keep=(plan,))
+    _check_plan(plan, Xh, device)
+    res = _run_quad_route(_ROUTES["bg_quad_rom_run_long"], Xh, plan, u0, mu1, mu2, dt, nsteps, proj, E, newton_tol,
+                          newton_itmax, device, balance)
     res.plan = plan
     return res
+
+
+def _quad_route(N, n, fused=True, long_mesh=False):
+    """Which way quadratic_run takes an (N, n) manifold: a device-side loop's entry point, or "host"."""
+    quad, long = _ROUTES["bg_quad_rom_run"], _ROUTES["bg_quad_rom_run_long"]
+    if long_mesh and fused and quad.max_n < N <= _limit(long.max_n) and n <= _limit(long.max_r):
+        return long.entry
+    if fused and N <= quad.max_n and n <= _limit(quad.max_r):
+        return quad.entry
+    return "host"
 
 
 def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0, newton_tol=1e-6,
@@ -736,23 +792,17 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_quad_rom_run_long_max_n() with n <=
     bg_quad_rom_run_long_max_r() take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration
     (``plan`` may then be a QuadLongPlan)."""
-    p = projection.lower()
-    if p not in PROJ:
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    proj = PROJ[p]
-    if long_mesh and fused:
-        L = _lib.load()
-        n_in, r_in = np.shape(Phi)[0], np.shape(Phi)[1]
-        if 512 < n_in <= L.bg_quad_rom_run_long_max_n() and r_in <= L.bg_quad_rom_run_long_max_r():
-            what = plan if isinstance(plan, QuadLongPlan) else (Phi, H)
-            return check_singular(quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, what, proj, E, newton_tol, newton_itmax, device))
+    proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
+    if long_mesh and fused and _quad_route(np.shape(Phi)[0], np.shape(Phi)[1], long_mesh=True) == "bg_quad_rom_run_long":
+        what = plan if isinstance(plan, QuadLongPlan) else (Phi, H)
+        return check_singular(quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, what, proj, E, newton_tol, newton_itmax, device))
     if isinstance(plan, QuadLongPlan):
         plan = None
     if fused:
         dev = _lib.require_device(device)
         if plan is None:
             plan = QuadFusedPlan(Phi, H, dev)
-        if plan.ok:
+        if plan.ok:                                      # _quad_route(N, n) of the plan's own basis
             return check_singular(quadratic_run_fused(X, u0, mu1, mu2, dt, nsteps, plan, proj, E, newton_tol, newton_itmax, dev))
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     Phid, Hd = _as_dev(Phi, c.device), _as_dev(np.ascontiguousarray(H) if isinstance(H, np.ndarray) else H, c.device)
@@ -776,9 +826,6 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
                        "bg_quad_features")
         return feat @ WT
 
-    hist, iters, flags = _alloc_hist(c, nsteps)
-    Ar, br, _, G = _workspace(c, n)
-    st = _IterState(c, n)
     H3t = H3.t().contiguous()
     Phi_flat = Phid.reshape(1, c.N * n)
     per = int(c.L.bg_rom_frag_elems(c.N, n))
@@ -787,12 +834,10 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
         NP = int(c.L.bg_rom_frag_pad(n))
         H3p = torch.nn.functional.pad(H3.reshape(c.N, n, n), (0, NP - n)).contiguous()
         qpad = torch.zeros((c.B, NP), dtype=torch.float64, device=c.device)
-    Un = c.u0.clone()
-    for m in range(nsteps):
-        _mass_rhs(c, Un, G)
+
+    def step(m, Un, st, Ar, br, _, G):
         q = (Un @ Phid).contiguous()                         # first guess            (:1129)
         u = decode(q).contiguous()
-        st.begin_step()
         while True:
             if Wf is not None:                               # fused HIP tangent -> fragment-major W -> MFMA reduce
                 if NP != n:
@@ -810,19 +855,15 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
             left = st.solve_update(2, Ar, br, None, q, newton_tol, newton_itmax)     # q += dq (:1161-1169)
             u = decode(q).contiguous()                       # inactive samples keep their q, hence their u
             if left == 0:
-                break
-        iters[:, m] = st.k
-        hist[:, m + 1] = u
-        Un = u
-    flags |= st.flags                                        # HIT_CAP = "Newton did not converge" (:1171)
-    return FomResult(hist, iters, flags, path="host")
+                return u
+
+    return _host_loop(c, nsteps, n, step)                    # HIT_CAP = "Newton did not converge" (:1171)
 
 
 # ----------------------------------------------------------------------- POD-ANN
 def _mlp_layers(model):
     """Recognise a plain MLP: nn.Sequential of Linear / ELU|ReLU|Tanh, or the reference's POD_ANN
     class (fc1..fcK + self.elu, POD-ANN/pod_ann.py:38-56).  Returns [(Linear, act-or-None)] or None."""
-    import torch.nn as nn
     acts = (nn.ELU, nn.ReLU, nn.Tanh)
     if isinstance(model, nn.Sequential):
         mods = list(model)
@@ -847,7 +888,6 @@ def _mlp_layers(model):
 
 def _mlp_forward_jacobian(layers, x, want_jac=True):
     """Forward pass and forward-mode input-Jacobian of a recognised MLP as batched GEMMs."""
-    import torch.nn as nn
     J = None
     for lin, act in layers:
         z = torch.addmm(lin.bias, x, lin.weight.t()) if lin.bias is not None else x @ lin.weight.t()
@@ -909,14 +949,12 @@ class AnnEvaluator:
         self.fused = self.layers is not None and self.dtype == torch.float32 and device.type == "cuda"
         if not self.fused:
             return
-        import torch.nn as nn
         L = _lib.load()
         self.q_in = torch.zeros((B, n), dtype=torch.float64, device=device)
         x0 = torch.zeros((B, 1 + n, n), dtype=torch.float32, device=device)
         x0[:, 1:, :] = torch.eye(n, dtype=torch.float32, device=device)
-        kinds = {type(None): _lib.BG_ACT_NONE, nn.ELU: _lib.BG_ACT_ELU, nn.ReLU: _lib.BG_ACT_RELU, nn.Tanh: _lib.BG_ACT_TANH}
         plan = [(lin.weight.detach().t().contiguous(), None if lin.bias is None else lin.bias.detach().contiguous(),
-                 kinds[type(act)], float(getattr(act, "alpha", 1.0))) for lin, act in self.layers]
+                 _ACT_KINDS[type(act)], float(getattr(act, "alpha", 1.0))) for lin, act in self.layers]
 
         def run():
             x0[:, 0, :] = self.q_in                                           # fp64 -> fp32 like q.to(float32)
@@ -1021,20 +1059,15 @@ def _ann_fused_plan(model, n, nbar, N, dtype, device):
     those pointers refer to), or None when the device-side loop does not apply (not a plain fp32 MLP the evaluator
     recognises, or beyond bg_ann_rom_limits)."""
     import ctypes
-    import torch.nn as nn
     if dtype != torch.float32 or N > 512:
         return None
     ann = AnnEvaluator(model, n, dtype)
     if ann.layers is None:
         return None
-    L = _lib.load()
-    lim = [ctypes.c_int() for _ in range(4)]
-    L.bg_ann_rom_limits(*[ctypes.byref(v) for v in lim])
-    max_n, max_nbar, max_w, max_l = (v.value for v in lim)
-    kinds = {type(None): _lib.BG_ACT_NONE, nn.ELU: _lib.BG_ACT_ELU, nn.ReLU: _lib.BG_ACT_RELU, nn.Tanh: _lib.BG_ACT_TANH}
+    max_n, max_nbar, max_w, max_l = _lib.limits("bg_ann_rom_limits", 4)
     widths = [ann.layers[0][0].in_features] + [lin.out_features for lin, _ in ann.layers]
     if (n > max_n or nbar > max_nbar or len(ann.layers) > max_l or max(widths[1:]) > max_w or widths[0] != n
-            or widths[-1] != nbar or any(type(act) not in kinds for _, act in ann.layers)):
+            or widths[-1] != nbar or any(type(act) not in _ACT_KINDS for _, act in ann.layers)):
         return None
     f32 = dict(dtype=torch.float32, device=device)
     # W^T zero-padded to [in rounded up to 4][out rounded up to 8]: a thread fetches the weights of 8 outputs of one input
@@ -1047,7 +1080,7 @@ def _ann_fused_plan(model, n, nbar, N, dtype, device):
         nl, (ctypes.c_int * (nl + 1))(*widths),
         (ctypes.c_void_p * nl)(*[w.data_ptr() for w in wts]),
         (ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in biases]),
-        (ctypes.c_int * nl)(*[kinds[type(act)] for _, act in ann.layers]),
+        (ctypes.c_int * nl)(*[_ACT_KINDS[type(act)] for _, act in ann.layers]),
         (ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in ann.layers])))
 
 
@@ -1070,7 +1103,7 @@ def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0,
     UT = torch.zeros((-(-(n + nbar) // 8) * 8, N), dtype=torch.float64, device=device)     # [U_p^T; U_s^T; zero rows]
     UT[:n] = Up.t()
     UT[n:n + nbar] = Us.t()
-    return _device_loop("bg_ann_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+    return _device_loop(_ROUTES["bg_ann_rom_run"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
                         lambda f, N, B, x, inputs, opts, outputs: f(
                             N, B, n, nbar, int(nsteps), proj, x, _lib.ptr(UT), *inputs, *plan.args, float(dt), float(E),
                             float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
@@ -1082,10 +1115,7 @@ def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG",
     reference uses float32, :1219,:1241); everything else is fp64.  ``fused`` (default): the device-side time loop
     bg_ann_rom_run when the closure is a plain float32 MLP within bg_ann_rom_limits; otherwise, or with
     ``fused=False``, the batched iteration driven from the host (MLP layers as GEMMs through PyTorch-ROCm)."""
-    p = projection.lower()
-    if p not in PROJ:
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    proj = PROJ[p]
+    proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
     if fused and ann_dtype == torch.float32:
         res = pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device)
         if res is not None:
@@ -1099,29 +1129,22 @@ def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG",
     ann = AnnEvaluator(model, n, ann_dtype)
     qs = torch.zeros((c.B, Us.shape[1]), dtype=torch.float64, device=c.device)
     ann.bind(c.B, n, c.device, tangent.jt, qs)
-    hist, iters, flags = _alloc_hist(c, nsteps)
-    Ar, br, _, G = _workspace(c, n)
-    st = _IterState(c, n)
-    U0 = c.u0.clone()
+
+    def step(nt, U0, st, Ar, br, _, G):
+        qp = (U0 @ Up).contiguous()                                         # (:1197)
+        ann.eval(qp)                                                        # dN at the first guess (:1219)
+        while True:
+            rom_reduce(c, tangent.gemm(), U0, G, proj, True, st.active, Ar, br, None, colmajor=True)   # (:1224)
+            left = st.solve_update(3, Ar, br, None, qp, tol, max_it)        # q_p += dq           (:1237-1244)
+            ann.eval(qp)                            # q_s = N(q_p) for the decode (:1241) and dN for the next pass
+            U0 = (qp @ UpT + qs @ UsT).contiguous()                         # (:1242)
+            if left == 0:
+                return U0
+
     try:
-        for nt in range(nsteps):
-            _mass_rhs(c, U0, G)
-            qp = (U0 @ Up).contiguous()                                         # (:1197)
-            st.begin_step()
-            ann.eval(qp)                                                        # dN at the first guess (:1219)
-            while True:
-                rom_reduce(c, tangent.gemm(), U0, G, proj, True, st.active, Ar, br, None, colmajor=True)   # (:1224)
-                left = st.solve_update(3, Ar, br, None, qp, tol, max_it)        # q_p += dq           (:1237-1244)
-                ann.eval(qp)                            # q_s = N(q_p) for the decode (:1241) and dN for the next pass
-                U0 = (qp @ UpT + qs @ UsT).contiguous()                         # (:1242)
-                if left == 0:
-                    break
-            iters[:, nt] = st.k
-            hist[:, nt + 1] = U0
-        flags |= st.flags
+        return _host_loop(c, nsteps, n, step)
     finally:
         ann.release()               # also on an exception (SingularReducedSystem): never leave the graph to the collector
-    return FomResult(hist, iters, flags, path="host")
 
 
 # ----------------------------------------------------------------------- POD-RBF
@@ -1186,8 +1209,6 @@ class RbfFusedPlan:
     beyond bg_rbf_rom_limits (N > 512, n > 20, nbar > 128 or too many centres)."""
 
     def __init__(self, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device):
-        import ctypes
-        L = _lib.load()
         self.Up, self.Us = _as_dev(U_p, device), _as_dev(U_s, device)
         if self.Up.dim() != 2 or self.Us.dim() != 2 or self.Up.shape[0] != self.Us.shape[0]:
             raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
@@ -1197,9 +1218,7 @@ class RbfFusedPlan:
         if rbf.n != self.n or rbf.Wd.shape[1] != self.nbar:
             raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
         self.Ns, self.kind, self.eps = rbf.Ns, rbf.kind, rbf.eps
-        lim = [ctypes.c_int() for _ in range(3)]
-        L.bg_rbf_rom_limits(*[ctypes.byref(v) for v in lim])
-        max_n, max_nbar, max_ns = (v.value for v in lim)
+        max_n, max_nbar, max_ns = _lib.limits("bg_rbf_rom_limits", 3)
         self.ok = self.N <= 512 and self.n <= max_n and self.nbar <= max_nbar and self.Ns <= max_ns
         if not self.ok:
             return
@@ -1221,9 +1240,7 @@ def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon
     the closure evaluated in-kernel in fp64, the reduced solve with partial pivoting.  Returns None when the closure is
     outside bg_rbf_rom_limits.  ``plan``: an RbfFusedPlan of the same closure and basis to reuse across calls
     (``res.plan``); the closure arguments are then not read again, U_p only for its shape."""
-    p = projection.lower()
-    if p not in PROJ:
-        raise ValueError("projection must be 'LSPG' or 'Galerkin'.")
+    proj = _projection(projection, "projection must be 'LSPG' or 'Galerkin'.")
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     if plan is None:
@@ -1233,9 +1250,9 @@ def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon
         raise ValueError("the plan must be built for this mesh and U_p (and live on the device of the call)")
     if not plan.ok:
         return None
-    res = _device_loop("bg_rbf_rom_run", Xh, u0, mu1, mu2, nsteps, device, True, options, 2 * _cu_count(device), 1, balance,
+    res = _device_loop(_ROUTES["bg_rbf_rom_run"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
                        lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.n, plan.nbar, plan.Ns, int(nsteps), PROJ[p], plan.kind, x, _lib.ptr(plan.UT),
+                           N, B, plan.n, plan.nbar, plan.Ns, int(nsteps), proj, plan.kind, x, _lib.ptr(plan.UT),
                            _lib.ptr(plan.XtT), _lib.ptr(plan.Wd), _lib.ptr(plan.bias), _lib.ptr(plan.x_min),
                            _lib.ptr(plan.dx), float(plan.eps), *inputs, float(dt), float(E), float(tol_newton),
                            int(max_newton), opts, *outputs), keep=(plan,))
@@ -1248,10 +1265,7 @@ def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_mi
     """Batched ``pod_rbf_prom`` (FEM/fem_burgers.py:1278-1398).  Default: the batched iteration driven from the host.
     ``fused``: the device-side time loop bg_rbf_rom_run (pod_rbf_run_fused) when the closure is within bg_rbf_rom_limits,
     otherwise the host-driven iteration as well."""
-    p = projection.lower()
-    if p not in PROJ:
-        raise ValueError("projection must be 'LSPG' or 'Galerkin'.")
-    proj = PROJ[p]
+    proj = _projection(projection, "projection must be 'LSPG' or 'Galerkin'.")
     if fused:
         res = pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
                                 projection, kernel, E, tol_newton, max_newton, device)
@@ -1263,14 +1277,9 @@ def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_mi
     n = Up.shape[1]
     UpT, UsT = Up.t().contiguous(), Us.t().contiguous()
     tangent = _ClosureTangent(Up, Us, c.B)
-    hist, iters, flags = _alloc_hist(c, nsteps)
-    Ar, br, _, G = _workspace(c, n)
-    st = _IterState(c, n)
-    U0 = c.u0.clone()
     q = torch.zeros((c.B, n), dtype=torch.float64, device=c.device)
-    for nt in range(nsteps):
-        _mass_rhs(c, U0, G)
-        st.begin_step()
+
+    def step(nt, U0, st, Ar, br, _, G):
         while True:
             qp = (U0 @ Up).contiguous()                                     # q_p = U_p^T U0        (:1352)
             tangent.jt.copy_(rbf.jacobian_t(qp))
@@ -1280,11 +1289,9 @@ def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_mi
             U1 = q @ UpT + rbf.value(q) @ UsT                               # (:1378-1381)
             U0 = torch.where(act[:, None], U1, U0).contiguous()
             if left == 0:
-                break
-        iters[:, nt] = st.k
-        hist[:, nt + 1] = U0
-    flags |= st.flags
-    return FomResult(hist, iters, flags, path="host")
+                return U0
+
+    return _host_loop(c, nsteps, n, step)
 
 
 # --------------------------------------------------------------------- local POD
@@ -1299,7 +1306,6 @@ class LocalPodPlan:
     NPAD = N rounded up to 64, zero rows and columns around it)."""
 
     def __init__(self, centres, local_bases, U_global, m, N, device, long_mesh=False):
-        import ctypes
         L = _lib.load()
         self.N, self.m = int(N), int(m)
         self.centres = _as_dev(centres, device)
@@ -1313,14 +1319,8 @@ class LocalPodPlan:
             if len(np.shape(b)) != 2 or np.shape(b)[0] != self.N:
                 raise ValueError(f"local basis {k} must have one row per mesh node (N = {self.N})")
         self.long_mesh = bool(long_mesh)
-        lim = [ctypes.c_int() for _ in range(4 if self.long_mesh else 3)]
-        if self.long_mesh:
-            L.bg_local_rom_run_long_limits(*[ctypes.byref(v) for v in lim])
-            max_n, max_r, max_m, max_c = (v.value for v in lim)
-        else:
-            L.bg_local_rom_limits(*[ctypes.byref(v) for v in lim])
-            max_n, (max_r, max_m, max_c) = 512, (v.value for v in lim)
         limits = "bg_local_rom_run_long_limits" if self.long_mesh else "bg_local_rom_limits"
+        max_n, max_r, max_m, max_c = _lib.limits(limits, 4) if self.long_mesh else (512,) + _lib.limits(limits, 3)
         self.widths_host = [int(np.shape(local_bases[c])[1]) if c in local_bases else 0 for c in range(self.C)]
         self.rmax = max(self.widths_host)
         missing = [c for c in range(self.C) if c not in local_bases]
@@ -1351,20 +1351,19 @@ class LocalPodPlan:
         self.UgT = Ug[:, :self.m].t().contiguous()
 
 
-def _local_device_loop(entry, grid, long_mesh, X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global,
+def _local_device_loop(route, X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global,
                        num_global_modes, projection, E, tol, max_it, device, plan, balance, options):
     """What local_prom_run_fused (bg_local_rom_run) and local_prom_run_long (bg_local_rom_run_long) share: the plan and
-    its checks, the launch with the ``clusters`` output, the result.  ``grid(device)``: the persistent workgroups.
-    Returns None when the plan's clustering is outside what the entry point covers."""
-    if projection not in ("Galerkin", "LSPG"):
-        raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
-    proj = PROJ[projection.lower()]
+    its checks, the launch with the ``clusters`` output, the result.  Returns None when the plan's clustering is outside
+    what the entry point covers."""
+    proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    long_mesh = route.entry == "bg_local_rom_run_long"
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     if plan is None:
         plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(Xh), device, long_mesh=long_mesh)
     if (plan.N != len(Xh) or plan.m != int(num_global_modes) or plan.centres.device != device
-            or plan.long_mesh != bool(long_mesh)):
+            or plan.long_mesh != long_mesh):
         raise ValueError("the plan must be built for this mesh, num_global_modes and entry point (and live on the device "
                          "of the call)")
     if not plan.ok:
@@ -1377,7 +1376,7 @@ def _local_device_loop(entry, grid, long_mesh, X, u0, mu1, mu2, dt, nsteps, cent
                  _lib.ptr(plan.UgT), _lib.ptr(plan.centres), *inputs, float(dt), float(E), float(tol), int(max_it), opts,
                  *outputs[:4], _lib.ptr(out["clusters"]), *outputs[4:])
 
-    res = _device_loop(entry, Xh, u0, mu1, mu2, nsteps, device, True, options, grid(device), 1, balance, launch, keep=(plan,))
+    res = _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance, launch, keep=(plan,))
     res.plan = plan
     res.clusters = out["clusters"]
     return res
@@ -1391,9 +1390,8 @@ def local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_gl
     changes.  Returns None when the clustering is outside what the kernel covers (LocalPodPlan.ok).  ``res.clusters``:
     (B, nsteps) int32, the centre index of every sample and step.  ``plan``: a LocalPodPlan of the same clustering to
     reuse across calls (``res.plan``); centres, bases and U_global are then not read again."""
-    return _local_device_loop("bg_local_rom_run", lambda d: 2 * _cu_count(d), False, X, u0, mu1, mu2, dt, nsteps, centers,
-                              local_bases, U_global, num_global_modes, projection, E, tol, max_it, device, plan, balance,
-                              options)
+    return _local_device_loop(_ROUTES["bg_local_rom_run"], X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global,
+                              num_global_modes, projection, E, tol, max_it, device, plan, balance, options)
 
 
 def local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
@@ -1409,9 +1407,16 @@ def local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_glo
         plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(check_mesh(X)), device, long_mesh=True)
     if not plan.ok:
         raise ValueError(f"bg_local_rom_run_long does not cover this clustering: {plan.reason}")
-    grid = lambda d: _lib.load().bg_rom_run_long_workgroups_per_cu() * _cu_count(d)
-    return _local_device_loop("bg_local_rom_run_long", grid, True, X, u0, mu1, mu2, dt, nsteps, None, None, None,
+    return _local_device_loop(_ROUTES["bg_local_rom_run_long"], X, u0, mu1, mu2, dt, nsteps, None, None, None,
                               num_global_modes, projection, E, tol, max_it, device, plan, balance, options)
+
+
+def _local_route(N, fused=False, long_mesh=False):
+    """The device loops local_prom_run tries for a mesh of N nodes, in this order; each is taken if the LocalPodPlan of the
+    clustering for it is ``ok`` (inside its limits, a basis for every centre), and "host" is what is left."""
+    if not fused:
+        return ()
+    return (("bg_local_rom_run_long",) if long_mesh and N > _ROUTES["bg_local_rom_run"].max_n else ()) + ("bg_local_rom_run",)
 
 
 def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
@@ -1427,20 +1432,19 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
     iteration.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= 1024 whose clustering is inside
     bg_local_rom_run_long_limits take the device-side loop bg_local_rom_run_long instead of the host-driven iteration."""
-    if projection not in ("Galerkin", "LSPG"):
-        raise ValueError(f"Projection method '{projection}' is not available. Please use 'Galerkin' or 'LSPG'.")
-    if fused and long_mesh and np.shape(X)[0] > 512:
+    proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    tries = _local_route(np.shape(X)[0], fused, long_mesh)
+    if "bg_local_rom_run_long" in tries:
         dev = _lib.require_device(device)
         plan = LocalPodPlan(centers, local_bases, U_global, num_global_modes, len(check_mesh(X)), dev, long_mesh=True)
         if plan.ok:
             return check_singular(local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, None, None, None, num_global_modes,
                                                       projection, E, tol, max_it, dev, plan=plan))
-    if fused:
+    if "bg_local_rom_run" in tries:
         res = local_prom_run_fused(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
                                    projection, E, tol, max_it, device)
         if res is not None:
             return check_singular(res)
-    proj = PROJ[projection.lower()]
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     ids = sorted(local_bases.keys())
     widths = [int(np.shape(local_bases[i])[1]) for i in ids]
@@ -1456,14 +1460,10 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
     col = torch.arange(rmax, device=c.device)
     stackT = stack.transpose(1, 2).contiguous()                              # (C, rmax, N)
     rows = torch.arange(c.B, device=c.device)
-    hist, iters, flags = _alloc_hist(c, nsteps)
     clusters = torch.zeros((c.B, nsteps), dtype=torch.int32, device=c.device)
-    Ar, br, wtu, G = _workspace(c, rmax)
-    st = _IterState(c, rmax)
     q = torch.zeros((c.B, rmax), dtype=torch.float64, device=c.device)
-    U0 = c.u0.clone()
-    for n in range(nsteps):
-        _mass_rhs(c, U0, G)
+
+    def step(n, U0, st, Ar, br, wtu, G):
         qg = U0 @ Ug                                                          # (:1011)
         cid = torch.cdist(qg, cen, compute_mode="donot_use_mm_for_euclid_dist").argmin(dim=1)   # kmeans.predict (:1012)
         slot = slot_of[cid]
@@ -1472,7 +1472,6 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
         clusters[:, n] = cid
         slot32 = slot.to(torch.int32)                                         # basis of each sample (:1013)
         pad = (col[None, :] >= width_t[slot][:, None]).to(torch.float64)      # 1 on padded reduced unknowns
-        st.begin_step()
         while True:
             rom_reduce(c, stack, U0, G, proj, True, st.active, Ar, br, wtu, w_index=slot32)
             Ar.diagonal(dim1=1, dim2=2).add_(pad * st.active[:, None].to(torch.float64))
@@ -1483,10 +1482,8 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
             U1 = torch.matmul(q, stackT)[slot, rows]                         # (C, B, N) -> (B, N)
             U0 = torch.where(act[:, None], U1, U0).contiguous()
             if left == 0:
-                break
-        iters[:, n] = st.k
-        hist[:, n + 1] = U0
-    flags |= st.flags
-    res = FomResult(hist, iters, flags, path="host")
+                return U0
+
+    res = _host_loop(c, nsteps, rmax, step)
     res.clusters = clusters
     return res
