@@ -119,6 +119,10 @@ _SIGNATURES = {
     "bg_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
     "bg_rom_run_long_phi_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_rom_run_long": _loop(5, [c_double_p]),
+    "bg_rom_run_long_wide_max_n": (ctypes.c_int, []),
+    "bg_rom_run_long_wide_max_r": (ctypes.c_int, []),
+    "bg_rom_run_long_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_rom_run_long_wide": _loop(5, [c_double_p]),
     "bg_rom_lift": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                    c_int_p, c_double_p, ctypes.c_void_p]),
     "bg_quad_features": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_double_p, ctypes.c_void_p]),

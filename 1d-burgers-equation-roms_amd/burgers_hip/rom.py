@@ -55,6 +55,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_rom_run_wide", 1, "bg_rom_run_wide_max_r", redo=True),
     _Route("bg_rom_run_blocked", 1, "bg_rom_run_blocked_max_r", min_n=3, redo=True),
     _Route("bg_rom_run_long", "bg_rom_run_long_workgroups_per_cu", "bg_rom_run_long_max_r", 3, "bg_rom_run_long_max_n"),
+    _Route("bg_rom_run_long_wide", 1, "bg_rom_run_long_wide_max_r", 3, "bg_rom_run_long_wide_max_n", redo=True),
     _Route("bg_quad_rom_run", 1, "bg_quad_rom_max_n", group=4, supg=False),
     _Route("bg_quad_rom_run_long", "bg_quad_rom_run_long_workgroups_per_cu", "bg_quad_rom_run_long_max_r", 513,
            "bg_quad_rom_run_long_max_n", group=4, supg=False),
@@ -397,7 +398,7 @@ def _redo_marked(res, Xh, plan, dt, nsteps, proj, E, tol, max_it, device):
 
 
 class _PaddedPodPlan:
-    """What the three streaming POD loops read, built once per basis on the device: the basis and its padded copy PhiP
+    """What the streaming POD loops read, built once per basis on the device: the basis and its padded copy PhiP
     (_padded_basis: ``cols(r)`` columns), checked against the entry's own count ``elems(N, r)``.  What the shape alone
     decides is refused before the device is touched; every refusal is a ValueError."""
     slots = work = None           # BlockedPodPlan: its workgroups and their workspace, one slot each
@@ -426,7 +427,7 @@ def _check_plan(plan, Xh, device):
 
 
 def _run_pod_route(route, plan_type, X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E, tol, max_it, device, options, balance):
-    """pod_prom_run_wide, _blocked and _long: the plan (or the basis to build one from), the launch, the redo on the host."""
+    """pod_prom_run_wide, _blocked, _long and _long_wide: the plan (or the basis to build one from), the launch, the redo on the host."""
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     plan = Phi_or_plan if isinstance(Phi_or_plan, plan_type) else plan_type(Phi_or_plan, device)
@@ -510,6 +511,27 @@ def pod_prom_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol
                           max_it, device, options, balance)
 
 
+class LongWidePodPlan(_PaddedPodPlan):
+    """The operand bg_rom_run_long_wide reads, built once per basis on the device (include/burgers_hip.h): the padded copy
+    PhiP [NPAD + 2][96] of ``Phi`` (WidePodPlan's layout on a mesh of up to 1024 nodes), kept together with the basis it
+    was built from, which the pivoting redo of pod_prom_run_long_wide uses."""
+
+    def __init__(self, Phi, device):
+        super().__init__(_ROUTES["bg_rom_run_long_wide"], Phi, device, 64, lambda r: 96,
+                         lambda N, r: _lib.load().bg_rom_run_long_wide_phi_elems(N))
+
+
+def pod_prom_run_long_wide(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                           options=0, balance=True):
+    """``pod_prom_burgers`` for meshes of up to bg_rom_run_long_wide_max_n() = 1024 nodes and bases of up to 96 modes with
+    the whole time loop on the device (bg_rom_run_long_wide): pod_prom_run_wide's loop and solve on pod_prom_run_long's
+    meshes.  Samples whose elimination would have needed a row exchange come back marked and are redone through the
+    library path, as in pod_prom_run_wide (so this wrapper synchronises the host).  ``Phi_or_plan``: the basis, or a
+    LongWidePodPlan of it to reuse across calls (``res.plan``)."""
+    return _run_pod_route(_ROUTES["bg_rom_run_long_wide"], LongWidePodPlan, X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj,
+                          E, tol, max_it, device, options, balance)
+
+
 def check_singular(res):
     """np.linalg.solve raises LinAlgError('Singular matrix') at :767; the device loop records it per sample."""
     info = getattr(res, "info", None)
@@ -518,12 +540,14 @@ def check_singular(res):
     return res
 
 
-def _pod_route(N, r, fused=True, blocked=False, long_mesh=False):
+def _pod_route(N, r, fused=True, blocked=False, long_mesh=False, long_wide=False):
     """Which way pod_prom_run takes an (N, r) basis, by the library's limits alone: a device loop's entry point, "library"
     or "host"; the first test that applies wins (the table in DESIGN.md, "Host side of the device-side loops")."""
-    run, wide, blk, long = (_ROUTES["bg_rom_run" + k] for k in ("", "_wide", "_blocked", "_long"))
+    run, wide, blk, long, lw = (_ROUTES["bg_rom_run" + k] for k in ("", "_wide", "_blocked", "_long", "_long_wide"))
     if long_mesh and fused and run.max_n < N <= _limit(long.max_n) and r <= _limit(long.max_r):
         return long.entry
+    if long_wide and fused and run.max_n < N <= _limit(lw.max_n) and _limit(long.max_r) < r <= _limit(lw.max_r):
+        return lw.entry
     if blocked and fused and _limit(wide.max_r) < r <= _limit(blk.max_r) and N <= blk.max_n:
         return blk.entry
     if fused and _limit(run.max_r) < r <= _limit(wide.max_r) and N <= wide.max_n:
@@ -536,21 +560,24 @@ def _pod_route(N, r, fused=True, blocked=False, long_mesh=False):
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
-                 device=None, fused=True, blocked=False, long_mesh=False):
+                 device=None, fused=True, blocked=False, long_mesh=False, long_wide=False):
     """Batched ``pod_prom_burgers``; ``projection`` is case-sensitive like the reference (:754-764).
     ``fused`` (default): the device-side time loop bg_rom_run where it applies (N <= 512, r <= 40); otherwise, or
     with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host.
     ``blocked`` (opt-in, with ``fused``): bases of bg_rom_run_wide_max_r() < r <= bg_rom_run_blocked_max_r() on
     N <= 512 take the device-side loop bg_rom_run_blocked instead of the library path.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_max_n() with r <= bg_rom_run_long_max_r()
-    take the device-side loop bg_rom_run_long instead of the library path."""
+    take the device-side loop bg_rom_run_long instead of the library path.
+    ``long_wide`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_wide_max_n() with bg_rom_run_long_max_r() < r
+    <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
-    route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh)
+    route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh, long_wide)
     if route == "library":
         return _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device)
     if route != "host":
         run = {"bg_rom_run": pod_prom_run_fused, "bg_rom_run_wide": pod_prom_run_wide,
-               "bg_rom_run_blocked": pod_prom_run_blocked, "bg_rom_run_long": pod_prom_run_long}[route]
+               "bg_rom_run_blocked": pod_prom_run_blocked, "bg_rom_run_long": pod_prom_run_long,
+               "bg_rom_run_long_wide": pod_prom_run_long_wide}[route]
         return check_singular(run(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device))
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     Phid = _as_dev(Phi, c.device)

@@ -1,6 +1,7 @@
 // rom_stream_device.hpp -- the whole POD-PROM time loop of one sample on one compute unit with the basis STREAMED through
 // LDS: the one source of bg_rom_run_wide (rom_wide.hip, 40 < r <= 96, N <= 512), bg_rom_run_long (rom_long.hip, r <= 40,
-// 513 <= N <= 1024) and bg_local_rom_run_long (rom_local_long.hip, local POD on the same meshes).
+// 513 <= N <= 1024), bg_rom_run_long_wide (rom_long_wide.hip, 40 < r <= 96 on those meshes) and bg_local_rom_run_long
+// (rom_local_long.hip, local POD on the same meshes).
 // reference: FEMBurgers.pod_prom_burgers, FEM/fem_burgers.py:709-785; local_prom_burgers, :979-1079.
 //
 // bg_rom_run (rom_fused.hip) keeps the basis in registers.  Here it streams through LDS, 64 mesh rows at a time (one pass over
@@ -15,7 +16,7 @@
 // Then the reduced system is parked in LDS over the dead slabs and solved (the kernel's own step), q = Phi^T u + dq, the
 // stopping test, and after the last iteration one lift-only sweep for U[:, n+1] = Phi q (:779).
 //
-// What the kernels do not share is stated once per kernel in a description K (WidePod, LongPod, LongLocal in the .hip files):
+// What the kernels do not share is stated once per kernel in a description K (WidePod, LongWidePod, LongPod, LongLocal):
 //   K::NB                        4-column blocks of the padded reduced dimension R = 4 NB: column NB t + c <-> (lane index t, block c)
 //   K::PS, K::SW                 doubles per row of the LDS slabs and of the parked system Ar | br | Phi^T u (16-byte aligned rows)
 //   K::NMAX                      mesh rows held: the length of u, g, h_f, dt F in LDS and of every per-node loop

@@ -9,222 +9,15 @@
 // 64-95 of a column live in two registers of lane = row mod 64; wave w owns the 4-column blocks b = w mod 4), one panel
 // of four columns at a time.  A sample whose elimination meets a multiplier above 1 (np.linalg.solve would have exchanged rows)
 // is marked BG_INFO_NEEDS_PIVOTING and redone by the caller through the library path (burgers_hip/rom.py does).
+// The solve and the description are rom_wide_device.hpp's (shared with the loop for long meshes, rom_long_wide.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
-#include "rom_stream_device.hpp"
+#include "rom_wide_device.hpp"
 
 namespace {
 
 using namespace bg;
-
-constexpr int WR = 96;                 // padded reduced dimension: column 24 t + c  <->  (lane index t, block c)
-constexpr int WNB = 24;                // 4-column blocks
-constexpr int WPS = 98;                // doubles per row of the LDS slabs and of the parked system (16-byte aligned rows)
-constexpr int WNMAX = 512;             // mesh rows
-
-typedef __attribute__((address_space(3))) double lds_double_t;
-typedef __attribute__((address_space(3))) int lds_int_t;
-
-// The 96 x 96 solve of one iteration by all four waves: ONE out-of-line copy for every wave and both halves of the panel
-// range (the wave number and the panel are run-time values here).  Inlined into the four per-wave bodies and unrolled over
-// its 24 panels it was 160 KB of straight-line code per pass and CU -- four waves streaming four different copies through
-// the instruction cache -- and took longer than the projection (111 k of 218 k clocks per pass).
-// In: the parked system S (Ar | br, LSPG: upper blocks).  Out: s_diag, s_y (x_k = y_k / d_k), s_bad[w] = guard of this wave.
-// wave w owns the column blocks b = w, w + 4, ... (six of 24); the right-hand side rides with wave 3.
-// col[s][tile][tt] = entry (row 64 tile + lane, column 4 (w + 4 s) + tt).  Contains workgroup barriers: all waves call it.
-template <bool GAL>
-__device__ __attribute__((noinline)) void wide_solve(const lds_double_t* S, lds_double_t* s_m, lds_double_t* s_diag, lds_double_t* s_y,
-                                                     lds_int_t* s_bad, int w, int lane, int r)
-{
-    double col[6][2][4], rhs[2];
-    auto entry = [&](int i, int j) -> double {   // (Ar | br)[i][j]; LSPG: the lower blocks by symmetry
-        int rr = i, cc = j;
-        if (!GAL && j < WR && (i % 24) > (j % 24)) { rr = j; cc = i; }
-        return S[rr * WPS + cc];
-    };
-#pragma unroll
-    for (int tile = 0; tile < 2; ++tile) {
-        const int row = 64 * tile + lane;
-        const bool rin = row < WR;
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                const int j = 4 * (w + 4 * s) + tt;
-                double v = 0.0;
-                if (rin) v = (row >= r || j >= r) ? ((row == j) ? 1.0 : 0.0) : entry(row, j);
-                col[s][tile][tt] = v;
-            }
-        }
-        rhs[tile] = (w == 3 && rin && row < r) ? -entry(row, WR) : 0.0;
-    }
-    double gmax = 0.0;
-    bool zero_piv = false;
-    // factor the panel p held in slot OS (pivot rows in row tile TK); multipliers of all 96 rows -> s_m[p & 1][kk][row]
-    auto factor = [&](int p, auto os_c, auto tk_c) {
-        constexpr int OS = decltype(os_c)::value, TK = decltype(tk_c)::value;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int kr = 4 * p + kk, lk = kr & 63;
-            const double piv = readlane_f64(col[OS][TK][kk], lk);
-            const double rp = rcp(piv);
-            zero_piv = zero_piv | (piv == 0.0);
-            double pvj[4];
-#pragma unroll
-            for (int jj = kk + 1; jj < 4; ++jj) pvj[jj] = readlane_f64(col[OS][TK][jj], lk);
-#pragma unroll
-            for (int tile = 0; tile < 2; ++tile) {
-                const int row = 64 * tile + lane;
-                const double m = (row != kr && row < WR) ? col[OS][tile][kk] * rp : 0.0;    // rows above the pivot too
-                gmax = fmax(gmax, (row > kr) ? fabs(m) : 0.0);
-#pragma unroll
-                for (int jj = kk + 1; jj < 4; ++jj) col[OS][tile][jj] = __builtin_fma(-m, pvj[jj], col[OS][tile][jj]);
-                if (row < WR) s_m[((p & 1) * 4 + kk) * WR + row] = m;
-            }
-        }
-    };
-    // apply panel p (multipliers m, pivot rows in row tile TK) to the block in slot SL
-    auto apply = [&](int p, auto sl_c, auto tk_c, const double (&m)[4][2]) {
-        constexpr int SL = decltype(sl_c)::value, TK = decltype(tk_c)::value;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int lk = (4 * p + kk) & 63;
-            double pv[4];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) pv[tt] = readlane_f64(col[SL][TK][tt], lk);
-#pragma unroll
-            for (int tile = 0; tile < 2; ++tile)
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) col[SL][tile][tt] = __builtin_fma(-m[kk][tile], pv[tt], col[SL][tile][tt]);
-        }
-    };
-    // `slot` is a run-time value: pick the register block with a (wave-uniform) switch
-    auto with_slot = [&](int slot, auto&& f) {
-        switch (slot) {
-            case 0: f(std::integral_constant<int, 0>{}); break;
-            case 1: f(std::integral_constant<int, 1>{}); break;
-            case 2: f(std::integral_constant<int, 2>{}); break;
-            case 3: f(std::integral_constant<int, 3>{}); break;
-            case 4: f(std::integral_constant<int, 4>{}); break;
-            default: f(std::integral_constant<int, 5>{}); break;
-        }
-    };
-    __syncthreads();                               // every wave has its columns: the parked system is dead
-    if (w == 0) factor(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-    __syncthreads();
-    // One barrier per panel: while the other waves apply panel p to their later blocks, the owner of panel p + 1 brings that
-    // block up to date first, factors it and publishes its multipliers (look-ahead), then does the rest.
-    double mprev[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
-    auto panels = [&](int p0, int p1, auto tk_c, auto tkprev_c) {   // pivots of panels [p0, p1) in row tile TK, of panel p0 - 1 in TKPREV
-#pragma unroll 1
-        for (int p = p0; p < p1; ++p) {
-            double m[4][2];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                m[kk][0] = s_m[((p & 1) * 4 + kk) * WR + lane];
-                m[kk][1] = (lane < WR - 64) ? s_m[((p & 1) * 4 + kk) * WR + 64 + lane] : 0.0;
-            }
-            const int nxt = p + 1;
-            const bool owner_next = nxt < WNB && (nxt & 3) == w;
-            const bool owner_this = p > 0 && (p & 3) == w;       // owned panel p: its other blocks still lack panel p - 1
-            if (owner_next) {
-                with_slot(nxt >> 2, [&](auto sl) {
-                    apply(p, sl, tk_c, m);
-                    if (nxt < 16) factor(nxt, sl, std::integral_constant<int, 0>{});
-                    else factor(nxt, sl, std::integral_constant<int, 1>{});
-                });
-            } else {
-                // the wave that factors the next panel leaves its other blocks for the next round (it is on the critical
-                // path: one block update + one factorisation against six block updates of the others)
-                auto own = [&](auto sl) {                  // this wave's block in slot SL
-                    const int b = w + 4 * decltype(sl)::value;
-                    if (b > p) {
-                        if (owner_this) apply(p - 1, sl, tkprev_c, mprev);
-                        apply(p, sl, tk_c, m);
-                    }
-                };
-                own(std::integral_constant<int, 0>{}); own(std::integral_constant<int, 1>{}); own(std::integral_constant<int, 2>{});
-                own(std::integral_constant<int, 3>{}); own(std::integral_constant<int, 4>{}); own(std::integral_constant<int, 5>{});
-            }
-            if (w == 3) {
-                constexpr int TK = decltype(tk_c)::value;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int lk = (4 * p + kk) & 63;
-                    const double pv = readlane_f64(rhs[TK], lk);
-                    rhs[0] = __builtin_fma(-m[kk][0], pv, rhs[0]);
-                    rhs[1] = __builtin_fma(-m[kk][1], pv, rhs[1]);
-                }
-            }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) { mprev[kk][0] = m[kk][0]; mprev[kk][1] = m[kk][1]; }
-            if (p + 1 < WNB) __syncthreads();
-        }
-    };
-    using T0 = std::integral_constant<int, 0>;
-    using T1 = std::integral_constant<int, 1>;
-    panels(0, 16, T0{}, T0{});
-    panels(16, 17, T1{}, T0{});                    // panel 16's deferred predecessor (15) has its pivots in the first row tile
-    panels(17, WNB, T1{}, T1{});
-    // what is left is diagonal: x_k = y_k / d_k.  Publish d (the owner of each column) and y (wave 3).
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            const int j = 4 * (w + 4 * s) + tt;   // this column's diagonal entry sits in row j
-            if (lane == (j & 63)) s_diag[j] = (j >> 6) ? col[s][1][tt] : col[s][0][tt];
-        }
-    }
-    if (w == 3) {
-        s_y[lane] = rhs[0];
-        if (lane < WR - 64) s_y[64 + lane] = rhs[1];
-    }
-    {
-        const unsigned long long anybad = __ballot(zero_piv | !(gmax <= 1.0));
-        if (lane == 0) s_bad[w] = anybad != 0ull;
-    }
-    __syncthreads();
-}
-
-struct WidePod {
-    using Args = StreamRunArgs;
-    static constexpr bool local = false;
-    static constexpr int NB = WNB, PS = WPS, SW = WPS, NMAX = WNMAX;
-    static constexpr bool cf_by_mesh_row = true;        // lo, di, up, R of all 512 mesh rows stay in LDS
-    static constexpr bool mirror_lspg = false;          // wide_solve reads the lower blocks by symmetry
-    static constexpr bool has_repair = false;           // marked samples go back to the caller
-#ifdef BG_WIDE_TIMING                   // diagnostic builds (tools/time_wide_rom.py --phases): kilo-clocks per phase in place of the counts
-    static constexpr bool timing = true;
-#else
-    static constexpr bool timing = false;
-#endif
-
-    // solve(Ar, -br) (:767): guarded pivot-free Gauss-Jordan, two row tiles, panels of four columns; two values of dq and q per lane.
-    // BG_OPT_FORCE_PIVOTED (tests): every sample is handed back to the caller after its first solve.
-    template <bool GAL, bool PIV, int W, class Lap>
-    static __device__ __forceinline__ void solve_update(const StreamRunArgs& a, const StreamLds& L, int r, int lane, bool& aborted, int&,
-                                                        double& nd, double& nq, const Lap& solved)
-    {
-        const double* S = L.slab;
-        const double wtu0 = (lane < r) ? S[lane * WPS + WR + 1] : 0.0;                     // Phi^T u, rows 0 .. 63
-        const double wtu1 = (64 + lane < r) ? S[(64 + lane) * WPS + WR + 1] : 0.0;         // rows 64 .. 95
-        wide_solve<GAL>((lds_double_t*)S, (lds_double_t*)L.m, (lds_double_t*)L.diag, (lds_double_t*)L.y, (lds_int_t*)L.bad, W, lane, r);
-        solved();
-        const bool tripped = ((L.bad[0] | L.bad[1] | L.bad[2] | L.bad[3]) != 0) || a.force_pivoted;   // workgroup-uniform
-        if (tripped) aborted = true;
-        const double dq0 = (lane < r) ? L.y[lane] * rcp(L.diag[lane]) : 0.0;
-        const double dq1 = (64 + lane < r) ? L.y[64 + lane] * rcp(L.diag[64 + lane]) : 0.0;
-        const double q0 = wtu0 + dq0, q1 = wtu1 + dq1;
-        wave_sum2(dq0 * dq0 + dq1 * dq1, q0 * q0 + q1 * q1, nd, nq);
-        if (W == 0) {
-            L.q[lane] = q0;
-            if (lane < WR - 64) L.q[64 + lane] = q1;
-        }
-    }
-};
 
 template <bool GAL>
 __global__ __launch_bounds__(256, 1) void rom_wide_kernel(StreamRunArgs a)

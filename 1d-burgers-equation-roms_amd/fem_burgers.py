@@ -96,16 +96,18 @@ class FEMBurgers:
         return self._finish(res, batched)
 
     # --------------------------------------------------------------- POD-Galerkin / LSPG
-    def pod_prom_burgers(self, At, nTimeSteps, u0, mu1, E, mu2, Phi, projection="Galerkin", blocked=False, long_mesh=False):
+    def pod_prom_burgers(self, At, nTimeSteps, u0, mu1, E, mu2, Phi, projection="Galerkin", blocked=False, long_mesh=False,
+                         long_wide=False):
         """POD projection ROM (reference :709-785).  ``projection`` is "Galerkin" or "LSPG",
         case-sensitive as in the reference; anything else raises ValueError.  ``blocked``: bases of
         97 .. 256 modes take the device-side loop bg_rom_run_blocked instead of the library path.
         ``long_mesh``: meshes of 513 .. 1024 nodes with at most 40 modes take the device-side loop bg_rom_run_long
-        instead of the library path."""
+        instead of the library path.  ``long_wide``: meshes of 513 .. 1024 nodes with 41 .. 96 modes take the device-side
+        loop bg_rom_run_long_wide instead of the library path."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                 np.asarray(Phi, dtype=np.float64), projection=projection, E=E, blocked=blocked,
-                                long_mesh=long_mesh)
+                                long_mesh=long_mesh, long_wide=long_wide)
         return self._finish(res, batched)
 
     # ---------------------------------------------------------------- quadratic manifold

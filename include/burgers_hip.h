@@ -319,6 +319,33 @@ int bg_rom_run_long(int N, int B, int r, int nsteps, int projection, const doubl
                     int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
                     const int32_t *order, void *stream);
 
+/* bg_rom_run_long_wide -- bg_rom_run_wide for long meshes: 3 <= N <= 1024 (bg_rom_run_long_wide_max_n; meant for N > 512,
+ *   where bg_rom_run_wide ends), r <= 96 (bg_rom_run_long_wide_max_r; meant for r > 40, where bg_rom_run_long ends).
+ *   reference: FEM/fem_burgers.py:709-785.
+ *   Opt-in: the facade routes 40 < r <= 96 on N > 512 here only when asked (burgers_hip/rom.py, long_wide=True).
+ *   Same arguments, outputs and semantics as bg_rom_run_wide except:
+ *   PhiP   [NPAD + 2][96], NPAD = N rounded up to 64 (bg_rom_run_long_wide_phi_elems(N) doubles, 16-byte aligned; 0 for an N
+ *          the kernel does not cover): bg_rom_run_wide's layout -- Phi row i at row index i + 1, zero rows around and beyond
+ *          the mesh, zero columns beyond r -- built once per basis by the caller;
+ *   order  [B] or NULL; entries outside [0, B) are skipped.
+ *   info   0, or BG_INFO_NEEDS_PIVOTING for a sample whose guarded pivot-free elimination met a multiplier above 1 below
+ *          the diagonal or a zero pivot: the caller redoes that sample with a pivoting solve (there is no second kernel
+ *          here; burgers_hip/rom.py sends it through the library path).
+ *   Errors: N < 3, r < 1, B or nsteps < 0, max_it < 1, dt <= 0, a null operand or output with B > 0, PhiP not 16-byte
+ *   aligned: BG_ERR_BAD_ARG; N > 1024: BG_ERR_UNSUPPORTED_N; r > 96: BG_ERR_UNSUPPORTED_R; an unknown projection:
+ *   BG_ERR_PROJECTION; B = 0: BG_OK with nothing launched.
+ *   The loop and the 96 x 96 solve by all four waves are bg_rom_run_wide's with u, g, h_f and dt F of 1024 mesh rows and
+ *   the coefficients of one 64-row slab in LDS (csrc/rom_long_wide.hip: 147 824 B); workgroup k of G = min(B, CUs) takes
+ *   the slots k, k + G, ...  options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED (tests: every sample is handed
+ *   back as if its elimination had needed a row exchange). */
+int bg_rom_run_long_wide_max_n(void);
+int bg_rom_run_long_wide_max_r(void);
+long long bg_rom_run_long_wide_phi_elems(int N);
+int bg_rom_run_long_wide(int N, int B, int r, int nsteps, int projection, const double *x, const double *PhiP,
+                         const double *u0, const double *mu1, const double *mu2, double dt, double E, double tol,
+                         int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
+                         const int32_t *order, void *stream);
+
 /* =================================================================================
  * bg_fd_run -- batched replacement of FDBurgers.fom_burgers_newton (analytical Jacobian)
  *   reference: FD/fd_burgers.py:59-107 (time + Newton loops), residual :28-35, Jacobian :37-44,
