@@ -4,12 +4,12 @@ import ctypes
 
 import pytest
 
+from loop_cases import built_library
+
 
 @pytest.fixture(scope="module")
 def L():
-    from burgers_hip import build, lib
-    build.build_library()
-    return lib.load()
+    return built_library()
 
 
 def _limits(L, name, n):

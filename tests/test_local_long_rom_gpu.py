@@ -2,7 +2,7 @@
 against the oracle and the host-driven iteration (the default route for N > 512).
 reference: FEMBurgers.local_prom_burgers, FEM/fem_burgers.py:979-1079.
 
-Clustering (as test_local_rom_fused_gpu._dense, on the bases of test_rom_long_gpu): Phi = U_global = the 40 leading left
+Clustering (as test_local_rom_fused_gpu._dense, on loop_cases.training_snapshots): Phi = U_global = the 40 leading left
 singular vectors of the FOM snapshots (oracle, C) of the 3 x 3 training grid, 200 steps; m = 12; 11 centres at U_g^T u of
 the oracle's LSPG r = 40 POD run at mu = (4.9, 0.022), steps 0, 4, ..., 40; bases Phi[:, :w], w in DENSE_WIDTHS.
 Tolerances: 1e-10 against the oracle (every ROM parity test here), 1e-11 per sample against the host path and 1e-12 between
@@ -14,9 +14,8 @@ import pytest
 import torch
 
 from conftest import mesh, rel_l2
+from loop_cases import DENSE_WIDTHS, _margins, _worst, draw, to_np, training_snapshots
 from oracle import burgers_ref as br
-from test_local_rom_fused_gpu import DENSE_WIDTHS, _margins, _worst
-from test_rom_long_gpu import _draw, _modes
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -25,14 +24,11 @@ NT = 40
 MUS = {"LSPG": [(4.9, 0.022), (5.4, 0.029)], "Galerkin": [(4.6, 0.02), (5.3, 0.028)]}
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 @functools.lru_cache(maxsize=None)
 def _clustering(N, dt, E=0.0, seed=None, widths=tuple(DENSE_WIDTHS)):
     """(X, centres, bases, U_global) of the module docstring for one mesh."""
-    X, U = _modes(N, dt, E, seed)
+    X, _, U = training_snapshots(N, dt, E, seed)
+    U = np.ascontiguousarray(U[:, :40])
     traj = br.pod_prom_burgers(X, dt, NT, np.ones(N), 4.9, E, 0.022, U, projection="LSPG")
     centres = (U[:, :12].T @ traj[:, ::4]).T.copy()
     assert centres.shape == (11, 12)
@@ -47,13 +43,13 @@ def _check_vs_oracle(res, X, dt, mus, centres, bases, Ug, proj, E=0.0, samples=N
         U, it, cl = br.local_prom_burgers(X, dt, NT, np.ones(len(X)), mus[b][0], E, mus[b][1], centres, bases, Ug, 12,
                                           projection=proj, return_iters=True)
         sw = int((np.diff(cl) != 0).sum())
-        err = rel_l2(_np(res.hist[b]).T, U)
+        err = rel_l2(to_np(res.hist[b]).T, U)
         print(f"N={len(X)} {proj} sample {b} mu={mus[b]}: rel-L2 {err:.2e}, {sw} switches through {len(np.unique(cl))} "
               f"clusters, iterations up to {int(it.max())}")
         if min_switches is not None:
             assert sw >= min_switches, (proj, b, sw)                 # from the oracle's own output
-        assert np.array_equal(_np(res.clusters[b]), cl), (proj, b)
-        assert np.array_equal(_np(res.iters[b]), it), (proj, b)
+        assert np.array_equal(to_np(res.clusters[b]), cl), (proj, b)
+        assert np.array_equal(to_np(res.iters[b]), it), (proj, b)
         assert err <= TOL, (proj, b, err)
         paths.append(cl)
     return paths
@@ -143,14 +139,14 @@ def test_nonuniform_mesh_with_diffusion(hip, proj):
 
 @pytest.mark.parametrize("proj", ["Galerkin", "LSPG"])
 def test_matches_the_host_path_at_batch_size(hip, proj):
-    """N = 1024, B = 1024, the draw of test_rom_long_gpu._draw.  The host-driven iteration is the reference.  Samples whose
+    """N = 1024, B = 1024, the draw of loop_cases.draw.  The host-driven iteration is the reference.  Samples whose
     Picard iteration hits the 20-iteration cap in some step (BG_FLAG_HIT_CAP, equal on both paths) are left out of the
     comparison: there the iteration does not contract and rounding decides the later steps (see
     test_local_rom_fused_gpu.test_matches_the_host_path_at_batch_size).  At least 75 % of the batch must remain."""
     from burgers_hip import lib, rom
     N, dt, B = 1024, 0.025, 1024
     X, centres, bases, Ug = _clustering(N, dt)
-    mu1, mu2 = _draw(B)
+    mu1, mu2 = draw(B)
     dev = rom.local_prom_run(X, np.ones(N), mu1, mu2, dt, NT, centres, bases, Ug, 12, projection=proj, fused=True,
                              long_mesh=True)
     host = rom.local_prom_run(X, np.ones(N), mu1, mu2, dt, NT, centres, bases, Ug, 12, projection=proj)
@@ -199,7 +195,7 @@ def test_plan_reuse(hip):
     from burgers_hip import rom
     N, dt = 1024, 0.025
     X, centres, bases, Ug = _clustering(N, dt)
-    mu1, mu2 = _draw(5, seed=9)
+    mu1, mu2 = draw(5, seed=9)
     first = rom.local_prom_run_long(X, np.ones(N), mu1, mu2, dt, NT, centres, bases, Ug, 12, projection="LSPG")
     again = rom.local_prom_run_long(X, np.ones(N), mu1, mu2, dt, NT, None, None, None, 12, projection="LSPG", plan=first.plan)
     torch.cuda.synchronize()

@@ -4,12 +4,12 @@ import ctypes
 
 import pytest
 
+from loop_cases import built_library, host_pointers
+
 
 @pytest.fixture(scope="module")
 def L():
-    from burgers_hip import build, lib
-    build.build_library()
-    return lib.load()
+    return built_library()
 
 
 def test_limits_cover_the_issue_sizes(L):
@@ -21,10 +21,7 @@ def test_limits_cover_the_issue_sizes(L):
 def test_argument_validation_before_launch(L):
     from burgers_hip import lib
     null = None
-    buf = (ctypes.c_double * 8)()
-    ibuf = (ctypes.c_int32 * 8)()
-    p = ctypes.cast(buf, ctypes.POINTER(ctypes.c_double))
-    ip = ctypes.cast(ibuf, ctypes.POINTER(ctypes.c_int32))
+    p, ip = host_pointers()
 
     def run(N=512, B=4, C=4, rmax=30, m=12, nsteps=2, proj=lib.BG_PROJ_GALERKIN, ops=p, widths=ip, outs=ip, dt=0.05,
             max_it=20):

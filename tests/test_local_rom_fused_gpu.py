@@ -6,15 +6,11 @@ import pytest
 import torch
 
 from conftest import load_golden, mesh, rel_l2
+from loop_cases import DENSE_WIDTHS, _margins, _worst, to_np
 from oracle import burgers_ref as br
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-DENSE_WIDTHS = [8, 40, 17, 24, 12, 33, 25, 9, 40, 30, 20]
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _fixture():
@@ -32,11 +28,6 @@ def _dense():
     return centres, bases, g["U_global"]
 
 
-def _worst(a, b):
-    d, h = a.hist.flatten(1), b.hist.flatten(1)
-    return float(((d - h).norm(dim=1) / h.norm(dim=1)).max())
-
-
 @pytest.mark.parametrize("proj", ["Galerkin", "LSPG"])
 def test_live_fixture(hip, proj):
     from burgers_hip import rom
@@ -48,17 +39,17 @@ def test_live_fixture(hip, proj):
     torch.cuda.synchronize()
     assert res.path == "bg_local_rom_run"
     assert int(res.info.abs().sum()) == 0
-    assert rel_l2(_np(res.hist[0]).T[:, ::stride], g["U_" + proj]) < TOL
-    assert np.array_equal(_np(res.iters[0]), g["iters_" + proj])
+    assert rel_l2(to_np(res.hist[0]).T[:, ::stride], g["U_" + proj]) < TOL
+    assert np.array_equal(to_np(res.iters[0]), g["iters_" + proj])
     for b, (m1, m2) in enumerate([(float(g["mu1"]), float(g["mu2"])), (5.4, 0.029)]):
         U, it, cl = br.local_prom_burgers(X, float(g["At"]), nT, np.ones(512), m1, 0.0, m2, g["centers"], bases,
                                           g["U_global"], 12, projection=proj, return_iters=True)
-        assert rel_l2(_np(res.hist[b]).T, U) < TOL
-        assert np.array_equal(_np(res.iters[b]), it)
-        assert np.array_equal(_np(res.clusters[b]), cl)
+        assert rel_l2(to_np(res.hist[b]).T, U) < TOL
+        assert np.array_equal(to_np(res.iters[b]), it)
+        assert np.array_equal(to_np(res.clusters[b]), cl)
         assert len(np.unique(cl)) >= 2                         # the run really switches
     if proj == "LSPG":
-        cl0 = _np(res.clusters[0])
+        cl0 = to_np(res.clusters[0])
         assert cl0[120] == 0 and cl0[121] == 3                 # the switch 0 -> 3 at step 121
 
 
@@ -74,18 +65,9 @@ def test_dense_switching_vs_oracle(hip, proj, mus):
         U, it, cl = br.local_prom_burgers(X, 0.05, 150, np.ones(512), m1, 0.0, m2, centres, bases, Ug, 12,
                                           projection=proj, return_iters=True)
         assert (np.diff(cl) != 0).sum() >= 10 and len(np.unique(cl)) == 11
-        assert np.array_equal(_np(res.clusters[b]), cl)
-        assert np.array_equal(_np(res.iters[b]), it)
-        assert rel_l2(_np(res.hist[b]).T, U) < TOL
-
-
-def _margins(res, centres, Ug):
-    """Relative gap between the best and second-best squared centre distance at the start of every step (host side)."""
-    u = res.hist[:, :-1].double()                                  # u^n of every step
-    qg = u @ torch.as_tensor(Ug[:, :12], device=u.device)
-    d = ((qg[:, :, None, :] - torch.as_tensor(centres, device=u.device)) ** 2).sum(-1)
-    two = d.topk(2, dim=-1, largest=False).values
-    return (two[..., 1] - two[..., 0]) / two[..., 1].clamp_min(1e-300)
+        assert np.array_equal(to_np(res.clusters[b]), cl)
+        assert np.array_equal(to_np(res.iters[b]), it)
+        assert rel_l2(to_np(res.hist[b]).T, U) < TOL
 
 
 @pytest.mark.parametrize("proj", ["Galerkin", "LSPG"])
@@ -159,9 +141,9 @@ def test_coarse_nonuniform_mesh_with_diffusion(hip):
             U, it, cl = br.local_prom_burgers(X, 0.05, 60, np.ones(256), m1, 0.02, m2, cen, bases, Ug, 12,
                                               projection=proj, return_iters=True)
             assert (np.diff(cl) != 0).sum() >= 4
-            assert np.array_equal(_np(res.clusters[b]), cl)
-            assert np.array_equal(_np(res.iters[b]), it)
-            assert rel_l2(_np(res.hist[b]).T, U) < TOL
+            assert np.array_equal(to_np(res.clusters[b]), cl)
+            assert np.array_equal(to_np(res.iters[b]), it)
+            assert rel_l2(to_np(res.hist[b]).T, U) < TOL
 
 
 def test_extreme_widths_and_global_modes(hip):
@@ -184,9 +166,9 @@ def test_extreme_widths_and_global_modes(hip):
         for b, (m1, m2) in enumerate([(4.9, 0.022), (5.3, 0.027)]):
             U, it, cl = br.local_prom_burgers(X, 0.05, 40, np.ones(512), m1, 0.0, m2, centres, bases, Ug64, m,
                                               projection="LSPG", return_iters=True)
-            assert np.array_equal(_np(res.clusters[b]), cl)
-            assert np.array_equal(_np(res.iters[b]), it)
-            assert rel_l2(_np(res.hist[b]).T, U) < TOL
+            assert np.array_equal(to_np(res.clusters[b]), cl)
+            assert np.array_equal(to_np(res.iters[b]), it)
+            assert rel_l2(to_np(res.hist[b]).T, U) < TOL
 
 
 def test_persistent_loop_and_empty_runs(hip):
@@ -205,7 +187,7 @@ def test_persistent_loop_and_empty_runs(hip):
     for b in (0, 777, 1199):
         U, it, cl = br.local_prom_burgers(X, 0.05, 40, np.ones(512), mu1[b], 0.0, mu2[b], centres, bases, Ug, 12,
                                           projection="Galerkin", return_iters=True)
-        assert np.array_equal(_np(dev.clusters[b]), cl) and rel_l2(_np(dev.hist[b]).T, U) < TOL
+        assert np.array_equal(to_np(dev.clusters[b]), cl) and rel_l2(to_np(dev.hist[b]).T, U) < TOL
     empty = rom.local_prom_run_fused(X, np.ones(512), np.zeros(0), np.zeros(0), 0.05, 10, centres, bases, Ug, 12)
     assert tuple(empty.hist.shape) == (0, 11, 512) and tuple(empty.clusters.shape) == (0, 10)
     none = rom.local_prom_run_fused(X, np.ones(512), [4.9, 5.1], [0.022, 0.02], 0.05, 0, centres, bases, Ug, 12)
@@ -246,8 +228,8 @@ def test_plans_and_fallbacks(hip):
     assert res.path != "bg_local_rom_run"
     U, ito, cl = br.local_prom_burgers(X, 0.05, 12, np.ones(512), 4.9, 0.0, 0.022, lp["centers"], wide, lp["U_global"],
                                        12, projection="Galerkin", return_iters=True)
-    assert rel_l2(_np(res.hist[0]).T, U) < 1e-9 and np.array_equal(_np(res.iters[0]), ito)
-    assert np.array_equal(_np(res.clusters[0]), cl)
+    assert rel_l2(to_np(res.hist[0]).T, U) < 1e-9 and np.array_equal(to_np(res.iters[0]), ito)
+    assert np.array_equal(to_np(res.clusters[0]), cl)
     # a centre without a basis: the plan declines, the host path raises when that centre is predicted
     partial = {c: b for c, b in bases.items() if c != 0}
     plan = rom.LocalPodPlan(centres, partial, Ug, 12, 512, torch.device("cuda", 0))

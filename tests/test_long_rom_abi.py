@@ -1,15 +1,13 @@
 """CPU-side checks of bg_rom_run_long (the device-side POD-PROM loop for meshes of 513 .. 1024 nodes): the limits and
 sizes it reports and the argument validation that happens before anything is launched."""
-import ctypes
-
 import pytest
+
+from loop_cases import built_library, check_pod_loop_argument_validation
 
 
 @pytest.fixture(scope="module")
 def L():
-    from burgers_hip import build, lib
-    build.build_library()
-    return lib.load()
+    return built_library()
 
 
 def test_limits_cover_the_headline_mesh(L):
@@ -31,30 +29,7 @@ def test_element_counts_are_positive_and_do_not_shrink(L):
 
 
 def test_argument_validation_before_launch(L):
-    from burgers_hip import lib
-    null = None
-    buf = (ctypes.c_double * 8)()
-    ibuf = (ctypes.c_int32 * 8)()
-    p = ctypes.cast(buf, ctypes.POINTER(ctypes.c_double))
-    ip = ctypes.cast(ibuf, ctypes.POINTER(ctypes.c_int32))
-
-    def run(N=1024, B=4, r=40, nsteps=2, proj=lib.BG_PROJ_GALERKIN, dt=0.025, max_it=20, ops=p, hist=p, outs=ip):
-        return L.bg_rom_run_long(N, B, r, nsteps, proj, ops, ops, ops, ops, ops, dt, 0.0, 1e-6, max_it,
-                                 lib.BG_OPT_SUPG, hist, outs, outs, outs, null, null)
-
-    assert run(N=2) == lib.BG_ERR_BAD_ARG
-    assert run(r=0) == lib.BG_ERR_BAD_ARG
-    assert run(nsteps=-1) == lib.BG_ERR_BAD_ARG
-    assert run(max_it=0) == lib.BG_ERR_BAD_ARG
-    assert run(dt=0.0) == lib.BG_ERR_BAD_ARG
-    assert run(B=-1) == lib.BG_ERR_BAD_ARG
-    assert run(proj=9) == lib.BG_ERR_PROJECTION
-    assert run(N=L.bg_rom_run_long_max_n() + 1) == lib.BG_ERR_UNSUPPORTED_N
-    assert run(r=L.bg_rom_run_long_max_r() + 1) == lib.BG_ERR_UNSUPPORTED_R
-    assert run(ops=null) == lib.BG_ERR_BAD_ARG             # null operands, B > 0
-    assert run(hist=null) == lib.BG_ERR_BAD_ARG            # null outputs, B > 0
-    assert run(outs=null) == lib.BG_ERR_BAD_ARG
-    assert run(B=0, ops=null, hist=null, outs=null) == lib.BG_OK     # empty batch: nothing to do
+    check_pod_loop_argument_validation(L, "bg_rom_run_long", 1024, 40, L.bg_rom_run_long_max_n(), L.bg_rom_run_long_max_r())
 
 
 def test_existing_limits_are_unchanged(L):

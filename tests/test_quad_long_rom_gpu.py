@@ -11,8 +11,8 @@ import pytest
 import torch
 
 from conftest import mesh, rel_l2
+from loop_cases import draw, same, training_snapshots
 from oracle import burgers_ref as br
-from oracle import burgers_ref_c as brc
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10        # BASELINE north_star: <= 1e-10 relative L2 vs the reference
@@ -21,30 +21,12 @@ ENTRY = "bg_quad_rom_run_long"
 
 
 @functools.lru_cache(maxsize=None)
-def _snapshots(N, dt, E=0.0, seed=None):
-    """(X, S, U): the mesh (``seed``: interior nodes moved by at most 0.2 h), the snapshots and their left singular vectors."""
-    X, _ = mesh(N)
-    if seed is not None:
-        X = X.copy()
-        X[1:-1] += np.random.default_rng(seed).uniform(-0.2, 0.2, N - 2) * (100.0 / (N - 1))
-    mu1 = np.repeat([4.25, 4.875, 5.5], 3); mu2 = np.tile([0.015, 0.0225, 0.03], 3)
-    hist, _ = brc.fom_run(X, np.ones(N), mu1, mu2, dt, 200, E=E)
-    S = np.ascontiguousarray(hist.reshape(-1, N).T)
-    return X, S, np.linalg.svd(S, full_matrices=False)[0]
-
-
-@functools.lru_cache(maxsize=None)
 def _manifold(N, dt, n, E=0.0, seed=None):
-    X, S, U = _snapshots(N, dt, E, seed)
+    X, S, U = training_snapshots(N, dt, E, seed)
     Phi = np.ascontiguousarray(U[:, :n])
     q = Phi.T @ S
     H = np.ascontiguousarray(br.compute_H(br.build_Q(q), S - Phi @ q, 1e-2))
     return X, Phi, H
-
-
-def _draw(B, seed=20251121):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(4.25, 5.5, B), rng.uniform(0.015, 0.03, B)
 
 
 def _check_vs_oracle(res, X, dt, nT, mu1, mu2, Phi, H, proj, E=0.0, samples=None, tol=TOL, itmax=CAP, capped=False):
@@ -74,16 +56,11 @@ CASES = [(1024, 0.025, 40, "LSPG"), (1024, 0.025, 40, "Galerkin"), (1024, 0.025,
 def test_parity_with_the_oracle(hip, N, dt, n, proj):
     from burgers_hip import rom
     X, Phi, H = _manifold(N, dt, n)
-    mu1, mu2 = _draw(6)
+    mu1, mu2 = draw(6)
     res = rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, 12, Phi, H, projection=proj, long_mesh=True)
     torch.cuda.synchronize()
     assert res.path == ENTRY
     _check_vs_oracle(res, X, dt, 12, mu1, mu2, Phi, H, proj)
-
-
-def _same(a, b):
-    for k in ("hist", "iters", "flags", "info"):
-        assert torch.equal(getattr(a, k), getattr(b, k)), k
 
 
 @pytest.mark.parametrize("proj", ["LSPG", "Galerkin"])
@@ -93,7 +70,7 @@ def test_at_batch_size_against_the_host_driven_route(hip, proj):
     from burgers_hip import rom
     N, dt, nT, B = 1024, 0.025, 4, 1024
     X, Phi, H = _manifold(N, dt, 40)
-    mu1, mu2 = _draw(B)
+    mu1, mu2 = draw(B)
     p = rom.PROJ[proj.lower()]
     res = rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, nT, Phi, H, projection=proj, long_mesh=True)
     ref = rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, nT, Phi, H, projection=proj)
@@ -112,7 +89,7 @@ def test_at_batch_size_against_the_host_driven_route(hip, proj):
     print(f"{proj}: worst rel-L2 against the host-driven route over {B} samples {worst:.2e}")
     assert worst <= TOL
     _check_vs_oracle(res, X, dt, nT, mu1, mu2, Phi, H, proj, samples=range(0, B, B // 16))
-    _same(plain, res)
+    same(plain, res)
     permd = torch.as_tensor(perm, device=res.hist.device)
     assert torch.equal(res.hist[permd], shuf.hist) and torch.equal(res.iters[permd], shuf.iters)
     assert torch.equal(res.hist[777], one.hist[0]) and torch.equal(res.iters[777], one.iters[0])
@@ -126,7 +103,7 @@ def test_diffusion_and_nonuniform_mesh(hip, case, proj):
     E, seed = (0.01, None) if case == "diffusion" else (0.0, 21)
     X, Phi, H = _manifold(N, dt, 40, E=E, seed=seed)
     assert lib.mesh_is_uniform(X) == (seed is None)
-    mu1, mu2 = _draw(3)
+    mu1, mu2 = draw(3)
     res = rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, nT, Phi, H, projection=proj, E=E, long_mesh=True)
     torch.cuda.synchronize()
     assert res.path == ENTRY
@@ -138,7 +115,7 @@ def test_iteration_cap(hip):
     from burgers_hip import lib, rom
     N, dt = 1024, 0.025
     X, Phi, H = _manifold(N, dt, 40)
-    mu1, mu2 = _draw(3)
+    mu1, mu2 = draw(3)
     r = rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, 3, Phi, H, newton_itmax=2, long_mesh=True)
     torch.cuda.synchronize()
     assert r.path == ENTRY
@@ -185,7 +162,7 @@ def test_plan_reuse_restart_and_refusals(hip, monkeypatch):
     from burgers_hip import rom
     N, dt = 1024, 0.025
     X, Phi, H = _manifold(N, dt, 40)
-    mu1, mu2 = _draw(5, seed=9)
+    mu1, mu2 = draw(5, seed=9)
     dev = torch.device("cuda", torch.cuda.current_device())
     p = rom.PROJ["lspg"]
     first = rom.quadratic_run_long(X, np.ones(N), mu1, mu2, dt, 5, (Phi, H), p)
@@ -193,7 +170,7 @@ def test_plan_reuse_restart_and_refusals(hip, monkeypatch):
     torch.cuda.synchronize()
     assert isinstance(first.plan, rom.QuadLongPlan) and again.plan is first.plan and again.path == ENTRY
     assert torch.equal(first.plan.Phi.cpu(), torch.as_tensor(Phi))           # the plan holds the basis it was built from
-    _same(again, first)
+    same(again, first)
     # restart: the second half of a run from the state the first half ended in
     head = rom.quadratic_run_long(X, np.ones(N), mu1, mu2, dt, 2, first.plan, p)
     tail = rom.quadratic_run_long(X, head.hist[:, -1].cpu().numpy(), mu1, mu2, dt, 3, first.plan, p)
@@ -224,7 +201,7 @@ def test_order_entries_outside_the_batch_are_skipped(hip):
     from burgers_hip import lib, rom
     N, dt, B, n = 600, 0.04, 6, 40
     X, Phi, H = _manifold(N, dt, n)
-    mu1, mu2 = _draw(B, seed=3)
+    mu1, mu2 = draw(B, seed=3)
     p = rom.PROJ["galerkin"]
     ref = rom.quadratic_run_long(X, np.ones(N), mu1, mu2, dt, 3, (Phi, H), p)
     dev = ref.hist.device
@@ -278,4 +255,4 @@ def test_facade_opt_in_and_unchanged_defaults(hip):
     also = rom.quadratic_run(X5, np.ones(512), [4.8], [0.021], 0.05, 2, Phi5, H5, long_mesh=True)
     torch.cuda.synchronize()
     assert short.path == "bg_quad_rom_run" and also.path == "bg_quad_rom_run"
-    _same(short, also)
+    same(short, also)

@@ -4,12 +4,12 @@ import ctypes
 
 import pytest
 
+from loop_cases import built_library, host_pointers
+
 
 @pytest.fixture(scope="module")
 def L():
-    from burgers_hip import build, lib
-    build.build_library()
-    return lib.load()
+    return built_library()
 
 
 def test_limits_cover_the_issue_sizes(L):
@@ -22,10 +22,7 @@ def test_limits_cover_the_issue_sizes(L):
 def test_argument_validation_before_launch(L):
     from burgers_hip import lib
     null = None
-    buf = (ctypes.c_double * 8)()
-    ibuf = (ctypes.c_int32 * 8)()
-    p = ctypes.cast(buf, ctypes.POINTER(ctypes.c_double))
-    ip = ctypes.cast(ibuf, ctypes.POINTER(ctypes.c_int32))
+    p, ip = host_pointers()
 
     def run(N=512, B=4, n=17, nbar=79, Ns=300, nsteps=2, proj=lib.BG_PROJ_LSPG, kind=lib.BG_RBF_GAUSSIAN, ops=p, outs=ip):
         return L.bg_rbf_rom_run(N, B, n, nbar, Ns, nsteps, proj, kind, ops, ops, ops, ops, ops, ops, ops, 1.0, ops, ops, ops,

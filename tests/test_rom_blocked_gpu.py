@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden, mesh, rel_l2
+from loop_cases import check_pod_vs_oracle, same
 from oracle import burgers_ref as br
 
 pytestmark = pytest.mark.gpu
@@ -39,13 +40,6 @@ def _oracle(X, nT, mu1, mu2, Phi, proj, E=0.0):
     return br.pod_prom_burgers(X, 0.05, nT, np.ones(len(X)), mu1, E, mu2, Phi, projection=proj, return_iters=True)
 
 
-def _check_vs_oracle(res, X, nT, mu1, mu2, Phi, proj, E=0.0):
-    for s in range(len(mu1)):
-        U, ito = _oracle(X, nT, mu1[s], mu2[s], Phi, proj, E)
-        assert rel_l2(res.hist[s].cpu().numpy().T, U) < TOL, (proj, s)
-        assert np.array_equal(res.iters[s].cpu().numpy(), ito), (proj, s)
-
-
 @pytest.mark.parametrize("K", [160, 227])
 @pytest.mark.parametrize("proj", ["Galerkin", "LSPG"])
 def test_thesis_bases_vs_oracle(thesis_bases, K, proj):
@@ -56,7 +50,7 @@ def test_thesis_bases_vs_oracle(thesis_bases, K, proj):
     res = rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 8, Phi, rom.PROJ[proj.lower()])
     torch.cuda.synchronize()
     assert res.path == "bg_rom_run_blocked" and res.redone == 0
-    _check_vs_oracle(res, X, 8, mu1, mu2, Phi, proj)
+    check_pod_vs_oracle(res, X, 0.05, 8, mu1, mu2, Phi, proj)
 
 
 @pytest.mark.parametrize("proj", ["Galerkin", "LSPG"])
@@ -117,7 +111,7 @@ def test_padding_and_full_width(thesis_bases, K):
         res = rom.pod_prom_run_blocked(X, np.ones(512), [4.6, 5.2], [0.017, 0.026], 0.05, 4, Phi, rom.PROJ[proj.lower()])
         torch.cuda.synchronize()
         assert res.path == "bg_rom_run_blocked"
-        _check_vs_oracle(res, X, 4, [4.6, 5.2], [0.017, 0.026], Phi, proj)
+        check_pod_vs_oracle(res, X, 0.05, 4, [4.6, 5.2], [0.017, 0.026], Phi, proj)
 
 
 def _fom_basis(X, E, K, nT=200):
@@ -141,19 +135,14 @@ def test_nonuniform_mesh_with_diffusion_and_small_mesh(hip):
         res = rom.pod_prom_run_blocked(Xn, np.ones(300), [4.6, 5.2], [0.017, 0.026], 0.05, 4, Phi, rom.PROJ[proj.lower()],
                                        E=0.5)
         torch.cuda.synchronize()
-        _check_vs_oracle(res, Xn, 4, [4.6, 5.2], [0.017, 0.026], Phi, proj, E=0.5)
+        check_pod_vs_oracle(res, Xn, 0.05, 4, [4.6, 5.2], [0.017, 0.026], Phi, proj, E=0.5)
     X2, _ = mesh(200)
     Phi2 = _fom_basis(X2, 0.0, 120)
     assert np.allclose(Phi2.T @ Phi2, np.eye(120), atol=1e-10)
     for proj in ("Galerkin", "LSPG"):
         res = rom.pod_prom_run_blocked(X2, np.ones(200), [4.9], [0.022], 0.05, 4, Phi2, rom.PROJ[proj.lower()])
         torch.cuda.synchronize()
-        _check_vs_oracle(res, X2, 4, [4.9], [0.022], Phi2, proj)
-
-
-def _same(a, b):
-    for k in ("hist", "iters", "flags", "info"):
-        assert torch.equal(getattr(a, k), getattr(b, k)), k
+        check_pod_vs_oracle(res, X2, 0.05, 4, [4.9], [0.022], Phi2, proj)
 
 
 def test_scheduling_and_workspace_reuse(thesis_bases):
@@ -166,13 +155,13 @@ def test_scheduling_and_workspace_reuse(thesis_bases):
     mu1, mu2 = rng.uniform(4.25, 5.5, B), rng.uniform(0.015, 0.03, B)
     p = rom.PROJ["lspg"]
     ref = rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 3, Phi, p)
-    _same(rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 3, Phi, p, balance=False), ref)
+    same(rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 3, Phi, p, balance=False), ref)
     small = rom.BlockedPodPlan(Phi, dev, slots=3)                   # 20 samples through 3 workspace slots
     first = rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 3, small, p)
     again = rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, 3, first.plan, p)
     assert first.plan is small and again.plan is small
-    _same(first, ref)
-    _same(again, ref)
+    same(first, ref)
+    same(again, ref)
     # an order with entries outside the batch: those slots are skipped, the others are computed as ever
     L = lib.load()
     u0d = torch.ones((B, 512), dtype=torch.float64, device=dev)
@@ -239,7 +228,7 @@ def test_interface_opt_in_and_unchanged_default(thesis_bases):
     res = rom.pod_prom_run(X, np.ones(512), [4.8], [0.021], 0.05, 4, Phi, projection="LSPG", blocked=True)
     torch.cuda.synchronize()
     assert res.path == "bg_rom_run_blocked"
-    _check_vs_oracle(res, X, 4, [4.8], [0.021], Phi, "LSPG")
+    check_pod_vs_oracle(res, X, 0.05, 4, [4.8], [0.021], Phi, "LSPG")
     U = FEMBurgers(X, T).pod_prom_burgers(0.05, 4, np.ones(512), 4.8, 0.0, 0.021, Phi, projection="Galerkin", blocked=True)
     Uo, _ = _oracle(X, 4, 4.8, 0.021, Phi, "Galerkin")
     assert rel_l2(np.asarray(U), Uo) < TOL

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import load_golden, mesh, rel_l2
+from loop_cases import check_order_entries_skipped
 from oracle import burgers_ref as br
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +113,7 @@ def test_wide_plan_reuse_and_checks(hip, monkeypatch):
 def test_order_entries_outside_the_batch_are_skipped(hip):
     """Two entries of ``order`` outside [0, B): the other samples are bit-equal to a run without ``order``, the rows of the
     samples no slot names keep what the caller put there."""
-    from burgers_hip import lib, rom
+    from burgers_hip import rom
     g = load_golden("committed_pod_r96.npz")
     N, dt, B = 512, 0.05, 6
     X, _ = mesh(N)
@@ -121,22 +122,4 @@ def test_order_entries_outside_the_batch_are_skipped(hip):
     p = rom.PROJ["galerkin"]
     ref = rom.pod_prom_run_wide(X, np.ones(N), mu1, mu2, dt, 3, g["Phi"], p, balance=False)
     assert ref.redone == 0
-    dev = ref.hist.device
-    L = lib.load()
-    u0d = torch.ones((B, N), dtype=torch.float64, device=dev)
-    mu1d, mu2d, Xd = torch.as_tensor(mu1, device=dev), torch.as_tensor(mu2, device=dev), torch.as_tensor(X, device=dev)
-    hist = torch.full((B, 4, N), -7.0, dtype=torch.float64, device=dev)
-    iters = torch.zeros((B, 3), dtype=torch.int32, device=dev)
-    flags = torch.full((B,), -3, dtype=torch.int32, device=dev)
-    info = torch.zeros((B,), dtype=torch.int32, device=dev)
-    order = torch.arange(B, dtype=torch.int32, device=dev)
-    order[1], order[4] = -1, B + 5
-    rc = L.bg_rom_run_wide(N, B, 96, 3, p, lib.ptr(Xd), lib.ptr(ref.plan.PhiP), lib.ptr(u0d), lib.ptr(mu1d), lib.ptr(mu2d),
-                           dt, 0.0, 1e-6, 20, lib.mesh_options(X, supg=True), lib.ptr(hist), lib.ptr(iters), lib.ptr(flags),
-                           lib.ptr(info), lib.ptr(order), lib.stream_ptr(dev))
-    assert rc == 0
-    torch.cuda.synchronize()
-    keep = [0, 2, 3, 5]
-    assert torch.equal(hist[keep], ref.hist[keep]) and torch.equal(iters[keep], ref.iters[keep])
-    assert torch.equal(flags[keep], ref.flags[keep]) and bool((info[keep] == 0).all())
-    assert bool((hist[[1, 4]] == -7.0).all()) and bool((flags[[1, 4]] == -3).all())
+    check_order_entries_skipped("bg_rom_run_wide", ref, X, dt, mu1, mu2, p)

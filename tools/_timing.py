@@ -1,0 +1,52 @@
+"""What at least three of the tools/time_*.py scripts share: the import path, the 3 x 3 training grid and its snapshots
+built on the device, the bench's parameter draw, the warm-up plus event-timed repetitions, and the tail of the report
+line.  What a script measures, its options and its FLOP count stay in the script."""
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
+sys.path[:0] = [REPO, os.path.join(REPO, "1d-burgers-equation-roms_amd")]
+import numpy as np, torch
+
+PEAK = 78.6e12                                             # fp64 matrix peak of one MI355X, FLOP/s
+
+
+def training_snapshots(N, dt, steps=200):
+    """(X, S): the uniform mesh and the snapshot matrix of the FOM runs of the 3 x 3 training grid, on the device."""
+    from burgers_hip import fom, pod
+    X = np.linspace(0, 100, N)
+    mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
+    return X, pod.snapshot_matrix(fom.fom_run(X, np.ones(N), mu1t, mu2t, dt, steps).hist).contiguous()
+
+
+def draw(B, seed=20251121):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(4.25, 5.5, B), rng.uniform(0.015, 0.03, B)
+
+
+def time_runs(run, reps=1):
+    """One warm-up call of ``run``, then ``reps`` calls between HIP events: (ms, res), the milliseconds of each repetition
+    and the last result."""
+    run(); torch.cuda.synchronize()                                 # warm-up
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); res = run(); e1.record(); torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms, res
+
+
+def rates_of(ms, res):
+    """Sample-Newton-steps/s of each repetition (every repetition of a run does the iterations of the last)."""
+    its = int(res.iters.sum().item())
+    return [its / t * 1e3 for t in ms]
+
+
+def rates_text(rates):
+    return ", ".join(f"{v:.3g}" for v in rates) + f" -> median {float(np.median(rates)):.3g} sample-Newton-steps/s"
+
+
+def peak_text(rates, flop):
+    """``flop``: floating-point operations per sample-Newton-step."""
+    return f"{float(np.median(rates)) * flop / PEAK:.3f} of the 78.6 TFLOP/s fp64 matrix peak"

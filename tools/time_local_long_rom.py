@@ -5,26 +5,22 @@ of the 3 x 3 training grid (200 steps), snapshot SVD truncated at 40 (Phi = U_gl
 LSPG r = 40 POD run at mu = (4.9, 0.022), steps 0, 4, ..., 40, bases Phi[:, :w] for w in 8, 40, 17, 24, 12, 33, 25, 9, 40, 30, 20.
 Prints one JSON line per projection: sample-Picard-steps/s of each route (median of --reps), their ratio, the switches.
 usage: python tools/time_local_long_rom.py [--batch 1024] [--steps 40] [--n 1024] [--dt 0.025] [--reps 3] [--host]"""
-import argparse, json, os, sys
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "1d-burgers-equation-roms_amd")]
+import argparse, json
+from _timing import draw, training_snapshots
 import numpy as np, torch
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--n", type=int, default=1024); ap.add_argument("--dt", type=float, default=0.025)
 ap.add_argument("--reps", type=int, default=3); ap.add_argument("--host", action="store_true")
 a = ap.parse_args()
-from burgers_hip import fom, pod, rom
+from burgers_hip import pod, rom
 N = a.n
-X = np.linspace(0, 100, N)
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-S = pod.snapshot_matrix(fom.fom_run(X, np.ones(N), mu1t, mu2t, a.dt, 200).hist).contiguous()
+X, S = training_snapshots(N, a.dt)
 Phi = pod.pod_basis(S, n_modes=40)[0].contiguous()
 traj = rom.pod_prom_run(X, np.ones(N), [4.9], [0.022], a.dt, 40, Phi, projection="LSPG", long_mesh=True).hist[0]    # (41, N)
 centres = (traj[::4] @ Phi[:, :12]).contiguous()
 bases = {c: Phi[:, :w].contiguous() for c, w in enumerate([8, 40, 17, 24, 12, 33, 25, 9, 40, 30, 20])}
-rng = np.random.default_rng(20251121)
-mu1, mu2 = rng.uniform(4.25, 5.5, a.batch), rng.uniform(0.015, 0.03, a.batch)
+mu1, mu2 = draw(a.batch)
 plan = rom.LocalPodPlan(centres, bases, Phi, 12, N, Phi.device, long_mesh=True)
 assert plan.ok, plan.reason
 for proj in ("Galerkin", "LSPG"):

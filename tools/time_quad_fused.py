@@ -3,29 +3,22 @@
   tools/build_variant.sh qt quad_fused.hip -DBG_QUAD_TIMING [-DBG_QUAD_CHUNK=..]
   BG_LIB_PATH=1d-burgers-equation-roms_amd/build/libvar_qt.so python tools/time_quad_fused.py [--batch 1024] [--steps 40]
 Bases: this framework's own training sweep, n = 40 (as bench.py --config quadratic)."""
-import argparse, os, sys
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "1d-burgers-equation-roms_amd")]
+import argparse
 import numpy as np, torch
+from _timing import draw, time_runs, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--proj", default="LSPG")
 a = ap.parse_args()
-from burgers_hip import fom, pod, rom
+from burgers_hip import pod, rom
 N = 512
-X = np.linspace(0, 100, N)
-m1, m2 = np.meshgrid(np.linspace(4.25, 5.5, 3), np.linspace(0.015, 0.03, 3), indexing="ij")
-res = fom.fom_run(X, np.ones(N), m1.ravel(), m2.ravel(), 0.05, 500)
-Phi, H, _ = pod.build_quadratic_manifold(pod.snapshot_matrix(res.hist).contiguous(), 40, alpha=1e-2)
+X, S = training_snapshots(N, 0.05, steps=500)
+Phi, H, _ = pod.build_quadratic_manifold(S, 40, alpha=1e-2)
 dev = torch.device("cuda", torch.cuda.current_device())
 plan = rom.QuadFusedPlan(Phi, H, dev)
-rng = np.random.default_rng(20251121)
-mu1, mu2 = rng.uniform(4.25, 5.5, a.batch), rng.uniform(0.015, 0.03, a.batch)
+mu1, mu2 = draw(a.batch)
 run = lambda: rom.quadratic_run(X, np.ones(N), mu1, mu2, 0.05, a.steps, Phi, H, projection=a.proj, plan=plan)
-run(); torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record(); r = run(); e1.record(); torch.cuda.synchronize()
-ms = e0.elapsed_time(e1)
+(ms,), r = time_runs(run)
 it = r.iters[:, :9].double().cpu().numpy()
 names = ["pass start (Phi q)", "tangent tiles", "wait: tangent done", "decode", "assembly + projection", "wait: slab done", "reduce + solve + update", "step start / end"]
 npass = np.median(it[:, 8])

@@ -4,10 +4,9 @@ reference's 300-centre closure (tests/golden/rbf_n17.npz) and the bench's (mu1, 
 after a warm-up, each run synchronised before the clock stops; prints sample-Newton-steps/s of both and the worst
 per-sample rel-L2 between them.
 usage: python tools/time_rbf_rom.py [--batch 2048] [--steps 12] [--reps 3] [--projection LSPG] [--kernel gaussian]"""
-import argparse, json, os, sys, time
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "1d-burgers-equation-roms_amd")]
+import argparse, json, os, time
 import numpy as np, torch
+from _timing import GOLDEN
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=2048); ap.add_argument("--steps", type=int, default=12)
 ap.add_argument("--reps", type=int, default=3); ap.add_argument("--projection", default="LSPG")
@@ -15,7 +14,7 @@ ap.add_argument("--kernel", default="gaussian", choices=("gaussian", "imq"))
 a = ap.parse_args()
 import bench
 from burgers_hip import rom
-g = np.load(os.path.join(REPO, "tests", "golden", "rbf_n17.npz"))
+g = np.load(os.path.join(GOLDEN, "rbf_n17.npz"))
 cl = (g["U_p"], g["U_s"], g["X_train"], g["W_" + a.kernel], float(g["eps_" + a.kernel]), g["x_min"], g["x_max"],
       g["y_min"], g["y_max"])
 X = np.linspace(0.0, 100.0, 512)
