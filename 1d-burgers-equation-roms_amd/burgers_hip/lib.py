@@ -141,6 +141,14 @@ _SIGNATURES = {
                                    c_int_p, c_double_p, c_int_p, ctypes.c_void_p]),
     "bg_jacobi_sweep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_int_p, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_double, c_int_p, ctypes.c_void_p]),
+    "bg_jacobi_sweep_batched": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, c_double_p, c_double_p,
+                                               c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_int_p, ctypes.c_void_p]),
+    "bg_kmeans_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
+    # Ns, m, C, q, centres, overlap, labels (int32), d2min, member (uint64 or null), changed (int32), stream
+    "bg_kmeans_assign": (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p, c_double_p, ctypes.c_double, c_int_p, c_double_p,
+                                        ctypes.c_void_p, c_int_p, ctypes.c_void_p]),
+    # Ns, m, C, q, labels, centres (in/out), counts (int32), stream
+    "bg_kmeans_update": (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p, c_int_p, c_double_p, c_int_p, ctypes.c_void_p]),
     "bg_rbf_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_void_p]),
     "bg_mlp_act_jvp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

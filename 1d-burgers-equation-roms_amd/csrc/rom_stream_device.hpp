@@ -105,7 +105,12 @@ __device__ __forceinline__ void local_global_coords(const double* UgT, const dou
 // kmeans.predict (:1012): lane c holds |q_g - centre_c|^2 (summed in j order), then the FIRST index of the minimum over the
 // wave (a NaN distance counts as the smallest, as in np.argmin).  Every wave computes it: the cluster is workgroup-uniform
 // without a broadcast.  C <= 64.
-__device__ __forceinline__ int local_nearest_centre(const double* s_qg, const double* centres, int C, int m, int lane)
+// KEEP (the offline clustering, kmeans.hip, which labels the training snapshots with this very function so that the same q_g
+// gets the same centre there and here): *d_lane receives this lane's distance (+inf beyond C), *d_min the smallest.  The
+// time loops call it without, and compile to what they were before the parameter existed.
+template <bool KEEP = false>
+__device__ __forceinline__ int local_nearest_centre(const double* s_qg, const double* centres, int C, int m, int lane,
+                                                    double* d_lane = nullptr, double* d_min = nullptr)
 {
     double d = __builtin_inf();
     int ci = lane;
@@ -117,6 +122,7 @@ __device__ __forceinline__ int local_nearest_centre(const double* s_qg, const do
             d = __builtin_fma(e, e, d);
         }
     }
+    if constexpr (KEEP) *d_lane = d;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const double od = __shfl_xor(d, off);
@@ -125,6 +131,7 @@ __device__ __forceinline__ int local_nearest_centre(const double* s_qg, const do
         d = take ? od : d;
         ci = take ? oc : ci;
     }
+    if constexpr (KEEP) *d_min = d;
     return __builtin_amdgcn_readfirstlane(ci);
 }
 

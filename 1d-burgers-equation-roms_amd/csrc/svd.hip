@@ -12,6 +12,10 @@
 // ordering: m/2 disjoint row pairs, one 256-thread workgroup per pair.  The caller zeroes the rows at the
 // rounding level (|g|^2 <= (eps |R|_F)^2) before each sweep and raises when a sweep still rotates at its
 // sweep limit (burgers_hip/pod.py jacobi_svd).
+//
+// bg_jacobi_sweep_batched runs the same step on `count` matrices of one size in one launch (the matrix is the second grid
+// dimension): the per-cluster cores of the local POD builder, which share m, ld and the pair schedule.  Each matrix has its
+// own rotation count; one that has converged makes no rotation and its workgroups leave after the three dot products.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,11 +27,12 @@ namespace {
 
 using namespace bg;
 
-__global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
-                                                          const int32_t* __restrict__ pairs, double tol,
-                                                          int32_t* __restrict__ rotations)
+// One row pair of one matrix, by one 256-thread workgroup: the body of both kernels below, so that a matrix of a batch
+// goes through the arithmetic of a matrix on its own.
+__device__ __forceinline__ void jacobi_pair(double* __restrict__ G, double* __restrict__ J, int m, int ld,
+                                            const int32_t* __restrict__ pairs, double tol, int32_t* __restrict__ rotations,
+                                            double (&s_part)[3][4])
 {
-    __shared__ double s_part[3][4];
     const int p = pairs[2 * blockIdx.x], q = pairs[2 * blockIdx.x + 1];
     if (p < 0 || q < 0 || p >= m || q >= m) return;                 // bye of an odd-sized tournament
     double* gp = G + (size_t)p * ld;
@@ -66,6 +71,24 @@ __global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G
     if (tid == 0) atomicAdd(rotations, 1);
 }
 
+__global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
+                                                          const int32_t* __restrict__ pairs, double tol,
+                                                          int32_t* __restrict__ rotations)
+{
+    __shared__ double s_part[3][4];
+    jacobi_pair(G, J, m, ld, pairs, tol, rotations, s_part);
+}
+
+// blockIdx.y: the matrix of the batch, `stride` doubles after the one before it, with a rotation count of its own
+__global__ __launch_bounds__(256) void jacobi_pair_batched_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
+                                                                  long long stride, const int32_t* __restrict__ pairs,
+                                                                  double tol, int32_t* __restrict__ rotations)
+{
+    __shared__ double s_part[3][4];
+    const size_t off = (size_t)blockIdx.y * (size_t)stride;
+    jacobi_pair(G + off, J + off, m, ld, pairs, tol, rotations + blockIdx.y, s_part);
+}
+
 }  // namespace
 
 extern "C" int bg_jacobi_sweep(int m, int ld, double* G, double* J, const int32_t* pairs, int n_steps, int n_pairs,
@@ -77,6 +100,20 @@ extern "C" int bg_jacobi_sweep(int m, int ld, double* G, double* J, const int32_
     hipStream_t st = (hipStream_t)stream;
     for (int s = 0; s < n_steps; ++s)
         hipLaunchKernelGGL(jacobi_pair_kernel, dim3(n_pairs), dim3(256), 0, st, G, J, m, ld,
+                           pairs + (size_t)s * n_pairs * 2, tol, rotations);
+    return bg::check_launch();
+}
+
+extern "C" int bg_jacobi_sweep_batched(int m, int ld, int count, long long stride, double* G, double* J, const int32_t* pairs,
+                                       int n_steps, int n_pairs, double tol, int32_t* rotations, void* stream)
+{
+    if (m < 1 || ld < m || count < 0 || n_steps < 0 || n_pairs < 0 || !(tol >= 0.0)) return BG_ERR_BAD_ARG;
+    if (count == 0 || n_steps == 0 || n_pairs == 0) return BG_OK;
+    if (count > 65535 || stride < (long long)(m - 1) * ld + m) return BG_ERR_BAD_ARG;      // a grid dimension; no overlap
+    if (!G || !J || !pairs || !rotations) return BG_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    for (int s = 0; s < n_steps; ++s)
+        hipLaunchKernelGGL(jacobi_pair_batched_kernel, dim3(n_pairs, count), dim3(256), 0, st, G, J, m, ld, stride,
                            pairs + (size_t)s * n_pairs * 2, tol, rotations);
     return bg::check_launch();
 }

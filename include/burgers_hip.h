@@ -603,6 +603,42 @@ int bg_decode_mlp_bf16(int N, int n, int B, int Nt, const uint16_t *Um, const do
 int bg_jacobi_sweep(int m, int ld, double *G, double *J, const int32_t *pairs, int n_steps, int n_pairs,
                     double tol, int32_t *rotations, void *stream);
 
+/* bg_jacobi_sweep_batched -- bg_jacobi_sweep on `count` matrices of one size in the launches of one (the per-cluster
+ * cores of the local POD builder, burgers_hip/pod.py jacobi_svd_batched).  Matrix k is G + k * stride and J + k * stride
+ * (stride in doubles, >= (m - 1) ld + m); all share m, ld, pairs and tol.
+ *   rotations [count] int32: += the rotations applied to matrix k
+ * Every matrix comes out bitwise as bg_jacobi_sweep leaves it on its own; one that has converged makes no rotation.
+ * count == 0: BG_OK, nothing is touched.  count > 65535 (a grid dimension) or an overlapping stride: BG_ERR_BAD_ARG. */
+int bg_jacobi_sweep_batched(int m, int ld, int count, long long stride, double *G, double *J, const int32_t *pairs,
+                            int n_steps, int n_pairs, double tol, int32_t *rotations, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * bg_kmeans_assign / bg_kmeans_update -- the two halves of a Lloyd iteration over snapshots in global POD coordinates:
+ *   the offline clustering behind the local POD PROM (burgers_hip/pod.py kmeans, build_local_bases; csrc/kmeans.hip).
+ *   q        [Ns][m] row-major: the points, q_g = U_global[:, :m]^T u of every snapshot
+ *   centres  [C][m]
+ *   Limits (bg_kmeans_limits): m <= 64, C <= 64, those of bg_local_rom_limits (BG_ERR_UNSUPPORTED_R beyond them).
+ *   Ns < 0, m < 1, C < 1, a negative or NaN overlap, or a null pointer with Ns > 0: BG_ERR_BAD_ARG.  Ns == 0: BG_OK.
+ * bg_kmeans_assign: for every point the squared distance to every centre, the first index of the minimum and that minimum,
+ *   with the arithmetic of the online pick (bg_local_rom_run: the distance summed in j order by FMA, the first index on ties,
+ *   a NaN distance counts as smallest), so a training snapshot is labelled as the time loop would label the same q_g.
+ *   overlap  membership factor, >= 0 (read only when member is given)
+ *   labels   [Ns] int32, in/out: the labels of the previous pass come in (anything, e.g. -1, before the first)
+ *   d2min    [Ns]: the squared distance to the nearest centre
+ *   member   [Ns] uint64 or NULL: bit c is set iff c == label or d2[i][c] < overlap * d2min[i]
+ *   changed  [1] int32: += the number of points whose label differs from the one passed in (an integer atomic)
+ * bg_kmeans_update: centres[c] = mean of the points labelled c; a cluster without points keeps its centre.
+ *   centres  [C][m], in/out;  counts [C] int32: the points of every cluster
+ *   No floating-point atomics: the sum of a cluster is taken over its points in input order with a fixed grouping of their
+ *   ranks within the cluster, so it is bitwise reproducible and does not depend on the other clusters' points.
+ *   Ns > INT32_MAX - 1024: BG_ERR_BAD_ARG.
+ * --------------------------------------------------------------------------------- */
+int bg_kmeans_limits(int *max_m, int *max_clusters);
+int bg_kmeans_assign(int Ns, int m, int C, const double *q, const double *centres, double overlap, int32_t *labels,
+                     double *d2min, uint64_t *member, int32_t *changed, void *stream);
+int bg_kmeans_update(int Ns, int m, int C, const double *q, const int32_t *labels, double *centres, int32_t *counts,
+                     void *stream);
+
 /* bg_rbf_eval -- kernel values and gradient factors of the scaled RBF closure of pod_rbf_prom
  *   reference: FEM/fem_burgers.py:160-260 (scaled gaussian / inverse-multiquadric closure and its Jacobian).
  *   qp [B][n] reduced coordinates; x_min, dx [n] input scaling (xs = 2 (qp - x_min)/dx - 1);
