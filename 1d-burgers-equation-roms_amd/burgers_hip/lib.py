@@ -151,6 +151,13 @@ _SIGNATURES = {
     "bg_kmeans_update": (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p, c_int_p, c_double_p, c_int_p, ctypes.c_void_p]),
     "bg_rbf_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_void_p]),
+    "bg_chol_max_n": (ctypes.c_int, []),
+    # Ns, n, kind, eps, ridge, XtT, A, lda, stream
+    "bg_rbf_gram": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_double] * 2 + [c_double_p, c_double_p, ctypes.c_int, ctypes.c_void_p]),
+    # n, A (in/out), lda, info (int32), stream
+    "bg_chol_factor": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, ctypes.c_void_p]),
+    # n, nrhs, L, lda, B (in/out), ldb, stream
+    "bg_chol_solve": (ctypes.c_int, [ctypes.c_int] * 2 + [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]),
     "bg_mlp_act_jvp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
     "bg_decode_modes_bf16": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,

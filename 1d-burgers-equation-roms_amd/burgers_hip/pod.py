@@ -4,6 +4,8 @@
   quadratic manifold  Quadratic_manifold/build_quadratic_manifold.py:25-48, quad_utils.py:63-81
   local POD           what FEMBurgers.local_prom_burgers consumes (FEM/fem_burgers.py:979-1079): k-means centres in global
                       POD coordinates and one overlapping basis per cluster (kmeans, build_local_bases)
+  POD-RBF closure     what FEMBurgers.pod_rbf_prom consumes (FEM/fem_burgers.py:1278-1398): scaled centres, ranges and the
+                      ridge-fitted weights (rbf_kernel_matrix, spd_solve, fit_rbf_weights, build_rbf_closure)
   snapshot files      FEM/paper_training_stage.py:52-53
 """
 from __future__ import annotations
@@ -435,6 +437,221 @@ def build_local_bases(S, n_clusters, num_global_modes, U_global=None, overlap=1.
     return LocalBases(km.centres, bases, U_global, m, labels, bits, counts, s_of, overlap, km)
 
 
+# ---- POD-RBF: the closure's centres, scaling and ridge fit ---------------------------------------------------------------
+RBF_KERNELS = ("gaussian", "imq")                          # index = BG_RBF_GAUSSIAN, BG_RBF_IMQ
+
+
+def _rbf_kind(kernel):
+    if kernel not in RBF_KERNELS:
+        raise ValueError("kernel must be 'gaussian' or 'imq'.")
+    return RBF_KERNELS.index(kernel)
+
+
+def _chol_max_n():
+    from . import lib as _lib
+    return int(_lib.load().bg_chol_max_n())
+
+
+def _check_order(Ns, who):
+    if Ns > _chol_max_n():
+        raise ValueError(f"{who}: {Ns} centres, beyond the {_chol_max_n()} of bg_chol_max_n (subsample with `centres`)")
+
+
+def rbf_kernel_matrix(Xs, epsilon, kernel, ridge=0.0):
+    """The (Ns, Ns) matrix k(eps |x_i - x_j|) + ridge I of the scaled centres ``Xs`` (Ns, n): gaussian exp(-eps^2 r^2) or imq
+    (1 + eps^2 r^2)^(-1/2), r^2 summed over the coordinates in their order -- the forms of the closure's evaluation
+    (csrc/rbf.hip).  Device tensors: bg_rbf_gram (both triangles bit for bit equal, the diagonal 1 + ridge exactly).  CPU
+    tensors: the same direct sum in torch."""
+    kind = _rbf_kind(kernel)
+    if Xs.dim() != 2 or Xs.shape[0] < 1 or Xs.shape[1] < 1:
+        raise ValueError("rbf_kernel_matrix takes the scaled centres as the rows of a (Ns, n) tensor")
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("ridge must be a non-negative finite number")
+    Xs = Xs.to(torch.float64)
+    Ns, n = Xs.shape
+    _check_order(Ns, "rbf_kernel_matrix")
+    eps2 = float(epsilon) * float(epsilon)
+    if not Xs.is_cuda:
+        r2 = torch.zeros((Ns, Ns), dtype=torch.float64)
+        for k in range(n):
+            d = Xs[:, None, k] - Xs[None, :, k]
+            r2 += d * d
+        A = torch.exp(-eps2 * r2) if kind == 0 else 1.0 / torch.sqrt(1.0 + eps2 * r2)
+        A.diagonal().fill_(1.0 + float(ridge))
+        return A
+    from . import lib as _lib
+    XtT = Xs.t().contiguous()
+    A = torch.empty((Ns, Ns), dtype=torch.float64, device=Xs.device)
+    with torch.cuda.device(Xs.device):
+        _lib.check(_lib.load().bg_rbf_gram(Ns, n, kind, float(epsilon), float(ridge), _lib.ptr(XtT), _lib.ptr(A), Ns,
+                                           _lib.stream_ptr(Xs.device)), "bg_rbf_gram")
+    return A
+
+
+def _spd_solve(A, Y, info, overwrite):
+    """spd_solve on a float64 matrix the caller gives up when ``overwrite`` (its lower triangle becomes the factor)."""
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or Y.shape[0] != A.shape[0] or Y.dim() not in (1, 2):
+        raise ValueError("spd_solve takes an (n, n) matrix and an (n,) or (n, nrhs) right-hand side")
+    if Y.device != A.device:
+        raise ValueError(f"spd_solve: the matrix lives on {A.device}, the right-hand side on {Y.device}")
+    _require_finite(Y, "spd_solve (right-hand side)")
+    n = A.shape[0]
+    B = Y.to(torch.float64).reshape(n, -1).contiguous().clone()
+    if not A.is_cuda:
+        L, bad = torch.linalg.cholesky_ex(A)
+        bad = int(bad)
+    else:
+        from . import lib as _lib
+        lib = _lib.load()
+        _check_order(n, "spd_solve")
+        L = A if (overwrite and A.is_contiguous()) else A.contiguous().clone()
+        flag = torch.zeros((1,), dtype=torch.int32, device=A.device)
+        with torch.cuda.device(A.device):
+            _lib.check(lib.bg_chol_factor(n, _lib.ptr(L), n, _lib.ptr(flag), _lib.stream_ptr(A.device)), "bg_chol_factor")
+            bad = int(flag.item()) if n else 0
+    if info is not None:
+        info["info"] = bad
+    if bad:
+        raise np.linalg.LinAlgError(f"spd_solve: pivot {bad - 1} of the Cholesky factorisation is not a positive finite number "
+                                    f"(info = {bad}): the matrix is not positive definite to rounding; a larger ridge makes it so")
+    if not A.is_cuda:
+        X = torch.cholesky_solve(B, L)
+    else:
+        with torch.cuda.device(A.device):
+            _lib.check(lib.bg_chol_solve(n, B.shape[1], _lib.ptr(L), n, _lib.ptr(B), B.shape[1], _lib.stream_ptr(A.device)),
+                       "bg_chol_solve")
+        X = B
+    return X.reshape(Y.shape)
+
+
+def spd_solve(A, Y, info=None):
+    """W with A W = Y for a symmetric positive definite float64 ``A`` (n, n), of which only the lower triangle is read, and
+    ``Y`` (n,) or (n, nrhs); A is left as it is.  Device tensors: the blocked Cholesky bg_chol_factor, one int read back after
+    it (as jacobi_svd reads its rotation count), then bg_chol_solve -- no workspace beyond the copy of A, bitwise reproducible,
+    and a column of W does not depend on the other columns of Y.  CPU tensors: torch.linalg.cholesky_ex + cholesky_solve.
+    A pivot that is not a positive finite number raises LinAlgError naming it; NaN / Inf in Y raises LinAlgError; an order
+    beyond bg_chol_max_n raises ValueError on the device.  ``info`` (a dict) receives LAPACK's ``info`` (0, or pivot + 1)."""
+    return _spd_solve(A.to(torch.float64), Y, info, overwrite=False)
+
+
+def backward_error(A, W, Y):
+    """|A W - Y|_F / (|A|_2 |W|_F + |Y|_F) of a symmetric positive semi-definite ``A``.  |A|_2 is the Rayleigh quotient after
+    30 power iterations from the vector of ones: at most the norm, so the figure errs upwards.  A kernel matrix has positive
+    entries and a dominant Perron value, which the quotient meets to well below a percent."""
+    W2, Y2 = W.reshape(A.shape[0], -1), Y.reshape(A.shape[0], -1)
+    v = torch.ones((A.shape[0],), dtype=A.dtype, device=A.device)
+    for _ in range(30):
+        v = A @ (v / torch.linalg.vector_norm(v))
+    v = v / torch.linalg.vector_norm(v)
+    norm2 = float(torch.dot(v, A @ v))
+    return float(torch.linalg.matrix_norm(A @ W2 - Y2)) / (norm2 * float(torch.linalg.matrix_norm(W2)) + float(torch.linalg.matrix_norm(Y2)))
+
+
+def fit_rbf_weights(Xs, Ys, epsilon, kernel="gaussian", ridge=1e-8, solver="cholesky", info=None):
+    """The closure weights W (Ns, nbar): (K + ridge I) W = Ys over the scaled centres ``Xs`` (Ns, n) and scaled targets ``Ys``
+    (Ns, nbar), K = rbf_kernel_matrix(Xs, epsilon, kernel).  ``solver``: "cholesky" is spd_solve (in-tree on the device);
+    "library" is torch.linalg.solve (LU) on the same matrix, kept for A/B runs and never the default.  ``info`` (a dict)
+    receives ``backward_error`` (see backward_error; costs a copy of the matrix) and, from the Cholesky route, ``info``."""
+    if solver not in ("cholesky", "library"):
+        raise ValueError("solver must be 'cholesky' or 'library'")
+    if Xs.dim() != 2 or Ys.dim() != 2 or Ys.shape[0] != Xs.shape[0] or Ys.device != Xs.device:
+        raise ValueError("fit_rbf_weights takes Xs (Ns, n) and Ys (Ns, nbar) on one device")
+    Ys = Ys.to(torch.float64)
+    A = rbf_kernel_matrix(Xs, epsilon, kernel, ridge)
+    if solver == "library":
+        _require_finite(Ys, "fit_rbf_weights (targets)")
+        W = torch.linalg.solve(A, Ys)
+    else:
+        W = _spd_solve(A, Ys, info, overwrite=info is None)
+    if info is not None:
+        info["backward_error"] = backward_error(A, W, Ys)
+    return W
+
+
+class RbfFit:
+    """What build_rbf_closure returns and save_rbf_closure stores: the bases ``U_p`` (N, n) and ``U_s`` (N, nbar), the scaled
+    centres ``X_train`` (Ns, n), the weights ``W`` (Ns, nbar), ``epsilon``, ``kernel``, the scaling ranges ``x_min, x_max``
+    (n,) and ``y_min, y_max`` (nbar,) over all snapshots, ``ridge``, ``centre_index`` (Ns,) int64 (the snapshot columns taken
+    as centres) and ``backward_error`` of the ridge system (see backward_error).  Tensors live on the device of the snapshots."""
+
+    def __init__(self, U_p, U_s, X_train, W, epsilon, kernel, x_min, x_max, y_min, y_max, ridge, centre_index, backward_error):
+        self.U_p, self.U_s, self.X_train, self.W = U_p, U_s, X_train, W
+        self.epsilon, self.kernel, self.ridge = float(epsilon), str(kernel), float(ridge)
+        self.x_min, self.x_max, self.y_min, self.y_max = x_min, x_max, y_min, y_max
+        self.centre_index, self.backward_error = centre_index, float(backward_error)
+
+    def prom_args(self):
+        """(U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max): the positional operands of
+        FEMBurgers.pod_rbf_prom and rom.pod_rbf_run after the initial condition and parameters (pass ``kernel=fit.kernel``
+        beside them).  The bases stay where they are; the closure's own operands go as host arrays, which is how
+        rom.RbfClosure takes them."""
+        host = lambda t: t.detach().cpu().numpy()
+        return (self.U_p, self.U_s, host(self.X_train), host(self.W), self.epsilon, host(self.x_min), host(self.x_max),
+                host(self.y_min), host(self.y_max))
+
+
+def _centre_rows(centres, Ns_all):
+    if centres is None:
+        return np.arange(Ns_all)
+    if np.ndim(centres) == 0:
+        k = int(centres)
+        if k < 1 or k > Ns_all:
+            raise ValueError(f"build_rbf_closure: {k} centres of {Ns_all} snapshots")
+        return np.linspace(0, Ns_all - 1, k).astype(int)
+    idx = np.asarray(centres.detach().cpu() if isinstance(centres, torch.Tensor) else centres).astype(np.int64).reshape(-1)
+    if idx.size < 1 or idx.min() < 0 or idx.max() >= Ns_all or len(np.unique(idx)) != idx.size:
+        raise ValueError("build_rbf_closure: centre indices must be distinct snapshot columns")
+    return idx
+
+
+def build_rbf_closure(S, n, nbar, epsilon, kernel="gaussian", ridge=1e-8, centres=None, U=None, solver="cholesky"):
+    """Snapshots S (N, Ns_all) -> the closure the POD-RBF PROM runs on, on S's device.
+
+      1. U = thin_svd(S)[0] unless given; U_p its first n columns, U_s the next nbar;  2. Q = (U_p^T S)^T, Qbar = (U_s^T S)^T;
+      3. x_min .. y_max: the column minima and maxima over ALL snapshots;  4. centres: every snapshot (None), the rows
+      np.linspace(0, Ns_all - 1, k).astype(int) (an int k) or the given distinct indices;  5. Xs = 2 (Q[idx] - x_min)/dx - 1,
+      Ys likewise with dy, ranges below 1e-15 replaced by 1 -- the guard and arithmetic of the closure's evaluation
+      (rom.RbfClosure, csrc/rbf.hip);  6. W = fit_rbf_weights(Xs, Ys, epsilon, kernel, ridge, solver).
+    This is the rule of this project's golden-fixture generator (tests/golden/make_golden.py fx_rbf), which solves the ridge
+    system by LU; the matrix is symmetric positive definite and the builder factors it by Cholesky (bg_chol_factor).
+
+    Any n and nbar are taken: the host-driven PROM has no limits of its own, while ``fused=True`` runs the device-side loop
+    only within bg_rbf_rom_limits (N <= 512, n <= 20, nbar <= 128, 65536 centres) and otherwise the host-driven iteration.
+    An unknown kernel or solver, n + nbar beyond the singular vectors at hand, an integer ``centres`` above Ns_all or indices
+    with duplicates, a negative ridge and more centres than bg_chol_max_n raise ValueError; a ridge too small for the matrix
+    to be positive definite to rounding raises LinAlgError.  Returns an RbfFit."""
+    _rbf_kind(kernel)
+    if solver not in ("cholesky", "library"):
+        raise ValueError("solver must be 'cholesky' or 'library'")
+    if S.dim() != 2:
+        raise ValueError("build_rbf_closure takes the (N, Ns) snapshot matrix")
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("ridge must be a non-negative finite number")
+    n, nbar = int(n), int(nbar)
+    N, Ns_all = S.shape
+    if n < 1 or nbar < 1 or n + nbar > (min(N, Ns_all) if U is None else int(np.shape(U)[1])):
+        raise ValueError(f"build_rbf_closure: n = {n} and nbar = {nbar} need {n + nbar} singular vectors")
+    idx = _centre_rows(centres, Ns_all)
+    _check_order(len(idx), "build_rbf_closure")
+    S = S.to(torch.float64)
+    _require_finite(S, "build_rbf_closure")
+    U = thin_svd(S)[0] if U is None else torch.as_tensor(U).to(device=S.device, dtype=torch.float64)
+    if U.dim() != 2 or U.shape[0] != N:
+        raise ValueError(f"U must be (N, >= n + nbar) with N = {N}")
+    U_p, U_s = U[:, :n].contiguous(), U[:, n:n + nbar].contiguous()
+    Q, Qb = (U_p.t() @ S).t().contiguous(), (U_s.t() @ S).t().contiguous()
+    x_min, x_max, y_min, y_max = Q.min(0).values, Q.max(0).values, Qb.min(0).values, Qb.max(0).values
+    dx, dy = x_max - x_min, y_max - y_min
+    dx[dx < 1e-15] = 1.0
+    dy[dy < 1e-15] = 1.0
+    rows = torch.as_tensor(idx, device=S.device)
+    Xs = (2.0 * ((Q[rows] - x_min) / dx) - 1.0).contiguous()
+    Ys = (2.0 * ((Qb[rows] - y_min) / dy) - 1.0).contiguous()
+    info = {}
+    W = fit_rbf_weights(Xs, Ys, epsilon, kernel, ridge, solver, info=info)
+    return RbfFit(U_p, U_s, Xs, W, epsilon, kernel, x_min, x_max, y_min, y_max, ridge, rows.to(torch.int64), info["backward_error"])
+
+
 # ---- .npy contracts --------------------------------------------------------------------------
 def snapshot_filename(mu1, mu2):
     return f"fem_simulation_mu1_{mu1:.3f}_mu2_{mu2:.4f}.npy"          # paper_training_stage.py:52
@@ -480,6 +697,31 @@ def save_local_bases(directory, result):
              n_iter=np.int64(km.n_iter), converged=np.bool_(km.converged), inertia=np.float64(km.inertia),
              changed=np.asarray(km.changed, dtype=np.int64))
     return directory
+
+
+_RBF_ARRAYS = ("U_p", "U_s", "X_train", "W", "x_min", "x_max", "y_min", "y_max", "centre_index")
+
+
+def save_rbf_closure(directory, fit):
+    """An RbfFit as .npy / .npz files (no pickles): one .npy per tensor (U_p, U_s, X_train, W, x_min, x_max, y_min, y_max,
+    centre_index) and closure.npz with the scalars (epsilon, ridge, backward_error, kernel as a string array).  Returns the
+    directory."""
+    os.makedirs(directory, exist_ok=True)
+    for name in _RBF_ARRAYS:
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(getattr(fit, name).detach().cpu().numpy()))
+    np.savez(os.path.join(directory, "closure.npz"), epsilon=np.float64(fit.epsilon), ridge=np.float64(fit.ridge),
+             backward_error=np.float64(fit.backward_error), kernel=np.array(fit.kernel, dtype=np.str_))
+    return directory
+
+
+def load_rbf_closure(directory, device="cpu"):
+    """The RbfFit save_rbf_closure wrote, as tensors on ``device``."""
+    t = {name: torch.as_tensor(np.load(os.path.join(directory, name + ".npy"), allow_pickle=False)).to(device).contiguous()
+         for name in _RBF_ARRAYS}
+    with np.load(os.path.join(directory, "closure.npz"), allow_pickle=False) as z:
+        meta = {k: z[k] for k in z.files}
+    return RbfFit(t["U_p"], t["U_s"], t["X_train"], t["W"], float(meta["epsilon"]), str(meta["kernel"]), t["x_min"], t["x_max"],
+                  t["y_min"], t["y_max"], float(meta["ridge"]), t["centre_index"], float(meta["backward_error"]))
 
 
 def load_local_bases(directory, device="cpu"):

@@ -649,6 +649,33 @@ int bg_kmeans_update(int Ns, int m, int C, const double *q, const int32_t *label
 int bg_rbf_eval(int B, int n, int Ns, int kind, double eps, const double *qp, const double *x_min,
                 const double *dx, const double *XtT, double *phi, double *GT, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * bg_rbf_gram / bg_chol_factor / bg_chol_solve -- the offline fit of the closure bg_rbf_eval and bg_rbf_rom_run evaluate:
+ *   the weights W solve (K + ridge I) W = Y, K[i][j] = k(|Xt_i - Xt_j|) over the Ns scaled centres (burgers_hip/pod.py
+ *   fit_rbf_weights, build_rbf_closure; csrc/rbf_fit.hip).  All three work in 64 x 64 tiles, mask a ragged last tile
+ *   themselves, use no workspace and no floating-point atomics: every element is summed in a fixed order, so the results
+ *   are bitwise reproducible and an element's bits depend on its own row and column of tiles alone.
+ *   Orders up to bg_chol_max_n() = 16384 (BG_ERR_UNSUPPORTED_R beyond); indices are size_t.
+ * bg_rbf_gram: A [Ns][lda] <- the full symmetric kernel matrix plus ridge on the diagonal.
+ *   XtT  [n][Ns] scaled centres, centre index fastest (the layout of bg_rbf_eval);  kind BG_RBF_GAUSSIAN or BG_RBF_IMQ
+ *   r2 = sum_k d_k^2 by FMA in the order of k, phi as in bg_rbf_eval; the two triangles are equal bit for bit and
+ *   A[i][i] = 1 + ridge exactly.  Columns Ns .. lda - 1 are not touched.
+ *   Ns < 0, n < 1, lda < Ns, an unknown kind, a negative or non-finite ridge, or a null operand with Ns > 0:
+ *   BG_ERR_BAD_ARG.  Ns == 0: BG_OK with nothing launched.
+ * bg_chol_factor: A [n][lda] symmetric positive definite, lower triangle <- L with A = L L^T (blocked, right-looking).
+ *   The upper triangle is not read and is left as it was.
+ *   info [1] device int <- 0, or k + 1 for the first pivot k that is not a positive finite number (LAPACK dpotrf's info);
+ *        the launches after that pivot return at once and A holds nothing of use.  Written with a plain store.
+ *   n < 0, lda < n or a null pointer with n > 0: BG_ERR_BAD_ARG.  n == 0: BG_OK with nothing launched (info untouched).
+ * bg_chol_solve: Bm [n][ldb] <- (L L^T)^-1 Bm in place, nrhs columns, L as bg_chol_factor left it (forward, then backward
+ *   substitution in 64-row blocks).  The result of a column does not depend on the other columns of the call.
+ *   n or nrhs < 0, lda < n, ldb < nrhs or a null pointer with work to do: BG_ERR_BAD_ARG.  n == 0 or nrhs == 0: BG_OK.
+ * --------------------------------------------------------------------------------- */
+int bg_chol_max_n(void);
+int bg_rbf_gram(int Ns, int n, int kind, double eps, double ridge, const double *XtT, double *A, int lda, void *stream);
+int bg_chol_factor(int n, double *A, int lda, int *info, void *stream);
+int bg_chol_solve(int n, int nrhs, const double *L, int lda, double *Bm, int ldb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
