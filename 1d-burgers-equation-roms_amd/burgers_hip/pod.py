@@ -56,74 +56,33 @@ def _require_finite(A, who):
         raise np.linalg.LinAlgError(f"{who}: the matrix holds NaN or Inf")
 
 
-def jacobi_svd(R, tol=1e-15, max_sweeps=80, info=None):
-    """SVD of a square device matrix by one-sided Jacobi on the HIP kernel bg_jacobi_sweep.
-    Returns U, s, Vh with R = U diag(s) Vh, s descending.  The rotations act on the ROWS of R, i.e.
-    on the columns of R^T: R^T J = W with orthogonal columns  =>  R = J (W^T): left vectors J, right W/|W|.
+def _jacobi(Rs, tol, max_sweeps, who, late):
+    """One-sided Jacobi on the HIP kernel of bg_jacobi_sweep_batched: the SVD of every matrix of the finite (count, m, m)
+    device tensor ``Rs``.  Returns stacked U, s, Vh with R = U diag(s) Vh, s descending, per matrix the sweep that made no
+    rotation, and the rotation counts per sweep and matrix.  The rotations act on the ROWS of R, i.e. on the columns of
+    R^T: R^T J = W with orthogonal columns  =>  R = J (W^T): left vectors J, right W/|W|.
 
     Before every sweep, rows whose squared norm is at or below (eps |R|_F)^2 are set to zero: they hold rounding
     noise of the input, which rotations against the large rows keep regenerating above the relative tol, so a
     rank-deficient core otherwise rotates forever (N x 808 bench gather: ~4800 rotations in every sweep).  Their
     singular values come back 0 and their rows of Vh zero; the kernel skips every pair holding a zero row.  A
     floor of m eps |R|_F would also converge but moves the modes near sigma/sigma_1 = 1e-7 by 4e-7 (measured).
-    Graded cores of condition 1e10 need up to ~46 sweeps at m = 512..777.  A sweep that still rotates at
-    max_sweeps raises RuntimeError; NaN / Inf input raises LinAlgError.  ``info`` (a dict) receives the sweep
-    count."""
+    Graded cores of condition 1e10 need up to ~46 sweeps at m = 512..777.  The floor and the rotation count are per matrix;
+    a matrix that has converged makes no rotation in the sweeps the others still need.  A sweep that still rotates at
+    max_sweeps raises RuntimeError: ``who``, then ``late(counts)`` on the matrices at fault."""
     from . import lib as _lib
     L = _lib.load()
-    _require_finite(R, "jacobi_svd")
-    m = R.shape[0]
-    G = R.contiguous().clone()
-    Jt = torch.eye(m, dtype=torch.float64, device=R.device)
-    pairs = _round_robin(m).to(R.device)
-    rot = torch.zeros((1,), dtype=torch.int32, device=R.device)
-    floor = (torch.finfo(torch.float64).eps * torch.linalg.matrix_norm(G)) ** 2
-    n_rot = sweep = 0
-    with torch.cuda.device(R.device):
-        for sweep in range(1, max_sweeps + 1):
-            G.masked_fill_((G * G).sum(1, keepdim=True) <= floor, 0.0)
-            rot.zero_()
-            _lib.check(L.bg_jacobi_sweep(m, m, _lib.ptr(G), _lib.ptr(Jt), _lib.ptr(pairs), pairs.shape[0], pairs.shape[1],
-                                         float(tol), _lib.ptr(rot), _lib.stream_ptr(R.device)), "bg_jacobi_sweep")
-            n_rot = int(rot.item())
-            if n_rot == 0:
-                break
-    if n_rot:
-        raise RuntimeError(f"jacobi_svd: not converged after {max_sweeps} sweeps (m = {m}, {n_rot} rotations in the last)")
-    if info is not None:
-        info["sweeps"] = sweep
-    s = torch.linalg.vector_norm(G, dim=1)
-    order = torch.argsort(s, descending=True)
-    s, G, Jt = s[order], G[order], Jt[order]
-    Vh = G / torch.clamp(s, min=torch.finfo(torch.float64).tiny)[:, None]
-    return Jt.t().contiguous(), s, Vh
-
-
-def jacobi_svd_batched(Rs, tol=1e-15, max_sweeps=80, info=None):
-    """jacobi_svd of every matrix of the (count, m, m) device tensor ``Rs`` in the launches of one (bg_jacobi_sweep_batched):
-    stacked U, s, Vh, each matrix finished and sorted as jacobi_svd does it, and bitwise what jacobi_svd returns for that
-    matrix alone.  The rounding floor and the rotation count are per matrix; a matrix that has converged makes no rotation
-    in the sweeps the others still need.  Raises RuntimeError naming the matrices that still rotate at ``max_sweeps``;
-    NaN / Inf raises LinAlgError.  ``info`` (a dict) receives ``sweeps`` (per matrix, the sweep that made no rotation) and
-    ``rotations`` (one list per sweep, one count per matrix)."""
-    from . import lib as _lib
-    L = _lib.load()
-    _require_finite(Rs, "jacobi_svd_batched")
-    if Rs.dim() != 3 or Rs.shape[1] != Rs.shape[2]:
-        raise ValueError("jacobi_svd_batched takes a (count, m, m) tensor")
     count, m = Rs.shape[0], Rs.shape[1]
     G = Rs.contiguous().clone()
     Jt = torch.eye(m, dtype=torch.float64, device=Rs.device).repeat(count, 1, 1)
     pairs = _round_robin(m).to(Rs.device)
     rot = torch.zeros((count,), dtype=torch.int32, device=Rs.device)
     eps = torch.finfo(torch.float64).eps
-    # (every per-matrix reduction runs on a copy of that matrix: the same shape and alignment as in jacobi_svd, hence its bits)
+    # (every per-matrix reduction runs on a copy of that matrix: one shape and alignment whatever the batch, hence one set of bits)
     floor = torch.stack([(eps * torch.linalg.matrix_norm(G[k].clone())) ** 2 for k in range(count)]).reshape(count, 1, 1)
     n_rot, sweeps, history = [0] * count, [0] * count, []
     with torch.cuda.device(Rs.device):
-        for sweep in range(1, max_sweeps + 1):
-            if count == 0:
-                break
+        for sweep in range(1, (max_sweeps if count else 0) + 1):
             G.masked_fill_((G * G).sum(2, keepdim=True) <= floor, 0.0)
             rot.zero_()
             _lib.check(L.bg_jacobi_sweep_batched(m, m, count, m * m, _lib.ptr(G), _lib.ptr(Jt), _lib.ptr(pairs), pairs.shape[0],
@@ -135,10 +94,7 @@ def jacobi_svd_batched(Rs, tol=1e-15, max_sweeps=80, info=None):
             if not any(n_rot):
                 break
     if any(n_rot):
-        late = ", ".join(f"matrix {k}: {n} rotations in the last" for k, n in enumerate(n_rot) if n)
-        raise RuntimeError(f"jacobi_svd_batched: not converged after {max_sweeps} sweeps (m = {m}; {late})")
-    if info is not None:
-        info["sweeps"], info["rotations"] = sweeps, history
+        raise RuntimeError(f"{who}: not converged after {max_sweeps} sweeps (m = {m}{late(n_rot)})")
     U, S, Vh = torch.empty_like(G), torch.empty((count, m), dtype=torch.float64, device=Rs.device), torch.empty_like(G)
     tiny = torch.finfo(torch.float64).tiny
     for k in range(count):
@@ -147,7 +103,33 @@ def jacobi_svd_batched(Rs, tol=1e-15, max_sweeps=80, info=None):
         order = torch.argsort(s, descending=True)
         s, Gk, Jk = s[order], Gk[order], Jk[order]
         U[k], S[k], Vh[k] = Jk.t(), s, Gk / torch.clamp(s, min=tiny)[:, None]
-    return U, S, Vh
+    return U, S, Vh, sweeps, history
+
+
+def jacobi_svd(R, tol=1e-15, max_sweeps=80, info=None):
+    """SVD of a square device matrix by one-sided Jacobi (_jacobi on the batch of this one matrix): U, s, Vh with
+    R = U diag(s) Vh, s descending.  A sweep that still rotates at max_sweeps raises RuntimeError; NaN / Inf input raises
+    LinAlgError.  ``info`` (a dict) receives the sweep count."""
+    _require_finite(R, "jacobi_svd")
+    U, s, Vh, sweeps, _ = _jacobi(R[None], tol, max_sweeps, "jacobi_svd", lambda n: f", {n[0]} rotations in the last")
+    if info is not None:
+        info["sweeps"] = sweeps[0]
+    return U[0], s[0], Vh[0]
+
+
+def jacobi_svd_batched(Rs, tol=1e-15, max_sweeps=80, info=None):
+    """jacobi_svd of every matrix of the (count, m, m) device tensor ``Rs`` in the launches of one: stacked U, s, Vh, bitwise
+    what jacobi_svd returns for each matrix alone.  Raises RuntimeError naming the matrices that still rotate at
+    ``max_sweeps``; NaN / Inf raises LinAlgError.  ``info`` (a dict) receives ``sweeps`` (per matrix, the sweep that made no
+    rotation) and ``rotations`` (one list per sweep, one count per matrix)."""
+    _require_finite(Rs, "jacobi_svd_batched")
+    if Rs.dim() != 3 or Rs.shape[1] != Rs.shape[2]:
+        raise ValueError("jacobi_svd_batched takes a (count, m, m) tensor")
+    late = lambda n_rot: "; " + ", ".join(f"matrix {k}: {n} rotations in the last" for k, n in enumerate(n_rot) if n)
+    U, s, Vh, sweeps, history = _jacobi(Rs, tol, max_sweeps, "jacobi_svd_batched", late)
+    if info is not None:
+        info["sweeps"], info["rotations"] = sweeps, history
+    return U, s, Vh
 
 
 def thin_svd(A, info=None):
@@ -221,6 +203,34 @@ def build_quadratic_manifold(S, n, alpha=1e-2):
     Q = build_Q(q)
     Em = S - Phi @ q
     return Phi, compute_H(Q, Em, alpha), q
+
+
+# ---- what the builders below share ----------------------------------------------------------------------------------------
+def _global_basis(S, U, cols, message):
+    """The global basis of the snapshots ``S``: ``U`` on S's device as float64, or thin_svd(S)[0]; (N, >= cols) or ValueError."""
+    U = thin_svd(S)[0] if U is None else torch.as_tensor(U).to(device=S.device, dtype=torch.float64)
+    if U.dim() != 2 or U.shape[0] != S.shape[0] or U.shape[1] < cols:
+        raise ValueError(message)
+    return U
+
+
+def _coordinates(Phi, S):
+    """(Phi^T S)^T contiguous: the coordinates of the snapshots in the columns ``Phi`` of a basis, one row per snapshot."""
+    return (Phi.t() @ S).t().contiguous()
+
+
+def _check_ridge(ridge):
+    if not (ridge >= 0.0 and np.isfinite(ridge)):
+        raise ValueError("ridge must be a non-negative finite number")
+
+
+def _check_solver(solver):
+    if solver not in ("cholesky", "library"):
+        raise ValueError("solver must be 'cholesky' or 'library'")
+
+
+_host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy())                          # a tensor as the array np.save gets
+_npy = lambda directory, name: np.load(os.path.join(directory, name), allow_pickle=False)  # .npy / .npz, never a pickle
 
 
 # ---- local POD: clustering in global POD coordinates and one overlapping basis per cluster ------------------------------
@@ -394,13 +404,8 @@ def build_local_bases(S, n_clusters, num_global_modes, U_global=None, overlap=1.
     if widths is not None and len(widths) != C:
         raise ValueError(f"n_modes must be an int or one per cluster ({C})")
     _require_finite(S, "build_local_bases")
-    if U_global is None:
-        U_global = thin_svd(S)[0]
-    else:
-        U_global = torch.as_tensor(U_global).to(device=S.device, dtype=torch.float64)
-    if U_global.dim() != 2 or U_global.shape[0] != N or U_global.shape[1] < m:
-        raise ValueError(f"U_global must be (N, >= num_global_modes) with N = {N}, num_global_modes = {m}")
-    Q = (U_global[:, :m].t() @ S).t().contiguous()
+    U_global = _global_basis(S, U_global, m, f"U_global must be (N, >= num_global_modes) with N = {N}, num_global_modes = {m}")
+    Q = _coordinates(U_global[:, :m], S)
     km = kmeans(Q, C, init=init, seed=seed, max_iter=max_iter)
     labels, _, bits, _ = _assign(Q, km.centres, overlap=overlap, labels=km.labels)
     columns = [torch.nonzero(member_mask(bits, c))[:, 0] for c in range(C)]
@@ -442,9 +447,17 @@ RBF_KERNELS = ("gaussian", "imq")                          # index = BG_RBF_GAUS
 
 
 def _rbf_kind(kernel):
+    """BG_RBF_GAUSSIAN or BG_RBF_IMQ of a kernel name; the one place that knows the names (rom.RbfClosure asks here)."""
     if kernel not in RBF_KERNELS:
         raise ValueError("kernel must be 'gaussian' or 'imq'.")
     return RBF_KERNELS.index(kernel)
+
+
+def _rbf_range(lo, hi):
+    """hi - lo with entries below 1e-15 replaced by 1: the closure's scaling guard, in its fit and in rom.RbfClosure alike."""
+    d = hi - lo
+    d[d < 1e-15] = 1.0
+    return d
 
 
 def _chol_max_n():
@@ -460,13 +473,12 @@ def _check_order(Ns, who):
 def rbf_kernel_matrix(Xs, epsilon, kernel, ridge=0.0):
     """The (Ns, Ns) matrix k(eps |x_i - x_j|) + ridge I of the scaled centres ``Xs`` (Ns, n): gaussian exp(-eps^2 r^2) or imq
     (1 + eps^2 r^2)^(-1/2), r^2 summed over the coordinates in their order -- the forms of the closure's evaluation
-    (csrc/rbf.hip).  Device tensors: bg_rbf_gram (both triangles bit for bit equal, the diagonal 1 + ridge exactly).  CPU
+    (csrc/rbf_device.hpp).  Device tensors: bg_rbf_gram (both triangles bit for bit equal, the diagonal 1 + ridge exactly).  CPU
     tensors: the same direct sum in torch."""
     kind = _rbf_kind(kernel)
     if Xs.dim() != 2 or Xs.shape[0] < 1 or Xs.shape[1] < 1:
         raise ValueError("rbf_kernel_matrix takes the scaled centres as the rows of a (Ns, n) tensor")
-    if not (ridge >= 0.0 and np.isfinite(ridge)):
-        raise ValueError("ridge must be a non-negative finite number")
+    _check_ridge(ridge)
     Xs = Xs.to(torch.float64)
     Ns, n = Xs.shape
     _check_order(Ns, "rbf_kernel_matrix")
@@ -552,8 +564,7 @@ def fit_rbf_weights(Xs, Ys, epsilon, kernel="gaussian", ridge=1e-8, solver="chol
     (Ns, nbar), K = rbf_kernel_matrix(Xs, epsilon, kernel).  ``solver``: "cholesky" is spd_solve (in-tree on the device);
     "library" is torch.linalg.solve (LU) on the same matrix, kept for A/B runs and never the default.  ``info`` (a dict)
     receives ``backward_error`` (see backward_error; costs a copy of the matrix) and, from the Cholesky route, ``info``."""
-    if solver not in ("cholesky", "library"):
-        raise ValueError("solver must be 'cholesky' or 'library'")
+    _check_solver(solver)
     if Xs.dim() != 2 or Ys.dim() != 2 or Ys.shape[0] != Xs.shape[0] or Ys.device != Xs.device:
         raise ValueError("fit_rbf_weights takes Xs (Ns, n) and Ys (Ns, nbar) on one device")
     Ys = Ys.to(torch.float64)
@@ -585,9 +596,8 @@ class RbfFit:
         FEMBurgers.pod_rbf_prom and rom.pod_rbf_run after the initial condition and parameters (pass ``kernel=fit.kernel``
         beside them).  The bases stay where they are; the closure's own operands go as host arrays, which is how
         rom.RbfClosure takes them."""
-        host = lambda t: t.detach().cpu().numpy()
-        return (self.U_p, self.U_s, host(self.X_train), host(self.W), self.epsilon, host(self.x_min), host(self.x_max),
-                host(self.y_min), host(self.y_max))
+        return (self.U_p, self.U_s, _host(self.X_train), _host(self.W), self.epsilon, _host(self.x_min), _host(self.x_max),
+                _host(self.y_min), _host(self.y_max))
 
 
 def _centre_rows(centres, Ns_all):
@@ -621,12 +631,10 @@ def build_rbf_closure(S, n, nbar, epsilon, kernel="gaussian", ridge=1e-8, centre
     with duplicates, a negative ridge and more centres than bg_chol_max_n raise ValueError; a ridge too small for the matrix
     to be positive definite to rounding raises LinAlgError.  Returns an RbfFit."""
     _rbf_kind(kernel)
-    if solver not in ("cholesky", "library"):
-        raise ValueError("solver must be 'cholesky' or 'library'")
+    _check_solver(solver)
     if S.dim() != 2:
         raise ValueError("build_rbf_closure takes the (N, Ns) snapshot matrix")
-    if not (ridge >= 0.0 and np.isfinite(ridge)):
-        raise ValueError("ridge must be a non-negative finite number")
+    _check_ridge(ridge)
     n, nbar = int(n), int(nbar)
     N, Ns_all = S.shape
     if n < 1 or nbar < 1 or n + nbar > (min(N, Ns_all) if U is None else int(np.shape(U)[1])):
@@ -635,15 +643,11 @@ def build_rbf_closure(S, n, nbar, epsilon, kernel="gaussian", ridge=1e-8, centre
     _check_order(len(idx), "build_rbf_closure")
     S = S.to(torch.float64)
     _require_finite(S, "build_rbf_closure")
-    U = thin_svd(S)[0] if U is None else torch.as_tensor(U).to(device=S.device, dtype=torch.float64)
-    if U.dim() != 2 or U.shape[0] != N:
-        raise ValueError(f"U must be (N, >= n + nbar) with N = {N}")
+    U = _global_basis(S, U, n + nbar, f"U must be (N, >= n + nbar) with N = {N}")
     U_p, U_s = U[:, :n].contiguous(), U[:, n:n + nbar].contiguous()
-    Q, Qb = (U_p.t() @ S).t().contiguous(), (U_s.t() @ S).t().contiguous()
+    Q, Qb = _coordinates(U_p, S), _coordinates(U_s, S)
     x_min, x_max, y_min, y_max = Q.min(0).values, Q.max(0).values, Qb.min(0).values, Qb.max(0).values
-    dx, dy = x_max - x_min, y_max - y_min
-    dx[dx < 1e-15] = 1.0
-    dy[dy < 1e-15] = 1.0
+    dx, dy = _rbf_range(x_min, x_max), _rbf_range(y_min, y_max)
     rows = torch.as_tensor(idx, device=S.device)
     Xs = (2.0 * ((Q[rows] - x_min) / dx) - 1.0).contiguous()
     Ys = (2.0 * ((Qb[rows] - y_min) / dy) - 1.0).contiguous()
@@ -684,13 +688,10 @@ def save_local_bases(directory, result):
     local_bases.npz and singular_values.npz (one array per cluster, named by its id) and clustering.npz (the scalars).
     Returns the directory."""
     os.makedirs(directory, exist_ok=True)
-    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy())
-    np.save(os.path.join(directory, "centres.npy"), host(result.centres))
-    np.save(os.path.join(directory, "U_global.npy"), host(result.U_global))
-    np.save(os.path.join(directory, "labels.npy"), host(result.labels))
-    np.save(os.path.join(directory, "member_bits.npy"), host(result.member_bits))
-    np.savez(os.path.join(directory, "local_bases.npz"), **{str(c): host(b) for c, b in result.local_bases.items()})
-    np.savez(os.path.join(directory, "singular_values.npz"), **{str(c): host(v) for c, v in result.singular_values.items()})
+    for name in ("centres", "U_global", "labels", "member_bits"):
+        np.save(os.path.join(directory, name + ".npy"), _host(getattr(result, name)))
+    np.savez(os.path.join(directory, "local_bases.npz"), **{str(c): _host(b) for c, b in result.local_bases.items()})
+    np.savez(os.path.join(directory, "singular_values.npz"), **{str(c): _host(v) for c, v in result.singular_values.items()})
     km = result.kmeans
     np.savez(os.path.join(directory, "clustering.npz"), num_global_modes=np.int64(result.num_global_modes),
              member_counts=np.asarray(result.member_counts, dtype=np.int64), overlap=np.float64(result.overlap),
@@ -708,7 +709,7 @@ def save_rbf_closure(directory, fit):
     directory."""
     os.makedirs(directory, exist_ok=True)
     for name in _RBF_ARRAYS:
-        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(getattr(fit, name).detach().cpu().numpy()))
+        np.save(os.path.join(directory, name + ".npy"), _host(getattr(fit, name)))
     np.savez(os.path.join(directory, "closure.npz"), epsilon=np.float64(fit.epsilon), ridge=np.float64(fit.ridge),
              backward_error=np.float64(fit.backward_error), kernel=np.array(fit.kernel, dtype=np.str_))
     return directory
@@ -716,9 +717,8 @@ def save_rbf_closure(directory, fit):
 
 def load_rbf_closure(directory, device="cpu"):
     """The RbfFit save_rbf_closure wrote, as tensors on ``device``."""
-    t = {name: torch.as_tensor(np.load(os.path.join(directory, name + ".npy"), allow_pickle=False)).to(device).contiguous()
-         for name in _RBF_ARRAYS}
-    with np.load(os.path.join(directory, "closure.npz"), allow_pickle=False) as z:
+    t = {name: torch.as_tensor(_npy(directory, name + ".npy")).to(device).contiguous() for name in _RBF_ARRAYS}
+    with _npy(directory, "closure.npz") as z:
         meta = {k: z[k] for k in z.files}
     return RbfFit(t["U_p"], t["U_s"], t["X_train"], t["W"], float(meta["epsilon"]), str(meta["kernel"]), t["x_min"], t["x_max"],
                   t["y_min"], t["y_max"], float(meta["ridge"]), t["centre_index"], float(meta["backward_error"]))
@@ -726,16 +726,15 @@ def load_rbf_closure(directory, device="cpu"):
 
 def load_local_bases(directory, device="cpu"):
     """The LocalBases save_local_bases wrote, as tensors on ``device``."""
-    load = lambda name: np.load(os.path.join(directory, name), allow_pickle=False)
     dev = lambda a: torch.as_tensor(a).to(device)
-    with load("local_bases.npz") as z:
+    with _npy(directory, "local_bases.npz") as z:
         bases = {int(k): dev(z[k]).contiguous() for k in z.files}
-    with load("singular_values.npz") as z:
+    with _npy(directory, "singular_values.npz") as z:
         svals = {int(k): dev(z[k]) for k in z.files}
-    with load("clustering.npz") as z:
+    with _npy(directory, "clustering.npz") as z:
         meta = {k: z[k] for k in z.files}
-    centres, labels = dev(load("centres.npy")), dev(load("labels.npy"))
+    centres, labels = dev(_npy(directory, "centres.npy")), dev(_npy(directory, "labels.npy"))
     km = KMeansResult(centres, labels, int(meta["n_iter"]), bool(meta["converged"]), float(meta["inertia"]), meta["changed"].tolist())
-    return LocalBases(centres, dict(sorted(bases.items())), dev(load("U_global.npy")), int(meta["num_global_modes"]), labels,
-                      dev(load("member_bits.npy")), meta["member_counts"].tolist(), dict(sorted(svals.items())),
+    return LocalBases(centres, dict(sorted(bases.items())), dev(_npy(directory, "U_global.npy")), int(meta["num_global_modes"]), labels,
+                      dev(_npy(directory, "member_bits.npy")), meta["member_counts"].tolist(), dict(sorted(svals.items())),
                       float(meta["overlap"]), km)

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as _lib
+from . import pod as _pod
 from .fom import FomResult, _as_dev, check_mesh
 from .fom import batch_inputs as _batch_inputs
 
@@ -1182,19 +1183,14 @@ class RbfClosure:
     ONE GEMM each against the output-scaled weights: q_s = phi Wd + (dy/2 + y_min), (dq_s/dq_p)^T = GT Wd."""
 
     def __init__(self, X_train, W, eps, kernel, x_min, x_max, y_min, y_max, device):
-        if kernel not in ("gaussian", "imq"):
-            raise ValueError("kernel must be 'gaussian' or 'imq'.")
+        self.kind = _pod._rbf_kind(kernel)                             # refuses an unknown name
         f = lambda a: _as_dev(np.asarray(a, dtype=np.float64), device)
         self.L = _lib.load()
         self.device = device
         Xt, Wm = f(X_train), f(W)
         self.eps = float(eps)
-        self.kind = _lib.BG_RBF_GAUSSIAN if kernel == "gaussian" else _lib.BG_RBF_IMQ
         self.x_min, y_min = f(x_min), f(y_min)
-        self.dx = f(x_max) - self.x_min
-        self.dx[self.dx < 1e-15] = 1.0
-        dy = f(y_max) - y_min
-        dy[dy < 1e-15] = 1.0
+        self.dx, dy = _pod._rbf_range(self.x_min, f(x_max)), _pod._rbf_range(y_min, f(y_max))
         if Wm.shape != (Xt.shape[0], dy.numel()) or Xt.shape[1] != self.dx.numel():
             raise ValueError("X_train must be (Ns, n) and W (Ns, nbar)")
         self.Ns, self.n = Xt.shape

@@ -4,7 +4,7 @@
 // sample b and training centre i,
 //     xs = 2 (q_p - x_min) / dx - 1,   d_ik = xs_k - Xt_ik,   r2_i = sum_k d_ik^2,
 //     gaussian:  phi_i = exp(-eps^2 r2_i),            dphi/dxs_k = -2 eps^2 phi_i   d_ik
-//     imq:       phi_i = (1 + eps^2 r2_i)^(-1/2),     dphi/dxs_k =   -eps^2 phi_i^3 d_ik
+//     imq:       phi_i = (1 + eps^2 r2_i)^(-1/2),     dphi/dxs_k =   -eps^2 phi_i^3 d_ik        (rbf_device.hpp)
 // and then contracts with the weights: q_s ~ phi W, dq_s/dq_p ~ (dphi/dxs)^T W (library GEMMs).  This
 // kernel writes phi [B][Ns] and the gradient factors already transposed and scaled by dxs/dq_p = 2/dx_k,
 // GT [B][n][Ns], so that both contractions are ONE GEMM each over B resp. B n rows.
@@ -13,6 +13,7 @@
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
+#include "rbf_device.hpp"
 
 namespace {
 
@@ -37,14 +38,8 @@ __global__ __launch_bounds__(256) void rbf_eval_kernel(const double* __restrict_
                 const double d = s_xs[k] - XtT[(size_t)k * Ns + i];
                 r2 = __builtin_fma(d, d, r2);
             }
-            double p, coef;
-            if (KIND == BG_RBF_GAUSSIAN) {
-                p = exp(-eps2 * r2);
-                coef = -2.0 * eps2 * p;
-            } else {
-                p = 1.0 / sqrt(1.0 + eps2 * r2);
-                coef = -eps2 * (p * p * p);
-            }
+            double coef;
+            const double p = bg::rbf_value_coef(KIND, eps2, r2, coef);
             if (phi) phi[(size_t)b * Ns + i] = p;
             if (GT) {
                 double* g = GT + (size_t)b * n * Ns + i;

@@ -3,7 +3,7 @@
 //
 // gram     bg_rbf_gram: one workgroup per tile (I, J); the two 64-centre coordinate blocks pass through LDS 32 coordinates
 //          at a time, thread (column, row group) keeps 16 squared distances, r2 += d^2 by FMA in the order of k -- the sum
-//          of csrc/rbf.hip.  (a - b)^2 = (b - a)^2, so tile (J, I) holds the transposed bits of tile (I, J).
+//          of csrc/rbf.hip, then the form of rbf_device.hpp.  (a - b)^2 = (b - a)^2, so tile (J, I) holds the transposed bits of tile (I, J).
 // factor   bg_chol_factor: right-looking over 64-column blocks, three launches per block column k:
 //            chol_panel<true>   one workgroup factors the diagonal tile and records info;
 //            chol_panel<false>  one workgroup per tile below solves X L11^T = A21;
@@ -25,6 +25,7 @@
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
+#include "rbf_device.hpp"
 
 namespace {
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void rbf_gram_kernel(int Ns, int n, const doub
     for (int q = 0; q < 16; ++q) {
         const int i = i0 + 16 * tg + q;
         if (i >= Ns) continue;
-        const double p = KIND == BG_RBF_GAUSSIAN ? exp(-eps2 * r2[q]) : 1.0 / sqrt(1.0 + eps2 * r2[q]);
+        const double p = bg::rbf_value(KIND, eps2, r2[q]);
         A[(size_t)i * lda + j] = i == j ? diag : p;
     }
 }

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
         }
         __syncthreads();
     };
-    // kernel value phi and gradient coefficient of centre i at s_xs (the forms of csrc/rbf.hip)
+    // phi and gradient coefficient of centre i at s_xs; repeats rbf_device.hpp (shared, this kernel's branches and spills change)
     auto centre = [&](int i, double (&d)[RW], double& p, double& coef) {
         double r2 = 0.0;
 #pragma unroll

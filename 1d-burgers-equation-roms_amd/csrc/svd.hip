@@ -11,11 +11,12 @@
 // J [m][ld] receives the same rotations starting from the identity.  One launch = one step of a round-robin
 // ordering: m/2 disjoint row pairs, one 256-thread workgroup per pair.  The caller zeroes the rows at the
 // rounding level (|g|^2 <= (eps |R|_F)^2) before each sweep and raises when a sweep still rotates at its
-// sweep limit (burgers_hip/pod.py jacobi_svd).
+// sweep limit (the Jacobi driver of burgers_hip/pod.py).
 //
-// bg_jacobi_sweep_batched runs the same step on `count` matrices of one size in one launch (the matrix is the second grid
-// dimension): the per-cluster cores of the local POD builder, which share m, ld and the pair schedule.  Each matrix has its
-// own rotation count; one that has converged makes no rotation and its workgroups leave after the three dot products.
+// There is one kernel and one launch loop.  The matrix is the second grid dimension: `count` matrices of one size, `stride`
+// doubles apart, share m, ld and the pair schedule (the per-cluster cores of the local POD builder), and each has its own
+// rotation count; one that has converged makes no rotation and its workgroups leave after the three dot products.
+// bg_jacobi_sweep is the batch of one matrix, so a matrix of a batch goes through the arithmetic of a matrix on its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,12 +28,17 @@ namespace {
 
 using namespace bg;
 
-// One row pair of one matrix, by one 256-thread workgroup: the body of both kernels below, so that a matrix of a batch
-// goes through the arithmetic of a matrix on its own.
-__device__ __forceinline__ void jacobi_pair(double* __restrict__ G, double* __restrict__ J, int m, int ld,
-                                            const int32_t* __restrict__ pairs, double tol, int32_t* __restrict__ rotations,
-                                            double (&s_part)[3][4])
+// One row pair of one matrix, by one 256-thread workgroup.  blockIdx.y: the matrix of the batch, `stride` doubles after the
+// one before it, with a rotation count of its own.
+__global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
+                                                          long long stride, const int32_t* __restrict__ pairs, double tol,
+                                                          int32_t* __restrict__ rotations)
 {
+    __shared__ double s_part[3][4];
+    const size_t off = (size_t)blockIdx.y * (size_t)stride;
+    G += off;
+    J += off;
+    rotations += blockIdx.y;
     const int p = pairs[2 * blockIdx.x], q = pairs[2 * blockIdx.x + 1];
     if (p < 0 || q < 0 || p >= m || q >= m) return;                 // bye of an odd-sized tournament
     double* gp = G + (size_t)p * ld;
@@ -51,7 +57,7 @@ __device__ __forceinline__ void jacobi_pair(double* __restrict__ G, double* __re
     const double alpha = (s_part[0][0] + s_part[0][1]) + (s_part[0][2] + s_part[0][3]);
     const double beta = (s_part[1][0] + s_part[1][1]) + (s_part[1][2] + s_part[1][3]);
     const double gamma = (s_part[2][0] + s_part[2][1]) + (s_part[2][2] + s_part[2][3]);
-    // already orthogonal, or a zero row: the caller (burgers_hip/pod.py jacobi_svd) zeroes every row with
+    // already orthogonal, or a zero row: the caller (burgers_hip/pod.py) zeroes every row with
     // |g|^2 <= (eps |R|_F)^2 before each sweep, since rows at the rounding level never meet the relative tol;
     // NaN input is refused there too (a NaN row would pass this test and come back as a NaN mode)
     if (!(fabs(gamma) > tol * sqrt(alpha * beta))) return;
@@ -71,38 +77,7 @@ __device__ __forceinline__ void jacobi_pair(double* __restrict__ G, double* __re
     if (tid == 0) atomicAdd(rotations, 1);
 }
 
-__global__ __launch_bounds__(256) void jacobi_pair_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
-                                                          const int32_t* __restrict__ pairs, double tol,
-                                                          int32_t* __restrict__ rotations)
-{
-    __shared__ double s_part[3][4];
-    jacobi_pair(G, J, m, ld, pairs, tol, rotations, s_part);
-}
-
-// blockIdx.y: the matrix of the batch, `stride` doubles after the one before it, with a rotation count of its own
-__global__ __launch_bounds__(256) void jacobi_pair_batched_kernel(double* __restrict__ G, double* __restrict__ J, int m, int ld,
-                                                                  long long stride, const int32_t* __restrict__ pairs,
-                                                                  double tol, int32_t* __restrict__ rotations)
-{
-    __shared__ double s_part[3][4];
-    const size_t off = (size_t)blockIdx.y * (size_t)stride;
-    jacobi_pair(G + off, J + off, m, ld, pairs, tol, rotations + blockIdx.y, s_part);
-}
-
 }  // namespace
-
-extern "C" int bg_jacobi_sweep(int m, int ld, double* G, double* J, const int32_t* pairs, int n_steps, int n_pairs,
-                               double tol, int32_t* rotations, void* stream)
-{
-    if (m < 1 || ld < m || n_steps < 0 || n_pairs < 0 || !(tol >= 0.0)) return BG_ERR_BAD_ARG;
-    if (n_steps == 0 || n_pairs == 0) return BG_OK;
-    if (!G || !J || !pairs || !rotations) return BG_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    for (int s = 0; s < n_steps; ++s)
-        hipLaunchKernelGGL(jacobi_pair_kernel, dim3(n_pairs), dim3(256), 0, st, G, J, m, ld,
-                           pairs + (size_t)s * n_pairs * 2, tol, rotations);
-    return bg::check_launch();
-}
 
 extern "C" int bg_jacobi_sweep_batched(int m, int ld, int count, long long stride, double* G, double* J, const int32_t* pairs,
                                        int n_steps, int n_pairs, double tol, int32_t* rotations, void* stream)
@@ -113,7 +88,14 @@ extern "C" int bg_jacobi_sweep_batched(int m, int ld, int count, long long strid
     if (!G || !J || !pairs || !rotations) return BG_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     for (int s = 0; s < n_steps; ++s)
-        hipLaunchKernelGGL(jacobi_pair_batched_kernel, dim3(n_pairs, count), dim3(256), 0, st, G, J, m, ld, stride,
+        hipLaunchKernelGGL(jacobi_pair_kernel, dim3(n_pairs, count), dim3(256), 0, st, G, J, m, ld, stride,
                            pairs + (size_t)s * n_pairs * 2, tol, rotations);
     return bg::check_launch();
+}
+
+// The batch of one matrix: with count = 1 and stride = m ld the checks above are, in order and code, the ones of one matrix.
+extern "C" int bg_jacobi_sweep(int m, int ld, double* G, double* J, const int32_t* pairs, int n_steps, int n_pairs,
+                               double tol, int32_t* rotations, void* stream)
+{
+    return bg_jacobi_sweep_batched(m, ld, 1, (long long)m * ld, G, J, pairs, n_steps, n_pairs, tol, rotations, stream);
 }

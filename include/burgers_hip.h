@@ -599,15 +599,17 @@ int bg_decode_mlp_bf16(int N, int n, int B, int Nt, const uint16_t *Um, const do
  *   tol    rows p, q are rotated when |g_p . g_q| > tol |g_p| |g_q|
  *   rotations [1] int32: += number of rotations applied (0 after a full sweep = converged)
  * After convergence the row norms of G are the singular values of the input, G[j]/|G[j]| its left
- * singular vectors (as rows), J its right singular vectors (as rows). */
+ * singular vectors (as rows), J its right singular vectors (as rows).
+ * This is bg_jacobi_sweep_batched with count = 1: one kernel and one launch loop serve both. */
 int bg_jacobi_sweep(int m, int ld, double *G, double *J, const int32_t *pairs, int n_steps, int n_pairs,
                     double tol, int32_t *rotations, void *stream);
 
-/* bg_jacobi_sweep_batched -- bg_jacobi_sweep on `count` matrices of one size in the launches of one (the per-cluster
- * cores of the local POD builder, burgers_hip/pod.py jacobi_svd_batched).  Matrix k is G + k * stride and J + k * stride
- * (stride in doubles, >= (m - 1) ld + m); all share m, ld, pairs and tol.
+/* bg_jacobi_sweep_batched -- the sweep on `count` matrices of one size in the launches of one (the per-cluster cores of
+ * the local POD builder, burgers_hip/pod.py jacobi_svd_batched): the matrix is the second grid dimension of the one sweep
+ * kernel.  Matrix k is G + k * stride and J + k * stride (stride in doubles, >= (m - 1) ld + m); all share m, ld, pairs
+ * and tol.
  *   rotations [count] int32: += the rotations applied to matrix k
- * Every matrix comes out bitwise as bg_jacobi_sweep leaves it on its own; one that has converged makes no rotation.
+ * Every matrix comes out bitwise as it does on its own, whatever its batch-mates; one that has converged makes no rotation.
  * count == 0: BG_OK, nothing is touched.  count > 65535 (a grid dimension) or an overlapping stride: BG_ERR_BAD_ARG. */
 int bg_jacobi_sweep_batched(int m, int ld, int count, long long stride, double *G, double *J, const int32_t *pairs,
                             int n_steps, int n_pairs, double tol, int32_t *rotations, void *stream);

@@ -172,6 +172,8 @@ def _cores(m):
 
 @pytest.mark.parametrize("m,count", [(96, 1), (96, 3), (65, 3)])
 def test_batched_jacobi_is_bitwise_the_single_one(hip, m, count):
+    """jacobi_svd is the batch of one matrix through the same driver and kernel, so this shows that a matrix of a batch does
+    not depend on its batch-mates: floor, rotations, sweep count and every bit of the factors."""
     import torch
     from burgers_hip import pod
     Rs = _dev(np.stack(_cores(m)[:count]))

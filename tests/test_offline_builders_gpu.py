@@ -3,7 +3,8 @@ committed POD / quadratic-manifold artefacts, LAPACK, and oracle.burgers_ref.com
 
 pod.thin_svd hands CPU tensors to LAPACK, so only device tensors reach the HIP kernel bg_jacobi_sweep.  The cases
 cover the sizes the project builds at (m = 512 training core, 1024 x 808 bench gather), the kernel's strided loops
-on two to four trips, a leading dimension above m, rank-deficient cores and the refusals.
+on two to four trips, a leading dimension above m, the single entry point as the batch of one, rank-deficient cores and
+the refusals.
 reference: POD/pod.py:8-14, :68-90; Quadratic_manifold/build_quadratic_manifold.py:25-48, quad_utils.py:63-81."""
 import numpy as np
 import pytest
@@ -141,6 +142,54 @@ def test_jacobi_sweep_leading_dimension(hip):
     assert r1 == r2 and r1 > 0
     assert torch.equal(G2[:, m:], pad_G) and torch.equal(J2[:, m:], pad_J)
     assert torch.equal(G2[:, :m], G1) and torch.equal(J2[:, :m], J1)
+
+
+def test_jacobi_sweep_is_the_batch_of_one(hip):
+    """bg_jacobi_sweep forwards to the batched sweep: at m = 65 (odd: a bye in every step; more columns than one wave) and
+    ld = 68, one sweep through bg_jacobi_sweep and through bg_jacobi_sweep_batched(count = 1, stride = m ld) leaves G, J,
+    the padding columns (at their sentinel) and the rotation count bit for bit equal.  With count = 2 and stride = m ld + 11
+    either matrix equals its count = 1 result, and the 11 doubles between the two stay at the sentinel."""
+    from burgers_hip import lib, pod
+    L = lib.load()
+    m, ld, gap, sentinel = 65, 68, 11, -7.25
+    rng = np.random.default_rng(65)
+    cores = [_dev(_graded(m, rng)[0]) for _ in range(2)]
+    pairs = pod._round_robin(m).cuda()
+    stream = lib.stream_ptr(torch.device("cuda"))
+
+    def sweep(mats, stride, batched):
+        count = len(mats)
+        G = torch.full(((count - 1) * stride + m * ld,), sentinel, dtype=torch.float64, device="cuda")
+        J = G.clone()
+        for k, A in enumerate(mats):
+            G[k * stride:k * stride + m * ld].view(m, ld)[:, :m] = A
+            J[k * stride:k * stride + m * ld].view(m, ld)[:, :m] = torch.eye(m, dtype=torch.float64, device="cuda")
+        rot = torch.zeros((count,), dtype=torch.int32, device="cuda")
+        if batched:
+            lib.check(L.bg_jacobi_sweep_batched(m, ld, count, stride, lib.ptr(G), lib.ptr(J), lib.ptr(pairs), pairs.shape[0],
+                                                pairs.shape[1], 1e-15, lib.ptr(rot), stream), "bg_jacobi_sweep_batched")
+        else:
+            lib.check(L.bg_jacobi_sweep(m, ld, lib.ptr(G), lib.ptr(J), lib.ptr(pairs), pairs.shape[0], pairs.shape[1], 1e-15,
+                                        lib.ptr(rot), stream), "bg_jacobi_sweep")
+        torch.cuda.synchronize()
+        return G, J, rot.tolist()
+
+    alone = []
+    for A in cores:
+        G1, J1, r1 = sweep([A], m * ld, batched=False)
+        Gb, Jb, rb = sweep([A], m * ld, batched=True)
+        assert r1 == rb and r1[0] > 0
+        assert torch.equal(G1, Gb) and torch.equal(J1, Jb)                      # padding columns included
+        for X in (G1, J1):
+            assert bool((X.view(m, ld)[:, m:] == sentinel).all())
+        assert not torch.equal(G1.view(m, ld)[:, :m], A)                        # the sweep did rotate
+        alone.append((G1, J1, r1[0]))
+    stride = m * ld + gap
+    G2, J2, r2 = sweep(cores, stride, batched=True)
+    for k, (G1, J1, r1) in enumerate(alone):
+        assert r2[k] == r1, k
+        assert torch.equal(G2[k * stride:k * stride + m * ld], G1) and torch.equal(J2[k * stride:k * stride + m * ld], J1), k
+    assert bool((G2[m * ld:stride] == sentinel).all()) and bool((J2[m * ld:stride] == sentinel).all())
 
 
 def test_jacobi_svd_rank_deficient(hip):
