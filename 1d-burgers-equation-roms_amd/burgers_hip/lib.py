@@ -172,6 +172,8 @@ _SIGNATURES = {
     "bg_ann_rom_run": _loop(6, [c_double_p], after_batch=_ANN_MLP),
     "bg_rbf_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
     "bg_rbf_rom_run": _loop(8, [c_double_p] * 6 + [ctypes.c_double]),
+    "bg_rbf_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
+    "bg_rbf_rom_run_long": _loop(8, [c_double_p] * 6 + [ctypes.c_double]),
     "bg_local_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
     "bg_local_rom_run": _loop(7, _LOCAL_OPERANDS, out=_LOOP_OUT_CLUSTERS),
     "bg_local_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),

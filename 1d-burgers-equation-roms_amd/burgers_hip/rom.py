@@ -62,6 +62,7 @@ _ROUTES = {r.entry: r for r in (
            "bg_quad_rom_run_long_max_n", group=4, supg=False),
     _Route("bg_ann_rom_run", 2), _Route("bg_rbf_rom_run", 2), _Route("bg_local_rom_run", 2),
     _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
+    _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
 )}
 
 
@@ -1229,9 +1230,23 @@ class RbfFusedPlan:
     """The operand copies bg_rbf_rom_run reads, built once per closure and basis on the device (include/burgers_hip.h):
     UT = [U_p^T; U_s^T] with row stride 512, the centres transposed, the output-scaled weights Wd and the bias padded to
     128 columns, x_min and dx (the closure's own scaling, RbfClosure).  ``ok`` is False when the closure or the mesh is
-    beyond bg_rbf_rom_limits (N > 512, n > 20, nbar > 128 or too many centres)."""
+    beyond bg_rbf_rom_limits (N > 512, n > 20, nbar > 128 or too many centres).
+    ``long_mesh``: the operands of bg_rbf_rom_run_long instead, UT with row stride 1024; ``ok`` only for 513 <= N <= 1024
+    within the closure limits of bg_rbf_rom_run_long_limits, and shapes that do not fit together raise ValueError before
+    anything is copied to the device."""
 
-    def __init__(self, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device):
+    def __init__(self, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device, long_mesh=False):
+        self.long_mesh = bool(long_mesh)
+        if self.long_mesh:
+            up, us, xt, w = (tuple(np.shape(a)) for a in (U_p, U_s, X_train, W))
+            if len(up) != 2 or len(us) != 2 or up[0] != us[0]:
+                raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
+            if len(xt) != 2 or len(w) != 2 or xt[1] != up[1] or w != (xt[0], us[1]):
+                raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
+            for name, v, k in (("x_min", x_min, up[1]), ("x_max", x_max, up[1]), ("y_min", y_min, us[1]), ("y_max", y_max, us[1])):
+                if tuple(np.shape(v)) != (k,):
+                    raise ValueError(f"{name} must have {k} entries")
+            device = _lib.require_device(device)
         self.Up, self.Us = _as_dev(U_p, device), _as_dev(U_s, device)
         if self.Up.dim() != 2 or self.Us.dim() != 2 or self.Up.shape[0] != self.Us.shape[0]:
             raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
@@ -1241,12 +1256,17 @@ class RbfFusedPlan:
         if rbf.n != self.n or rbf.Wd.shape[1] != self.nbar:
             raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
         self.Ns, self.kind, self.eps = rbf.Ns, rbf.kind, rbf.eps
-        max_n, max_nbar, max_ns = _lib.limits("bg_rbf_rom_limits", 3)
-        self.ok = self.N <= 512 and self.n <= max_n and self.nbar <= max_nbar and self.Ns <= max_ns
+        if self.long_mesh:
+            ld, max_n, max_nbar, max_ns = _lib.limits("bg_rbf_rom_run_long_limits", 4)
+            self.ok = 512 < self.N <= ld and self.n <= max_n and self.nbar <= max_nbar and self.Ns <= max_ns
+        else:
+            ld = 512
+            max_n, max_nbar, max_ns = _lib.limits("bg_rbf_rom_limits", 3)
+            self.ok = self.N <= 512 and self.n <= max_n and self.nbar <= max_nbar and self.Ns <= max_ns
         if not self.ok:
             return
         f64 = dict(dtype=torch.float64, device=device)
-        self.UT = torch.zeros((self.n + self.nbar, 512), **f64)
+        self.UT = torch.zeros((self.n + self.nbar, ld), **f64)
         self.UT[:self.n, :self.N] = self.Up.t()
         self.UT[self.n:, :self.N] = self.Us.t()
         self.XtT, self.x_min, self.dx = rbf.XtT, rbf.x_min.contiguous(), rbf.dx.contiguous()
@@ -1256,24 +1276,24 @@ class RbfFusedPlan:
         self.bias[:self.nbar] = rbf.bias
 
 
-def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
-                      projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None,
-                      plan=None, balance=True, options=0):
-    """``pod_rbf_prom`` for a batch with the whole time loop on the device (bg_rbf_rom_run): one workgroup per sample,
-    the closure evaluated in-kernel in fp64, the reduced solve with partial pivoting.  Returns None when the closure is
-    outside bg_rbf_rom_limits.  ``plan``: an RbfFusedPlan of the same closure and basis to reuse across calls
-    (``res.plan``); the closure arguments are then not read again, U_p only for its shape."""
+def _rbf_device_loop(route, X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                     projection, kernel, E, tol_newton, max_newton, device, plan, balance, options):
+    """What pod_rbf_run_fused (bg_rbf_rom_run) and pod_rbf_run_long (bg_rbf_rom_run_long) share: the plan and its checks,
+    the launch, the result.  Returns None when the plan's closure or mesh is outside what the entry point covers."""
     proj = _projection(projection, "projection must be 'LSPG' or 'Galerkin'.")
+    long_mesh = route.entry == "bg_rbf_rom_run_long"
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     if plan is None:
-        plan = RbfFusedPlan(U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device)
+        plan = (RbfFusedPlan(U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device, long_mesh=True)
+                if long_mesh else RbfFusedPlan(U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, device))
     Up = U_p if isinstance(U_p, torch.Tensor) else np.asarray(U_p)
-    if plan.N != len(Xh) or tuple(Up.shape) != (plan.N, plan.n) or plan.Up.device != device:
-        raise ValueError("the plan must be built for this mesh and U_p (and live on the device of the call)")
+    if (plan.N != len(Xh) or tuple(Up.shape) != (plan.N, plan.n) or plan.Up.device != device
+            or plan.long_mesh != long_mesh):
+        raise ValueError("the plan must be built for this mesh, U_p and entry point (and live on the device of the call)")
     if not plan.ok:
         return None
-    res = _device_loop(_ROUTES["bg_rbf_rom_run"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
+    res = _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance,
                        lambda f, N, B, x, inputs, opts, outputs: f(
                            N, B, plan.n, plan.nbar, plan.Ns, int(nsteps), proj, plan.kind, x, _lib.ptr(plan.UT),
                            _lib.ptr(plan.XtT), _lib.ptr(plan.Wd), _lib.ptr(plan.bias), _lib.ptr(plan.x_min),
@@ -1283,13 +1303,52 @@ def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon
     return res
 
 
+def pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                      projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None,
+                      plan=None, balance=True, options=0):
+    """``pod_rbf_prom`` for a batch with the whole time loop on the device (bg_rbf_rom_run): one workgroup per sample,
+    the closure evaluated in-kernel in fp64, the reduced solve with partial pivoting.  Returns None when the closure is
+    outside bg_rbf_rom_limits.  ``plan``: an RbfFusedPlan of the same closure and basis to reuse across calls
+    (``res.plan``); the closure arguments are then not read again, U_p only for its shape."""
+    return _rbf_device_loop(_ROUTES["bg_rbf_rom_run"], X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min,
+                            x_max, y_min, y_max, projection, kernel, E, tol_newton, max_newton, device, plan, balance, options)
+
+
+def pod_rbf_run_long(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                     projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None,
+                     plan=None, balance=True, options=0):
+    """pod_rbf_run_fused for meshes of 513 <= N <= 1024 nodes (bg_rbf_rom_run_long): the same loop on eight waves, one
+    workgroup per compute unit.  Returns None when the mesh or the closure is outside bg_rbf_rom_run_long_limits.
+    ``plan``: an RbfFusedPlan built with ``long_mesh=True`` (``res.plan``)."""
+    return _rbf_device_loop(_ROUTES["bg_rbf_rom_run_long"], X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon,
+                            x_min, x_max, y_min, y_max, projection, kernel, E, tol_newton, max_newton, device, plan, balance,
+                            options)
+
+
+def _rbf_route(N, fused=False, long_mesh=False):
+    """The device loops pod_rbf_run tries for a mesh of N nodes, in this order; each is taken if the RbfFusedPlan of the
+    closure for it is ``ok`` (inside its limits), and "host" is what is left."""
+    if not fused:
+        return ()
+    return (("bg_rbf_rom_run_long",) if long_mesh and N > _ROUTES["bg_rbf_rom_run"].max_n else ()) + ("bg_rbf_rom_run",)
+
+
 def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
-                projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None, fused=False):
+                projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None, fused=False,
+                long_mesh=False):
     """Batched ``pod_rbf_prom`` (FEM/fem_burgers.py:1278-1398).  Default: the batched iteration driven from the host.
     ``fused``: the device-side time loop bg_rbf_rom_run (pod_rbf_run_fused) when the closure is within bg_rbf_rom_limits,
-    otherwise the host-driven iteration as well."""
+    otherwise the host-driven iteration as well.
+    ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= 1024 whose closure is inside bg_rbf_rom_run_long_limits
+    take the device-side loop bg_rbf_rom_run_long (pod_rbf_run_long) instead of the host-driven iteration."""
     proj = _projection(projection, "projection must be 'LSPG' or 'Galerkin'.")
-    if fused:
+    tries = _rbf_route(np.shape(X)[0], fused, long_mesh)
+    if "bg_rbf_rom_run_long" in tries:
+        res = pod_rbf_run_long(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                               projection, kernel, E, tol_newton, max_newton, device)
+        if res is not None:
+            return check_singular(res)
+    if "bg_rbf_rom_run" in tries:
         res = pod_rbf_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
                                 projection, kernel, E, tol_newton, max_newton, device)
         if res is not None:

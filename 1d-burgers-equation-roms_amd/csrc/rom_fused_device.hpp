@@ -41,7 +41,8 @@ __device__ __forceinline__ void lds_add_f64(double* p, double v)
 // Galerkin passes split the B side (cb): a pass forms only the (A Phi) operands of its own column blocks, so two passes
 // form every operand once (a split of the A side formed all of them twice: 240 instructions).
 // NRED: how the four waves' partial systems meet.  4: one LDS buffer per wave, summed by the reader as
-// (w0 + w1) + (w2 + w3) (the batched path's order).  2: waves 0, 1 store, a workgroup barrier, waves 2, 3 add theirs on
+// (w0 + w1) + (w2 + w3) (the batched path's order); 8: the same for a workgroup of eight waves (rom_rbf_fused's long
+// instantiation), summed as ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).  2: waves 0, 1 store, a workgroup barrier, waves 2, 3 add theirs on
 // top (every address receives exactly one add: the result does not depend on timing); the reader sums
 // (w0 + w2) + (w1 + w3).  Half the LDS (28 KB instead of 56 KB at r = 40) for one more barrier per pass.
 template <int NB>
@@ -88,7 +89,7 @@ __device__ __forceinline__ void mfma_pass(const double (&frag)[NB][S], const Hal
                                           int rowbase, int t, int w, int lane,
                                           double (*__restrict__ s_red)[RW][RW + 4], double (*__restrict__ s_wtu)[RW])
 {
-    static_assert(NRED == 4 || NRED == 2, "four per-wave partial systems, or two shared by wave pairs");
+    static_assert(NRED == 8 || NRED == 4 || NRED == 2, "one partial system per wave (four or eight waves), or two shared by wave pairs");
     static_assert(!PENTA || (GAL && CW >= 6), "the pentadiagonal form runs the Galerkin pass on six coefficients per row");
     constexpr int NROW = pass_rows<NB, GAL, PENTA>(CA0, CA1);
     constexpr int NACC = NROW + (LAST ? NB : 0);
@@ -195,7 +196,7 @@ __device__ __forceinline__ void mfma_pass(const double (&frag)[NB][S], const Hal
         double v = 0.0;
 #pragma unroll
         for (int q = 0; q < NACC; ++q) v += acc[q];
-        if (writer) s_red[NRED == 4 ? w : (w & 1)][oi][oj] = v;
+        if (writer) s_red[NRED != 2 ? w : (w & 1)][oi][oj] = v;
         if constexpr (NRED == 2) __syncthreads();
         return;
     }
@@ -231,7 +232,7 @@ __device__ __forceinline__ void mfma_pass(const double (&frag)[NB][S], const Hal
             }
         }
     };
-    if constexpr (NRED == 4) {
+    if constexpr (NRED != 2) {
         for_each_acc([&](int p, int ca, int cb) { if (writer) s_red[w][4 * ca + oi][4 * cb + oj] = acc[p]; });
     } else {
         double (*dst)[RW + 4] = s_red[w & 1];
@@ -321,11 +322,14 @@ __device__ __forceinline__ void lu_factor_panel(double (&c)[4], int p, int lane,
 // The partial-pivoting solve of the repair kernel (PIV): one wave reloads the summed system from the per-wave partials and
 // runs the routine of bg_lu_solve.  It lives in a kernel of its own: as a cold branch (even out of line) inside the fast
 // kernel it cost 4.7 us per iteration through the register allocation around the call site.
-// sum of the per-wave (NRED = 4) / per-wave-pair (NRED = 2, see mfma_pass) partial systems
+// sum of the per-wave (NRED = 4, 8) / per-wave-pair (NRED = 2, see mfma_pass) partial systems
 template <int NRED, int RW>
 __device__ __forceinline__ double red_sum(const double (*__restrict__ s_red)[RW][RW + 4], int rr, int cc)
 {
-    if constexpr (NRED == 4) return (s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc]);
+    if constexpr (NRED == 8)
+        return ((s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc])) +
+               ((s_red[4][rr][cc] + s_red[5][rr][cc]) + (s_red[6][rr][cc] + s_red[7][rr][cc]));
+    else if constexpr (NRED == 4) return (s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc]);
     else return s_red[0][rr][cc] + s_red[1][rr][cc];
 }
 

@@ -1,7 +1,8 @@
 // rom_rbf_fused.hip -- the whole POD-RBF PROM time loop of one sample on one compute unit, and its C-ABI entry point.
 //
 // Replaces FEMBurgers.pod_rbf_prom (reference FEM/fem_burgers.py:1278-1398, closure :160-260) for a batch of samples: one
-// 256-thread workgroup owns a sample for ALL time steps and Gauss-Newton iterations.  Per iteration, all fp64, with no
+// 256-thread workgroup (512 threads for meshes of 513 .. 1024 nodes, bg_rbf_rom_run_long) owns a sample for ALL time steps
+// and Gauss-Newton iterations.  Per iteration, all fp64, with no
 // kernel boundary (the arithmetic of the reference and of the host-driven path burgers_hip/rom.py::pod_rbf_run):
 //     q_p = U_p^T U0, recomputed from the current iterate every iteration                       :1352
 //     -> closure Jacobian at q_p: xs = 2 (q_p - x_min) / dx - 1, per centre the kernel value and the gradient factors
@@ -32,13 +33,14 @@ constexpr int RBF_NB = 5;                    // column blocks of the projection:
 constexpr int RBF_MAX_N = 4 * RBF_NB;
 constexpr int RBF_MAX_NBAR = 128;            // Wd and bias are padded to this many columns
 constexpr int RBF_MAX_NS = 1 << 16;          // centres: streamed in tiles, the bound only keeps Ns * 128 in int range
-constexpr int RBF_UT_LD = 512;               // row stride of UT: the largest N
+constexpr int RBF_UT_LD = 512;               // row stride of UT: the largest N of bg_rbf_rom_run
+constexpr int RBF_LONG_UT_LD = 1024;         // ... and of bg_rbf_rom_run_long
 constexpr int RBF_TILE = 128;                // centres per LDS tile
 constexpr int RBF_GS = 24;                   // s_G row: wave w's five k = 5 w .. 5 w + 4 at [6 w .. 6 w + 4] (16-byte reads)
 
 struct RbfRunArgs {
     const double* x;        // [N]
-    const double* UT;       // [n + nbar][512]: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, zero columns from N
+    const double* UT;       // [n + nbar][UT_LD]: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, zero columns from N
     const double* XtT;      // [n][Ns] centres, centre index fastest
     const double* Wd;       // [Ns][128] W dy/2, zero columns from nbar
     const double* bias;     // [128] dy/2 + y_min, zero from nbar
@@ -58,7 +60,7 @@ struct RbfRunArgs {
 
 // The halo rows of a lane's block of S tangent rows: the last row of the block below and the first row of the block above,
 // published by their owners in s_ehi / s_elo (the tangent is formed in registers, see the kernel); zero outside the mesh.
-template <int NB>
+template <int NB, int LAST = 63>
 struct HaloEdges {
     const double (*elo)[4 * NB];
     const double (*ehi)[4 * NB];
@@ -70,16 +72,25 @@ struct HaloEdges {
             const double v = ehi[owner > 0 ? owner - 1 : 0][4 * c + t];
             return owner > 0 ? v : 0.0;
         }
-        const double v = elo[owner < 63 ? owner + 1 : 63][4 * c + t];
-        return owner < 63 ? v : 0.0;
+        const double v = elo[owner < LAST ? owner + 1 : LAST][4 * c + t];
+        return owner < LAST ? v : 0.0;
     }
 };
 
-template <int S, int PROJ>
-__global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
+// UT_LD: the row stride of UT; NW: waves per workgroup.  The defaults are bg_rbf_rom_run's: four waves, 64 owners of S rows,
+// two workgroups per CU.  bg_rbf_rom_run_long runs the same code at S = 8 on eight waves (N <= 1024: 128 owners), one
+// workgroup per CU: the register profile and the two waves per SIMD of the S = 8 instantiation, 141 KB of LDS.  What the
+// eight waves change: one partial system per wave summed in a fixed order (NRED = 8), waves 4 .. 7 take the second half of
+// every centre tile in the Jacobian, the value phase splits a tile in four, the strided loops step by 512.
+template <int S, int PROJ, int UT_LD = RBF_UT_LD, int NW = 4>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunArgs a)
 {
+    static_assert(NW == 4 || NW == 8, "four waves, or eight: 128 owners of S rows each");
     constexpr int NB = RBF_NB;
-    constexpr int NPAD = 64 * S;
+    constexpr int NT = 64 * NW, NOWN = 16 * NW;  // threads, owners of S rows
+    constexpr int NPAD = NOWN * S;
+    constexpr int NIT = NPAD / NT;               // rows per thread of the strided loops
+    constexpr int NP = NT / RBF_MAX_NBAR;        // parts of a tile in the value phase
     constexpr int RW = 4 * NB;
     constexpr bool GAL = PROJ == BG_PROJ_GALERKIN;
     // Accumulators per projection pass next to the 2 S NB fragment registers: two passes for either form (Galerkin 30 as
@@ -90,22 +101,22 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
     __shared__ double s_g[NPAD], s_h[NPAD];
     __shared__ double s_fdt[NPAD];              // dt F (in LDS: live across the whole sample, it took registers from the projection)
     __shared__ double s_q[RW], s_x[RW], s_xs[RW], s_sc[RW];
-    __shared__ double s_part[4][RW];             // per-wave partial sums of U_p^T u
-    __shared__ double s_fp[2][RBF_MAX_NBAR];     // closure value: partial sums of the two halves of every tile
+    __shared__ double s_part[NW][RW];            // per-wave partial sums of U_p^T u
+    __shared__ double s_fp[NP][RBF_MAX_NBAR];    // closure value: partial sums of the NP parts of every tile
     __shared__ double s_f[RBF_MAX_NBAR];
     __shared__ int s_info;
-    // Phases of an iteration never overlap in time and share one block of LDS (two workgroups per CU need <= 80 KB each):
+    // Phases of an iteration never overlap in time and share one block of LDS (four waves: two workgroups per CU need <= 80 KB each):
     //   Jacobian + tangent: s_G, s_J  |  assembly + projection + solve: s_coef, s_elo, s_ehi, s_red  |  value: s_phi
     constexpr int kGB = RBF_TILE * RBF_GS * 8, kJB = RBF_MAX_NBAR * RW * 8;
-    constexpr int kCoefB = NPAD * 4 * 8, kEdgeB = 64 * RW * 8, kRedB = 4 * RW * (RW + 4) * 8;
+    constexpr int kCoefB = NPAD * 4 * 8, kEdgeB = NOWN * RW * 8, kRedB = NW * RW * (RW + 4) * 8;
     constexpr int kPhaseJ = kGB + kJB, kPhaseP = kCoefB + 2 * kEdgeB + kRedB;
     __shared__ __attribute__((aligned(16))) unsigned char s_shared[kPhaseJ > kPhaseP ? kPhaseJ : kPhaseP];
     auto& s_G = *reinterpret_cast<double (*)[RBF_TILE][RBF_GS]>(s_shared);
     auto& s_J = *reinterpret_cast<double (*)[RBF_MAX_NBAR][RW]>(s_shared + kGB);
     auto& s_coef = *reinterpret_cast<double (*)[NPAD][4]>(s_shared);
-    auto& s_elo = *reinterpret_cast<double (*)[64][RW]>(s_shared + kCoefB);
-    auto& s_ehi = *reinterpret_cast<double (*)[64][RW]>(s_shared + kCoefB + kEdgeB);
-    auto& s_red = *reinterpret_cast<double (*)[4][RW][RW + 4]>(s_shared + kCoefB + 2 * kEdgeB);
+    auto& s_elo = *reinterpret_cast<double (*)[NOWN][RW]>(s_shared + kCoefB);
+    auto& s_ehi = *reinterpret_cast<double (*)[NOWN][RW]>(s_shared + kCoefB + kEdgeB);
+    auto& s_red = *reinterpret_cast<double (*)[NW][RW][RW + 4]>(s_shared + kCoefB + 2 * kEdgeB);
     auto& s_phi = *reinterpret_cast<double (*)[RBF_TILE]>(s_shared);
 
     // The thread-index family is re-derived from an opaque copy at the top of every Gauss-Newton pass and of its register-heavy
@@ -163,8 +174,8 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
         __syncthreads();
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
 #pragma unroll 1
-        for (int ii = 0; ii < S / 4; ++ii) {
-            const int i = tid + 256 * ii;
+        for (int ii = 0; ii < NIT; ++ii) {
+            const int i = tid + NT * ii;
             double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
             if (i < N) {
                 rom_nodal_forcing(a.x, i, N, mu2, h, a.nonuniform, frPrev, fl, hf);
@@ -181,8 +192,8 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
         for (int step = 0; step < a.nsteps && info_out == 0; ++step) {
             // ---- g = M u^n + dt F (:1330) ------------------------------------------------------------------------------
 #pragma unroll 1
-            for (int ii = 0; ii < S / 4; ++ii) {
-                const int i = tid + 256 * ii;
+            for (int ii = 0; ii < NIT; ++ii) {
+                const int i = tid + NT * ii;
                 double g = 0.0;
                 if (i < N) g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], s_u[i + 2], s_u[i + 3], s_fdt[i], h, a.nonuniform);
                 s_g[i] = g;
@@ -198,12 +209,12 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
 #pragma unroll
                     for (int c = 0; c < RW; ++c) part[c] = 0.0;
 #pragma unroll 1
-                    for (int ii = 0; ii < S / 4; ++ii) {
-                        const int i = tid + 256 * ii;
+                    for (int ii = 0; ii < NIT; ++ii) {
+                        const int i = tid + NT * ii;
                         const double uc = s_u[i + 2];    // zero beyond N
 #pragma unroll
                         for (int c = 0; c < RW; ++c)
-                            if (c < n) part[c] = __builtin_fma(UT[(size_t)c * RBF_UT_LD + i], uc, part[c]);
+                            if (c < n) part[c] = __builtin_fma(UT[(size_t)c * UT_LD + i], uc, part[c]);
                     }
 #pragma unroll
                     for (int c = 0; c < RW; ++c) {
@@ -213,14 +224,22 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                         }
                     }
                     __syncthreads();
-                    if (tid < RW) s_q[tid] = (tid < n) ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0;
+                    if constexpr (NW == 4) {
+                        if (tid < RW) s_q[tid] = (tid < n) ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0;
+                    } else {
+                        if (tid < RW)
+                            s_q[tid] = (tid < n) ? ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) +
+                                                       ((s_part[4][tid] + s_part[5][tid]) + (s_part[6][tid] + s_part[7][tid])) : 0.0;
+                    }
                     __syncthreads();
                 }
                 scale();
                 // ---- closure Jacobian at q_p (:238-260): J[j][k] = sum_i Wd[i][j] G[i][k] ----------------------------
                 // thread (w, lane) owns j = 2 lane, 2 lane + 1 and k = 5 w .. 5 w + 4: per centre one 16-byte load of Wd
-                // (L2, shared by the four waves), three broadcast LDS reads of G, ten FMAs
+                // (L2, shared by the four waves), three broadcast LDS reads of G, ten FMAs.  Eight waves: k = 5 (w & 3) ...,
+                // waves 4 .. 7 take the second half of every tile and add their sums onto those of waves 0 .. 3 in LDS
                 {
+                    const int wk = NW == 8 ? (w & 3) : w;
                     double jacc[2][5];
 #pragma unroll
                     for (int e = 0; e < 2; ++e)
@@ -241,13 +260,15 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                         }
                         __syncthreads();
                         const int tn = (Ns - i0 < RBF_TILE) ? Ns - i0 : RBF_TILE;
+                        const int ib = NW == 8 ? (w >> 2) * (RBF_TILE / 2) : 0;
+                        const int ie = (NW == 8 && ib + RBF_TILE / 2 < tn) ? ib + RBF_TILE / 2 : tn;
                         const double* __restrict__ wrow = a.Wd + (size_t)i0 * RBF_MAX_NBAR + 2 * lane;
 #pragma unroll 8
-                        for (int ii = 0; ii < tn; ++ii) {
+                        for (int ii = ib; ii < ie; ++ii) {
                             const double2 wd = *reinterpret_cast<const double2*>(wrow + (size_t)ii * RBF_MAX_NBAR);
-                            const double2 g01 = *reinterpret_cast<const double2*>(&s_G[ii][6 * w]);
-                            const double2 g23 = *reinterpret_cast<const double2*>(&s_G[ii][6 * w + 2]);
-                            const double g4 = s_G[ii][6 * w + 4];
+                            const double2 g01 = *reinterpret_cast<const double2*>(&s_G[ii][6 * wk]);
+                            const double2 g23 = *reinterpret_cast<const double2*>(&s_G[ii][6 * wk + 2]);
+                            const double g4 = s_G[ii][6 * wk + 4];
                             const double g[5] = {g01.x, g01.y, g23.x, g23.y, g4};
 #pragma unroll
                             for (int kk = 0; kk < 5; ++kk) {
@@ -256,11 +277,27 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                             }
                         }
                     }
+                    if constexpr (NW == 4) {
 #pragma unroll
-                    for (int e = 0; e < 2; ++e)
+                        for (int e = 0; e < 2; ++e)
 #pragma unroll
-                        for (int kk = 0; kk < 5; ++kk) s_J[2 * lane + e][5 * w + kk] = jacc[e][kk];
+                            for (int kk = 0; kk < 5; ++kk) s_J[2 * lane + e][5 * w + kk] = jacc[e][kk];
+                    } else if (w < 4) {
+#pragma unroll
+                        for (int e = 0; e < 2; ++e)
+#pragma unroll
+                            for (int kk = 0; kk < 5; ++kk) s_J[2 * lane + e][5 * wk + kk] = jacc[e][kk];
+                    }
                     __syncthreads();
+                    if constexpr (NW == 8) {             // every entry gets exactly one add: the sum does not depend on timing
+                        if (w >= 4) {
+#pragma unroll
+                            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                                for (int kk = 0; kk < 5; ++kk) s_J[2 * lane + e][5 * wk + kk] += jacc[e][kk];
+                        }
+                        __syncthreads();
+                    }
                 }
                 // ---- tangent W = U_p + U_s J (:1361) in this lane's projection fragments: rows rowbase .. + S - 1,
                 // column 4 c + t (the layout of mfma_pass); rows beyond N are zero (UT is zero there)
@@ -271,13 +308,13 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                     for (int c = 0; c < NB; ++c)
 #pragma unroll
                         for (int s = 0; s < S; ++s) frag[c][s] = 0.0;
-                    const double* __restrict__ us = UT + (size_t)n * RBF_UT_LD + rowbase;
+                    const double* __restrict__ us = UT + (size_t)n * UT_LD + rowbase;
 #pragma unroll 4
                     for (int j = 0; j < nbar; ++j) {
                         double uv[S];
 #pragma unroll
                         for (int s = 0; s < S; s += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(us + (size_t)j * RBF_UT_LD + s);
+                            const double2 v = *reinterpret_cast<const double2*>(us + (size_t)j * UT_LD + s);
                             uv[s] = v.x; uv[s + 1] = v.y;
                         }
                         double jv[NB];
@@ -291,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
 #pragma unroll
                     for (int c = 0; c < NB; ++c) {
                         const int col = 4 * c + t;
-                        const double* __restrict__ up = UT + (size_t)(col < n ? col : 0) * RBF_UT_LD + rowbase;
+                        const double* __restrict__ up = UT + (size_t)(col < n ? col : 0) * UT_LD + rowbase;
 #pragma unroll
                         for (int s = 0; s < S; s += 2) {
                             const double2 v = *reinterpret_cast<const double2*>(up + s);
@@ -307,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                     s_ehi[owner][4 * c + t] = frag[c][S - 1];
                 }
                 // ---- assembly: A(u_k), R(u_k) per row into LDS (:1330-1346) ------------------------------------------
-                for (int i = tid; i < NPAD; i += 256) {
+                for (int i = tid; i < NPAD; i += NT) {
                     double lo, di, up, R;
                     const bool in = i < N;
                     const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
@@ -320,12 +357,12 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                 // ---- projection (:1361) ------------------------------------------------------------------------------
                 {
                     double (*s_wtu)[RW] = s_part;        // the Phi^T u extras of the LSPG pass: not used here
-                    mfma_passes<S, NB, GAL, RW, 4, kAccBudget>(frag, HaloEdges<NB>{s_elo, s_ehi, owner, t}, s_coef, s_u,
+                    mfma_passes<S, NB, GAL, RW, NW, kAccBudget>(frag, HaloEdges<NB, NOWN - 1>{s_elo, s_ehi, owner, t}, s_coef, s_u,
                                                                rowbase, t, w, lane, s_red, s_wtu);
                 }
                 __syncthreads();
                 // ---- reduced solve with partial pivoting (np.linalg.solve :1365) -------------------------------------
-                if (w == 0) pivoted_solve<NB, GAL, 4>(s_red, s_x, &s_info, lane, n);
+                if (w == 0) pivoted_solve<NB, GAL, NW>(s_red, s_x, &s_info, lane, n);
                 __syncthreads();
                 if (s_info != 0 && info_out == 0) info_out = s_info;
                 // ---- q_new = q_p + dq, err = |dq| / |q_new| (|dq| when |q_new| = 0) (:1366-1390) ----------------------
@@ -358,33 +395,37 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
                         }
                         __syncthreads();
                         const int tn = (Ns - i0 < RBF_TILE) ? Ns - i0 : RBF_TILE;
-                        const int ib = half * (RBF_TILE / 2), ie = (ib + RBF_TILE / 2 < tn) ? ib + RBF_TILE / 2 : tn;
+                        const int ib = half * (RBF_TILE / NP), ie = (ib + RBF_TILE / NP < tn) ? ib + RBF_TILE / NP : tn;
                         const double* __restrict__ wcol = a.Wd + (size_t)i0 * RBF_MAX_NBAR + j;
 #pragma unroll 8
                         for (int ii = ib; ii < ie; ++ii) facc = __builtin_fma(s_phi[ii], wcol[(size_t)ii * RBF_MAX_NBAR], facc);
                     }
                     s_fp[half][j] = facc;
                     __syncthreads();
-                    if (tid < RBF_MAX_NBAR) s_f[tid] = (s_fp[0][tid] + s_fp[1][tid]) + a.bias[tid];
+                    if constexpr (NP == 2) {
+                        if (tid < RBF_MAX_NBAR) s_f[tid] = (s_fp[0][tid] + s_fp[1][tid]) + a.bias[tid];
+                    } else {
+                        if (tid < RBF_MAX_NBAR) s_f[tid] = ((s_fp[0][tid] + s_fp[1][tid]) + (s_fp[2][tid] + s_fp[3][tid])) + a.bias[tid];
+                    }
                     __syncthreads();
                 }
                 // ---- decode U1 = U_p q_new + U_s f (:1378-1381) ------------------------------------------------------
                 rederive();
 #pragma unroll 1
-                for (int ii = 0; ii < S / 4; ++ii) {
-                    const int i = tid + 256 * ii;
+                for (int ii = 0; ii < NIT; ++ii) {
+                    const int i = tid + NT * ii;
                     double up = 0.0, us = 0.0;
 #pragma unroll 4
-                    for (int c = 0; c < n; ++c) up = __builtin_fma(UT[(size_t)c * RBF_UT_LD + i], s_q[c], up);
-                    const double* __restrict__ ucol = UT + (size_t)n * RBF_UT_LD + i;
+                    for (int c = 0; c < n; ++c) up = __builtin_fma(UT[(size_t)c * UT_LD + i], s_q[c], up);
+                    const double* __restrict__ ucol = UT + (size_t)n * UT_LD + i;
 #pragma unroll 8
-                    for (int j = 0; j < nbar; ++j) us = __builtin_fma(ucol[(size_t)j * RBF_UT_LD], s_f[j], us);
+                    for (int j = 0; j < nbar; ++j) us = __builtin_fma(ucol[(size_t)j * UT_LD], s_f[j], us);
                     s_u[i + 2] = (i < N) ? up + us : 0.0;
                 }
                 __syncthreads();
             }
             double* hrow = hist + (size_t)(step + 1) * N;
-            for (int i = tid; i < N; i += 256) hrow[i] = s_u[i + 2];
+            for (int i = tid; i < N; i += NT) hrow[i] = s_u[i + 2];
             if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
         }
         if (tid == 0) {
@@ -394,13 +435,47 @@ __global__ __launch_bounds__(256, 2) void rom_rbf_fused_kernel(RbfRunArgs a)
     }
 }
 
-template <int S>
+template <int S, int UT_LD = RBF_UT_LD, int NW = 4>
 void launch_rbf(int projection, int grid, hipStream_t st, const RbfRunArgs& a)
 {
     if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_GALERKIN>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_GALERKIN, UT_LD, NW>), dim3(grid), dim3(64 * NW), 0, st, a);
     else
-        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_LSPG>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_LSPG, UT_LD, NW>), dim3(grid), dim3(64 * NW), 0, st, a);
+}
+
+// The two entry points: argument checks in the order the header documents, the operand frame, the launch.
+// ``long_mesh``: bg_rbf_rom_run_long, 513 <= N <= 1024; otherwise bg_rbf_rom_run, N <= 512.
+int rbf_run(bool long_mesh, int N, int B, int n, int nbar, int Ns, int nsteps, int projection, int kind, const double* x,
+            const double* UT, const double* XtT, const double* Wd, const double* bias, const double* x_min,
+            const double* dx, double eps, const double* u0, const double* mu1, const double* mu2, double dt, double E,
+            double tol, int max_it, int options, double* hist, int32_t* iters, int32_t* flags, int32_t* info,
+            const int32_t* order, void* stream)
+{
+    if ((!long_mesh && N < 3) || B < 0 || n < 1 || nbar < 1 || Ns < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0))
+        return BG_ERR_BAD_ARG;
+    if (kind != BG_RBF_GAUSSIAN && kind != BG_RBF_IMQ) return BG_ERR_BAD_ARG;
+    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
+    if (long_mesh ? (N <= RBF_UT_LD || N > RBF_LONG_UT_LD) : N > RBF_UT_LD) return BG_ERR_UNSUPPORTED_N;
+    if (n > RBF_MAX_N || nbar > RBF_MAX_NBAR || Ns > RBF_MAX_NS) return BG_ERR_UNSUPPORTED_R;
+    if (B == 0) return BG_OK;
+    if (!x || !UT || !XtT || !Wd || !bias || !x_min || !dx || !u0 || !mu1 || !mu2 || !hist || !flags || !info ||
+        (nsteps > 0 && !iters))
+        return BG_ERR_BAD_ARG;
+    if (((uintptr_t)UT & 15) || ((uintptr_t)Wd & 15)) return BG_ERR_BAD_ARG;     // 16-byte loads
+    RbfRunArgs a;
+    a.x = x; a.UT = UT; a.XtT = XtT; a.Wd = Wd; a.bias = bias; a.x_min = x_min; a.dx = dx; a.u0 = u0; a.mu1 = mu1;
+    a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.info = info; a.order = order;
+    a.eps2 = eps * eps; a.dt = dt; a.E = E; a.tol = tol;
+    a.N = N; a.B = B; a.n = n; a.nbar = nbar; a.Ns = Ns; a.nsteps = nsteps; a.max_it = max_it; a.kind = kind;
+    a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
+    const int slots = (long_mesh ? 1 : 2) * device_cu_count();        // workgroups per CU
+    const int grid = B < slots ? B : slots;
+    hipStream_t st = (hipStream_t)stream;
+    if (long_mesh) launch_rbf<8, RBF_LONG_UT_LD, 8>(projection, grid, st, a);
+    else if (N <= 256) launch_rbf<4>(projection, grid, st, a);
+    else launch_rbf<8>(projection, grid, st, a);
+    return check_launch();
 }
 
 }  // namespace
@@ -421,27 +496,27 @@ int bg_rbf_rom_run(int N, int B, int n, int nbar, int Ns, int nsteps, int projec
                    double E, double tol, int max_it, int options, double* hist, int32_t* iters, int32_t* flags,
                    int32_t* info, const int32_t* order, void* stream)
 {
-    if (N < 3 || B < 0 || n < 1 || nbar < 1 || Ns < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
-    if (kind != BG_RBF_GAUSSIAN && kind != BG_RBF_IMQ) return BG_ERR_BAD_ARG;
-    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
-    if (N > RBF_UT_LD) return BG_ERR_UNSUPPORTED_N;
-    if (n > RBF_MAX_N || nbar > RBF_MAX_NBAR || Ns > RBF_MAX_NS) return BG_ERR_UNSUPPORTED_R;
-    if (B == 0) return BG_OK;
-    if (!x || !UT || !XtT || !Wd || !bias || !x_min || !dx || !u0 || !mu1 || !mu2 || !hist || !flags || !info ||
-        (nsteps > 0 && !iters))
-        return BG_ERR_BAD_ARG;
-    if (((uintptr_t)UT & 15) || ((uintptr_t)Wd & 15)) return BG_ERR_BAD_ARG;     // 16-byte loads
-    RbfRunArgs a;
-    a.x = x; a.UT = UT; a.XtT = XtT; a.Wd = Wd; a.bias = bias; a.x_min = x_min; a.dx = dx; a.u0 = u0; a.mu1 = mu1;
-    a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.info = info; a.order = order;
-    a.eps2 = eps * eps; a.dt = dt; a.E = E; a.tol = tol;
-    a.N = N; a.B = B; a.n = n; a.nbar = nbar; a.Ns = Ns; a.nsteps = nsteps; a.max_it = max_it; a.kind = kind;
-    a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
-    const int slots = 2 * device_cu_count();         // two workgroups per CU
-    const int grid = B < slots ? B : slots;
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 256) launch_rbf<4>(projection, grid, st, a); else launch_rbf<8>(projection, grid, st, a);
-    return check_launch();
+    return rbf_run(false, N, B, n, nbar, Ns, nsteps, projection, kind, x, UT, XtT, Wd, bias, x_min, dx, eps, u0, mu1, mu2,
+                   dt, E, tol, max_it, options, hist, iters, flags, info, order, stream);
+}
+
+int bg_rbf_rom_run_long_limits(int* max_n, int* max_r, int* max_nbar, int* max_ns)
+{
+    if (max_n) *max_n = RBF_LONG_UT_LD;
+    if (max_r) *max_r = RBF_MAX_N;
+    if (max_nbar) *max_nbar = RBF_MAX_NBAR;
+    if (max_ns) *max_ns = RBF_MAX_NS;
+    return BG_OK;
+}
+
+int bg_rbf_rom_run_long(int N, int B, int n, int nbar, int Ns, int nsteps, int projection, int kind, const double* x,
+                        const double* UT, const double* XtT, const double* Wd, const double* bias, const double* x_min,
+                        const double* dx, double eps, const double* u0, const double* mu1, const double* mu2, double dt,
+                        double E, double tol, int max_it, int options, double* hist, int32_t* iters, int32_t* flags,
+                        int32_t* info, const int32_t* order, void* stream)
+{
+    return rbf_run(true, N, B, n, nbar, Ns, nsteps, projection, kind, x, UT, XtT, Wd, bias, x_min, dx, eps, u0, mu1, mu2,
+                   dt, E, tol, max_it, options, hist, iters, flags, info, order, stream);
 }
 
 }  // extern "C"

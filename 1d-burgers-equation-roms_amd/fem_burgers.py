@@ -138,13 +138,15 @@ class FEMBurgers:
     # --------------------------------------------------------------------------- POD-RBF
     def pod_rbf_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, X_train, W, epsilon,
                      x_min, x_max, y_min, y_max, projection="LSPG", kernel="gaussian",
-                     tol_newton=1e-6, max_newton=30, fused=False):
+                     tol_newton=1e-6, max_newton=30, fused=False, long_mesh=False):
         """POD-RBF PROM with the scaled Gaussian / IMQ closure (reference :1278-1398).  ``fused``: the whole time loop
-        on the device (bg_rbf_rom_run) when the closure is within its limits; the default is the host-driven iteration."""
+        on the device (bg_rbf_rom_run) when the closure is within its limits; the default is the host-driven iteration.
+        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_rbf_rom_run_long."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_rbf_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps), U_p, U_s,
                                X_train, W, epsilon, x_min, x_max, y_min, y_max, projection=projection,
-                               kernel=kernel, E=E, tol_newton=tol_newton, max_newton=max_newton, fused=fused)
+                               kernel=kernel, E=E, tol_newton=tol_newton, max_newton=max_newton, fused=fused,
+                               long_mesh=long_mesh)
         return self._finish(res, batched)
 
     # ------------------------------------------------------------------------- local POD

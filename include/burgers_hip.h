@@ -514,6 +514,25 @@ int bg_rbf_rom_run(int N, int B, int n, int nbar, int Ns, int nsteps, int projec
                    int32_t *info, const int32_t *order, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * bg_rbf_rom_run_long -- bg_rbf_rom_run for meshes of 513 <= N <= 1024 nodes
+ *   The same kernel source, mathematics, phases, result contract, flags and info as bg_rbf_rom_run, instantiated for ONE
+ *   512-thread workgroup of eight waves per compute unit: 128 owners of 8 mesh rows, the register profile and the two waves
+ *   per SIMD of bg_rbf_rom_run at N = 512, eight per-wave partial systems summed in a fixed order; 141 KB of LDS.
+ *   Operand copies as bg_rbf_rom_run except
+ *     UT     [n + nbar][1024], 16-byte aligned, zero columns from N   (burgers_hip/rom.py::RbfFusedPlan(long_mesh=True))
+ *   Limits (bg_rbf_rom_run_long_limits: max_n 1024, max_r 20, max_nbar 128, max_ns 65536; every output optional):
+ *   N > 1024 and N <= 512 are BG_ERR_UNSUPPORTED_N (bg_rbf_rom_run covers the short meshes: what is accepted is what is
+ *   tested); n > 20, nbar > 128, Ns > 65536: BG_ERR_UNSUPPORTED_R.  BG_ERR_BAD_ARG and BG_ERR_PROJECTION as bg_rbf_rom_run,
+ *   checked in the same order; B = 0 returns BG_OK before any pointer is looked at.
+ * --------------------------------------------------------------------------------- */
+int bg_rbf_rom_run_long_limits(int *max_n, int *max_r, int *max_nbar, int *max_ns);
+int bg_rbf_rom_run_long(int N, int B, int n, int nbar, int Ns, int nsteps, int projection, int kind, const double *x,
+                        const double *UT, const double *XtT, const double *Wd, const double *bias, const double *x_min,
+                        const double *dx, double eps, const double *u0, const double *mu1, const double *mu2, double dt,
+                        double E, double tol, int max_it, int options, double *hist, int32_t *iters, int32_t *flags,
+                        int32_t *info, const int32_t *order, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * bg_local_rom_run -- batched replacement of FEMBurgers.local_prom_burgers, the WHOLE time loop on the device
  *   reference: FEM/fem_burgers.py:979-1079.  bg_rom_run with one basis per time step (csrc/rom_fused.hip, the LOCAL
  *   variant of the same kernel): at the start of every step the sample's cluster is c = argmin_c |q_g - centres[c]|^2
