@@ -518,15 +518,12 @@ inline int quad_rom_launch(int N, int B, int n, int nsteps, int projection, cons
     a.x = x; a.PhiT = PhiT; a.Phif = Phif; a.H3f = H3f; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters;
     a.flags = flags; a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.NPAD = ((N + 63) / 64) * 64; a.NG = (N + 3) / 4;
     a.B = B; a.n = n; a.nsteps = nsteps; a.max_it = max_it; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
-    const int cus = device_cu_count();
-    const int groups = (B + QG - 1) / QG;
-    const int grid = groups < cus ? groups : cus;
+    const int grid = persistent_grid((B + QG - 1) / QG, 1);
     hipStream_t st = (hipStream_t)stream;
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((quad_rom_kernel<K, true>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((quad_rom_kernel<K, false>), dim3(grid), dim3(256), 0, st, a);
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        hipLaunchKernelGGL((quad_rom_kernel<K, decltype(p)::galerkin>), dim3(grid), dim3(256), 0, st, a);
+        return check_launch();
+    });
 }
 
 }  // namespace bg

@@ -35,25 +35,10 @@ __global__ __launch_bounds__(256) void forcing_setup_kernel(const double* __rest
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const double hu = (x[N - 1] - x[0]) / (double)(N - 1);
+    const double h = (x[N - 1] - x[0]) / (double)(N - 1);
     for (int b = blockIdx.y; b < B; b += gridDim.y) {      // grid.y is capped at 65535
-        const double m = mu2[b];
-        double frPrev = 0.0, fl = 0.0, hf = 0.0;
-        if (i > 0) {
-            const double xl = x[i - 1], xr = x[i];
-            const double h = nonuniform ? xr - xl : hu;
-            const double f1 = 0.02 * exp(m * (GP_A * xl + GP_B * xr));
-            const double f2 = 0.02 * exp(m * (GP_B * xl + GP_A * xr));
-            frPrev = (f1 * GP_B + f2 * GP_A) * (0.5 * h);
-        }
-        if (i < N - 1) {
-            const double xl = x[i], xr = x[i + 1];
-            const double h = nonuniform ? xr - xl : hu;
-            const double f1 = 0.02 * exp(m * (GP_A * xl + GP_B * xr));
-            const double f2 = 0.02 * exp(m * (GP_B * xl + GP_A * xr));
-            fl = (f1 * GP_A + f2 * GP_B) * (0.5 * h);
-            hf = h * (f1 + f2);
-        }
+        double frPrev, fl, hf;
+        rom_nodal_forcing(x, i, N, mu2[b], h, nonuniform, frPrev, fl, hf);
         fdt[(size_t)b * N + i] = dt * (frPrev + fl);
         hfs[(size_t)b * N + i] = hf;
     }
@@ -67,24 +52,11 @@ __global__ __launch_bounds__(256) void mass_rhs_kernel(const double* __restrict_
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const double h6 = (x[N - 1] - x[0]) / (double)(N - 1) / 6.0;
+    const double h = (x[N - 1] - x[0]) / (double)(N - 1);
     for (int b = blockIdx.y; b < B; b += gridDim.y) {          // grid.y is capped at 65535
         const double* u = un + (size_t)b * N;
-        if (nonuniform) {
-            double v = 0.0;
-            if (i > 0) v = (x[i] - x[i - 1]) / 6.0 * __builtin_fma(2.0, u[i], u[i - 1]);
-            if (i < N - 1) v = __builtin_fma((x[i + 1] - x[i]) / 6.0, __builtin_fma(2.0, u[i], u[i + 1]), v);
-            g[(size_t)b * N + i] = v + fdt[(size_t)b * N + i];
-            continue;
-        }
-        double acc;
-        if (i == 0)
-            acc = __builtin_fma(2.0, u[0], u[1]);
-        else if (i == N - 1)
-            acc = __builtin_fma(2.0, u[i], u[i - 1]);
-        else
-            acc = __builtin_fma(4.0, u[i], u[i - 1]) + u[i + 1];
-        g[(size_t)b * N + i] = __builtin_fma(h6, acc, fdt[(size_t)b * N + i]);
+        const double um = i > 0 ? u[i - 1] : 0.0, ur = i < N - 1 ? u[i + 1] : 0.0;
+        g[(size_t)b * N + i] = rom_mass_rhs_node(x, i, N, um, u[i], ur, fdt[(size_t)b * N + i], h, nonuniform);
     }
 }
 
@@ -724,6 +696,41 @@ int dispatch_lu(int n, F&& f)
     return BG_ERR_UNSUPPORTED_R;
 }
 
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// The fragment shape of the 4x4x4 kernels: NB 4-column blocks cover r <= 40, every owner holds S rows of N <= 512.
+int frag_nb(int r) { return r <= 8 ? 2 : (r <= 16 ? 4 : (r <= 24 ? 6 : (r <= 32 ? 8 : 10))); }
+int frag_s(int N) { return N <= 256 ? 4 : 8; }
+
+// f(S, NB) for rom_reduce4_kernel and quad_tangent_kernel
+template <typename F>
+int dispatch_frag(int N, int r, F&& f)
+{
+    auto with_s = [&](auto nb) { return frag_s(N) == 4 ? f(ic<4>{}, nb) : f(ic<8>{}, nb); };
+    switch (frag_nb(r)) {
+        case 2: return with_s(ic<2>{});
+        case 4: return with_s(ic<4>{});
+        case 6: return with_s(ic<6>{});
+        case 8: return with_s(ic<8>{});
+        case 10: return with_s(ic<10>{});
+    }
+    return BG_ERR_UNSUPPORTED_R;
+}
+
+// f(S, NT) for rom_reduce_kernel: 16 S rows cover N <= 512, NT 16-column tiles r <= 47 and the extra column that carries R
+template <typename F>
+int dispatch_tiles(int N, int r, F&& f)
+{
+    auto with_s = [&](auto nt) { return N <= 128 ? f(ic<8>{}, nt) : (N <= 256 ? f(ic<16>{}, nt) : f(ic<32>{}, nt)); };
+    switch ((r + 1 + 15) / 16) {
+        case 1: return with_s(ic<1>{});
+        case 2: return with_s(ic<2>{});
+        case 3: return with_s(ic<3>{});
+    }
+    return BG_ERR_UNSUPPORTED_R;
+}
+
 }  // namespace
 
 extern "C" {
@@ -775,63 +782,26 @@ static int rom_reduce_impl(int N, int B, int r, int projection, const double* x,
     a.w_index = w_index;
     const bool force16 = (supg & BG_OPT_MFMA_16X16) != 0;
     if (w_frag && (r > 40 || force16)) return BG_ERR_UNSUPPORTED_R;
-    const int cus = device_cu_count();
-    const int grid = B < cus ? B : cus;
+    const dim3 grid(persistent_grid(B, 1)), block(256);
     hipStream_t st = (hipStream_t)stream;
     // fast path: v_mfma_f64_4x4x4_4b kernel, r <= 40 (accumulators and fragments must fit the register file)
-    if (r <= 40 && !force16) {
-        const int nb = r <= 8 ? 2 : (r <= 16 ? 4 : (r <= 24 ? 6 : (r <= 32 ? 8 : 10)));
-        const bool want_wtu = wtu != nullptr;
-        const bool gal = projection == BG_PROJ_GALERKIN;
-        const int s4 = N <= 256 ? 4 : 8;
-#define BG_LAUNCH_R4(SV, NBV)                                                                                      \
-    do {                                                                                                           \
-        if (gal)                                                                                                   \
-            hipLaunchKernelGGL((rom_reduce4_kernel<SV, NBV, BG_PROJ_GALERKIN, true>), dim3(grid), dim3(256), 0, st, a); \
-        else if (want_wtu)                                                                                         \
-            hipLaunchKernelGGL((rom_reduce4_kernel<SV, NBV, BG_PROJ_LSPG, true>), dim3(grid), dim3(256), 0, st, a);    \
-        else                                                                                                       \
-            hipLaunchKernelGGL((rom_reduce4_kernel<SV, NBV, BG_PROJ_LSPG, false>), dim3(grid), dim3(256), 0, st, a);   \
-    } while (0)
-        switch (s4 * 100 + nb) {
-            case 402: BG_LAUNCH_R4(4, 2); break;
-            case 404: BG_LAUNCH_R4(4, 4); break;
-            case 406: BG_LAUNCH_R4(4, 6); break;
-            case 408: BG_LAUNCH_R4(4, 8); break;
-            case 410: BG_LAUNCH_R4(4, 10); break;
-            case 802: BG_LAUNCH_R4(8, 2); break;
-            case 804: BG_LAUNCH_R4(8, 4); break;
-            case 806: BG_LAUNCH_R4(8, 6); break;
-            case 808: BG_LAUNCH_R4(8, 8); break;
-            case 810: BG_LAUNCH_R4(8, 10); break;
-            default: return BG_ERR_UNSUPPORTED_R;
-        }
-#undef BG_LAUNCH_R4
-        return check_launch();
-    }
-    const int S = N <= 128 ? 8 : (N <= 256 ? 16 : 32);
-    const int NT = (r + 1 + 15) / 16;     // room for the extra column that carries R
-#define BG_LAUNCH_REDUCE(SV, NTV)                                                                              \
-    do {                                                                                                       \
-        if (projection == BG_PROJ_GALERKIN)                                                                    \
-            hipLaunchKernelGGL((rom_reduce_kernel<SV, NTV, BG_PROJ_GALERKIN>), dim3(grid), dim3(256), 0, st, a); \
-        else                                                                                                   \
-            hipLaunchKernelGGL((rom_reduce_kernel<SV, NTV, BG_PROJ_LSPG>), dim3(grid), dim3(256), 0, st, a);     \
-    } while (0)
-    switch (S * 10 + NT) {
-        case 81: BG_LAUNCH_REDUCE(8, 1); break;
-        case 82: BG_LAUNCH_REDUCE(8, 2); break;
-        case 83: BG_LAUNCH_REDUCE(8, 3); break;
-        case 161: BG_LAUNCH_REDUCE(16, 1); break;
-        case 162: BG_LAUNCH_REDUCE(16, 2); break;
-        case 163: BG_LAUNCH_REDUCE(16, 3); break;
-        case 321: BG_LAUNCH_REDUCE(32, 1); break;
-        case 322: BG_LAUNCH_REDUCE(32, 2); break;
-        case 323: BG_LAUNCH_REDUCE(32, 3); break;
-        default: return BG_ERR_UNSUPPORTED_R;
-    }
-#undef BG_LAUNCH_REDUCE
-    return check_launch();
+    if (r <= 40 && !force16)
+        return dispatch_frag(N, r, [&](auto s, auto nb) {
+            constexpr int S = decltype(s)::value, NB = decltype(nb)::value;
+            if (projection == BG_PROJ_GALERKIN)
+                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_GALERKIN, true>), grid, block, 0, st, a);
+            else if (wtu)
+                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_LSPG, true>), grid, block, 0, st, a);
+            else                              // LSPG without W^T u: NB accumulators fewer
+                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_LSPG, false>), grid, block, 0, st, a);
+            return check_launch();
+        });
+    return dispatch_tiles(N, r, [&](auto s, auto nt) {
+        return dispatch_projection(projection, [&](auto p) {
+            hipLaunchKernelGGL((rom_reduce_kernel<decltype(s)::value, decltype(nt)::value, decltype(p)::value>), grid, block, 0, st, a);
+            return check_launch();
+        });
+    });
 }
 
 int bg_rom_reduce(int N, int B, int r, int projection, const double* x, const double* W, long long w_stride,
@@ -861,9 +831,6 @@ int bg_rom_reduce_lifted(int N, int B, int r, int projection, const double* x, c
     return rom_reduce_impl(N, B, r, projection, x, Phi, 0, nullptr, G, hfs, mu1, dt, E, supg, active, Ar, br, wtu, q,
                            U, 0, stream);
 }
-
-static int frag_nb(int r) { return r <= 8 ? 2 : (r <= 16 ? 4 : (r <= 24 ? 6 : (r <= 32 ? 8 : 10))); }
-static int frag_s(int N) { return N <= 256 ? 4 : 8; }
 
 int bg_rom_frag_pad(int r) { return (r < 1 || r > 40) ? 0 : 4 * frag_nb(r); }
 
@@ -895,22 +862,11 @@ int bg_quad_tangent(int N, int B, int n, const double* Phi, const double* H3, co
     const dim3 grid(NB * S, (B + chunk - 1) / chunk), block(256);
     const size_t lds = (size_t)chunk * (4 + 32 * NB);
     hipStream_t st = (hipStream_t)stream;
-#define BG_QT(SV, NKCV) hipLaunchKernelGGL((quad_tangent_kernel<SV, NKCV>), grid, block, lds, st, Phi, H3, q, active, Wfrag, N, B, n, NB, chunk)
-    switch (S * 100 + NB) {
-        case 402: BG_QT(4, 2); break;
-        case 404: BG_QT(4, 4); break;
-        case 406: BG_QT(4, 6); break;
-        case 408: BG_QT(4, 8); break;
-        case 410: BG_QT(4, 10); break;
-        case 802: BG_QT(8, 2); break;
-        case 804: BG_QT(8, 4); break;
-        case 806: BG_QT(8, 6); break;
-        case 808: BG_QT(8, 8); break;
-        case 810: BG_QT(8, 10); break;
-        default: return BG_ERR_UNSUPPORTED_R;
-    }
-#undef BG_QT
-    return check_launch();
+    return dispatch_frag(N, n, [&](auto s, auto nb) {
+        hipLaunchKernelGGL((quad_tangent_kernel<decltype(s)::value, decltype(nb)::value>), grid, block, lds, st, Phi, H3, q, active, Wfrag,
+                           N, B, n, NB, chunk);
+        return check_launch();
+    });
 }
 
 int bg_quad_features(int B, int n, const double* q, const int32_t* pair_i, const int32_t* pair_j, double* feat, void* stream)

@@ -665,15 +665,6 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     }
 }
 
-template <int S>
-void launch_ann(int projection, int grid, hipStream_t st, const AnnRunArgs& a)
-{
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_ann_fused_kernel<S, BG_PROJ_GALERKIN>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_ann_fused_kernel<S, BG_PROJ_LSPG>), dim3(grid), dim3(256), 0, st, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -713,11 +704,14 @@ int bg_ann_rom_run(int N, int B, int n, int nbar, int nsteps, int projection, co
     a.info = info; a.order = order; a.nl = n_layers; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.n = n; a.nbar = nbar;
     a.nsteps = nsteps; a.max_it = max_it; a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
     a.no_reuse = (options & BG_OPT_NO_TANGENT_REUSE) ? 1 : 0;
-    const int slots = 2 * device_cu_count();         // two workgroups per CU: one's memory latency hides behind the other
-    const int grid = B < slots ? B : slots;
+    const int grid = persistent_grid(B, 2);          // two workgroups per CU: one's memory latency hides behind the other
     hipStream_t st = (hipStream_t)stream;
-    if (N <= 256) launch_ann<4>(projection, grid, st, a); else launch_ann<8>(projection, grid, st, a);
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        constexpr int PROJ = decltype(p)::value;
+        if (N <= 256) hipLaunchKernelGGL((rom_ann_fused_kernel<4, PROJ>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((rom_ann_fused_kernel<8, PROJ>), dim3(grid), dim3(256), 0, st, a);
+        return check_launch();
+    });
 }
 
 }  // extern "C"

@@ -487,11 +487,10 @@ int bg_rom_run_blocked(int N, int B, int r, int nsteps, int projection, const do
     a.force_handback = (options & BG_OPT_FORCE_PIVOTED) ? 1 : 0;      // tests: every sample is handed back to the caller
     const int grid = B < slots ? B : slots;
     hipStream_t st = (hipStream_t)stream;
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_blocked_kernel<true>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_blocked_kernel<false>), dim3(grid), dim3(256), 0, st, a);
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        hipLaunchKernelGGL((rom_blocked_kernel<decltype(p)::galerkin>), dim3(grid), dim3(256), 0, st, a);
+        return check_launch();
+    });
 }
 
 }  // extern "C"

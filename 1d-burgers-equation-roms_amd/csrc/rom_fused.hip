@@ -408,53 +408,43 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
     }
 }
 
-template <int S, int NB, bool LOCAL>
-void launch_fused(int projection, int grid, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
+// The instantiation that covers N and the (widest) basis width r: f(S, NB) as compile-time constants.
+template <class F>
+int dispatch_fused_shape(int N, int r, F&& f)
 {
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_GALERKIN, false, LOCAL>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_fused_kernel<S, NB, BG_PROJ_LSPG, false, LOCAL>), dim3(grid), dim3(256), 0, st, a);
-}
-
-// The repair kernel: samples the fast kernel gave up on (info = BG_INFO_NEEDS_PIVOTING), redone from u0 with the
-// partial-pivoting solve.  One shape covers every N <= 512 and r <= 40 (zero padding); it is not a hot path.
-template <bool LOCAL>
-void launch_repair(int projection, int grid, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
-{
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_GALERKIN, true, LOCAL>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_fused_kernel<8, 10, BG_PROJ_LSPG, true, LOCAL>), dim3(grid), dim3(256), 0, st, a);
+    using std::integral_constant;
+    const int nb = r <= 8 ? 2 : (r <= 24 ? 6 : 10);
+    const int s4 = N <= 256 ? 4 : 8;
+    switch (s4 * 100 + nb) {
+#ifndef BG_FUSED_ONLY_810                 // (experiments compile the headline instantiation alone)
+        case 402: return f(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+        case 406: return f(integral_constant<int, 4>{}, integral_constant<int, 6>{});
+        case 410: return f(integral_constant<int, 4>{}, integral_constant<int, 10>{});
+        case 802: return f(integral_constant<int, 8>{}, integral_constant<int, 2>{});
+        case 806: return f(integral_constant<int, 8>{}, integral_constant<int, 6>{});
+#endif
+        case 810: return f(integral_constant<int, 8>{}, integral_constant<int, 10>{});
+        default: return BG_ERR_UNSUPPORTED_R;
+    }
 }
 
 // Both entry points: the fast kernel of the instantiation that covers N and r (2 workgroups per CU), then the repair
-// kernel (1 per CU).  r: the (widest) basis width.
+// kernel (1 per CU): samples the fast kernel gave up on (info = BG_INFO_NEEDS_PIVOTING), redone from u0 with the
+// partial-pivoting solve.  One repair shape covers every N <= 512 and r <= 40 (zero padding); it is not a hot path.
 template <bool LOCAL>
 int launch_run(int N, int B, int r, int projection, hipStream_t st, const typename RunArgsOf<LOCAL>::type& a)
 {
-    const int cus = device_cu_count();
-    const int grid = B < 2 * cus ? B : 2 * cus;              // two resident workgroups per CU
-    const int grid_repair = B < cus ? B : cus;
-    const int nb = r <= 8 ? 2 : (r <= 24 ? 6 : 10);
-    const int s4 = N <= 256 ? 4 : 8;
-    if (!a.force_pivoted) {
-        switch (s4 * 100 + nb) {
-#ifndef BG_FUSED_ONLY_810                 // (experiments compile the headline instantiation alone)
-            case 402: launch_fused<4, 2, LOCAL>(projection, grid, st, a); break;
-            case 406: launch_fused<4, 6, LOCAL>(projection, grid, st, a); break;
-            case 410: launch_fused<4, 10, LOCAL>(projection, grid, st, a); break;
-            case 802: launch_fused<8, 2, LOCAL>(projection, grid, st, a); break;
-            case 806: launch_fused<8, 6, LOCAL>(projection, grid, st, a); break;
-#endif
-            case 810: launch_fused<8, 10, LOCAL>(projection, grid, st, a); break;
-            default: return BG_ERR_UNSUPPORTED_R;
-        }
-        const int rc = check_launch();
-        if (rc != BG_OK) return rc;
-    }
-    if (kAblate < 0) launch_repair<LOCAL>(projection, grid_repair, st, a);     // every workgroup leaves at once unless a sample is flagged
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        constexpr int PROJ = decltype(p)::value;
+        return dispatch_fused_shape(N, r, [&](auto s, auto nb) {
+            return launch_fast_then_repair(B, 2, a.force_pivoted != 0, [&](auto piv, int grid) {
+                if constexpr (!decltype(piv)::value)
+                    hipLaunchKernelGGL((rom_fused_kernel<decltype(s)::value, decltype(nb)::value, PROJ, false, LOCAL>), dim3(grid), dim3(256), 0, st, a);
+                else if (kAblate < 0)
+                    hipLaunchKernelGGL((rom_fused_kernel<8, 10, PROJ, true, LOCAL>), dim3(grid), dim3(256), 0, st, a);
+            });
+        });
+    });
 }
 
 }  // namespace

@@ -36,15 +36,6 @@ __global__ __launch_bounds__(256, PIV ? 1 : LWG_PER_CU) void rom_local_long_kern
     BG_LONG_KERNEL_BODY(LongLocal, LMAXM);
 }
 
-template <bool PIV>
-void launch_local_long(int projection, int grid, hipStream_t st, const LocalStreamRunArgs& a)
-{
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_local_long_kernel<true, PIV>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_local_long_kernel<false, PIV>), dim3(grid), dim3(256), 0, st, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -81,9 +72,10 @@ int bg_local_rom_run_long(int N, int B, int C, int rmax, int m, int nsteps, int 
     if (!widths || !UgT || !centres) return BG_ERR_BAD_ARG;
     a.widths = widths; a.UgT = UgT; a.centres = centres; a.clusters = clusters; a.C = C; a.m = m;
     hipStream_t st = (hipStream_t)stream;
-    return long_launch_pair(B, a.force_pivoted != 0, [&](bool piv, int grid) {
-        if (piv) launch_local_long<true>(projection, grid, st, a);
-        else launch_local_long<false>(projection, grid, st, a);
+    return dispatch_projection(projection, [&](auto p) {
+        return launch_fast_then_repair(B, LWG_PER_CU, a.force_pivoted != 0, [&](auto piv, int grid) {
+            hipLaunchKernelGGL((rom_local_long_kernel<decltype(p)::galerkin, decltype(piv)::value>), dim3(grid), dim3(256), 0, st, a);
+        });
     });
 }
 

@@ -32,15 +32,6 @@ __global__ __launch_bounds__(256, PIV ? 1 : LWG_PER_CU) void rom_long_kernel(Str
     BG_LONG_KERNEL_BODY(LongPod, 0);
 }
 
-template <bool PIV>
-void launch_long(int projection, int grid, hipStream_t st, const StreamRunArgs& a)
-{
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_long_kernel<true, PIV>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_long_kernel<false, PIV>), dim3(grid), dim3(256), 0, st, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -65,9 +56,10 @@ int bg_rom_run_long(int N, int B, int r, int nsteps, int projection, const doubl
                                    hist, iters, flags, info, order);
     if (rc != BG_OK || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return long_launch_pair(B, a.force_pivoted != 0, [&](bool piv, int grid) {
-        if (piv) launch_long<true>(projection, grid, st, a);
-        else launch_long<false>(projection, grid, st, a);
+    return dispatch_projection(projection, [&](auto p) {
+        return launch_fast_then_repair(B, LWG_PER_CU, a.force_pivoted != 0, [&](auto piv, int grid) {
+            hipLaunchKernelGGL((rom_long_kernel<decltype(p)::galerkin, decltype(piv)::value>), dim3(grid), dim3(256), 0, st, a);
+        });
     });
 }
 

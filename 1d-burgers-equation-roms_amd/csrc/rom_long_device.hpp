@@ -83,22 +83,4 @@ struct LongLayout {
     rom_stream_waves<K, GAL, PIV>(a, StreamLds{s_slab, s_u, s_g, s_h, s_fdt, s_cf, s_q, s_m, s_diag, s_diag + 64, s_diag + 128,     \
                                                s_bad, (QG) > 0 ? s_qg : nullptr})
 
-// The two launches of an entry point: the fast kernel (guarded pivot-free elimination, LWG_PER_CU workgroups per CU) unless
-// BG_OPT_FORCE_PIVOTED, then the repair kernel (one per CU; every workgroup leaves at once unless a sample is marked).
-// `launch(piv, grid)` launches the instantiation for the projection at hand.
-template <class Launch>
-int long_launch_pair(int B, bool force_pivoted, const Launch& launch)
-{
-    const int cus = device_cu_count();
-    const int grid = B < LWG_PER_CU * cus ? B : LWG_PER_CU * cus;
-    const int grid_repair = B < cus ? B : cus;
-    if (!force_pivoted) {
-        launch(false, grid);
-        const int rc_fast = check_launch();
-        if (rc_fast != BG_OK) return rc_fast;
-    }
-    launch(true, grid_repair);
-    return check_launch();
-}
-
 }  // namespace bg

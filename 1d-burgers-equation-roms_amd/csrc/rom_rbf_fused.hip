@@ -435,15 +435,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
     }
 }
 
-template <int S, int UT_LD = RBF_UT_LD, int NW = 4>
-void launch_rbf(int projection, int grid, hipStream_t st, const RbfRunArgs& a)
-{
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_GALERKIN, UT_LD, NW>), dim3(grid), dim3(64 * NW), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_rbf_fused_kernel<S, BG_PROJ_LSPG, UT_LD, NW>), dim3(grid), dim3(64 * NW), 0, st, a);
-}
-
 // The two entry points: argument checks in the order the header documents, the operand frame, the launch.
 // ``long_mesh``: bg_rbf_rom_run_long, 513 <= N <= 1024; otherwise bg_rbf_rom_run, N <= 512.
 int rbf_run(bool long_mesh, int N, int B, int n, int nbar, int Ns, int nsteps, int projection, int kind, const double* x,
@@ -469,13 +460,15 @@ int rbf_run(bool long_mesh, int N, int B, int n, int nbar, int Ns, int nsteps, i
     a.eps2 = eps * eps; a.dt = dt; a.E = E; a.tol = tol;
     a.N = N; a.B = B; a.n = n; a.nbar = nbar; a.Ns = Ns; a.nsteps = nsteps; a.max_it = max_it; a.kind = kind;
     a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
-    const int slots = (long_mesh ? 1 : 2) * device_cu_count();        // workgroups per CU
-    const int grid = B < slots ? B : slots;
+    const int grid = persistent_grid(B, long_mesh ? 1 : 2);
     hipStream_t st = (hipStream_t)stream;
-    if (long_mesh) launch_rbf<8, RBF_LONG_UT_LD, 8>(projection, grid, st, a);
-    else if (N <= 256) launch_rbf<4>(projection, grid, st, a);
-    else launch_rbf<8>(projection, grid, st, a);
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        constexpr int PROJ = decltype(p)::value;
+        if (long_mesh) hipLaunchKernelGGL((rom_rbf_fused_kernel<8, PROJ, RBF_LONG_UT_LD, 8>), dim3(grid), dim3(512), 0, st, a);
+        else if (N <= 256) hipLaunchKernelGGL((rom_rbf_fused_kernel<4, PROJ>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((rom_rbf_fused_kernel<8, PROJ>), dim3(grid), dim3(256), 0, st, a);
+        return check_launch();
+    });
 }
 
 }  // namespace

@@ -51,14 +51,11 @@ int bg_rom_run_wide(int N, int B, int r, int nsteps, int projection, const doubl
     const int rc = stream_run_args(a, 2, WNMAX, WR, N, B, r, nsteps, projection, x, PhiP, u0, mu1, mu2, dt, E, tol, max_it, options,
                                    hist, iters, flags, info, order);
     if (rc != BG_OK || B == 0) return rc;
-    const int cus = device_cu_count();
-    const int grid = B < cus ? B : cus;
     hipStream_t st = (hipStream_t)stream;
-    if (projection == BG_PROJ_GALERKIN)
-        hipLaunchKernelGGL((rom_wide_kernel<true>), dim3(grid), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((rom_wide_kernel<false>), dim3(grid), dim3(256), 0, st, a);
-    return check_launch();
+    return dispatch_projection(projection, [&](auto p) {
+        hipLaunchKernelGGL((rom_wide_kernel<decltype(p)::galerkin>), dim3(persistent_grid(B, 1)), dim3(256), 0, st, a);
+        return check_launch();
+    });
 }
 
 }  // extern "C"

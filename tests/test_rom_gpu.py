@@ -80,6 +80,47 @@ def test_rom_reduce_vs_oracle(hip, N, r, shared):
                 assert rel_l2(wtu[b], Wb.T @ U[b]) < 1e-13
 
 
+# Worst figure of the six cases below, measured on one MI355X with the library as it was before forcing_setup_kernel and
+# mass_rhs_kernel called rom_device.hpp's per-node helpers: 4.384e-16 (hfs at N = 257 on the jittered mesh; dt F 3.047e-16
+# and g 2.570e-16 in the same case; the smallest, g at N = 2, 1.101e-16).  The gate is four times that: the device's exp and
+# libm's differ by an ulp or two.
+FORCING_PARENT_WORST = 4.384e-16
+
+
+@pytest.mark.parametrize("jitter", [False, True])
+@pytest.mark.parametrize("N", [2, 3, 257])
+def test_forcing_setup_and_mass_rhs_vs_numpy(hip, N, jitter):
+    """bg_forcing_setup (dt F and h_e (f(gp1) + f(gp2))) and bg_mass_rhs (M u + dt F) against numpy: compute_forcing_vector
+    (:427-461), the f_gp of :556-558 and `M @ U[:, n] + At*F` (:683).  N = 2 has no interior node, N = 3 is the first size with
+    one, N = 257 takes a second block; ``jitter``: interior nodes moved by up to 0.2 h and BG_OPT_NONUNIFORM (per-element
+    lengths).  Figure: max |device - numpy| / max |numpy| per tensor."""
+    B, dt = 3, 0.05
+    X, _ = mesh(N)
+    if jitter:
+        X[1:-1] += np.random.default_rng(N).uniform(-0.2, 0.2, N - 2) * (100.0 / (N - 1))
+    rng = np.random.default_rng(7 * N + jitter)
+    mu2 = rng.uniform(0.015, 0.03, B)
+    u = rng.uniform(0.5, 1.5, (B, N))
+    _, _, Ng, _ = br.gauss_tables()
+    xl, xr = X[:-1], X[1:]
+    f_gp = [0.02 * np.exp(mu2[:, None] * (Ng[gp, 0] * xl + Ng[gp, 1] * xr)) for gp in range(2)]
+    ref = {"fdt": dt * br.forcing_vector(X, mu2), "hfs": np.zeros((B, N))}
+    ref["hfs"][:, :-1] = (xr - xl) * (f_gp[0] + f_gp[1])
+    ref["g"] = br.tridiag_matvec(*br.mass_tridiag(X), u) + ref["fdt"]
+    opt = hip.BG_OPT_NONUNIFORM if jitter else 0
+    L, Xd, mu2d, ud = hip.load(), _dev(X), _dev(mu2), _dev(u)
+    got = {k: torch.full((B, N), -7.0, dtype=torch.float64, device="cuda") for k in ref}
+    s = hip.stream_ptr(Xd.device)
+    assert L.bg_forcing_setup(N, B, hip.ptr(Xd), hip.ptr(mu2d), dt, opt, hip.ptr(got["fdt"]), hip.ptr(got["hfs"]), s) == 0
+    assert L.bg_mass_rhs(N, B, hip.ptr(Xd), hip.ptr(ud), hip.ptr(got["fdt"]), opt, hip.ptr(got["g"]), s) == 0
+    torch.cuda.synchronize()
+    worst = {k: float(np.abs(got[k].cpu().numpy() - ref[k]).max() / np.abs(ref[k]).max()) for k in ref}
+    print(f"forcing figures N={N} jitter={jitter}: " + " ".join(f"{k}={v:.3e}" for k, v in worst.items()))
+    assert bool((got["hfs"][:, -1] == 0.0).all())
+    for k, v in worst.items():
+        assert v <= 4.0 * FORCING_PARENT_WORST, (k, v)
+
+
 def test_pod_prom_golden_and_live(hip):
     from burgers_hip import rom
     g = load_golden("committed_pod_r40.npz")
