@@ -170,6 +170,8 @@ _SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_float), c_double_p, ctypes.c_void_p]),
     "bg_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
     "bg_ann_rom_run": _loop(6, [c_double_p], after_batch=_ANN_MLP),
+    "bg_ann_rom_run_wide_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
+    "bg_ann_rom_run_wide": _loop(6, [c_double_p], after_batch=_ANN_MLP),
     "bg_rbf_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
     "bg_rbf_rom_run": _loop(8, [c_double_p] * 6 + [ctypes.c_double]),
     "bg_rbf_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),

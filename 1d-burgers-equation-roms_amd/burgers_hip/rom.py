@@ -60,7 +60,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_quad_rom_run", 1, "bg_quad_rom_max_n", group=4, supg=False),
     _Route("bg_quad_rom_run_long", "bg_quad_rom_run_long_workgroups_per_cu", "bg_quad_rom_run_long_max_r", 513,
            "bg_quad_rom_run_long_max_n", group=4, supg=False),
-    _Route("bg_ann_rom_run", 2), _Route("bg_rbf_rom_run", 2), _Route("bg_local_rom_run", 2),
+    _Route("bg_ann_rom_run", 2), _Route("bg_ann_rom_run_wide", 2), _Route("bg_rbf_rom_run", 2), _Route("bg_local_rom_run", 2),
     _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
 )}
@@ -1083,17 +1083,17 @@ class _ClosureTangent:
         return self.gemm()
 
 
-def _ann_fused_plan(model, n, nbar, N, dtype, device):
-    """The closure as bg_ann_rom_run wants it (``args``: its part of the argument list; ``keep``: the device copies
-    those pointers refer to), or None when the device-side loop does not apply (not a plain fp32 MLP the evaluator
-    recognises, or beyond bg_ann_rom_limits)."""
+def _ann_fused_plan(model, n, nbar, N, dtype, device, limits="bg_ann_rom_limits"):
+    """The closure as bg_ann_rom_run and bg_ann_rom_run_wide want it (``args``: its part of the argument list; ``keep``:
+    the device copies those pointers refer to), or None when the device-side loop does not apply (not a plain fp32 MLP
+    the evaluator recognises, or beyond ``limits``, the entry point's own ``*_limits`` symbol)."""
     import ctypes
     if dtype != torch.float32 or N > 512:
         return None
     ann = AnnEvaluator(model, n, dtype)
     if ann.layers is None:
         return None
-    max_n, max_nbar, max_w, max_l = _lib.limits("bg_ann_rom_limits", 4)
+    max_n, max_nbar, max_w, max_l = _lib.limits(limits, 4)
     widths = [ann.layers[0][0].in_features] + [lin.out_features for lin, _ in ann.layers]
     if (n > max_n or nbar > max_nbar or len(ann.layers) > max_l or max(widths[1:]) > max_w or widths[0] != n
             or widths[-1] != nbar or any(type(act) not in _ACT_KINDS for _, act in ann.layers)):
@@ -1138,17 +1138,56 @@ def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0,
                             float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
 
 
+def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, tol=1e-6, max_it=50, device=None,
+                     options=0, plan=None, balance=True):
+    """pod_ann_run_fused for models of up to 20 primary modes (bg_ann_rom_run_wide): the closure MLP of bg_ann_rom_run on
+    the mesh side of bg_rbf_rom_run.  Runs any model inside bg_ann_rom_run_wide_limits, the n <= 8 ones included; returns
+    None outside them.  ``plan``: an _ann_fused_plan(..., limits="bg_ann_rom_run_wide_limits") to reuse across calls."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    N = len(Xh)
+    Up, Us = _as_dev(U_p, device), _as_dev(U_s, device)
+    if Up.dim() != 2 or Us.dim() != 2 or Up.shape[0] != N or Us.shape[0] != N:
+        raise ValueError("U_p and U_s must have one row per mesh node")
+    n, nbar = Up.shape[1], Us.shape[1]
+    if plan is None:
+        plan = _ann_fused_plan(model.to(device=device, dtype=torch.float32).eval(), n, nbar, N, torch.float32, device,
+                               "bg_ann_rom_run_wide_limits")
+    if plan is None:
+        return None
+    UT = torch.zeros((n + nbar, 512), dtype=torch.float64, device=device)     # [U_p^T; U_s^T], zero columns from N
+    UT[:n, :N] = Up.t()
+    UT[n:, :N] = Us.t()
+    return _device_loop(_ROUTES["bg_ann_rom_run_wide"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
+                        lambda f, N, B, x, inputs, opts, outputs: f(
+                            N, B, n, nbar, int(nsteps), proj, x, _lib.ptr(UT), *inputs, *plan.args, float(dt), float(E),
+                            float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
+
+
+def _ann_route(n, fused=True, wide=False):
+    """The device-side loops pod_ann_run tries, in order: bg_ann_rom_run_wide first only for an opted-in model with more
+    primary modes than bg_ann_rom_run takes."""
+    if not fused:
+        return ()
+    return (("bg_ann_rom_run_wide",) if wide and n > _lib.limits("bg_ann_rom_limits", 4)[0] else ()) + ("bg_ann_rom_run",)
+
+
 def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG", E=0.0, tol=1e-6, max_it=50,
-                device=None, ann_dtype=torch.float32, fused=True):
+                device=None, ann_dtype=torch.float32, fused=True, wide=False):
     """Batched ``pod_ann_prom``.  The MLP and its Jacobian are evaluated in ``ann_dtype`` (the
     reference uses float32, :1219,:1241); everything else is fp64.  ``fused`` (default): the device-side time loop
     bg_ann_rom_run when the closure is a plain float32 MLP within bg_ann_rom_limits; otherwise, or with
-    ``fused=False``, the batched iteration driven from the host (MLP layers as GEMMs through PyTorch-ROCm)."""
+    ``fused=False``, the batched iteration driven from the host (MLP layers as GEMMs through PyTorch-ROCm).
+    ``wide`` (opt-in, with ``fused`` and float32): a model with more primary modes than bg_ann_rom_limits allows that is
+    inside bg_ann_rom_run_wide_limits (n <= 20) takes the device-side loop bg_ann_rom_run_wide instead of the host-driven
+    iteration; every other model routes as without the flag."""
     proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
-    if fused and ann_dtype == torch.float32:
-        res = pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device)
-        if res is not None:
-            return check_singular(res)
+    if ann_dtype == torch.float32:
+        for entry in _ann_route(np.shape(U_p)[1], fused, wide):
+            run = pod_ann_run_wide if entry == "bg_ann_rom_run_wide" else pod_ann_run_fused
+            res = run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device)
+            if res is not None:
+                return check_singular(res)
     c = _setup(X, u0, mu1, mu2, dt, E, device)
     Up, Us = _as_dev(U_p, c.device), _as_dev(U_s, c.device)
     n = Up.shape[1]

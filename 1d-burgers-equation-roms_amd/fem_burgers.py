@@ -125,14 +125,15 @@ class FEMBurgers:
         return self._finish(res, batched)
 
     # --------------------------------------------------------------------------- POD-ANN
-    def pod_ann_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, model, projection="LSPG"):
+    def pod_ann_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, model, projection="LSPG", wide=False):
         """POD-ANN PROM (reference :1177-1251).  ``model`` is any torch.nn.Module mapping
-        (., n) -> (., nbar); it is borrowed and evaluated in float32 like the reference."""
+        (., n) -> (., nbar); it is borrowed and evaluated in float32 like the reference.  ``wide``: a plain MLP with
+        9 .. 20 primary modes takes the device-side loop bg_ann_rom_run_wide instead of the host-driven iteration."""
         import copy
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_ann_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                np.asarray(U_p, dtype=np.float64), np.asarray(U_s, dtype=np.float64),
-                               copy.deepcopy(model), projection=projection, E=E)
+                               copy.deepcopy(model), projection=projection, E=E, wide=wide)
         return self._finish(res, batched)
 
     # --------------------------------------------------------------------------- POD-RBF

@@ -483,6 +483,39 @@ int bg_ann_rom_run(int N, int B, int n, int nbar, int nsteps, int projection, co
                    int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * bg_ann_rom_run_wide -- bg_ann_rom_run for models of up to 20 primary modes (the reference's n = 17, nbar = 79 POD-ANN model)
+ *   reference: FEM/fem_burgers.py:1177-1251 (loop), compute_ann_jacobian :1254-1275, model POD-ANN/pod_ann.py:38-56.
+ *   The mathematics, phases, result contract, flags and info of bg_ann_rom_run (csrc/rom_ann_wide.hip): one workgroup owns
+ *   one sample for all time steps and Gauss-Newton iterations; q_p = U_p^T u^n at the start of a time step only (:1197),
+ *   q_p += dq, err = |dq| / (|q_p| + 1e-14) (:1238-1244); the closure N(q_p) and its input-Jacobian in ONE float32
+ *   forward-mode pass (:1219, :1241), everything else fp64.  The mesh side is bg_rbf_rom_run's: the tangent
+ *   W = U_p + U_s dN (:1224) is formed in the projection's fragment registers from an nbar x 20 table, five 4-column MFMA
+ *   blocks, and the n x n solve (:1237) is np.linalg.solve's elimination with the pivot search, always; info = k + 1 on an
+ *   exactly zero pivot.
+ *   UT     [n + nbar][512] row-major, 16-byte aligned: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, every row
+ *          with zero columns from N to 511 (the layout bg_rbf_rom_run reads: the mesh-side code is the same).
+ *   the closure: n_layers, widths, wt, bias, acts, alphas exactly as bg_ann_rom_run takes them (wt[l] float32 [in4][ld],
+ *          16-byte aligned, in4 = widths[l] rounded up to 4 rows, ld = widths[l+1] rounded up to 8 columns, zero fill;
+ *          a thread fetches the weights of 4 outputs of one input as one 16-byte load, unguarded).
+ *   Limits (bg_ann_rom_run_wide_limits: max_n 20, max_nbar 128, max_width 256, max_layers 8; every output optional):
+ *   2 <= N <= 512, 1 <= n <= 20 (n <= 8 is accepted on purpose: the two entry points can be compared on one model).
+ *   Checks, in this order: BG_ERR_BAD_ARG (N < 2, B < 0, n < 1, nbar < 1, nsteps < 0, max_it < 1, dt <= 0, n_layers < 1),
+ *   BG_ERR_PROJECTION, BG_ERR_UNSUPPORTED_N (N > 512), BG_ERR_UNSUPPORTED_R (n > 20, nbar > 128, n_layers > 8), then
+ *   BG_ERR_BAD_ARG for a null closure array, widths[0] != n or widths[n_layers] != nbar, per layer BG_ERR_UNSUPPORTED_R
+ *   for a width outside 1 .. 256 and BG_ERR_BAD_ARG for a null or misaligned wt[l] or an unknown activation; B = 0 returns
+ *   BG_OK before any batch pointer is looked at; then null batch pointers and a misaligned UT are BG_ERR_BAD_ARG.
+ *   u0, mu1, mu2, hist, iters, flags (BG_FLAG_HIT_CAP, BG_FLAG_NONFINITE), info: as bg_ann_rom_run.  order: as bg_rom_run;
+ *   entries outside [0, B) are skipped.  options BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_NO_TANGENT_REUSE: the tangent is
+ *   not resident across the projection, so the closure is evaluated at every step start and the last option changes nothing.
+ * --------------------------------------------------------------------------------- */
+int bg_ann_rom_run_wide_limits(int *max_n, int *max_nbar, int *max_width, int *max_layers);
+int bg_ann_rom_run_wide(int N, int B, int n, int nbar, int nsteps, int projection, const double *x, const double *UT,
+                        const double *u0, const double *mu1, const double *mu2, int n_layers, const int *widths,
+                        const float *const *wt, const float *const *bias, const int *acts, const float *alphas,
+                        double dt, double E, double tol, int max_it, int options, double *hist, int32_t *iters,
+                        int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * bg_rbf_rom_run -- batched replacement of FEMBurgers.pod_rbf_prom, the WHOLE time loop on the device
  *   reference: FEM/fem_burgers.py:1278-1398 (loop), the scaled RBF closure :160-260 (interpolate_with_rbf_scaled
  *   :225-236, compute_rbf_jacobian_full :238-260).
