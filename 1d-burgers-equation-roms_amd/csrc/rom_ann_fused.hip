@@ -14,7 +14,8 @@
 //        iteration's tangent W = U_p + U_s dN (:1224) together, straight into LDS.
 // HBM sees u0 once and one N-row history write per time step; the MLP weights (0.5 MB) and U_s (0.4 MB) are re-read from
 // L2 every iteration.  Host-side the batched iteration of burgers_hip/rom.py needs ~40 dependent launches per iteration
-// for the same work.
+// for the same work.  The float32 fold helpers (dpp_f32, swap16_add, swap32_add) and the activation arithmetic
+// (mlp_activate) are wave_ops.hpp's, shared with rom_ann_wide.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -38,25 +39,6 @@ constexpr int ANN_MAX_LAYERS = 8;
 constexpr int ANN_MAX_WIDTH = 256;      // one thread per neuron
 constexpr int ANN_MAX_N = 8;            // reduced coordinates: two 4-column MFMA blocks
 constexpr int ANN_MAX_ROWS = 1 + ANN_MAX_N;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-// a + (a of the neighbouring row) in the even rows of 16 lanes, b + (b of the neighbouring row) in the odd rows
-__device__ __forceinline__ float swap16_add(float a, float b)
-{
-    const auto t = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
-}
-// a + (a of the other half) in lanes 0..31, b + (b of the other half) in lanes 32..63
-__device__ __forceinline__ float swap32_add(float a, float b)
-{
-    const auto t = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
-}
 
 // value of lane `src` (any lane), two ds_bpermute
 __device__ __forceinline__ double lane_f64(double v, int src)
@@ -293,21 +275,8 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
             const int half_og = half + 4 * og;
             const int kind = a.act[l];
             const float alpha = a.alpha[l];
-            // bias, activation, derivative scaling: the arithmetic of bg_mlp_act_jvp (csrc/mlp.hip)
-            auto activate = [&](float v, float& av, float& d) {
-                av = v; d = 1.0f;
-                if (kind == BG_ACT_ELU) {
-                    const float e = alpha * expf(v);
-                    av = v > 0.0f ? v : e - alpha;
-                    d = v > 0.0f ? 1.0f : e;
-                } else if (kind == BG_ACT_RELU) {
-                    av = v > 0.0f ? v : 0.0f;
-                    d = v > 0.0f ? 1.0f : 0.0f;
-                } else if (kind == BG_ACT_TANH) {
-                    av = tanhf(v);
-                    d = 1.0f - av * av;
-                }
-            };
+            // bias, activation, derivative scaling
+            auto activate = [&](float v, float& av, float& d) { mlp_activate(kind, alpha, v, av, d); };
             if constexpr (skip(8192)) lap(4);
             const bool swapfold = (NRT == 6 || NRT == 1) && span == 64 && !skip(2048);      // workgroup-uniform
             if (swapfold) {

@@ -18,15 +18,15 @@
 // feeds the decode alone and is a value-only one (1 row instead of 1 + n); row 0 is computed by the same operations in the
 // same order in either kind.  The tangent is not kept across time steps (it is not resident during the projection), so
 // BG_OPT_NO_TANGENT_REUSE is accepted and changes nothing.
-// HaloEdges and the phase structure repeat rom_rbf_fused.hip, the activation and the fold helpers rom_ann_fused.hip: those
-// two files keep their code and their register allocation.
+// The mesh side is rom_closure_device.hpp's, shared with rom_rbf_fused.hip; the float32 fold helpers and the activation
+// arithmetic are wave_ops.hpp's, shared with rom_ann_fused.hip.  This file keeps the closure, the LDS overlay and the loop.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
-#include "rom_fused_device.hpp"
+#include "rom_closure_device.hpp"
 
 namespace {
 
@@ -40,25 +40,6 @@ constexpr int AW_MAX_LAYERS = 8;
 constexpr int AW_MAX_WIDTH = 256;
 constexpr int AW_MAX_ROWS = 1 + AW_MAX_N;      // value + tangent directions
 constexpr int AW_UT_LD = 512;                  // row stride of UT: the largest N
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-// a + (a of the neighbouring row) in the even rows of 16 lanes, b + (b of the neighbouring row) in the odd rows
-__device__ __forceinline__ float swap16_add(float a, float b)
-{
-    const auto t = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
-}
-// a + (a of the other half) in lanes 0..31, b + (b of the other half) in lanes 32..63
-__device__ __forceinline__ float swap32_add(float a, float b)
-{
-    const auto t = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
-}
 
 struct AnnWideArgs {
     const double* x;        // [N]
@@ -79,25 +60,6 @@ struct AnnWideArgs {
     int nl;
     double dt, E, tol;
     int N, B, n, nbar, nsteps, max_it, supg, nonuniform;
-};
-
-// The halo rows of a lane's block of S tangent rows (as rom_rbf_fused.hip): the last row of the block below and the first
-// row of the block above, published by their owners in s_ehi / s_elo; zero outside the mesh.
-template <int NB>
-struct HaloEdges {
-    const double (*elo)[4 * NB];
-    const double (*ehi)[4 * NB];
-    int owner, t;
-    template <int S>
-    __device__ __forceinline__ double operator()(int side, int c, const double (&)[NB][S], int = 0) const
-    {
-        if (side == 0) {
-            const double v = ehi[owner > 0 ? owner - 1 : 0][4 * c + t];
-            return owner > 0 ? v : 0.0;
-        }
-        const double v = elo[owner < 63 ? owner + 1 : 63][4 * c + t];
-        return owner < 63 ? v : 0.0;
-    }
 };
 
 template <int S, int PROJ>
@@ -238,20 +200,8 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
             const float alpha = a.alpha[l];
             if ((lane & 15) >= 16 - P && ogr < ogn) {
                 const bool real = o0 < out;
-                // bias, activation, derivative scaling: the arithmetic of bg_mlp_act_jvp (csrc/mlp.hip)
-                const float v = res[0] + (real ? bias_0 : 0.0f);
-                float av = v, d = 1.0f;
-                if (kind == BG_ACT_ELU) {
-                    const float e = alpha * expf(v);
-                    av = v > 0.0f ? v : e - alpha;
-                    d = v > 0.0f ? 1.0f : e;
-                } else if (kind == BG_ACT_RELU) {
-                    av = v > 0.0f ? v : 0.0f;
-                    d = v > 0.0f ? 1.0f : 0.0f;
-                } else if (kind == BG_ACT_TANH) {
-                    av = tanhf(v);
-                    d = 1.0f - av * av;
-                }
+                float av, d;                                         // bias, activation, derivative scaling
+                mlp_activate(kind, alpha, res[0] + (real ? bias_0 : 0.0f), av, d);
                 s_act[cur ^ 1][0][o0] = real ? av : 0.0f;            // the padding outputs feed the next layer's padded inputs
 #pragma unroll
                 for (int r = 1; r < NRT; ++r)
@@ -272,49 +222,18 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
         __syncthreads();
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
 #pragma unroll 1
-        for (int ii = 0; ii < NIT; ++ii) {
-            const int i = tid + 256 * ii;
-            double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
-            if (i < N) {
-                rom_nodal_forcing(a.x, i, N, mu2, h, a.nonuniform, frPrev, fl, hf);
-                u = a.u0[(size_t)smp * N + i];
-                hist[i] = u;
-            }
-            s_fdt[i] = a.dt * (frPrev + fl);
-            s_h[i] = hf;
-            s_u[i + 2] = u;
-        }
+        for (int ii = 0; ii < NIT; ++ii)
+            sample_setup_row(tid + 256 * ii, a.x, a.u0, smp, hist, N, mu2, h, a.nonuniform, a.dt, s_u, s_fdt, s_h);
         __syncthreads();
 
         int flags = 0, info_out = 0;
         for (int step = 0; step < a.nsteps && info_out == 0; ++step) {
             // ---- g = M u^n + dt F (:1214) and q_p = U_p^T u^n (:1197) --------------------------------------------------
-            {
-                double part[RW];
-#pragma unroll
-                for (int c = 0; c < RW; ++c) part[c] = 0.0;
-#pragma unroll 1
-                for (int ii = 0; ii < NIT; ++ii) {
-                    const int i = tid + 256 * ii;
-                    double g = 0.0;
-                    const double uc = s_u[i + 2];        // zero beyond N
-                    if (i < N) g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], uc, s_u[i + 3], s_fdt[i], h, a.nonuniform);
-                    s_g[i] = g;
-#pragma unroll
-                    for (int c = 0; c < RW; ++c)
-                        if (c < n) part[c] = __builtin_fma(UT[(size_t)c * AW_UT_LD + i], uc, part[c]);
-                }
-#pragma unroll
-                for (int c = 0; c < RW; ++c) {
-                    if (c < n) {
-                        const double sm = wave_sum(part[c]);
-                        if (lane == 0) s_part[w][c] = sm;
-                    }
-                }
-                __syncthreads();
-                if (tid < RW) s_q[tid] = (tid < n) ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0;
-                __syncthreads();
-            }
+            project_q<NIT, 256, 4, AW_UT_LD, RW>(UT, s_u, n, tid, lane, w, s_part, s_q, [&](int i, double uc) {
+                double g = 0.0;
+                if (i < N) g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], uc, s_u[i + 3], s_fdt[i], h, a.nonuniform);
+                s_g[i] = g;
+            });
             int k = 0;
             bool more = true, decode = false;
             while (true) {
@@ -341,76 +260,17 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
                 }
                 __syncthreads();
                 // ---- decode U1 = U_p q_p + U_s N(q_p) (:1242) ------------------------------------------------------------
-                if (decode) {
-#pragma unroll 1
-                    for (int ii = 0; ii < NIT; ++ii) {
-                        const int i = tid + 256 * ii;
-                        double up = 0.0, us = 0.0;
-#pragma unroll 4
-                        for (int c = 0; c < n; ++c) up = __builtin_fma(UT[(size_t)c * AW_UT_LD + i], s_q[c], up);
-                        const double* __restrict__ ucol = UT + (size_t)n * AW_UT_LD + i;
-#pragma unroll 8
-                        for (int j = 0; j < nbar; ++j) us = __builtin_fma(ucol[(size_t)j * AW_UT_LD], s_f[j], us);
-                        s_u[i + 2] = (i < N) ? up + us : 0.0;
-                    }
-                    __syncthreads();
-                }
+                if (decode) decode_u<NIT, 256, AW_UT_LD>(s_u, UT, s_q, s_f, N, n, nbar, tid);
                 if (!more) break;
                 decode = true;
-                // ---- tangent W = U_p + U_s dN (:1224) in this lane's projection fragments: rows rowbase .. + S - 1,
-                // column 4 c + t (the layout of mfma_pass); rows beyond N are zero (UT is zero there)
+                // ---- tangent W = U_p + U_s dN (:1224) in this lane's projection fragments -----------------------------------
                 rederive();
                 double frag[NB][S];
-                {
-#pragma unroll
-                    for (int c = 0; c < NB; ++c)
-#pragma unroll
-                        for (int s = 0; s < S; ++s) frag[c][s] = 0.0;
-                    const double* __restrict__ us = UT + (size_t)n * AW_UT_LD + rowbase;
-#pragma unroll 4
-                    for (int j = 0; j < nbar; ++j) {
-                        double uv[S];
-#pragma unroll
-                        for (int s = 0; s < S; s += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(us + (size_t)j * AW_UT_LD + s);
-                            uv[s] = v.x; uv[s + 1] = v.y;
-                        }
-                        double jv[NB];
-#pragma unroll
-                        for (int c = 0; c < NB; ++c) jv[c] = s_J[j][4 * c + t];
-#pragma unroll
-                        for (int c = 0; c < NB; ++c)
-#pragma unroll
-                            for (int s = 0; s < S; ++s) frag[c][s] = __builtin_fma(uv[s], jv[c], frag[c][s]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < NB; ++c) {
-                        const int col = 4 * c + t;
-                        const double* __restrict__ up = UT + (size_t)(col < n ? col : 0) * AW_UT_LD + rowbase;
-#pragma unroll
-                        for (int s = 0; s < S; s += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(up + s);
-                            frag[c][s] += col < n ? v.x : 0.0;
-                            frag[c][s + 1] += col < n ? v.y : 0.0;
-                        }
-                    }
-                }
+                tangent_fragments<S, NB, AW_UT_LD>(frag, UT, s_J, n, nbar, rowbase, t);
                 __syncthreads();                         // s_J consumed: the projection phase reuses its LDS
-#pragma unroll
-                for (int c = 0; c < NB; ++c) {
-                    s_elo[owner][4 * c + t] = frag[c][0];
-                    s_ehi[owner][4 * c + t] = frag[c][S - 1];
-                }
+                publish_edges<S, NB>(frag, s_elo, s_ehi, owner, t);
                 // ---- assembly: A(u_k), R(u_k) per row into LDS -------------------------------------------------------
-                for (int i = tid; i < NPAD; i += 256) {
-                    double lo, di, up, R;
-                    const bool in = i < N;
-                    const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-                    rom_assemble_row(i, N, s_u[i + 1], s_u[i + 2], (i + 1 < N) ? s_u[i + 3] : 0.0, in ? s_g[i] : 0.0,
-                                     (in && i > 0) ? s_h[i - 1] : 0.0, (in && i < N - 1) ? s_h[i] : 0.0, mu1, mc,
-                                     a.nonuniform, a.x, a.dt, a.E, lo, di, up, R);
-                    s_coef[i][0] = lo; s_coef[i][1] = di; s_coef[i][2] = up; s_coef[i][3] = R;
-                }
+                assemble_rows<NPAD, 256>(s_coef, s_u, s_g, s_h, a.x, N, h, a.dt, a.E, a.supg, a.nonuniform, mu1, tid);
                 __syncthreads();
                 // ---- projection (:1224-1233) -------------------------------------------------------------------------
                 {
@@ -424,22 +284,13 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
                 __syncthreads();
                 if (s_info != 0 && info_out == 0) info_out = s_info;
                 // ---- q_p += dq, err = |dq| / (|q_p| + 1e-14)  (:1238-1244) ---------------------------------------------
-                const double dq = (lane < n) ? s_x[lane] : 0.0;
-                const double qn = (lane < n) ? s_q[lane] + dq : 0.0;
-                double nd, nq;
-                wave_sum2(dq * dq, qn * qn, nd, nq);
-                nd = sqrt(nd); nq = sqrt(nq);
-                const double err = nd / (nq + 1e-14);
+                const double err = update_q<RW>(s_q, s_x, n, lane, w, [](double nd, double nq) { return nd / (nq + 1e-14); });
                 ++k;
                 more = (err > a.tol) && (k < a.max_it) && info_out == 0;
                 if (!(err - err == 0.0)) flags |= BG_FLAG_NONFINITE;
                 if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
-                __syncthreads();                         // every wave has read s_q and s_x
-                if (w == 0 && lane < RW) s_q[lane] = qn;
-                __syncthreads();
             }
-            double* hrow = hist + (size_t)(step + 1) * N;
-            for (int i = tid; i < N; i += 256) hrow[i] = s_u[i + 2];
+            write_hist_row<256>(hist + (size_t)(step + 1) * N, s_u, N, tid);
             if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
         }
         if (tid == 0) {

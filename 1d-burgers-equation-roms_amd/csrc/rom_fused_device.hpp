@@ -1,6 +1,7 @@
 // rom_fused_device.hpp -- device pieces shared by the fused (one workgroup per sample) ROM kernels: the MFMA projection
 // pass, the cooperative guarded elimination of the reduced system, the partial-pivoting solve of the repair kernels.
-// Used by rom_fused.hip (POD: bg_rom_run) and rom_ann_fused.hip (POD-ANN: bg_ann_rom_run).
+// Used by rom_fused.hip (POD: bg_rom_run), rom_ann_fused.hip (POD-ANN: bg_ann_rom_run) and, through rom_closure_device.hpp,
+// by the closure loops rom_rbf_fused.hip and rom_ann_wide.hip.
 #pragma once
 #include "rom_device.hpp"
 

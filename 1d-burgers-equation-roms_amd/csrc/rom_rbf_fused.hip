@@ -17,12 +17,14 @@
 //     -> decode U1 = U_p q_new + U_s f                                                                  :1378-1381
 // The centres and weights stream from L2 in tiles (any Ns), U_p and U_s are re-read from L2 every iteration; HBM sees u0
 // once and one N-row history write per time step.
+// This file holds the closure (scale, centre, the Jacobian and value tiles), the LDS overlay and the loop; the mesh side
+// (q_p, tangent, halo edges, assembly, update of q_p, decode) is rom_closure_device.hpp's, shared with rom_ann_wide.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
-#include "rom_fused_device.hpp"
+#include "rom_closure_device.hpp"
 
 namespace {
 
@@ -56,25 +58,6 @@ struct RbfRunArgs {
     const int32_t* order;   // [B] or null: slot i of the persistent loop works on sample order[i]
     double eps2, dt, E, tol;
     int N, B, n, nbar, Ns, nsteps, max_it, kind, supg, nonuniform;
-};
-
-// The halo rows of a lane's block of S tangent rows: the last row of the block below and the first row of the block above,
-// published by their owners in s_ehi / s_elo (the tangent is formed in registers, see the kernel); zero outside the mesh.
-template <int NB, int LAST = 63>
-struct HaloEdges {
-    const double (*elo)[4 * NB];
-    const double (*ehi)[4 * NB];
-    int owner, t;
-    template <int S>
-    __device__ __forceinline__ double operator()(int side, int c, const double (&)[NB][S], int = 0) const
-    {
-        if (side == 0) {
-            const double v = ehi[owner > 0 ? owner - 1 : 0][4 * c + t];
-            return owner > 0 ? v : 0.0;
-        }
-        const double v = elo[owner < LAST ? owner + 1 : LAST][4 * c + t];
-        return owner < LAST ? v : 0.0;
-    }
 };
 
 // UT_LD: the row stride of UT; NW: waves per workgroup.  The defaults are bg_rbf_rom_run's: four waves, 64 owners of S rows,
@@ -174,18 +157,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
         __syncthreads();
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
 #pragma unroll 1
-        for (int ii = 0; ii < NIT; ++ii) {
-            const int i = tid + NT * ii;
-            double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
-            if (i < N) {
-                rom_nodal_forcing(a.x, i, N, mu2, h, a.nonuniform, frPrev, fl, hf);
-                u = a.u0[(size_t)smp * N + i];
-                hist[i] = u;
-            }
-            s_fdt[i] = a.dt * (frPrev + fl);
-            s_h[i] = hf;
-            s_u[i + 2] = u;
-        }
+        for (int ii = 0; ii < NIT; ++ii)
+            sample_setup_row(tid + NT * ii, a.x, a.u0, smp, hist, N, mu2, h, a.nonuniform, a.dt, s_u, s_fdt, s_h);
         __syncthreads();
 
         int flags = 0, info_out = 0;
@@ -204,35 +177,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
             while (more) {
                 rederive();
                 // ---- q_p = U_p^T U0 (:1352) -------------------------------------------------------------------------
-                {
-                    double part[RW];
-#pragma unroll
-                    for (int c = 0; c < RW; ++c) part[c] = 0.0;
-#pragma unroll 1
-                    for (int ii = 0; ii < NIT; ++ii) {
-                        const int i = tid + NT * ii;
-                        const double uc = s_u[i + 2];    // zero beyond N
-#pragma unroll
-                        for (int c = 0; c < RW; ++c)
-                            if (c < n) part[c] = __builtin_fma(UT[(size_t)c * UT_LD + i], uc, part[c]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < RW; ++c) {
-                        if (c < n) {
-                            const double sm = wave_sum(part[c]);
-                            if (lane == 0) s_part[w][c] = sm;
-                        }
-                    }
-                    __syncthreads();
-                    if constexpr (NW == 4) {
-                        if (tid < RW) s_q[tid] = (tid < n) ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0;
-                    } else {
-                        if (tid < RW)
-                            s_q[tid] = (tid < n) ? ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) +
-                                                       ((s_part[4][tid] + s_part[5][tid]) + (s_part[6][tid] + s_part[7][tid])) : 0.0;
-                    }
-                    __syncthreads();
-                }
+                project_q<NIT, NT, NW, UT_LD, RW>(UT, s_u, n, tid, lane, w, s_part, s_q, [](int, double) {});
                 scale();
                 // ---- closure Jacobian at q_p (:238-260): J[j][k] = sum_i Wd[i][j] G[i][k] ----------------------------
                 // thread (w, lane) owns j = 2 lane, 2 lane + 1 and k = 5 w .. 5 w + 4: per centre one 16-byte load of Wd
@@ -299,60 +244,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
                         __syncthreads();
                     }
                 }
-                // ---- tangent W = U_p + U_s J (:1361) in this lane's projection fragments: rows rowbase .. + S - 1,
-                // column 4 c + t (the layout of mfma_pass); rows beyond N are zero (UT is zero there)
+                // ---- tangent W = U_p + U_s J (:1361) in this lane's projection fragments ------------------------------
                 rederive();
                 double frag[NB][S];
-                {
-#pragma unroll
-                    for (int c = 0; c < NB; ++c)
-#pragma unroll
-                        for (int s = 0; s < S; ++s) frag[c][s] = 0.0;
-                    const double* __restrict__ us = UT + (size_t)n * UT_LD + rowbase;
-#pragma unroll 4
-                    for (int j = 0; j < nbar; ++j) {
-                        double uv[S];
-#pragma unroll
-                        for (int s = 0; s < S; s += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(us + (size_t)j * UT_LD + s);
-                            uv[s] = v.x; uv[s + 1] = v.y;
-                        }
-                        double jv[NB];
-#pragma unroll
-                        for (int c = 0; c < NB; ++c) jv[c] = s_J[j][4 * c + t];
-#pragma unroll
-                        for (int c = 0; c < NB; ++c)
-#pragma unroll
-                            for (int s = 0; s < S; ++s) frag[c][s] = __builtin_fma(uv[s], jv[c], frag[c][s]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < NB; ++c) {
-                        const int col = 4 * c + t;
-                        const double* __restrict__ up = UT + (size_t)(col < n ? col : 0) * UT_LD + rowbase;
-#pragma unroll
-                        for (int s = 0; s < S; s += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(up + s);
-                            frag[c][s] += col < n ? v.x : 0.0;
-                            frag[c][s + 1] += col < n ? v.y : 0.0;
-                        }
-                    }
-                }
+                tangent_fragments<S, NB, UT_LD>(frag, UT, s_J, n, nbar, rowbase, t);
                 __syncthreads();                         // s_J consumed: the projection phase reuses its LDS
-#pragma unroll
-                for (int c = 0; c < NB; ++c) {
-                    s_elo[owner][4 * c + t] = frag[c][0];
-                    s_ehi[owner][4 * c + t] = frag[c][S - 1];
-                }
+                publish_edges<S, NB>(frag, s_elo, s_ehi, owner, t);
                 // ---- assembly: A(u_k), R(u_k) per row into LDS (:1330-1346) ------------------------------------------
-                for (int i = tid; i < NPAD; i += NT) {
-                    double lo, di, up, R;
-                    const bool in = i < N;
-                    const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-                    rom_assemble_row(i, N, s_u[i + 1], s_u[i + 2], (i + 1 < N) ? s_u[i + 3] : 0.0, in ? s_g[i] : 0.0,
-                                     (in && i > 0) ? s_h[i - 1] : 0.0, (in && i < N - 1) ? s_h[i] : 0.0, mu1, mc,
-                                     a.nonuniform, a.x, a.dt, a.E, lo, di, up, R);
-                    s_coef[i][0] = lo; s_coef[i][1] = di; s_coef[i][2] = up; s_coef[i][3] = R;
-                }
+                assemble_rows<NPAD, NT>(s_coef, s_u, s_g, s_h, a.x, N, h, a.dt, a.E, a.supg, a.nonuniform, mu1, tid);
                 __syncthreads();
                 // ---- projection (:1361) ------------------------------------------------------------------------------
                 {
@@ -366,19 +265,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
                 __syncthreads();
                 if (s_info != 0 && info_out == 0) info_out = s_info;
                 // ---- q_new = q_p + dq, err = |dq| / |q_new| (|dq| when |q_new| = 0) (:1366-1390) ----------------------
-                const double dq = (lane < n) ? s_x[lane] : 0.0;
-                const double qn = (lane < n) ? s_q[lane] + dq : 0.0;
-                double nd, nq;
-                wave_sum2(dq * dq, qn * qn, nd, nq);
-                nd = sqrt(nd); nq = sqrt(nq);
-                const double err = nq > 0.0 ? nd / nq : nd;
+                const double err = update_q<RW>(s_q, s_x, n, lane, w, [](double nd, double nq) { return nq > 0.0 ? nd / nq : nd; });
                 ++k;
                 more = (err > a.tol) && (k < a.max_it) && info_out == 0;
                 if (!(err - err == 0.0)) flags |= BG_FLAG_NONFINITE;
                 if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
-                __syncthreads();                         // every wave has read s_q and s_x
-                if (w == 0 && lane < RW) s_q[lane] = qn;
-                __syncthreads();
                 scale();
                 // ---- closure value at q_new (:225-236): f_j = sum_i phi_i Wd[i][j] + bias_j --------------------------
                 rederive();
@@ -411,21 +302,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(RbfRunAr
                 }
                 // ---- decode U1 = U_p q_new + U_s f (:1378-1381) ------------------------------------------------------
                 rederive();
-#pragma unroll 1
-                for (int ii = 0; ii < NIT; ++ii) {
-                    const int i = tid + NT * ii;
-                    double up = 0.0, us = 0.0;
-#pragma unroll 4
-                    for (int c = 0; c < n; ++c) up = __builtin_fma(UT[(size_t)c * UT_LD + i], s_q[c], up);
-                    const double* __restrict__ ucol = UT + (size_t)n * UT_LD + i;
-#pragma unroll 8
-                    for (int j = 0; j < nbar; ++j) us = __builtin_fma(ucol[(size_t)j * UT_LD], s_f[j], us);
-                    s_u[i + 2] = (i < N) ? up + us : 0.0;
-                }
-                __syncthreads();
+                decode_u<NIT, NT, UT_LD>(s_u, UT, s_q, s_f, N, n, nbar, tid);
             }
-            double* hrow = hist + (size_t)(step + 1) * N;
-            for (int i = tid; i < N; i += NT) hrow[i] = s_u[i + 2];
+            write_hist_row<NT>(hist + (size_t)(step + 1) * N, s_u, N, tid);
             if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
         }
         if (tid == 0) {

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/burgers_hip.h"
+
 namespace bg {
 
 constexpr int WAVE = 64;
@@ -103,5 +105,43 @@ __device__ __forceinline__ void wave_sum2(double a, double b, double& sa, double
 }
 
 __device__ __forceinline__ double sel(bool c, double a, double b) { return c ? a : b; }
+
+// ---- float32: DPP move, and folds across the rows of 16 lanes on the VALU (v_permlane16_swap / v_permlane32_swap) ----
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
+// a + (a of the neighbouring row) in the even rows of 16 lanes, b + (b of the neighbouring row) in the odd rows
+__device__ __forceinline__ float swap16_add(float a, float b)
+{
+    const auto t = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
+}
+// a + (a of the other half) in lanes 0..31, b + (b of the other half) in lanes 32..63
+__device__ __forceinline__ float swap32_add(float a, float b)
+{
+    const auto t = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
+}
+
+// ---- MLP activation of the pre-activation v (bias added): value av and derivative d, the arithmetic of bg_mlp_act_jvp
+// (csrc/mlp.hip); BG_ACT_NONE: av = v, d = 1
+__device__ __forceinline__ void mlp_activate(int kind, float alpha, float v, float& av, float& d)
+{
+    av = v; d = 1.0f;
+    if (kind == BG_ACT_ELU) {
+        const float e = alpha * expf(v);
+        av = v > 0.0f ? v : e - alpha;
+        d = v > 0.0f ? 1.0f : e;
+    } else if (kind == BG_ACT_RELU) {
+        av = v > 0.0f ? v : 0.0f;
+        d = v > 0.0f ? 1.0f : 0.0f;
+    } else if (kind == BG_ACT_TANH) {
+        av = tanhf(v);
+        d = 1.0f - av * av;
+    }
+}
 
 }  // namespace bg
