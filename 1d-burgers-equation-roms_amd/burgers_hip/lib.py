@@ -119,6 +119,10 @@ _SIGNATURES = {
     "bg_rom_run_long_workgroups_per_cu": (ctypes.c_int, []),
     "bg_rom_run_long_phi_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_rom_run_long": _loop(5, [c_double_p]),
+    "bg_hyper_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
+    "bg_hyper_rom_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    # N, B, r, m, nsteps, projection, rows, xi, xs, PhiS, q0, u0s, mu1, mu2, the step, the outputs (qhist for hist)
+    "bg_hyper_rom_run": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),
     "bg_rom_run_long_wide_max_n": (ctypes.c_int, []),
     "bg_rom_run_long_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_long_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),

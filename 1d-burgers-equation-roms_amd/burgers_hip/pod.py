@@ -656,6 +656,196 @@ def build_rbf_closure(S, n, nbar, epsilon, kernel="gaussian", ridge=1e-8, centre
     return RbfFit(U_p, U_s, Xs, W, epsilon, kernel, x_min, x_max, y_min, y_max, ridge, rows.to(torch.int64), info["backward_error"])
 
 
+# ---- row sampling for the hyper-reduced POD PROM (rom.pod_prom_run_hyper, bg_hyper_rom_run) ----
+class RowSampling:
+    """What build_row_sampling returns and save_row_sampling stores: the sampled mesh ``rows`` (m,) int32, ascending, row 0
+    among them; their weights ``xi`` (m,) float64 >= 0 (row 0: 1); the ``projection`` they were trained for ("galerkin" or
+    "lspg"); ``residual`` = |G xi - d| / |d| on the training data, ``pairs`` the number of training pairs and ``tau`` the
+    bound asked for.  The tensors live on the host."""
+
+    def __init__(self, rows, xi, projection, residual, pairs, tau):
+        self.rows, self.xi = torch.as_tensor(rows, dtype=torch.int32), torch.as_tensor(xi, dtype=torch.float64)
+        self.projection, self.residual, self.pairs, self.tau = str(projection), float(residual), int(pairs), float(tau)
+
+    @property
+    def m(self):
+        return int(self.rows.numel())
+
+
+_GP_A, _GP_B = 0.5 * (1.0 + 1.0 / np.sqrt(3.0)), 0.5 * (1.0 - 1.0 / np.sqrt(3.0))      # P1 shape values at the two Gauss points
+
+
+def picard_rows(X, U0, Un, mu1, mu2, dt, E=0.0, supg=True):
+    """The three diagonals lo, di, up of the Picard matrix A(U0) = M + dt C(U0) + dt E K with the Dirichlet row 0, and
+    R = A U0 - b, b = M Un + dt F - dt S(U0), b[0] = mu1 (FEM/fem_burgers.py:730-753), for one state on the host: the closed
+    forms of the two-point Gauss rule on P1 elements, in numpy.  This is training arithmetic for build_row_sampling, not a
+    stepper: the device kernels assemble their own rows."""
+    X, U0, Un = (np.asarray(v, dtype=np.float64) for v in (X, U0, Un))
+    N = len(X)
+    h = np.diff(X)
+    ul, ur = U0[:-1], U0[1:]
+    a, b = (2.0 * ul + ur) / 6.0, (ul + 2.0 * ur) / 6.0         # int N_l u, int N_r u over the element, divided by h
+    off, dd = h / 6.0 - dt * E / h, h / 3.0 + dt * E / h
+    lo, di, up = np.zeros(N), np.zeros(N), np.zeros(N)
+    di[:-1] += dd - dt * a
+    di[1:] += dd + dt * b
+    up[:-1] = off + dt * a
+    lo[1:] = off - dt * b
+    xl, xr = X[:-1], X[1:]
+    f1 = 0.02 * np.exp(mu2 * (_GP_A * xl + _GP_B * xr))
+    f2 = 0.02 * np.exp(mu2 * (_GP_B * xl + _GP_A * xr))
+    rhs = np.zeros(N)
+    rhs[:-1] += h / 6.0 * (2.0 * Un[:-1] + Un[1:]) + dt * (f1 * _GP_A + f2 * _GP_B) * (0.5 * h)
+    rhs[1:] += h / 6.0 * (Un[:-1] + 2.0 * Un[1:]) + dt * (f1 * _GP_B + f2 * _GP_A) * (0.5 * h)
+    if supg:
+        ue = 0.5 * (ul + ur)
+        tau_e = 0.5 * h / (2.0 * np.maximum(np.abs(ue), 1.0e-10))
+        s = 0.5 * tau_e * ((ul + ur) * (ur - ul) / h - (f1 + f2))
+        rhs[:-1] += dt * s
+        rhs[1:] -= dt * s
+    lo[0], di[0], up[0], rhs[0] = 0.0, 1.0, 0.0, mu1
+    R = di * U0 - rhs
+    R[1:] += lo[1:] * U0[:-1]
+    R[:-1] += up[:-1] * U0[1:]
+    return lo, di, up, R
+
+
+def row_contributions(X, Phi, U0, Un, mu1, mu2, dt, projection, E=0.0, supg=True):
+    """(r, N): column i is c_i = w_i R_i, the share of mesh row i in the reduced right-hand side br = sum_i c_i at the state
+    U0 (previous step Un); w_i = Phi[i] for "galerkin", (A Phi)[i] for "lspg"."""
+    lo, di, up, R = picard_rows(X, U0, Un, mu1, mu2, dt, E, supg)
+    W = Phi
+    if projection == "lspg":
+        W = di[:, None] * Phi
+        W[1:] += lo[1:, None] * Phi[:-1]
+        W[:-1] += up[:-1, None] * Phi[1:]
+    return (W * R[:, None]).T
+
+
+def nnls_rows(G, d, tau, min_cols, max_cols):
+    """Active-set NNLS (Lawson-Hanson) for min |G x - d|, x >= 0, stopped as soon as |G x - d| <= tau |d|; after that the
+    same greedy rule (the column with the largest gradient G^T (d - G x)) goes on adding columns until ``min_cols`` are
+    active.  ValueError when ``max_cols`` would be exceeded or no column is left to add.  Returns (x, relative residual)."""
+    n = G.shape[1]
+    x = np.zeros(n)
+    active = np.zeros(n, dtype=bool)
+    tabu = np.zeros(n, dtype=bool)                 # fill phase: columns the least-squares fit threw out again
+    dn = float(np.linalg.norm(d))
+    res = d.copy()
+    for _ in range(3 * n + 10):
+        rel = float(np.linalg.norm(res)) / dn if dn > 0.0 else 0.0
+        fit_done = rel <= tau
+        if fit_done and int(active.sum()) >= min_cols:
+            return x, rel
+        w = G.T @ res
+        w[active | tabu] = -np.inf
+        j = int(np.argmax(w))
+        if not np.isfinite(w[j]) or (not fit_done and w[j] <= 0.0):
+            raise ValueError(f"row sampling: no column left to add at {int(active.sum())} columns, residual {rel:.2e} "
+                             f"(asked: {tau:.1e}, at least {min_cols} columns)")
+        if int(active.sum()) + 1 > max_cols:
+            raise ValueError(f"row sampling: more than max_rows = {max_cols + 1} rows needed (residual {rel:.2e} at that "
+                             f"point, asked: {tau:.1e} with at least {min_cols + 1} rows)")
+        active[j] = True
+        while True:
+            idx = np.flatnonzero(active)
+            s = np.linalg.lstsq(G[:, idx], d, rcond=None)[0]
+            if s.min() > 0.0:
+                x[:] = 0.0
+                x[idx] = s
+                break
+            neg = s <= 0.0                            # step towards s as far as x stays non-negative, drop what reaches 0
+            xa = x[idx]
+            ratio = np.where(neg, xa / np.where(neg, xa - s, 1.0), np.inf)
+            xa = xa + float(ratio.min()) * (s - xa)
+            xa[ratio <= ratio.min()] = 0.0
+            x[:] = 0.0
+            x[idx] = np.maximum(xa, 0.0)
+            active[idx[x[idx] <= 0.0]] = False
+        if active[j] and not fit_done:
+            tabu[:] = False
+        elif not active[j]:
+            tabu[j] = True                             # the fit threw the new column out again: not this one next time
+        res = d - G[:, active] @ x[active]
+    raise ValueError("row sampling: the active-set iteration did not end")
+
+
+def hyper_rom_limits():
+    """(max_r, max_m) of bg_hyper_rom_run.  Needs no device."""
+    from . import lib as _lib
+    return _lib.limits("bg_hyper_rom_limits", 2)
+
+
+def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None):
+    """The sampled mesh rows and weights of the hyper-reduced POD PROM (ECSW-style: energy-conserving sampling and
+    weighting), fitted on the host by non-negative least squares.
+
+    ``runs``: a list of (hist (N, nT+1), mu1, mu2), CPU or device tensors or arrays.  For every run and every ``stride``-th
+    step n the pair Un = Phi Phi^T s_n, U0 = Phi Phi^T s_{n+1} gives the contributions c_i = w_i R_i (row_contributions) of
+    all mesh rows to the reduced right-hand side; stacked they are G (pairs r, N), and d = G 1 is what the full sum gives.
+    Row 0 (the Dirichlet row) is forced in with weight 1 and moved to the right-hand side; the other weights are
+    nnls_rows(G[:, 1:], d - G[:, 0]): stopped at |G xi - d| <= tau |d|, then filled by the same greedy rule up to
+    ``min_rows`` rows (default 3 r: fewer rows have diverged at r = 40 even where the training residual was met).
+    ``max_rows`` defaults to the kernel's limit (hyper_rom_limits); needing more is a ValueError.  Returns a RowSampling."""
+    projection = str(projection).lower()
+    if projection not in ("galerkin", "lspg"):
+        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
+    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    Phi = np.ascontiguousarray(Phi.detach().cpu().numpy() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64)
+    N = len(X)
+    if Phi.ndim != 2 or Phi.shape[0] != N:
+        raise ValueError("Phi must have one row per mesh node")
+    r = Phi.shape[1]
+    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
+        raise ValueError("build_row_sampling takes at least one run, stride >= 1 and tau > 0")
+    min_rows = min(3 * r, N) if min_rows is None else int(min_rows)
+    max_rows = hyper_rom_limits()[1] if max_rows is None else int(max_rows)
+    G, pairs = row_sampling_system(X, Phi, runs, dt, projection, E, supg, stride)
+    d = G.sum(axis=1)
+    x, _ = nnls_rows(G[:, 1:], d - G[:, 0], float(tau) * float(np.linalg.norm(d)) / max(float(np.linalg.norm(d - G[:, 0])), 1e-300),
+                     max(min_rows - 1, 0), max_rows - 1)
+    xi_full = np.concatenate([[1.0], x])
+    rows = np.flatnonzero(xi_full > 0.0)
+    residual = float(np.linalg.norm(G[:, rows] @ xi_full[rows] - d) / np.linalg.norm(d))
+    return RowSampling(rows.astype(np.int32), xi_full[rows], projection, residual, pairs, tau)
+
+
+def row_sampling_system(X, Phi, runs, dt, projection, E=0.0, supg=True, stride=10):
+    """(G, pairs): the training matrix of build_row_sampling, (pairs r, N), column i the contributions of mesh row i; the
+    full reduced right-hand sides are d = G 1.  ``X``, ``Phi``: host arrays; ``projection``: "galerkin" or "lspg"."""
+    N = len(X)
+    blocks = []
+    for hist, mu1, mu2 in runs:
+        Sn = np.asarray(hist.detach().cpu() if isinstance(hist, torch.Tensor) else hist, dtype=np.float64)
+        if Sn.ndim != 2 or Sn.shape[0] != N or Sn.shape[1] < 2:
+            raise ValueError("every run is (hist (N, nT+1), mu1, mu2)")
+        P = Phi @ (Phi.T @ Sn)
+        for n in range(0, Sn.shape[1] - 1, int(stride)):
+            blocks.append(row_contributions(X, Phi, P[:, n + 1], P[:, n], float(mu1), float(mu2), float(dt), projection, float(E), supg))
+    G = np.concatenate(blocks, axis=0)
+    if not np.isfinite(G).all():
+        raise ValueError("build_row_sampling: the training data is not finite")
+    return G, len(blocks)
+
+
+def save_row_sampling(directory, sampling):
+    """A RowSampling as rows.npy, xi.npy and row_sampling.npz (projection, residual, pairs, tau); no pickles.  Returns the directory."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rows.npy"), _host(sampling.rows))
+    np.save(os.path.join(directory, "xi.npy"), _host(sampling.xi))
+    np.savez(os.path.join(directory, "row_sampling.npz"), projection=np.array(sampling.projection, dtype=np.str_),
+             residual=np.float64(sampling.residual), pairs=np.int64(sampling.pairs), tau=np.float64(sampling.tau))
+    return directory
+
+
+def load_row_sampling(directory):
+    """The RowSampling save_row_sampling wrote."""
+    with _npy(directory, "row_sampling.npz") as z:
+        meta = {k: z[k] for k in z.files}
+    return RowSampling(_npy(directory, "rows.npy"), _npy(directory, "xi.npy"), str(meta["projection"]), float(meta["residual"]),
+                       int(meta["pairs"]), float(meta["tau"]))
+
+
 # ---- .npy contracts --------------------------------------------------------------------------
 def snapshot_filename(mu1, mu2):
     return f"fem_simulation_mu1_{mu1:.3f}_mu2_{mu2:.4f}.npy"          # paper_training_stage.py:52

@@ -63,6 +63,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_ann_rom_run", 2), _Route("bg_ann_rom_run_wide", 2), _Route("bg_rbf_rom_run", 2), _Route("bg_local_rom_run", 2),
     _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
+    _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
 )}
 
 
@@ -305,20 +306,21 @@ def _host_loop(c, nsteps, n, step):
 
 
 # --------------------------------------------------------------------------- POD
-def _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance, launch, keep=(), slots=None):
+def _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance, launch, keep=(), slots=None, cols=None):
     """What the device-side time loops (_ROUTES) share: the batched inputs, the outputs, the sample order over the grid
     (``slots``, or the route's workgroups per CU on every compute unit; ``route.group`` samples per slot), the launch and its
     FomResult.  ``Xh``: the mesh as check_mesh returned it.  ``launch(f, N, B, x, inputs, opts, outputs)`` calls the C
     entry point ``f`` with its own argument list; ``inputs`` are the pointers u0, mu1, mu2 and ``outputs`` hist, iters,
     flags, info, order, stream.  Nothing is synchronised: ``res.info`` is checked lazily by the caller, and the operands
-    live in ``res._keep`` (inputs first, then ``keep``) as long as the result, since the launch is asynchronous."""
+    live in ``res._keep`` (inputs first, then ``keep``) as long as the result, since the launch is asynchronous.
+    ``cols``: the entries per row of ``hist`` where the loop does not write mesh rows (bg_hyper_rom_run: r)."""
     grid = slots if slots is not None else _limit(route.wg_per_cu) * _cu_count(device)
     opts = _lib.mesh_options(Xh, supg=route.supg) | options
     Xd = _as_dev(Xh, device)
     N = Xd.numel()
     u0d, mu1d, mu2d = _batch_inputs(u0, mu1, mu2, N, device)
     B = mu1d.numel()
-    hist = torch.empty((B, nsteps + 1, N), dtype=torch.float64, device=device)
+    hist = torch.empty((B, nsteps + 1, N if cols is None else cols), dtype=torch.float64, device=device)
     iters = torch.zeros((B, nsteps), dtype=torch.int32, device=device)
     flags = torch.zeros((B,), dtype=torch.int32, device=device)
     info = torch.zeros((B,), dtype=torch.int32, device=device)
@@ -534,6 +536,104 @@ def pod_prom_run_long_wide(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0
                           E, tol, max_it, device, options, balance)
 
 
+class HyperPodPlan:
+    """What bg_hyper_rom_run reads besides the batch, built once per basis, sampling and mesh on the device
+    (include/burgers_hip.h): the packed stencil table PhiS (rows Phi[i-1], Phi[i], Phi[i+1] of every sampled row, 42 doubles
+    each, zero outside the mesh and beyond r), the stencil coordinates xs (m, 3), the rows and weights, and the gather
+    index of the stencil nodes (``stencil``, clipped to the mesh, with ``inside`` marking the slots that exist).
+    ``sampling``: a pod.RowSampling.  What the shapes and the sampling alone decide is refused before the device is
+    touched; every refusal is a ValueError."""
+
+    def __init__(self, Phi, sampling, X, device):
+        shape = tuple(np.shape(Phi))
+        if len(shape) != 2:
+            raise ValueError("Phi must be (N, r)")
+        N, r = shape
+        route = _ROUTES["bg_hyper_rom_run"]
+        max_r, max_m = _lib.limits("bg_hyper_rom_limits", 2)
+        Xh = check_mesh(X)
+        if r < 1 or r > max_r:
+            raise ValueError(f"Phi must be (N, r) with 1 <= r <= {max_r}")
+        if N < route.min_n or N > _limit(route.max_n) or len(Xh) != N:
+            raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of Phi per mesh node")
+        rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
+        xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
+        m = len(rows)
+        if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
+            raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
+        if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
+            raise ValueError("the weights must be finite and >= 0")
+        elems = _lib.load().bg_hyper_rom_table_elems(m, r)
+        if m > max_m or elems == 0:
+            raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+        device = _lib.require_device(device)
+        self.Phi = _as_dev(Phi, device)
+        self.N, self.r, self.m, self.Xh = N, r, m, Xh.copy()
+        self.projection = PROJ[str(sampling.projection).lower()]
+        self.sampling = sampling
+        idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
+        self.inside = (idx >= 0) & (idx < N)
+        self.stencil = idx.clamp(0, N - 1)
+        cols = elems // (3 * ((m + 31) // 32 * 32))
+        table = torch.zeros((elems // (3 * cols), 3, cols), dtype=torch.float64, device=device)
+        table[:m, :, :r] = self.Phi[self.stencil] * self.inside[:, :, None]
+        self.PhiS = table
+        self.xs = _as_dev(Xh, device)[self.stencil].contiguous()
+        self.rows = torch.as_tensor(rows, dtype=torch.int32, device=device)
+        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+
+
+class HyperRomResult:
+    """Result of pod_prom_run_hyper: the reduced coordinates ``q`` (B, nT+1, r), ``iters``, ``flags``, ``info`` and the
+    ``plan``.  ``hist`` (B, nT+1, N) is decoded on demand, U = Phi q as one batched product with u0 itself in column 0 as in
+    every other loop, and kept; ``snapshots()`` is its (B, N, nT+1) layout."""
+
+    def __init__(self, res, plan, u0d):
+        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
+        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
+
+    @property
+    def hist(self):
+        if self._hist is None:
+            self._hist = torch.matmul(self.q, self.plan.Phi.t())
+            self._hist[:, 0] = self._u0
+        return self._hist
+
+    def snapshots(self):
+        return FomResult(self.hist, self.iters, self.flags).snapshots()
+
+    @property
+    def newton_steps(self):
+        return int(self.iters.sum().item())
+
+
+def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                       options=0, balance=True):
+    """``pod_prom_burgers`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_rom_run): the reduced system
+    is assembled from the sampled mesh rows of a pod.RowSampling (pod.build_row_sampling) with their weights, so an
+    iteration costs O(m r^2) whatever the mesh: N up to bg_fom_max_n(), r <= 40, m <= 256 (bg_hyper_rom_limits).  The
+    pivoting repair runs inside the call, nothing is synchronised.  ``sampling_or_plan``: the sampling, or a HyperPodPlan
+    of this basis, sampling and mesh to reuse across calls (``res.plan``; ``Phi`` is then not looked at).  A sampling trained
+    for the other projection is refused.  Returns a HyperRomResult."""
+    device = _lib.require_device(device)
+    Xh = check_mesh(X)
+    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperPodPlan) else HyperPodPlan(Phi, sampling_or_plan, Xh, device)
+    _check_plan(plan, Xh, device)
+    if not np.array_equal(plan.Xh, Xh):
+        raise ValueError("the plan was built for another mesh")
+    if plan.projection != proj:
+        raise ValueError("the row sampling was trained for the other projection")
+    u0d, _, mu2d = _batch_inputs(u0, mu1, mu2, plan.N, device)
+    q0 = (u0d @ plan.Phi).contiguous()
+    u0s = (u0d[:, plan.stencil] * plan.inside).contiguous()
+    res = _device_loop(_ROUTES["bg_hyper_rom_run"], Xh, u0d, mu1, mu2, nsteps, device, options, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.r, plan.m, int(nsteps), proj, _lib.ptr(plan.rows), _lib.ptr(plan.xi), _lib.ptr(plan.xs),
+                           _lib.ptr(plan.PhiS), _lib.ptr(q0), _lib.ptr(u0s), *inputs[1:], float(dt), float(E), float(tol),
+                           int(max_it), opts, *outputs), keep=(plan, q0, u0s), cols=plan.r)
+    return HyperRomResult(res, plan, u0d)
+
+
 def check_singular(res):
     """np.linalg.solve raises LinAlgError('Singular matrix') at :767; the device loop records it per sample."""
     info = getattr(res, "info", None)
@@ -562,7 +662,7 @@ def _pod_route(N, r, fused=True, blocked=False, long_mesh=False, long_wide=False
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
-                 device=None, fused=True, blocked=False, long_mesh=False, long_wide=False):
+                 device=None, fused=True, blocked=False, long_mesh=False, long_wide=False, hyper=None):
     """Batched ``pod_prom_burgers``; ``projection`` is case-sensitive like the reference (:754-764).
     ``fused`` (default): the device-side time loop bg_rom_run where it applies (N <= 512, r <= 40); otherwise, or
     with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host.
@@ -571,8 +671,13 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_max_n() with r <= bg_rom_run_long_max_r()
     take the device-side loop bg_rom_run_long instead of the library path.
     ``long_wide`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_wide_max_n() with bg_rom_run_long_max_r() < r
-    <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path."""
+    <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path.
+    ``hyper`` (opt-in): a pod.RowSampling or a HyperPodPlan sends the call through the hyper-reduced loop
+    pod_prom_run_hyper, which assembles the reduced system from the sampled mesh rows only; sizes it does not cover are
+    refused, not rerouted."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    if hyper is not None:
+        return check_singular(pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device))
     route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh, long_wide)
     if route == "library":
         return _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device)

@@ -319,6 +319,41 @@ int bg_rom_run_long(int N, int B, int r, int nsteps, int projection, const doubl
                     int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
                     const int32_t *order, void *stream);
 
+/* bg_hyper_rom_run -- the POD PROM time loop HYPER-REDUCED: the reduced system is assembled from m sampled mesh rows with
+ *   weights xi >= 0 (ECSW-style), Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j over the rows i_j = rows[j] only,
+ *   y_j = (A Phi)[i_j], R_j = (A u - b)[i_j], w_j = Phi[i_j] (Galerkin) or y_j (LSPG).  3 <= N <= bg_fom_max_n(): the kernel
+ *   never touches a vector of mesh length; r <= 40, m <= 256 (bg_hyper_rom_limits).  reference: FEM/fem_burgers.py:709-785
+ *   with the sums over mesh rows restricted and weighted; with all rows and unit weights the loop is the reference's.
+ *   Opt-in: nothing routes here unless asked (burgers_hip/rom.py, pod_prom_run_hyper; the facade's hyper=).
+ *   rows   [m] int32, ascending, distinct, in [0, N) (the caller's duty: they live on the device and are not checked here);
+ *   xi     [m] finite, >= 0 (likewise);
+ *   xs     [m][3] the coordinates x[i-1], x[i], x[i+1] of every sampled row; slots outside the mesh are ignored.  Without
+ *          BG_OPT_NONUNIFORM the spacing is (last stencil node - first stencil node) / (their index distance), which is
+ *          (x[N-1] - x[0]) / (N - 1) when rows 0 and N - 1 are sampled;
+ *   PhiS   [MPAD][3][42], MPAD = m rounded up to 32 (bg_hyper_rom_table_elems(m, r) doubles, 16-byte aligned; 0 for an m or r
+ *          the kernel does not cover): rows Phi[i-1], Phi[i], Phi[i+1] of sampled row j at row indices 3 j .. 3 j + 2, zero
+ *          rows outside the mesh and beyond m, zero columns beyond r -- built once per basis and sampling by the caller;
+ *   q0     [B][r] = Phi^T u0;   u0s  [B][m][3] u0 at the stencil nodes (slots outside the mesh ignored);
+ *   qhist  [B][nsteps+1][r] the reduced coordinates, row 0 = q0; the caller decodes U = Phi q;
+ *   iters, flags, info, order, options: as bg_rom_run_long (pivoting repaired inside the call, so the caller never sees
+ *          BG_INFO_NEEDS_PIVOTING; entries of order outside [0, B) are skipped).
+ *   Row 0 is the Dirichlet row, row N - 1 has no right element.  The state at the stencil is PhiS q, except in the first
+ *   iteration of the run, which assembles at u0s itself and takes u^n = u0s (the reference starts from u0, not from
+ *   Phi Phi^T u0).  The update is q <- q + dq: equal to the reference's Phi^T u_k + dq for an orthonormal Phi, as
+ *   u_k = Phi q; the stopping rule is |dq| / |q| > tol and k < max_it.
+ *   Errors: N < 3, r < 1, m < 1, B or nsteps < 0, max_it < 1, dt <= 0, m > N, a null operand or output with B > 0, PhiS not
+ *   16-byte aligned: BG_ERR_BAD_ARG; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; r > 40 or m > 256 (like the row and centre
+ *   counts of the local loops): BG_ERR_UNSUPPORTED_R; an unknown projection: BG_ERR_PROJECTION; B = 0: BG_OK with nothing
+ *   launched.  Sizes the kernel does not cover are refused, never rerouted.
+ *   The table streams through LDS 32 sampled rows at a time, the accumulators of the reduced system are dealt to the four
+ *   waves (csrc/rom_hyper.hip); workgroup k of G = min(B, 2 CUs) takes the slots k, k + G, ... */
+int bg_hyper_rom_limits(int *max_r, int *max_m);
+long long bg_hyper_rom_table_elems(int m, int r);
+int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, const int32_t *rows, const double *xi,
+                     const double *xs, const double *PhiS, const double *q0, const double *u0s, const double *mu1,
+                     const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
+                     int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
 /* bg_rom_run_long_wide -- bg_rom_run_wide for long meshes: 3 <= N <= 1024 (bg_rom_run_long_wide_max_n; meant for N > 512,
  *   where bg_rom_run_wide ends), r <= 96 (bg_rom_run_long_wide_max_r; meant for r > 40, where bg_rom_run_long ends).
  *   reference: FEM/fem_burgers.py:709-785.
