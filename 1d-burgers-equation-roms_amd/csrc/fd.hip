@@ -170,7 +170,7 @@ __device__ __forceinline__ void fd_sample(const FdArgs& a, Topo& tp, int s)
             }
             const double rel = tp.gmax(dloc) / fmax(umax_int, 1e-15);
             ++k;
-            if (!(rel - rel == 0.0)) flags |= BG_FLAG_NONFINITE;
+            if (uniform_nonfinite(rel)) flags |= BG_FLAG_NONFINITE;
             if (rel < a.tol) { converged = true; break; }
         }
         if (!converged) flags |= BG_FLAG_HIT_CAP;

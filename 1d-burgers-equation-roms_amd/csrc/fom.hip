@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs
             // reference: error = ||dU|| / ||U1||; continue while error > tol and k < cap.
             // NaN compares false and ends the loop, as in the reference.
             more = (nd > a.tol2 * nu) && (k < a.max_it);
-            if (!(nd - nd == 0.0) || !(nu - nu == 0.0)) flags |= BG_FLAG_NONFINITE;
+            flags |= uniform_nonfinite(nd, nu) ? BG_FLAG_NONFINITE : 0;   // scalar: nd, nu are readlane results
         } while (more);
         if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
         store_rows<R>(hist + (size_t)(step + 1) * N, N, row0, FULL, u);
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 1) void fom_wide_kernel(FomArgs a)
             wide_sum2(lds, g, nd, nu, nd, nu);
             ++k;
             more = (nd > a.tol2 * nu) && (k < a.max_it);
-            if (!(nd - nd == 0.0) || !(nu - nu == 0.0)) flags |= BG_FLAG_NONFINITE;
+            flags |= uniform_nonfinite(nd, nu) ? BG_FLAG_NONFINITE : 0;
         } while (more);
         if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
         store_rows<R>(hist + (size_t)(step + 1) * N, N, row0, false, u);

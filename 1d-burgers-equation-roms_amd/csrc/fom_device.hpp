@@ -379,23 +379,22 @@ __device__ __forceinline__ void assemble_general(const ElemGeom<R>& gm, double d
 // One PCR step on normalised equations A x[j-s] + x[j] + C x[j+s] = D; neighbours come from
 // DPP moves (CTRL_DN: from lower lanes, CTRL_UP: from higher lanes, applied REPS times, zero
 // filled out of range, which is the identity equation).  LAST skips the A/C update.
-// The step comes in two halves, because pcr64 branches between them: first the new diagonal Bn and the new
-// right-hand side Dn, which do not depend on LAST ...
+// The new right-hand side Dn is a function of its own, because on its short exit pcr64 needs nothing else of a step
+// (a LAST step whose new diagonal is exactly 1, see there).
 template <int CTRL_DN, int CTRL_UP, int REPS>
-__device__ __forceinline__ void pcr_step_head(double A, double C, double D, double& Bn, double& Dn)
+__device__ __forceinline__ double pcr_step_rhs(double A, double C, double D)
 {
     const double Dm = dpp_shift<CTRL_DN, REPS>(D), Dp = dpp_shift<CTRL_UP, REPS>(D);
-    const double Cm = dpp_shift<CTRL_DN, REPS>(C), Ap = dpp_shift<CTRL_UP, REPS>(A);
-    Bn = __builtin_fma(-Cm, A, 1.0);
-    Bn = __builtin_fma(-Ap, C, Bn);
-    Dn = __builtin_fma(-Dm, A, D);
-    Dn = __builtin_fma(-Dp, C, Dn);
+    return __builtin_fma(-Dp, C, __builtin_fma(-Dm, A, D));
 }
 
-// ... then the division by Bn and, unless LAST, the new couplings (the controls are used for those only)
 template <int CTRL_DN, int CTRL_UP, int REPS, bool LAST>
-__device__ __forceinline__ void pcr_step_tail(double& A, double& C, double& D, double Bn, double Dn)
+__device__ __forceinline__ void pcr_step(double& A, double& C, double& D)
 {
+    const double Cm = dpp_shift<CTRL_DN, REPS>(C), Ap = dpp_shift<CTRL_UP, REPS>(A);
+    double Bn = __builtin_fma(-Cm, A, 1.0);
+    Bn = __builtin_fma(-Ap, C, Bn);
+    const double Dn = pcr_step_rhs<CTRL_DN, CTRL_UP, REPS>(A, C, D);
     const double rb = BG_RCP(Bn);
     D = Dn * rb;
     if (!LAST) {
@@ -403,14 +402,6 @@ __device__ __forceinline__ void pcr_step_tail(double& A, double& C, double& D, d
         A = -(Am * A) * rb;
         C = -(Cp * C) * rb;
     }
-}
-
-template <int CTRL_DN, int CTRL_UP, int REPS, bool LAST>
-__device__ __forceinline__ void pcr_step(double& A, double& C, double& D)
-{
-    double Bn, Dn;
-    pcr_step_head<CTRL_DN, CTRL_UP, REPS>(A, C, D, Bn, Dn);
-    pcr_step_tail<CTRL_DN, CTRL_UP, REPS, LAST>(A, C, D, Bn, Dn);
 }
 
 // ---- Wang partition inside one lane, in pieces (shared by the one-wave and the workgroup-wide solver) ----
@@ -480,14 +471,21 @@ __device__ __forceinline__ void wang_finish(const double (&lo)[R], const double 
 // Early exit (BG_PCR_EARLY_EXIT): a step multiplies the couplings pairwise (A' = -A_m A / B), so they are
 // squared per step, and on diagonally dominant systems the late steps change nothing.  After the stride-4
 // step the wave asks whether EVERY lane has |A| <= tau and |C| <= tau, tau = 2^-31.  If so, the stride-8
-// step runs in its LAST form and strides 16 and 32 are dropped (fom_fused_kernel<16>: 750 instead of 782 VALU
-// instructions per iteration).  With all couplings <= m going into a step,
+// step runs in its LAST form and strides 16 and 32 are dropped.  With all couplings <= m going into a step,
 // B_n >= 1 - 2 m^2 and the couplings coming out are <= m^2 / (1 - 2 m^2); with m <= 2^-31 they are
 // <= 2^-62 (1 + eps) after the LAST step.  Each dropped step would have changed D_j by at most twice that
 // times max|D|, so the truncated solve differs from the full one by < 2^-60 max_j |X_j|: below half an ulp
 // of the largest interface unknown.  The test is written so that a NaN or inf coupling fails it, and it is
 // one ballot, uniform over the wave (the DPP moves below it need all 64 lanes): a wave with one lane over
 // tau, or a non-finite one, takes the full path, whose arithmetic is that of -DBG_PCR_EARLY_EXIT=0.
+//
+// B_n == 1 on the short exit.  That LAST step computes D = D_n * rcp1(B_n), B_n = fma(-A_p, C, fma(-C_m, A, 1)).
+// Every coupling that passed the ballot is finite and <= 2^-31 (a neighbour out of range is the zero fill), so
+// each product is <= 2^-62, and 1 - x rounds to 1 for |x| < 2^-54 (half the spacing of the doubles below 1):
+// both FMAs return exactly 1.0, rcp1(1.0) is exactly 1.0 (v_rcp_f64 of a power of two is exact, the Newton
+// step then adds r * 0), and D_n * 1.0 is D_n, bit for bit.  So the short exit forms D_n alone: no DPP moves of
+// the couplings, no reciprocal, no multiply, and the chain in front of the back-transpose is two DPP moves and
+// two FMAs long (budget and measurements: DESIGN.md K1).
 __device__ __forceinline__ double pcr64(double A, double C, double D)
 {
     const int lane = lane_id();
@@ -502,17 +500,18 @@ __device__ __forceinline__ double pcr64(double A, double C, double D)
     constexpr double tau = 0x1p-31;
     const bool coupled = !(__builtin_fabs(A) <= tau && __builtin_fabs(C) <= tau);
     const bool full = __builtin_amdgcn_ballot_w64(coupled) != 0;
-    // Bn and Dn of the stride-8 step are the same in its LAST and its full form, so they are formed ahead of the
-    // branch: the full path is one `if` without an `else` and the short path falls through one not-taken scalar
-    // branch (an if / else cost the short path three more branches and measured 0.5 % slower).
-    double Bn, Dn;
-    pcr_step_head<0x112, 0x102, 1>(A, C, D, Bn, Dn);
+    // The short exit's whole stride-8 step (D = Dn, see above) is formed ahead of the branch and the old D kept, so
+    // that the full path is one `if` without an `else`, which starts again from the old D, and the short path falls
+    // through one not-taken scalar branch (an if / else cost the short path three more branches and measured 0.5 %
+    // slower).
+    const double D4 = D;
+    D = pcr_step_rhs<0x112, 0x102, 1>(A, C, D4);
     if (__builtin_expect(full, 0)) {
-        pcr_step_tail<0x112, 0x102, 1, false>(A, C, D, Bn, Dn);
+        D = D4;
+        pcr_step<0x112, 0x102, 1, false>(A, C, D);
         pcr_step<0x114, 0x104, 1, false>(A, C, D);
-        pcr_step_head<0x118, 0x108, 1>(A, C, D, Bn, Dn);
+        pcr_step<0x118, 0x108, 1, true>(A, C, D);
     }
-    pcr_step_tail<0x118, 0x108, 1, true>(A, C, D, Bn, Dn);
 #else
     pcr_step<0x112, 0x102, 1, false>(A, C, D);
     pcr_step<0x114, 0x104, 1, false>(A, C, D);

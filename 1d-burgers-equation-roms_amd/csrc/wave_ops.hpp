@@ -106,6 +106,27 @@ __device__ __forceinline__ void wave_sum2(double a, double b, double& sa, double
 
 __device__ __forceinline__ double sel(bool c, double a, double b) { return c ? a : b; }
 
+// inf or NaN in a WAVE-UNIFORM value (every lane holds the same v): exponent field all ones; zeros and denormals are
+// finite.  The same predicate as !(v - v == 0.0), but an integer test of the high word on the scalar unit: where v
+// already sits in an SGPR pair (the readlane results of wave_sum2) it is an s_and and an s_cmp instead of a v_add_f64
+// and a v_cmp_eq_f64.  The empty asm with its SGPR constraint is what keeps it there: the compiler turns every bare
+// spelling of the integer test back into a floating-point class compare on the vector unit.  It emits nothing, and
+// the readfirstlane folds away on an SGPR operand.
+constexpr unsigned F64_EXP_HI = 0x7ff00000u;
+__device__ __forceinline__ unsigned uniform_exponent_bits(double v)
+{
+    unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(v));
+    asm("" : "+s"(hi));
+    return hi & F64_EXP_HI;
+}
+__device__ __forceinline__ bool uniform_nonfinite(double v) { return uniform_exponent_bits(v) == F64_EXP_HI; }
+// either of two (the masked fields are <= F64_EXP_HI, so one s_max_u32 and one compare serve both)
+__device__ __forceinline__ bool uniform_nonfinite(double a, double b)
+{
+    const unsigned ea = uniform_exponent_bits(a), eb = uniform_exponent_bits(b);
+    return (ea > eb ? ea : eb) == F64_EXP_HI;
+}
+
 // ---- float32: DPP move, and folds across the rows of 16 lanes on the VALU (v_permlane16_swap / v_permlane32_swap) ----
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v)
