@@ -29,7 +29,7 @@
 // What the two kernels do not share is stated once per kernel in a description K (QuadFused, QuadLong in the .hip files),
 // and the kernel is quad_rom_kernel<K, Galerkin or LSPG>:
 //   K::rows                      mesh rows held (a multiple of 64): the length of u in LDS and of every per-node loop
-//   K::window, K::timing         the build macros: slots of the tangent stream in flight, shader clocks instead of counts
+//   K::window                    the build macro: slots of the tangent stream in flight
 //   K::pick_sample(a, grp, w, valid, sb)    which sample wave w of group grp works on; false: the whole group is skipped
 //   K::Nodes                     where g = M u^n + dt F and dt F of the wave's sample live between the step start and the
 //                                assembly: put_fdt, and init if dt F is `staged` through the tangent rows (setup), fdt,
@@ -91,7 +91,6 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
     constexpr int NACC = QuadAcc<GAL>::total;
     constexpr int QM = K::rows / 64;              // mesh rows per lane of a per-node sweep: row lane + 64 m
     constexpr int QW = K::window;                 // 16-byte slots of the tangent stream in flight per wave (divides 28)
-    constexpr bool kQT = K::timing;               // diagnostic builds: shader clocks per phase in place of the iteration counts (see the end)
     static_assert(K::rows % 64 == 0, "a per-node sweep is whole wavefronts");
     static_assert(QP2 % QW == 0, "the ring of slots runs across row groups with static indices");
     __shared__ __attribute__((aligned(16))) double s_T[QG * QTJ];          // tangent rows of the slab, per sample
@@ -141,16 +140,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
             for (int m = 0; m < QM; ++m) nodes.init(m, Tw[lane + 64 * m]);
         }
         int flags = 0, info_out = 0;
-        long long cyc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        long long tick = kQT ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        auto lap = [&](int i) {
-            if constexpr (kQT) {
-                const long long now = (long long)__builtin_amdgcn_s_memtime();
-                cyc[i] += now - tick;
-                tick = now;
-            }
-        };
-        int npass = 0;
+        PhaseClock<kPhaseClock, 8> clk;                // diagnostic builds (tools/time_quad_fused.py)
         // T rows of a row group (4 mesh rows) for the four samples.  H3 of a mesh row is symmetric: only its 55 upper 4 x 4 blocks
         // (a <= b) are stored and streamed -- 3.7 MB instead of 6.5 MB per pass through the CU's vector-memory path, which bounded
         // this phase (first version: every (tile, k chunk) operand loaded, 48 B/clk/CU).  Block (a, b) feeds tile a as it stands
@@ -275,16 +265,16 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
             }
             int k = 0;
             bool act = valid && info_out == 0;             // a sample with a singular reduced system stays frozen
-            lap(7);
+            clk.lap(7);
             while (true) {
-                ++npass;
+                clk.pass();
                 // ---- pass start: publish q and the activity flag (Phi q, the seed of the decode, comes out of the tangent stream) ----
                 if (lane < QN) s_q[w][lane] = q;
                 if (lane == 0) s_act[w] = act ? 1 : 0;
                 start_stream(w == 0 ? 0 : 1 + 4 * w);
-                lap(0);
+                clk.lap(0);
                 __syncthreads();
-                lap(5);
+                clk.lap(5);
                 const bool any = (s_act[0] | s_act[1] | s_act[2] | s_act[3]) != 0;     // workgroup-uniform
                 // B operand of the tangent: lane 16 k + 4 blk + j holds q_j[4 kc + k]
                 double bq[QKC];
@@ -307,9 +297,9 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                         for (int m = 0; m < 4; ++m)
                             tangent_group(g0 + m, m < 3 ? g0 + m + 1 : (slab + 1 < nslab ? g0 + 16 : first), bq);
                     }
-                    lap(1);
+                    clk.lap(1);
                     __syncthreads();
-                    lap(2);
+                    clk.lap(2);
                     // ---- decode of this wave's sample, rows [r0, r0 + 64]:  u = 1/2 (Phi q + T q)  (:1116-1118) -------------
                     {
                         const double* trow = Tw + ring_row(r0 + lane) * QTS;
@@ -335,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    lap(3);
+                    clk.lap(3);
                     if (act) {
                         // ---- assembly: A(u), R(u) of row r0 + lane (no SUPG term in this variant, :1142) --------------------
                         {
@@ -394,9 +384,9 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                             }
                         }
                     }
-                    lap(4);
+                    clk.lap(4);
                     __syncthreads();                       // every wave is done with this slab's tangent rows
-                    lap(5);
+                    clk.lap(5);
                 }
                 if (!any) break;                           // that was the sweep for u(q_K): U[:, m+1] = u  (:1173)
                 if (act) {
@@ -486,9 +476,9 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                         else if (k >= a.max_it) { act = false; flags |= BG_FLAG_HIT_CAP; }   // "Newton did not converge" (:1171)
                     }
                 }
-                lap(6);
+                clk.lap(6);
             }
-            lap(7);
+            clk.lap(7);
             // ---- U[:, m+1] = u (:1173): one coalesced row per sample ---------------------------------------------------------
             if (valid) {
                 double* hrow = hist + (size_t)(step + 1) * N;
@@ -499,10 +489,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
         if (valid && lane == 0) {
             a.flags[smp] = flags;
             a.info[smp] = info_out;
-            if (kQT && a.nsteps >= 10) {                  // kilo-clocks per phase and the number of passes, in place of the counts
-                for (int i = 0; i < 8; ++i) a.iters[(size_t)smp * a.nsteps + i] = (int)(cyc[i] >> 10);
-                a.iters[(size_t)smp * a.nsteps + 8] = npass;
-            }
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
         }
     }
 }

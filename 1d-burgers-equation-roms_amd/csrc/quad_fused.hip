@@ -20,11 +20,6 @@ __shared__ __attribute__((aligned(16))) double s_fdt[QG][QNMAX];           // dt
 struct QuadFused {
     static constexpr int rows = QNMAX;
     static constexpr int window = BG_QUAD_WINDOW;
-#ifdef BG_QUAD_TIMING                   // diagnostic builds (tools/time_quad_fused.py)
-    static constexpr bool timing = true;
-#else
-    static constexpr bool timing = false;
-#endif
 
     // wave w of group grp takes order[4 grp + w]; a padding wave (beyond B) computes on a copy of the last sample
     static __device__ __forceinline__ bool pick_sample(const QuadRunArgs& a, int grp, int w, bool& valid, int& sb)

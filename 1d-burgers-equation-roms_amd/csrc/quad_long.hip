@@ -24,11 +24,6 @@ constexpr int QNMIN = 513;             // below: bg_quad_rom_run
 struct QuadLong {
     static constexpr int rows = QNMAX;
     static constexpr int window = BG_QUAD_LONG_WINDOW;
-#ifdef BG_QUAD_LONG_TIMING              // diagnostic builds (tools/time_quad_long_rom.py)
-    static constexpr bool timing = true;
-#else
-    static constexpr bool timing = false;
-#endif
 
     // wave w of group grp takes order[4 grp + w]; entries outside [0, B) are skipped.  One exit, and the test last: with
     // an early `return false` the kernel spilled three more scalar registers.

@@ -126,14 +126,14 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     __shared__ double s_part[4][RW];             // per-wave partial sums of U_p^T u
     __shared__ int s_info;
     // The two halves of an iteration never overlap in time and share one block of LDS (two workgroups per CU need
-    // <= 80 KB each):  projection + solve: s_coef, s_halo, s_red   |   closure: s_act, s_dN, s_qs
+    // <= 80 KB each):  projection + solve: s_coef, s_halo, s_red   |   closure: s_act, s_dN
     constexpr int kCoefB = NPAD * 4 * 8, kHaloB = 2 * NB * 256 * 8, kRedB = 4 * RW * (RW + 4) * 8;
     constexpr int kSweepDepth = 3;                 // register buffers of the sweep (groups of 4 modes in flight + 1); 6 measured slower
     constexpr int kModes = 128 + ANN_MAX_N + 4 * kSweepDepth;   // secondary + primary modes of the sweep + zero modes that round its trip count up
     constexpr int kBW = 12;                        // columns of the sweep's right-hand matrix: n derivatives + 1 coefficient, padded to 3 blocks of 4
     constexpr int kBS = 13;                        // its row stride in doubles (odd: the row-per-lane writes spread over the banks)
-    constexpr int kActB = 2 * ANN_MAX_ROWS * ANN_MAX_WIDTH * 4, kDnB = kModes * kBS * 8, kQsB = 0;
-    constexpr int kPhaseA = kCoefB + kHaloB + kRedB, kPhaseB = kActB + kDnB + kQsB;
+    constexpr int kActB = 2 * ANN_MAX_ROWS * ANN_MAX_WIDTH * 4, kDnB = kModes * kBS * 8;
+    constexpr int kPhaseA = kCoefB + kHaloB + kRedB, kPhaseB = kActB + kDnB;
     __shared__ __attribute__((aligned(16))) unsigned char s_shared[kPhaseA > kPhaseB ? kPhaseA : kPhaseB];
     auto& s_coef = *reinterpret_cast<double (*)[NPAD][4]>(s_shared);
     auto& s_halo = *reinterpret_cast<double (*)[2][NB][256]>(s_shared + kCoefB);
@@ -164,23 +164,12 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     for (int e = tid; e < (NPAD + 2) * RW; e += 256) (&s_W[0][0])[e] = 0.0;
     if (tid < RW) s_q[tid] = 0.0;
 
-    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions --------
-    long long cyc[16];                           // timing builds only: shader clocks per phase, see the end of the sample loop
-#pragma unroll
-    for (int i = 0; i < 16; ++i) cyc[i] = 0;
-    long long tick = 0;
-    auto lap = [&](int i) {
-        if constexpr (kTiming) {
-            const long long now = (long long)__builtin_amdgcn_s_memtime();
-            cyc[i] += now - tick;
-            tick = now;
-        }
-    };
+    using Clock = PhaseClock<kTiming || kPhaseClock, 16>;        // diagnostic builds (tools/time_ann_fused.py): one per sample
     // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions --------
     // Layer l on all 256 threads.  A thread owns 8 outputs (two 16-byte weight loads per input k, no guards: the host
     // pads W^T to [in4][ld]) and every KPw-th group of 4 inputs; lane = (input slice) * P + (output group), so that
     // neighbouring lanes read neighbouring 16-byte chunks of a weight row.  NRT = rows compiled in.
-    auto mlp_impl = [&](auto nrt_c) __attribute__((always_inline)) {
+    auto mlp_impl = [&](auto nrt_c, Clock& clk) __attribute__((always_inline)) {
         constexpr int NRT = decltype(nrt_c)::value;
         int cur = 0;
         if (tid < RW) {                                              // inputs padded with zeros to a multiple of 4
@@ -190,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
             for (int r = 1; r < ANN_MAX_ROWS; ++r) s_act[0][r][tid] = (r - 1 == tid && tid < n) ? 1.0f : 0.0f;
         }
         __syncthreads();
-        lap(14);
+        clk.lap(14);
         for (int l = 0; l < (skip(128) ? 0 : a.nl); ++l) {          // (128: timing builds only)
             const int in4 = (a.width[l] + 3) & ~3, out = a.width[l + 1], ldw = (out + 7) & ~7, ogn = ldw >> 3;
             int P = 1, pshift = 0;
@@ -258,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                 kload(kb, wa);
                 kfma(kb, wa);
             }
-            if constexpr (skip(8192)) lap(3);                          // (8192: timing only: sub-phases of a layer summed over the layers)
+            if constexpr (skip(8192)) clk.lap(3);                      // (8192: timing only: sub-phases of a layer summed over the layers)
             // fold the KPw input slices (lanes P apart): inside a row of 16 lanes with shifts towards the higher lanes, so
             // the row total lands in its last P lanes; across the four rows with ds_bpermute
             auto fold = [&](auto get) {
@@ -277,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
             const float alpha = a.alpha[l];
             // bias, activation, derivative scaling
             auto activate = [&](float v, float& av, float& d) { mlp_activate(kind, alpha, v, av, d); };
-            if constexpr (skip(8192)) lap(4);
+            if constexpr (skip(8192)) clk.lap(4);
             const bool swapfold = (NRT == 6 || NRT == 1) && span == 64 && !skip(2048);      // workgroup-uniform
             if (swapfold) {
                 // Across the four rows of 16 lanes with v_permlane16_swap / v_permlane32_swap (VALU; ds_bpermute would make
@@ -323,9 +312,9 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                     }
                 }
             }
-            if constexpr (skip(8192)) lap(5);
+            if constexpr (skip(8192)) clk.lap(5);
             __syncthreads();
-            if constexpr (skip(8192)) lap(6);
+            if constexpr (skip(8192)) clk.lap(6);
             cur ^= 1;
             if (!swapfold) {                                          // second stage, one output per thread
                 if (tid < ldw && !skip(4096)) {
@@ -341,11 +330,11 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                 }
                 __syncthreads();
             }
-            if constexpr (skip(8192)) lap(7);
-            else if constexpr (kTiming) {
+            if constexpr (skip(8192)) clk.lap(7);
+            else if constexpr (kTiming || kPhaseClock) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
-                    if (i == l) lap(3 + i);
+                    if (i == l) clk.lap(3 + i);
             }
         }
         // the sweep's right-hand matrix: row j = mode j = [d c_j / d q_p (n columns) | c_j | zeros]; modes 0 .. n-1 are the
@@ -363,25 +352,23 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
 #pragma unroll
             for (int c = 0; c < kBW; ++c) {
                 double dv = 0.0;
-                if constexpr (true) {
-                    if (c < ANN_MAX_N && 1 + c < NRT) {                  // compile-time
-                        const double d = prim ? (tid == c ? 1.0 : 0.0) : (sec ? (double)rv[(1 + c < NRT) ? 1 + c : 0] : 0.0);
-                        dv = c < n ? d : 0.0;
-                    }
+                if (c < ANN_MAX_N && 1 + c < NRT) {                      // compile-time
+                    const double d = prim ? (tid == c ? 1.0 : 0.0) : (sec ? (double)rv[(1 + c < NRT) ? 1 + c : 0] : 0.0);
+                    dv = c < n ? d : 0.0;
                 }
                 dv = (c == n) ? cv : dv;
                 s_dN[tid][c] = dv;
             }
         }
         __syncthreads();
-        lap(11);
+        clk.lap(11);
     };
     // value_only: an evaluation that feeds the decode alone leaves the n tangent rows -- 5/6 of the layer arithmetic at n = 5 --
     // out; row 0 is computed by the same operations in the same order either way (same slices, same fold).
-    auto mlp = [&](bool value_only) __attribute__((always_inline)) {
-        if (value_only) mlp_impl(std::integral_constant<int, 1>{});
-        else if (nr <= 6) mlp_impl(std::integral_constant<int, 6>{});
-        else mlp_impl(std::integral_constant<int, ANN_MAX_ROWS>{});
+    auto mlp = [&](bool value_only, Clock& clk) __attribute__((always_inline)) {
+        if (value_only) mlp_impl(std::integral_constant<int, 1>{}, clk);
+        else if (nr <= 6) mlp_impl(std::integral_constant<int, 6>{}, clk);
+        else mlp_impl(std::integral_constant<int, ANN_MAX_ROWS>{}, clk);
     };
 
     // ---- one sweep over [U_p | U_s]: T = U . B with B = s_dN gives the tangent W = U_p + U_s dN (columns 0 .. n-1, into
@@ -472,7 +459,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     for (int slot = blockIdx.x; slot < a.B; slot += gridDim.x) {
         const int smp = a.order ? a.order[slot] : slot;
         const double mu1 = a.mu1[smp], mu2 = a.mu2[smp];
-        if constexpr (kTiming) tick = (long long)__builtin_amdgcn_s_memtime();
+        Clock clk;
         double* hist = a.hist + (size_t)smp * (size_t)(a.nsteps + 1) * (size_t)N;
         __syncthreads();
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
@@ -531,7 +518,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
             bool skip_eval = have_tangent && !kTiming && !a.no_reuse;
 #pragma unroll
             for (int c = 0; c < RW; ++c) skip_eval = skip_eval && ((c < n ? (float)s_q[c] : 0.0f) == s_qlast[c]);
-            lap(13);
+            clk.lap(13);
             int k = 0;
             bool more = true, decode = false;
             while (true) {
@@ -539,14 +526,14 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                 // ---- closure at the current q_p (one call site: the code is inlined once).  First pass of a time step:
                 // dN at the first guess (:1219), tangent only, U0 stays u^n.  Later passes: q_s = N(q_p) for the decode
                 // (:1241-1242) and dN for the next projection (:1219-1224).
-                lap(2);
+                clk.lap(2);
                 if (!skip_eval) {
                     // the last evaluation of the last step feeds the decode alone: value only
                     const bool value_only = !more && step == a.nsteps - 1 && !kTiming;
 #if BG_ANN_PRIO & 2
                     __builtin_amdgcn_s_setprio(0);
 #endif
-                    mlp(value_only);
+                    mlp(value_only, clk);
 #if BG_ANN_PRIO & 1
                     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -557,7 +544,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                     have_tangent = !value_only;
                 }
                 skip_eval = false;
-                lap(12);
+                clk.lap(12);
                 if (!more) break;
                 decode = true;
                 // ---- assembly: A(u_k), R(u_k) per row into LDS ----------------------------------------------------
@@ -580,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                     s_halo[1][c][tid] = s_W[rowbase + S + 1][4 * c + t];
                 }
                 __syncthreads();
-                lap(0);
+                clk.lap(0);
 #if BG_ANN_PRIO & 4
                 __builtin_amdgcn_s_setprio(0);
 #endif
@@ -590,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                 __builtin_amdgcn_s_setprio(3);
 #endif
                 __syncthreads();
-                lap(1);
+                clk.lap(1);
                 // ---- reduced solve -------------------------------------------------------------------------------
                 // np.linalg.solve's partial-pivoting elimination by wave 0 (pivoted_gj8).  The guarded pivot-free
                 // elimination of bg_rom_run does not apply here: the columns of U_p + U_s dN are far from orthonormal, the
@@ -609,6 +596,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / (nq + 1e-14);
                 ++k;
+                clk.pass();
                 more = (err > a.tol) && (k < a.max_it) && info_out == 0;
                 if (kTiming) more = k < 5;
                 if (!(err - err == 0.0)) flags |= BG_FLAG_NONFINITE;
@@ -624,12 +612,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
         if (tid == 0) {
             a.flags[smp] = flags;
             a.info[smp] = info_out;
-        }
-        if (kTiming && tid == 0 && a.nsteps >= 16) {     // diagnostic builds only: kilo-clocks per phase in place of the counts
-#pragma unroll
-            for (int i = 0; i < 16; ++i) a.iters[(size_t)smp * a.nsteps + i] = (int)(cyc[i] >> 10);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) cyc[i] = 0;
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
         }
     }
 }

@@ -47,12 +47,6 @@ constexpr int BLS = 17;                // row stride of the multiplier panel in 
 constexpr int BUS = BMAX_R + 16;       // row stride of the U12 panel in LDS
 constexpr int BREGION = 2 * BBUF > BMAX_R * BLS + 16 * BUS + 16 * BLS ? 2 * BBUF : BMAX_R * BLS + 16 * BUS + 16 * BLS;
 
-#ifdef BG_BLOCKED_TIMING              // diagnostic builds (tools/time_blocked_rom.py --phases): kilo-clocks per phase in place of the counts
-constexpr bool kBT = true;
-#else
-constexpr bool kBT = false;
-#endif
-
 struct BlockedRunArgs {
     const double* x;        // [N]
     const double* PhiP;     // [NPAD + 2][RP]: Phi row i at index i + 1, zero rows around and beyond N, zero columns beyond r
@@ -141,16 +135,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
 
         int flags = 0, info_out = 0;
         bool aborted = false;
-        long long cyc[4] = {0, 0, 0, 0};
-        long long tick = kBT ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        int npass = 0;
-        auto lap = [&](int i) {
-            if constexpr (kBT) {
-                const long long now = (long long)__builtin_amdgcn_s_memtime();
-                cyc[i] += now - tick;
-                tick = now;
-            }
-        };
+        PhaseClock<kPhaseClock, 4> clk;                          // diagnostic builds (tools/time_blocked_rom.py --phases)
 
         for (int step = 0; step < a.nsteps && info_out == 0 && !aborted; ++step) {
             // ---- g = M u^n + dt F (`M @ U[:, n] + At*F`, :746) -------------------------------------------------------------
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
             int k = 0;
             bool proj = true;
             while (true) {
-                lap(3);
+                clk.lap(3);
                 // ---- u = Phi q (:773) for iterations after the first and for U[:, n+1] (:779): 16 lanes per mesh row -------
                 if (k > 0) {
                     const int c16 = lane & 15;
@@ -183,7 +168,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
                     __syncthreads();
                 }
                 if (!proj) break;                          // that was the lift for U[:, n+1] = Phi q (:779)
-                ++npass;
+                clk.pass();
                 // ---- A(u), R(u) of every row (:730-753) ---------------------------------------------------------------------
                 {
                     const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
                     }
                 }
                 __syncthreads();
-                lap(0);
+                clk.lap(0);
                 // ---- projection: sweeps over the mesh, BT tiles per wave and sweep ------------------------------------------
                 for (int base = 0; base < nitems; base += 4 * BT) {
                     const int left = nitems - base - w;
@@ -272,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
                     }
                     __syncthreads();                           // slab buffers free for the next sweep; the tiles are stored
                 }
-                lap(1);
+                clk.lap(1);
                 // ---- solve(Ar, -br) (:767): blocked guarded pivot-free Gauss-Jordan over 16-column panels -------------------
                 double* const sL = s_reg;                      // [RP][BLS]  multipliers of every row (0 for the panel rows)
                 double* const sU = s_reg + BMAX_R * BLS;       // [16][BUS]  the panel rows right of the panel (incl. -br)
@@ -402,7 +387,7 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
                 }
                 if (w == 0 && lane == 0) s_zero = zstep;
                 const bool anybad = __syncthreads_or(bad) != 0;
-                lap(2);
+                clk.lap(2);
                 const bool tripped = anybad || a.force_handback;                       // workgroup-uniform
                 if (tripped) aborted = true;
                 else if (s_zero >= 0) info_out = s_zero + 1;                            // exactly singular (LAPACK info)
@@ -430,15 +415,12 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
             double* hrow = hist + (size_t)(step + 1) * N;
             for (int i = tid; i < N; i += 256) hrow[i] = s_u[i + 2];
             if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
-            lap(3);
+            clk.lap(3);
         }
         if (tid == 0) {
             a.flags[smp] = flags;
             a.info[smp] = aborted ? BG_INFO_NEEDS_PIVOTING : info_out;
-        }
-        if (kBT && tid == 0 && a.nsteps >= 8) {
-            for (int i = 0; i < 4; ++i) a.iters[(size_t)smp * a.nsteps + i] = (int)(cyc[i] >> 10);
-            a.iters[(size_t)smp * a.nsteps + 4] = npass;
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
         }
     }
 }

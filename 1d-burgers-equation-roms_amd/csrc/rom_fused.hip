@@ -184,17 +184,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
         }
         __syncthreads();
 
-        long long cyc[6] = {0, 0, 0, 0, 0, 0};          // timing builds only: shader clocks per phase
-        long long tick = kTiming ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        auto lap = [&](int i) {
-            if constexpr (kTiming) {
-                const long long now = (long long)__builtin_amdgcn_s_memtime();
-                cyc[i] += now - tick;
-                tick = now;
-            }
-        };
-        const long long stamp0 = kTiming ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        const long long real0 = kTiming ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
+        PhaseClock<kTiming || kPhaseClock, 6> clk;      // diagnostic builds (tools/time_fused.py)
         int flags = 0, info_out = 0;
         bool aborted = false;                    // fast kernel: the multiplier guard tripped, the repair kernel redoes this sample
         for (int step = 0; step < a.nsteps && info_out == 0 && !aborted; ++step) {
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
             }
             int k = 0;
             bool more;
-            lap(5);
+            clk.lap(5);
             do {
                 // Per-lane addresses are loop invariants of this whole kernel; the optimiser hoists them out of the time loop by
                 // the dozen and then spills them.  An opaque copy of the thread index per iteration keeps them recomputed
@@ -322,7 +312,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
                     }
                     __syncthreads();
                 }
-                lap(0);
+                clk.lap(0);
                 // ---- projection on the matrix cores -----------------------------------------------------------------
                 // as many passes over the rows as the accumulator budget of this instantiation demands (mfma_passes)
                 __builtin_amdgcn_s_setprio(0);
@@ -330,7 +320,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
                     mfma_passes<S, NB, true, RW, NRED, kAccBudget, 0, !GAL, CW>(frag, halo, s_coef, s_u, rowbase, t, w, lane, s_red, s_wtu);
                 __builtin_amdgcn_s_setprio(3);
                 __syncthreads();
-                lap(1);
+                clk.lap(1);
                 // ---- reduced solve: load own columns (sum of the four waves' partials), eliminate ----------------
                 auto entry = [&](int i, int j) -> double {               // (Ar | br | wtu)[i][j], j <= RW + 1
                     int rr = i, cc = j;
@@ -351,7 +341,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
 
                     if (!kTiming && tripped) aborted = true;
                 }
-                lap(2);
+                clk.lap(2);
                 // ---- q = Phi^T u_k + dq, err = |dq| / |q|  (:770-776) ---------------------------------------------
                 double wtu = 0.0;
                 if (lane < rr) wtu = entry(lane, RW + 1);       // Phi^T u: the second column of the extra block (both forms)
@@ -362,13 +352,14 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;
+                clk.pass();
                 more = (err > a.tol) && (k < a.max_it) && info_out == 0 && !aborted;
                 if (kTiming) more = k < 5;
                 if (!(err - err == 0.0)) flags |= BG_FLAG_NONFINITE;
                 if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
                 if (w == 0 && lane < RW) s_q[lane] = qn;
                 __syncthreads();
-                lap(3);
+                clk.lap(3);
                 // ---- lift u_{k+1} = Phi q from the register-resident basis (:773) --------------------------------
                 if (!skip(8)) {
                     double qv[NB];
@@ -388,7 +379,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
                     }
                 }
                 __syncthreads();
-                lap(4);
+                clk.lap(4);
             } while (more);
             // ---- U[:, n+1] = U1 (:779): one coalesced row ----------------------------------------------------------
             double* hrow = hist + (size_t)(step + 1) * N;
@@ -398,12 +389,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : 2) void rom_fused_kernel(typename Ru
         if (tid == 0) {
             a.flags[smp] = flags;
             a.info[smp] = aborted ? BG_INFO_NEEDS_PIVOTING : info_out;
-            if (kTiming && a.nsteps >= 2) {      // diagnostic builds only: shader cycles and 100 MHz ticks of this sample, in kilo-units
-                a.iters[(size_t)smp * a.nsteps] = (int)(((long long)__builtin_amdgcn_s_memtime() - stamp0) >> 10);
-                a.iters[(size_t)smp * a.nsteps + 1] = (int)(((long long)__builtin_amdgcn_s_memrealtime() - real0) >> 10);
-                if (a.nsteps >= 8)
-                    for (int i = 0; i < 6; ++i) a.iters[(size_t)smp * a.nsteps + 2 + i] = (int)(cyc[i] >> 10);
-            }
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
         }
     }
 }

@@ -8,8 +8,8 @@
 // Phase ablation for tools/time_fused.py (never defined in the product build): BG_FUSED_ABLATE is a bit mask of phases to
 // compile out (1 MFMA passes, 2 elimination, 8 lift, 16 assembly, 32 MFMA epilogue, 64 per-step operand formation); the
 // iteration count is then fixed at 5 per time step, the multiplier guard is ignored and the repair kernel is not launched,
-// so that the garbage values cannot change the control flow.  Such builds also stamp s_memtime / s_memrealtime per sample
-// into iters[b][0..1] (the in-kernel clock, printed by tools/time_fused.py).
+// so that the garbage values cannot change the control flow.  Such builds also turn the phase clock on (PhaseClock,
+// wave_ops.hpp), as -DBG_PHASE_CLOCK alone does without any of the above.
 #ifndef BG_FUSED_ABLATE
 #define BG_FUSED_ABLATE -1
 #endif

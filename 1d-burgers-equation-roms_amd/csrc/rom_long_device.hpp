@@ -29,7 +29,6 @@ struct LongLayout {
     static constexpr bool cf_by_mesh_row = false;       // lo, di, up, R of the slab at hand only: 2 KB instead of 32
     static constexpr bool mirror_lspg = true;           // the solves read the system through a plain accessor
     static constexpr bool has_repair = true;
-    static constexpr bool timing = false;
 
     // solve(Ar, -br) (:767) by rom_fused_device.hpp's routines, one value of dq and q per lane.  BG_OPT_FORCE_PIVOTED: the
     // entry point skips the fast launch and the repair kernel takes every sample.

@@ -23,7 +23,6 @@
 //   K::cf_by_mesh_row            the coefficients lo, di, up, R in LDS are indexed by mesh row (all NMAX kept) or by slab row (one slab's)
 //   K::mirror_lspg               LSPG parks the lower block pairs too; otherwise the solve reads them through a symmetric accessor
 //   K::has_repair                a second instantiation PIV redoes the samples marked BG_INFO_NEEDS_PIVOTING (and only those)
-//   K::timing                    diagnostic build: shader clocks per phase in place of the iteration counts (see the end of the body)
 //   K::solve_update<GAL, PIV, W> solve(Ar, -br) of the parked system (r live unknowns) by all four waves, q = Phi^T u + dq into L.q,
 //                                |dq|^2 and |q|^2
 //   K::Args                      the kernel's argument struct: StreamRunArgs, or LocalStreamRunArgs when K::local
@@ -228,7 +227,6 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
     static_assert(!PIV || K::has_repair, "this kernel has no repair instantiation");
     constexpr int NB = K::NB, R = 4 * NB, PS = K::PS, NMAX = K::NMAX, SLAB = StreamDims<K>::SLAB, CHUNKS = StreamDims<K>::CHUNKS;
     constexpr int NACC = StreamItems<K, GAL>::per_wave;
-    constexpr bool kT = K::timing;
     constexpr int w = W;
     double* const s_slab = L.slab;
     double* const s_u = L.u;
@@ -269,16 +267,7 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
 
         int flags = 0, info_out = 0;
         bool aborted = false;
-        long long cyc[6] = {0, 0, 0, 0, 0, 0};
-        long long tick = kT ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        int npass = 0;
-        auto lap = [&](int i) {
-            if constexpr (kT) {
-                const long long now = (long long)__builtin_amdgcn_s_memtime();
-                cyc[i] += now - tick;
-                tick = now;
-            }
-        };
+        PhaseClock<kPhaseClock && W == 0, 6> clk;                // diagnostic builds (tools/time_wide_rom.py --phases); thread 0 stores
         // K::local: the step's basis and width are the picked cluster's (wave-uniform: the DMA source base stays in scalar
         // registers); otherwise the arguments are read where they are used, as before there was a pick
         const double* PhiL = nullptr;
@@ -330,8 +319,8 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                 double acc[NACC];
 #pragma unroll
                 for (int p = 0; p < NACC; ++p) acc[p] = 0.0;
-                ++npass;
-                lap(5);
+                clk.pass();
+                clk.lap(5);
                 slab_dma(0, 0);                                // (not across the pass boundary: the parked system lies over both buffers)
                 for (int slab = 0; slab < nslab; ++slab) {
                     const int r0 = slab * SRS, cur = slab & 1;
@@ -339,7 +328,7 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                     const double* s_P = s_slab + cur * SLAB;                  // local row l = mesh row r0 - 1 + l
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's DMA pieces of the slab have landed
                     __syncthreads();                                          // ... and everybody's; the other buffer (and a per-slab s_cf) is no longer read
-                    lap(0);
+                    clk.lap(0);
                     if (slab + 1 < nslab) slab_dma(slab + 1, cur ^ 1);        // the next slab lands while this one is worked on
                     // ---- four lanes per row i = r0 + q4: u_{i-1}, u_i, u_{i+1} = Phi q (:773), then A(u), R(u) of row i --------------
                     {
@@ -377,7 +366,7 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                             *reinterpret_cast<double2*>(&s_cf[cf0 + q4][2]) = make_double2(up, R_i);
                         }
                     }
-                    lap(1);
+                    clk.lap(1);
                     if (proj) {
                         __syncthreads();                                      // the slab's coefficients (and u) are in LDS
                         // ---- projection: four steps of 16 rows; lane (k, blk, t): row 16 st + 4 k + blk, columns NB t + c ------------
@@ -402,17 +391,17 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                             stream_step_mfma<K, GAL, W>(Y, P, X, acc);
                         }
                     }
-                    lap(2);
+                    clk.lap(2);
                 }
                 __syncthreads();                               // the last slab's rows are no longer read (the system is parked over them)
                 if (!proj) break;                              // that was the lift for U[:, n+1] = Phi q (:779)
                 // ---- park the reduced system (over the dead slabs) ---------------------------------------------------------------
                 stream_park<K, GAL, W>(acc, S, lane);
                 __syncthreads();
-                lap(3);
+                clk.lap(3);
                 // ---- solve(Ar, -br) (:767), q = Phi^T u_k + dq, err = |dq| / |q|  (:770-776) -------------------------------------
                 double nd, nq;
-                K::template solve_update<GAL, PIV, W>(a, L, step_width(), lane, aborted, info_out, nd, nq, [&] { lap(4); });
+                K::template solve_update<GAL, PIV, W>(a, L, step_width(), lane, aborted, info_out, nd, nq, [&] { clk.lap(4); });
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;
@@ -431,10 +420,7 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
         if (tid == 0) {
             a.flags[smp] = flags;
             a.info[smp] = aborted ? BG_INFO_NEEDS_PIVOTING : info_out;
-        }
-        if (kT && W == 0 && tid == 0 && a.nsteps >= 8) {
-            for (int i = 0; i < 6; ++i) a.iters[(size_t)smp * a.nsteps + i] = (int)(cyc[i] >> 10);
-            a.iters[(size_t)smp * a.nsteps + 6] = npass;
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
         }
     }
 }

@@ -188,11 +188,6 @@ struct WidePod {
     static constexpr bool cf_by_mesh_row = true;        // lo, di, up, R of all 512 mesh rows stay in LDS
     static constexpr bool mirror_lspg = false;          // wide_solve reads the lower blocks by symmetry
     static constexpr bool has_repair = false;           // marked samples go back to the caller
-#ifdef BG_WIDE_TIMING                   // diagnostic builds (tools/time_wide_rom.py --phases): kilo-clocks per phase in place of the counts
-    static constexpr bool timing = true;
-#else
-    static constexpr bool timing = false;
-#endif
 
     // solve(Ar, -br) (:767): guarded pivot-free Gauss-Jordan, two row tiles, panels of four columns; two values of dq and q per lane.
     // BG_OPT_FORCE_PIVOTED (tests): every sample is handed back to the caller after its first solve.

@@ -165,4 +165,51 @@ __device__ __forceinline__ void mlp_activate(int kind, float alpha, float v, flo
     }
 }
 
+// ---- phase clock of the diagnostic builds (-DBG_PHASE_CLOCK; never defined in the product build) ---------------------
+// A device-side time loop constructs one per sample: lap(i) adds the shader clocks since the previous lap (or the
+// construction) to slot i, pass() counts a Picard / Gauss-Newton pass, store() overwrites the head of the sample's row
+// of iteration counts with the one record tools/_timing.py (phase_report) reads:
+//   [0, SLOTS) kilo-clocks per phase (>> 10) | [SLOTS] passes | [SLOTS + 1] shader kilo-clocks, [SLOTS + 2] 100 MHz
+//   kilo-ticks since construction; nothing when the run has fewer than SLOTS + 3 time steps.  ON = false is empty.
+#ifdef BG_PHASE_CLOCK
+constexpr bool kPhaseClock = true;
+#else
+constexpr bool kPhaseClock = false;
+#endif
+
+template <bool ON, int SLOTS>
+struct PhaseClock {
+    long long cyc[SLOTS] = {};
+    long long real0, tick;
+    int passes = 0;
+    __device__ __forceinline__ PhaseClock()
+        : real0((long long)__builtin_amdgcn_s_memrealtime()), tick((long long)__builtin_amdgcn_s_memtime()) {}
+    __device__ __forceinline__ void lap(int i)
+    {
+        const long long now = (long long)__builtin_amdgcn_s_memtime();
+        cyc[i] += now - tick;
+        tick = now;
+    }
+    __device__ __forceinline__ void pass() { ++passes; }
+    __device__ __forceinline__ void store(int32_t* iters_row, int nsteps) const
+    {
+        if (nsteps < SLOTS + 3) return;
+        long long total = (long long)__builtin_amdgcn_s_memtime() - tick;      // the laps partition the time before `tick`
+#pragma unroll
+        for (int i = 0; i < SLOTS; ++i) {
+            iters_row[i] = (int)(cyc[i] >> 10);
+            total += cyc[i];
+        }
+        iters_row[SLOTS] = passes;
+        iters_row[SLOTS + 1] = (int)(total >> 10);
+        iters_row[SLOTS + 2] = (int)(((long long)__builtin_amdgcn_s_memrealtime() - real0) >> 10);
+    }
+};
+template <int SLOTS>
+struct PhaseClock<false, SLOTS> {
+    __device__ __forceinline__ void lap(int) const {}
+    __device__ __forceinline__ void pass() const {}
+    __device__ __forceinline__ void store(int32_t*, int) const {}
+};
+
 }  // namespace bg

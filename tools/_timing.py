@@ -1,6 +1,7 @@
 """What at least three of the tools/time_*.py scripts share: the import path, the 3 x 3 training grid and its snapshots
-built on the device, the bench's parameter draw, the warm-up plus event-timed repetitions, and the tail of the report
-line.  What a script measures, its options and its FLOP count stay in the script."""
+built on the device, the bench's parameter draw, the warm-up plus event-timed repetitions, the tail of the report
+line, and the decoder of the phase-clock record.  What a script measures, its options and its FLOP count stay in the script."""
+import collections
 import os
 import sys
 
@@ -45,6 +46,26 @@ def rates_of(ms, res):
 
 def rates_text(rates):
     return ", ".join(f"{v:.3g}" for v in rates) + f" -> median {float(np.median(rates)):.3g} sample-Newton-steps/s"
+
+
+PhaseReport = collections.namedtuple("PhaseReport", "per_pass total passes mhz")
+
+
+def phase_report(res, names, passes_per_step=None):
+    """Decode the record PhaseClock<ON, SLOTS>::store (csrc/wave_ops.hpp) leaves at the head of every row of ``res.iters``
+    in a clock build (-DBG_PHASE_CLOCK, or -DBG_FUSED_ABLATE=bits for the fused loops); SLOTS = len(names):
+      [0, SLOTS) kilo-clocks (units of 1024) per phase | [SLOTS] passes | [SLOTS + 1] shader kilo-clocks and
+      [SLOTS + 2] 100 MHz kilo-ticks of the whole sample.
+    Returns the medians over the samples: per_pass, the thousands of shader clocks per pass of each phase; their total;
+    the passes per sample; the in-kernel clock in MHz.  ``passes_per_step``: the ablation builds' fixed iterations per
+    time step, which then replace the counted passes."""
+    slots, steps = len(names), res.iters.shape[1]
+    if steps < slots + 3:
+        raise ValueError(f"the phase-clock record of {slots} phases needs {slots + 3} time steps; the run had {steps}")
+    it = res.iters[:, :slots + 3].double().cpu().numpy()
+    passes = float(np.median(it[:, slots])) if passes_per_step is None else float(passes_per_step * steps)
+    per_pass = np.median(it[:, :slots], axis=0) * 1.024 / passes
+    return PhaseReport(per_pass, float(per_pass.sum()), passes, float(np.median(it[:, slots + 1] / it[:, slots + 2])) * 100.0)
 
 
 def peak_text(rates, flop):

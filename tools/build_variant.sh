@@ -2,6 +2,7 @@
 # One experimental build of the library with a single source recompiled under extra flags (kernel A/B timing through
 # BG_LIB_PATH): build/libvar_<name>.so (git-ignored, travels with gpurun).  Needs an up-to-date product build.
 # usage: tools/build_variant.sh <name> <csrc file> [hipcc flags...]     e.g.  tools/build_variant.sh b20 rom_fused.hip -DBG_ACC_BUDGET=20
+#        phase-clock build of a device-side loop:                        tools/build_variant.sh wt rom_wide.hip -DBG_PHASE_CLOCK
 set -e
 name=$1; src=$2; shift 2
 cd "$(dirname "$0")/../1d-burgers-equation-roms_amd"

@@ -6,7 +6,7 @@ loads + FMAs, DPP folds, swap fold + activation + write, barrier wait, second st
 usage: python tools/time_ann_fused.py [--batch 512] [--steps 20] [--proj LSPG|Galerkin] [--fused 0|1]"""
 import argparse, os
 import numpy as np, torch
-from _timing import draw, time_runs
+from _timing import draw, phase_report, time_runs
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=512); ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--same-mu", action="store_true"); ap.add_argument("--proj", default="LSPG"); ap.add_argument("--fused", type=int, default=1)
@@ -23,15 +23,14 @@ run = lambda: rom.pod_ann_run(X, np.ones(512), mu1, mu2, 0.05, a.steps, g["U_p"]
 ms, res = time_runs(run, 3)
 best = min(ms)
 timing_build = "abl" in os.environ.get("BG_LIB_PATH", "")
-if timing_build and a.steps >= 16:
-    ph = res.iters[:, :16].double().cpu().numpy() * 1024.0 / (5.0 * a.steps)          # shader clocks per iteration and phase
+if timing_build:
     names = ["assembly+fragments", "mfma pass", "solve+update"] + [f"mlp layer {i}" for i in range(8)] + ["mlp output table", "sweep", "per-step work", "mlp input set-up", "-"]
-    med = np.median(ph, axis=0)
+    rep = phase_report(res, names, passes_per_step=5)
     print("in-kernel shader clocks per iteration (median over samples):")
-    for nm, v in zip(names, med):
+    for nm, v in zip(names, rep.per_pass):
         if v > 0:
-            print(f"  {nm:20s} {v:9.0f}")
-    print(f"  {'total':20s} {med.sum():9.0f}")
+            print(f"  {nm:20s} {1e3 * v:9.0f}")
+    print(f"  {'total':20s} {1e3 * rep.total:9.0f}")
     res.iters[:] = 5
 its = int(res.iters.sum().item())
 slots = 2 * torch.cuda.get_device_properties(0).multi_processor_count

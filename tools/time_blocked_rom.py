@@ -4,11 +4,11 @@ r = 227 bases, rebuilt from the 9 training runs (eps^2 = 1e-5, 1e-6).
 usage: python tools/time_blocked_rom.py [--batch 1024] [--steps 20] [--r 160 227] [--no-library] [--phases]"""
 import argparse
 import numpy as np
-from _timing import draw, time_runs, training_snapshots
+from _timing import draw, phase_report, time_runs, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--r", type=int, nargs="+", default=[160, 227]); ap.add_argument("--no-library", action="store_true")
-ap.add_argument("--phases", action="store_true", help="BG_BLOCKED_TIMING build (BG_LIB_PATH): kilo-clocks per phase and pass")
+ap.add_argument("--phases", action="store_true", help="-DBG_PHASE_CLOCK build of rom_blocked.hip (BG_LIB_PATH): kilo-clocks per phase and pass")
 a = ap.parse_args()
 from burgers_hip import pod, rom
 X, S = training_snapshots(512, 0.05, steps=500)
@@ -23,11 +23,10 @@ for r in a.r:
         p = rom.PROJ[proj.lower()]
         (ms,), res = time_runs(lambda: rom.pod_prom_run_blocked(X, np.ones(512), mu1, mu2, 0.05, a.steps, plan, p))
         if a.phases:
-            it = res.iters[:, :5].double().cpu().numpy(); npass = np.median(it[:, 4])
             names = ["lift + assembly", "projection", "solve", "other (q update, final lift, per step)"]
-            print(f"r={k} {proj}: {ms:.1f} ms, passes per sample (median) {npass:.0f}; kilo-clocks per pass: " +
-                  ", ".join(f"{nm} {np.median(it[:, i]) * 1.024 / npass:.1f}" for i, nm in enumerate(names)) +
-                  f"; total {np.median(it[:, :4].sum(1)) * 1.024 / npass:.1f} k", flush=True)
+            rep = phase_report(res, names)
+            print(f"r={k} {proj}: {ms:.1f} ms, passes per sample (median) {rep.passes:.0f}; kilo-clocks per pass: " +
+                  ", ".join(f"{nm} {v:.1f}" for nm, v in zip(names, rep.per_pass)) + f"; total {rep.total:.1f} k at {rep.mhz:.0f} MHz", flush=True)
             continue
         its = int(res.iters.sum().item())
         line = (f"bg_rom_run_blocked {proj} r={k} B={a.batch} steps={a.steps}: {ms:.1f} ms, {its} sample-iterations, "

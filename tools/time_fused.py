@@ -5,7 +5,7 @@ fixed at 5 per time step, so builds with phases compiled out can be subtracted f
 usage: python tools/time_fused.py [--batch 256] [--steps 40] [--proj Galerkin|LSPG] [--r 40]"""
 import argparse, os
 import numpy as np, torch
-from _timing import GOLDEN, draw, time_runs
+from _timing import GOLDEN, draw, phase_report, time_runs
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=256); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--same-mu", action="store_true", help="every sample the same (mu1, mu2): equal iteration counts")
@@ -25,17 +25,15 @@ ms, res = time_runs(run, 3)
 best = min(ms)
 timing_build = "abl" in os.environ.get("BG_LIB_PATH", "")
 if timing_build:
-    st = res.iters[:, :2].double().cpu().numpy(); clk = np.median(st[:, 0] / st[:, 1]) * 100.0
-    if a.steps >= 8:
-        ph = np.median(res.iters[:, 2:8].double().cpu().numpy(), axis=0) * 1024.0 / (5.0 * a.steps)
-        print("in-kernel shader clocks per iteration (median over samples): " +
-              ", ".join(f"{nm} {v:.0f}" for nm, v in zip(["assembly", "mfma", "solve", "update", "lift", "per-step"], ph)) + f", total {ph.sum():.0f}")
-    res.iters[:, :8] = 5
-    res.iters[:, :2] = 5
+    names = ["assembly", "mfma", "solve", "update", "lift", "per-step"]
+    rep = phase_report(res, names, passes_per_step=5)
+    print("in-kernel shader clocks per iteration (median over samples): " +
+          ", ".join(f"{nm} {1e3 * v:.0f}" for nm, v in zip(names, rep.per_pass)) + f", total {1e3 * rep.total:.0f}")
+    res.iters[:, :len(names) + 3] = 5
 its = int(res.iters.sum().item())
 cus = torch.cuda.get_device_properties(0).multi_processor_count
 waves = -(-a.batch // cus)
 if timing_build:
-    print(f"in-kernel clock (median over samples): {clk:.0f} MHz")
+    print(f"in-kernel clock (median over samples): {rep.mhz:.0f} MHz")
 print(f"{os.path.basename(os.environ.get('BG_LIB_PATH', 'product'))}: {a.proj} r={a.r} B={a.batch} steps={a.steps}: {best:.2f} ms, {its} sample-iterations, "
       f"{best * 1e3 / (its / a.batch * waves):.2f} us per sample-iteration per workgroup, {its / best * 1e3:.3g} sample-steps/s")

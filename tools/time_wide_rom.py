@@ -3,11 +3,11 @@
 usage: python tools/time_wide_rom.py [--batch 1024] [--steps 40] [--r 96] [--library]"""
 import argparse, os
 import numpy as np
-from _timing import GOLDEN, draw, time_runs
+from _timing import GOLDEN, draw, phase_report, time_runs
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--r", type=int, default=96); ap.add_argument("--library", action="store_true")
-ap.add_argument("--phases", action="store_true", help="BG_WIDE_TIMING build (BG_LIB_PATH): kilo-clocks per phase and pass")
+ap.add_argument("--phases", action="store_true", help="-DBG_PHASE_CLOCK build of rom_wide.hip (BG_LIB_PATH): kilo-clocks per phase and pass")
 a = ap.parse_args()
 from burgers_hip import rom
 g = np.load(os.path.join(GOLDEN, "committed_pod_r96.npz"))
@@ -19,11 +19,10 @@ for proj in ("Galerkin", "LSPG"):
     (ms,), res = time_runs(run)
     its = int(res.iters.sum().item())
     if a.phases:
-        it = res.iters[:, :7].double().cpu().numpy(); npass = np.median(it[:, 6])
         names = ["wait slab + barrier", "lift + assembly", "projection (+ coefficient barrier)", "park", "solve", "update / per-step / pass start"]
-        print(f"{proj}: {ms:.1f} ms, passes per sample (median) {npass:.0f}; kilo-clocks per pass: " +
-              ", ".join(f"{nm} {np.median(it[:, i]) * 1.024 / npass:.1f}" for i, nm in enumerate(names)) +
-              f"; total {np.median(it[:, :6].sum(1)) * 1.024 / npass:.1f} k")
+        rep = phase_report(res, names)
+        print(f"{proj}: {ms:.1f} ms, passes per sample (median) {rep.passes:.0f}; kilo-clocks per pass: " +
+              ", ".join(f"{nm} {v:.1f}" for nm, v in zip(names, rep.per_pass)) + f"; total {rep.total:.1f} k at {rep.mhz:.0f} MHz")
         continue
     print(f"{'library path' if a.library else 'bg_rom_run_wide'} {proj} r={a.r} B={a.batch} steps={a.steps}: {ms:.1f} ms, {its} sample-iterations, "
           f"{its / ms * 1e3:.3g} sample-Newton-steps/s" + (f", handed back {res.redone}" if res.path == "bg_rom_run_wide" else ""))
