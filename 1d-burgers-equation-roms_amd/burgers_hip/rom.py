@@ -1218,11 +1218,11 @@ def _ann_fused_plan(model, n, nbar, N, dtype, device, limits="bg_ann_rom_limits"
         (ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in ann.layers])))
 
 
-def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, tol=1e-6, max_it=50, device=None,
-                      options=0, plan=None, balance=True):
-    """``pod_ann_prom`` for a batch with the whole time loop on the device (bg_ann_rom_run): one workgroup per sample,
-    the closure MLP evaluated in-kernel in float32, the reduced solve with partial pivoting.  Returns None when the model
-    is outside what that kernel covers.  ``plan``: an _ann_fused_plan of the model to reuse across calls."""
+def _ann_device_loop(route, limits, ut_rows, X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device,
+                     options, plan, balance):
+    """What pod_ann_run_fused (bg_ann_rom_run) and pod_ann_run_wide (bg_ann_rom_run_wide) share: the basis checks, the
+    plan, UT = [U_p^T; U_s^T] in the entry point's layout (``ut_rows(n, nbar, N)``: its shape), the launch, the result.
+    Returns None when the model is outside ``limits``."""
     device = _lib.require_device(device)
     Xh = check_mesh(X)
     N = len(Xh)
@@ -1231,16 +1231,26 @@ def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0,
         raise ValueError("U_p and U_s must have one row per mesh node")
     n, nbar = Up.shape[1], Us.shape[1]
     if plan is None:
-        plan = _ann_fused_plan(model.to(device=device, dtype=torch.float32).eval(), n, nbar, N, torch.float32, device)
+        plan = _ann_fused_plan(model.to(device=device, dtype=torch.float32).eval(), n, nbar, N, torch.float32, device, limits)
     if plan is None:
         return None
-    UT = torch.zeros((-(-(n + nbar) // 8) * 8, N), dtype=torch.float64, device=device)     # [U_p^T; U_s^T; zero rows]
-    UT[:n] = Up.t()
-    UT[n:n + nbar] = Us.t()
-    return _device_loop(_ROUTES["bg_ann_rom_run"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
+    UT = torch.zeros(ut_rows(n, nbar, N), dtype=torch.float64, device=device)
+    UT[:n, :N] = Up.t()
+    UT[n:n + nbar, :N] = Us.t()
+    return _device_loop(route, Xh, u0, mu1, mu2, nsteps, device, options, balance,
                         lambda f, N, B, x, inputs, opts, outputs: f(
                             N, B, n, nbar, int(nsteps), proj, x, _lib.ptr(UT), *inputs, *plan.args, float(dt), float(E),
                             float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
+
+
+def pod_ann_run_fused(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, tol=1e-6, max_it=50, device=None,
+                      options=0, plan=None, balance=True):
+    """``pod_ann_prom`` for a batch with the whole time loop on the device (bg_ann_rom_run): one workgroup per sample,
+    the closure MLP evaluated in-kernel in float32, the reduced solve with partial pivoting.  Returns None when the model
+    is outside what that kernel covers.  ``plan``: an _ann_fused_plan of the model to reuse across calls."""
+    return _ann_device_loop(_ROUTES["bg_ann_rom_run"], "bg_ann_rom_limits",
+                            lambda n, nbar, N: (-(-(n + nbar) // 8) * 8, N),       # zero rows up to a multiple of 8
+                            X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
 def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, tol=1e-6, max_it=50, device=None,
@@ -1248,25 +1258,9 @@ def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, 
     """pod_ann_run_fused for models of up to 20 primary modes (bg_ann_rom_run_wide): the closure MLP of bg_ann_rom_run on
     the mesh side of bg_rbf_rom_run.  Runs any model inside bg_ann_rom_run_wide_limits, the n <= 8 ones included; returns
     None outside them.  ``plan``: an _ann_fused_plan(..., limits="bg_ann_rom_run_wide_limits") to reuse across calls."""
-    device = _lib.require_device(device)
-    Xh = check_mesh(X)
-    N = len(Xh)
-    Up, Us = _as_dev(U_p, device), _as_dev(U_s, device)
-    if Up.dim() != 2 or Us.dim() != 2 or Up.shape[0] != N or Us.shape[0] != N:
-        raise ValueError("U_p and U_s must have one row per mesh node")
-    n, nbar = Up.shape[1], Us.shape[1]
-    if plan is None:
-        plan = _ann_fused_plan(model.to(device=device, dtype=torch.float32).eval(), n, nbar, N, torch.float32, device,
-                               "bg_ann_rom_run_wide_limits")
-    if plan is None:
-        return None
-    UT = torch.zeros((n + nbar, 512), dtype=torch.float64, device=device)     # [U_p^T; U_s^T], zero columns from N
-    UT[:n, :N] = Up.t()
-    UT[n:, :N] = Us.t()
-    return _device_loop(_ROUTES["bg_ann_rom_run_wide"], Xh, u0, mu1, mu2, nsteps, device, options, balance,
-                        lambda f, N, B, x, inputs, opts, outputs: f(
-                            N, B, n, nbar, int(nsteps), proj, x, _lib.ptr(UT), *inputs, *plan.args, float(dt), float(E),
-                            float(tol), int(max_it), opts, *outputs), keep=(plan, UT))
+    return _ann_device_loop(_ROUTES["bg_ann_rom_run_wide"], "bg_ann_rom_run_wide_limits",
+                            lambda n, nbar, N: (n + nbar, 512),                    # zero columns from N
+                            X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
 def _ann_route(n, fused=True, wide=False):

@@ -8,21 +8,23 @@
 //     -> n x n solve with partial pivoting (one wave, n <= 8)              np.linalg.solve :1237
 //     -> q_p += dq, err = |dq| / (|q_p| + 1e-14), stopping test            :1238-1244
 //     -> closure at the new q_p: the MLP value N(q_p) AND its input-Jacobian in ONE forward-mode pass in float32 (the
-//        value and the n tangent directions are the 1 + n rows of a small matrix in LDS; a thread owns 4 outputs of a
+//        value and the n tangent directions are the 1 + n rows of a small matrix in LDS; a thread owns 8 outputs of a
 //        layer and a slice of its inputs, the weights stream from L2 as 16-byte loads of W^T) -- the reference evaluates both in float32 too
 //        (:1219, :1241) -- then ONE sweep over U_s^T that forms the decode u = U_p q_p + U_s N(q_p) (:1242) and the next
 //        iteration's tangent W = U_p + U_s dN (:1224) together, straight into LDS.
 // HBM sees u0 once and one N-row history write per time step; the MLP weights (0.5 MB) and U_s (0.4 MB) are re-read from
 // L2 every iteration.  Host-side the batched iteration of burgers_hip/rom.py needs ~40 dependent launches per iteration
-// for the same work.  The float32 fold helpers (dpp_f32, swap16_add, swap32_add) and the activation arithmetic
-// (mlp_activate) are wave_ops.hpp's, shared with rom_ann_wide.hip.
+// for the same work.  The closure MLP -- its limits, its arguments (AnnModel in AnnRunArgs), the entry point's model check
+// and the layer loop ann_layers -- is rom_ann_device.hpp's, shared with rom_ann_wide.hip: here with two 16-byte chunks of
+// outputs per thread, the two-stage fold always and the swap fold for 1 and 6 rows.  This file keeps the input set-up
+// (s_qlast), the sweep and its table s_dN, pivoted_gj8, the LDS overlay and the loop.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
-#include "rom_fused_device.hpp"
+#include "rom_ann_device.hpp"
 
 namespace {
 
@@ -35,8 +37,6 @@ using namespace bg::fused;
 #ifndef BG_ANN_PRIO
 #define BG_ANN_PRIO 3
 #endif
-constexpr int ANN_MAX_LAYERS = 8;
-constexpr int ANN_MAX_WIDTH = 256;      // one thread per neuron
 constexpr int ANN_MAX_N = 8;            // reduced coordinates: two 4-column MFMA blocks
 constexpr int ANN_MAX_ROWS = 1 + ANN_MAX_N;
 
@@ -89,27 +89,6 @@ __device__ __forceinline__ void pivoted_gj8(const double (*__restrict__ s_red)[8
     if (lane == 0) *s_info = info;
 }
 
-struct AnnRunArgs {
-    const double* x;        // [N]
-    const double* UT;       // [m8][N]: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, zero rows up to m8 = (n + nbar) rounded up to 8
-    const double* u0;       // [B][N]
-    const double* mu1;      // [B]
-    const double* mu2;      // [B]
-    double* hist;           // [B][nsteps+1][N]
-    int32_t* iters;         // [B][nsteps]
-    int32_t* flags;         // [B]
-    int32_t* info;          // [B]
-    const int32_t* order;   // [B] or null: slot i of the persistent loop works on sample order[i]
-    const float* wt[ANN_MAX_LAYERS];     // layer l: W^T, [in4][ld] row-major: width[l] rounded up to 4 rows, width[l+1] to 8 columns, zero fill
-    const float* bias[ANN_MAX_LAYERS];   // [width[l+1]] or null
-    int width[ANN_MAX_LAYERS + 1];
-    int act[ANN_MAX_LAYERS];
-    float alpha[ANN_MAX_LAYERS];
-    int nl;
-    double dt, E, tol;
-    int N, B, n, nbar, nsteps, max_it, supg, nonuniform, no_reuse;
-};
-
 template <int S, int PROJ>
 __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
 {
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     // <= 80 KB each):  projection + solve: s_coef, s_halo, s_red   |   closure: s_act, s_dN
     constexpr int kCoefB = NPAD * 4 * 8, kHaloB = 2 * NB * 256 * 8, kRedB = 4 * RW * (RW + 4) * 8;
     constexpr int kSweepDepth = 3;                 // register buffers of the sweep (groups of 4 modes in flight + 1); 6 measured slower
-    constexpr int kModes = 128 + ANN_MAX_N + 4 * kSweepDepth;   // secondary + primary modes of the sweep + zero modes that round its trip count up
+    constexpr int kModes = ANN_MAX_NBAR + ANN_MAX_N + 4 * kSweepDepth;   // secondary + primary modes of the sweep + zero modes that round its trip count up
     constexpr int kBW = 12;                        // columns of the sweep's right-hand matrix: n derivatives + 1 coefficient, padded to 3 blocks of 4
     constexpr int kBS = 13;                        // its row stride in doubles (odd: the row-per-lane writes spread over the banks)
     constexpr int kActB = 2 * ANN_MAX_ROWS * ANN_MAX_WIDTH * 4, kDnB = kModes * kBS * 8;
@@ -165,13 +144,10 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
     if (tid < RW) s_q[tid] = 0.0;
 
     using Clock = PhaseClock<kTiming || kPhaseClock, 16>;        // diagnostic builds (tools/time_ann_fused.py): one per sample
-    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions --------
-    // Layer l on all 256 threads.  A thread owns 8 outputs (two 16-byte weight loads per input k, no guards: the host
-    // pads W^T to [in4][ld]) and every KPw-th group of 4 inputs; lane = (input slice) * P + (output group), so that
-    // neighbouring lanes read neighbouring 16-byte chunks of a weight row.  NRT = rows compiled in.
+    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions (ann_layers),
+    // then the sweep's table.  NRT = rows compiled in.
     auto mlp_impl = [&](auto nrt_c, Clock& clk) __attribute__((always_inline)) {
         constexpr int NRT = decltype(nrt_c)::value;
-        int cur = 0;
         if (tid < RW) {                                              // inputs padded with zeros to a multiple of 4
             s_act[0][0][tid] = tid < n ? (float)s_q[tid] : 0.0f;
             s_qlast[tid] = tid < n ? (float)s_q[tid] : 0.0f;
@@ -180,163 +156,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_fused_kernel(AnnRunArgs a)
         }
         __syncthreads();
         clk.lap(14);
-        for (int l = 0; l < (skip(128) ? 0 : a.nl); ++l) {          // (128: timing builds only)
-            const int in4 = (a.width[l] + 3) & ~3, out = a.width[l + 1], ldw = (out + 7) & ~7, ogn = ldw >> 3;
-            int P = 1, pshift = 0;
-            while (4 * P < ogn) { P <<= 1; ++pshift; }                // output groups per wave (a power of two, <= 8)
-            int KPw = 64 >> pshift;                                   // input slices per wave ...
-            while (4 * KPw > in4 && KPw > 1) KPw >>= 1;               // ... at most one per group of 4 inputs (small layers)
-            const int span = P * KPw;                                 // lanes of a wave that carry partial sums
-            const int kp = lane >> pshift, ogr = w * P + (lane & (P - 1));    // neighbouring lanes: neighbouring 16-byte chunks
-            const int og = ogr < ogn ? ogr : ogn - 1;                 // spare lanes redo the last group (no guarded loads)
-            // the 8 outputs of a thread are two chunks of 4: [4 og, 4 og + 4) and the same in the second half of the row
-            const float* __restrict__ wp = a.wt[l] + 4 * og;
-            const int half = 4 * ogn;
-            // this thread's bias for the activation stage, fetched now so that its latency hides behind the layer
-            const float bias_v = a.bias[l] ? a.bias[l][tid < out ? tid : out - 1] : 0.0f;
-            // ... and the two outputs this lane finishes when the layer takes the swap fold below
-            const int o0 = ((lane >> 4) < 2 ? 4 * og + 2 * (lane >> 4) : half + 4 * og + 2 * ((lane >> 4) - 2));
-            const float bias_0 = a.bias[l] ? a.bias[l][o0 < out ? o0 : out - 1] : 0.0f;
-            const float bias_1 = a.bias[l] ? a.bias[l][o0 + 1 < out ? o0 + 1 : out - 1] : 0.0f;
-            float acc[NRT][8];
-#pragma unroll
-            for (int r = 0; r < NRT; ++r)
-#pragma unroll
-                for (int c = 0; c < 8; ++c) acc[r][c] = 0.0f;
-            auto kload = [&](int kb, float4 (&wv)[4][2]) {
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const float4* src = reinterpret_cast<const float4*>(wp + (size_t)(kb + kk) * ldw);
-                    if constexpr (skip(1024)) {                          // timing only: no weight traffic
-                        wv[kk][0] = make_float4(1.0f * kb, 2.0f, 3.0f, 4.0f); wv[kk][1] = wv[kk][0];
-                    } else {
-                        wv[kk][0] = src[0];
-                        wv[kk][1] = src[ogn];
-                    }
-                }
-            };
-            auto kfma = [&](int kb, const float4 (&wv)[4][2]) {
-#pragma unroll
-                for (int r = 0; r < (skip(512) ? 1 : NRT); ++r) {      // (512: timing only: weight traffic, one row of arithmetic)
-                    const float4 xv = *reinterpret_cast<const float4*>(&s_act[cur][r][kb]);
-                    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        acc[r][0] = __builtin_fmaf(xs[kk], wv[kk][0].x, acc[r][0]); acc[r][1] = __builtin_fmaf(xs[kk], wv[kk][0].y, acc[r][1]);
-                        acc[r][2] = __builtin_fmaf(xs[kk], wv[kk][0].z, acc[r][2]); acc[r][3] = __builtin_fmaf(xs[kk], wv[kk][0].w, acc[r][3]);
-                        acc[r][4] = __builtin_fmaf(xs[kk], wv[kk][1].x, acc[r][4]); acc[r][5] = __builtin_fmaf(xs[kk], wv[kk][1].y, acc[r][5]);
-                        acc[r][6] = __builtin_fmaf(xs[kk], wv[kk][1].z, acc[r][6]); acc[r][7] = __builtin_fmaf(xs[kk], wv[kk][1].w, acc[r][7]);
-                    }
-                }
-            };
-            // Two slices per trip: 16 weight loads in flight.  A rolling ring of fetches that also runs ahead into the next
-            // layer was tried: with the 256-register budget of two workgroups per CU it spills, and was slower.
-            const int kstride = 4 * KPw;
-            int kb = kp < KPw ? 4 * kp : in4;                         // lanes beyond the span hold zeros and stay out of the fold
-            if constexpr (NRT <= 6) {
-                for (; kb + kstride < in4; kb += 2 * kstride) {
-                    float4 wa[4][2], wb[4][2];
-                    kload(kb, wa);
-                    kload(kb + kstride, wb);
-                    kfma(kb, wa);
-                    kfma(kb + kstride, wb);
-                }
-            }
-            for (; kb < in4; kb += kstride) {
-                float4 wa[4][2];
-                kload(kb, wa);
-                kfma(kb, wa);
-            }
-            if constexpr (skip(8192)) clk.lap(3);                      // (8192: timing only: sub-phases of a layer summed over the layers)
-            // fold the KPw input slices (lanes P apart): inside a row of 16 lanes with shifts towards the higher lanes, so
-            // the row total lands in its last P lanes; across the four rows with ds_bpermute
-            auto fold = [&](auto get) {
-                if constexpr (skip(2048)) return;                     // timing only
-#pragma unroll
-                for (int r = 0; r < NRT; ++r)
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) acc[r][c] += get(acc[r][c]);
-            };
-            if (P <= 1 && span > 1) fold([](float v) { return dpp_f32<0x111>(v); });      // row_shr:1
-            if (P <= 2 && span > 2) fold([](float v) { return dpp_f32<0x112>(v); });      // row_shr:2
-            if (P <= 4 && span > 4) fold([](float v) { return dpp_f32<0x114>(v); });      // row_shr:4
-            if (span > 8) fold([](float v) { return dpp_f32<0x118>(v); });                // row_shr:8
-            const int half_og = half + 4 * og;
-            const int kind = a.act[l];
-            const float alpha = a.alpha[l];
-            // bias, activation, derivative scaling
-            auto activate = [&](float v, float& av, float& d) { mlp_activate(kind, alpha, v, av, d); };
-            if constexpr (skip(8192)) clk.lap(4);
-            const bool swapfold = (NRT == 6 || NRT == 1) && span == 64 && !skip(2048);      // workgroup-uniform
-            if (swapfold) {
-                // Across the four rows of 16 lanes with v_permlane16_swap / v_permlane32_swap (VALU; ds_bpermute would make
-                // the LDS pipe the bottleneck).  One swap + add folds two values, and the pairing is chosen so that row rho of
-                // the wave ends up with the totals of outputs 2 rho, 2 rho + 1 of the thread's eight, for ALL 1 + n rows:
-                // the value and its tangent rows meet in one lane, which applies bias, activation and derivative scaling
-                // in registers -- no second stage, one barrier per layer.
-                float res[NRT][2];
-#pragma unroll
-                for (int r = 0; r < NRT; ++r) {
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const float s01 = swap16_add(acc[r][e], acc[r][2 + e]);
-                        const float s23 = swap16_add(acc[r][4 + e], acc[r][6 + e]);
-                        res[r][e] = swap32_add(s01, s23);
-                    }
-                }
-                if ((lane & 15) >= 16 - P && ogr < ogn) {
-                    float outv[NRT][2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int o = o0 + e;
-                        const bool real = o < out;
-                        float av, d;
-                        activate(res[0][e] + (real ? (e ? bias_1 : bias_0) : 0.0f), av, d);
-                        outv[0][e] = real ? av : 0.0f;                  // the padding outputs feed the next layer's padded inputs
-#pragma unroll
-                        for (int r = 1; r < NRT; ++r) outv[r][e] = real ? ((kind != BG_ACT_NONE) ? res[r][e] * d : res[r][e]) : 0.0f;
-                    }
-#pragma unroll
-                    for (int r = 0; r < NRT; ++r)
-                        *reinterpret_cast<float2*>(&s_act[cur ^ 1][r][o0]) = make_float2(outv[r][0], outv[r][1]);
-                }
-            } else {
-                if (span > 16) fold([](float v) { return __shfl_xor(v, 16); });
-                if (span > 32) fold([](float v) { return __shfl_xor(v, 32); });
-                const int top = span < 16 ? span : 16;                // the totals sit in the last P lanes below `top`
-                if (lane >= top - P && lane < top && ogr < ogn) {     // pre-activations of 8 outputs, all rows
-#pragma unroll
-                    for (int r = 0; r < NRT; ++r) {
-                        *reinterpret_cast<float4*>(&s_act[cur ^ 1][r][4 * og]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
-                        *reinterpret_cast<float4*>(&s_act[cur ^ 1][r][half_og]) = make_float4(acc[r][4], acc[r][5], acc[r][6], acc[r][7]);
-                    }
-                }
-            }
-            if constexpr (skip(8192)) clk.lap(5);
-            __syncthreads();
-            if constexpr (skip(8192)) clk.lap(6);
-            cur ^= 1;
-            if (!swapfold) {                                          // second stage, one output per thread
-                if (tid < ldw && !skip(4096)) {
-                    const bool real = tid < out;
-                    float av, d;
-                    activate(s_act[cur][0][tid] + (real ? bias_v : 0.0f), av, d);
-                    if (!real) { av = 0.0f; d = 0.0f; }
-                    s_act[cur][0][tid] = av;
-                    if (kind != BG_ACT_NONE || !real) {
-#pragma unroll
-                        for (int r = 1; r < NRT; ++r) s_act[cur][r][tid] *= d;
-                    }
-                }
-                __syncthreads();
-            }
-            if constexpr (skip(8192)) clk.lap(7);
-            else if constexpr (kTiming || kPhaseClock) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (i == l) clk.lap(3 + i);
-            }
-        }
+        const int cur = ann_layers<NRT, 2, NRT == 6 || NRT == 1, true>(a.m, s_act, tid, lane, w, clk);
         // the sweep's right-hand matrix: row j = mode j = [d c_j / d q_p (n columns) | c_j | zeros]; modes 0 .. n-1 are the
         // primary ones (c = q_p, derivative = identity), modes n .. n+nbar-1 the closure outputs, the rest (up to m8) zero
         // (all reads unconditional, all choices selects: the branchy form of this table took 4.7 k clocks)
@@ -624,7 +444,7 @@ extern "C" {
 int bg_ann_rom_limits(int* max_n, int* max_nbar, int* max_width, int* max_layers)
 {
     if (max_n) *max_n = ANN_MAX_N;
-    if (max_nbar) *max_nbar = 128;
+    if (max_nbar) *max_nbar = ANN_MAX_NBAR;
     if (max_width) *max_width = ANN_MAX_WIDTH;
     if (max_layers) *max_layers = ANN_MAX_LAYERS;
     return BG_OK;
@@ -639,21 +459,12 @@ int bg_ann_rom_run(int N, int B, int n, int nbar, int nsteps, int projection, co
     if (N < 2 || B < 0 || n < 1 || nbar < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0) || n_layers < 1) return BG_ERR_BAD_ARG;
     if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
     if (N > 512) return BG_ERR_UNSUPPORTED_N;
-    if (n > ANN_MAX_N || nbar > 128 || n_layers > ANN_MAX_LAYERS) return BG_ERR_UNSUPPORTED_R;
-    if (!widths || !wt || !bias || !acts || !alphas) return BG_ERR_BAD_ARG;
-    if (widths[0] != n || widths[n_layers] != nbar) return BG_ERR_BAD_ARG;
     AnnRunArgs a;
-    for (int l = 0; l < n_layers; ++l) {
-        if (widths[l + 1] < 1 || widths[l + 1] > ANN_MAX_WIDTH) return BG_ERR_UNSUPPORTED_R;
-        if (!wt[l] || ((uintptr_t)wt[l] & 15)) return BG_ERR_BAD_ARG;
-        if (acts[l] != BG_ACT_NONE && acts[l] != BG_ACT_ELU && acts[l] != BG_ACT_RELU && acts[l] != BG_ACT_TANH) return BG_ERR_BAD_ARG;
-        a.wt[l] = wt[l]; a.bias[l] = bias[l]; a.act[l] = acts[l]; a.alpha[l] = alphas[l];
-    }
-    for (int l = 0; l <= n_layers; ++l) a.width[l] = widths[l];
+    if (const int rc = ann_model_check(ANN_MAX_N, n, nbar, n_layers, widths, wt, bias, acts, alphas, a.m)) return rc;
     if (B == 0) return BG_OK;
     if (!x || !UT || !u0 || !mu1 || !mu2 || !hist || !flags || !info || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
     a.x = x; a.UT = UT; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags;
-    a.info = info; a.order = order; a.nl = n_layers; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.n = n; a.nbar = nbar;
+    a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.n = n; a.nbar = nbar;
     a.nsteps = nsteps; a.max_it = max_it; a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
     a.no_reuse = (options & BG_OPT_NO_TANGENT_REUSE) ? 1 : 0;
     const int grid = persistent_grid(B, 2);          // two workgroups per CU: one's memory latency hides behind the other

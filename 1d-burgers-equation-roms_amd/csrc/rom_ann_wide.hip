@@ -18,14 +18,17 @@
 // feeds the decode alone and is a value-only one (1 row instead of 1 + n); row 0 is computed by the same operations in the
 // same order in either kind.  The tangent is not kept across time steps (it is not resident during the projection), so
 // BG_OPT_NO_TANGENT_REUSE is accepted and changes nothing.
-// The mesh side is rom_closure_device.hpp's, shared with rom_rbf_fused.hip; the float32 fold helpers and the activation
-// arithmetic are wave_ops.hpp's, shared with rom_ann_fused.hip.  This file keeps the closure, the LDS overlay and the loop.
+// The mesh side is rom_closure_device.hpp's, shared with rom_rbf_fused.hip; the closure MLP -- its limits, its arguments
+// (AnnModel in AnnRunArgs), the entry point's model check and the layer loop ann_layers -- is rom_ann_device.hpp's, shared
+// with rom_ann_fused.hip: here with one 16-byte chunk of outputs per thread and the swap fold only.  This file keeps the
+// input set-up, the tables s_f and s_J, the LDS overlay and the loop.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
+#include "rom_ann_device.hpp"
 #include "rom_closure_device.hpp"
 
 namespace {
@@ -35,35 +38,11 @@ using namespace bg::fused;
 
 constexpr int AW_NB = 5;                       // column blocks of the projection: n <= 20
 constexpr int AW_MAX_N = 4 * AW_NB;
-constexpr int AW_MAX_NBAR = 128;
-constexpr int AW_MAX_LAYERS = 8;
-constexpr int AW_MAX_WIDTH = 256;
 constexpr int AW_MAX_ROWS = 1 + AW_MAX_N;      // value + tangent directions
 constexpr int AW_UT_LD = 512;                  // row stride of UT: the largest N
 
-struct AnnWideArgs {
-    const double* x;        // [N]
-    const double* UT;       // [n + nbar][512]: rows 0 .. n-1 = U_p^T, rows n .. n+nbar-1 = U_s^T, zero columns from N
-    const double* u0;       // [B][N]
-    const double* mu1;      // [B]
-    const double* mu2;      // [B]
-    double* hist;           // [B][nsteps+1][N]
-    int32_t* iters;         // [B][nsteps]
-    int32_t* flags;         // [B]
-    int32_t* info;          // [B]
-    const int32_t* order;   // [B] or null: slot i of the persistent loop works on sample order[i]
-    const float* wt[AW_MAX_LAYERS];     // layer l: W^T, [in4][ld] row-major: width[l] rounded up to 4 rows, width[l+1] to 8 columns, zero fill
-    const float* bias[AW_MAX_LAYERS];   // [width[l+1]] or null
-    int width[AW_MAX_LAYERS + 1];
-    int act[AW_MAX_LAYERS];
-    float alpha[AW_MAX_LAYERS];
-    int nl;
-    double dt, E, tol;
-    int N, B, n, nbar, nsteps, max_it, supg, nonuniform;
-};
-
 template <int S, int PROJ>
-__global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
+__global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnRunArgs a)
 {
     constexpr int NB = AW_NB;
     constexpr int NPAD = 64 * S;
@@ -76,18 +55,18 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
     __shared__ double s_fdt[NPAD];               // dt F
     __shared__ double s_q[RW], s_x[RW];
     __shared__ double s_part[4][RW];             // per-wave partial sums of U_p^T u
-    __shared__ double s_f[AW_MAX_NBAR];          // N(q_p) of the latest evaluation
+    __shared__ double s_f[ANN_MAX_NBAR];         // N(q_p) of the latest evaluation
     __shared__ int s_info;
     // The two halves of a pass never overlap in time and share one block of LDS (two workgroups per CU need <= 80 KB each):
     //   closure: s_act (two buffers of 21 rows x 256 floats); the finished table s_J takes the buffer the last layer read
     //   tangent -> assembly + projection + solve: s_J until the fragments are formed, then s_coef, s_elo, s_ehi, s_red
-    constexpr int kActHalfB = AW_MAX_ROWS * AW_MAX_WIDTH * 4, kActB = 2 * kActHalfB;
-    constexpr int kJB = AW_MAX_NBAR * RW * 8;
+    constexpr int kActHalfB = AW_MAX_ROWS * ANN_MAX_WIDTH * 4, kActB = 2 * kActHalfB;
+    constexpr int kJB = ANN_MAX_NBAR * RW * 8;
     static_assert(kJB <= kActHalfB && kActHalfB % 16 == 0, "s_J fits the idle activation buffer");
     constexpr int kCoefB = NPAD * 4 * 8, kEdgeB = 64 * RW * 8, kRedB = 4 * RW * (RW + 4) * 8;
     constexpr int kPhaseP = kCoefB + 2 * kEdgeB + kRedB;
     __shared__ __attribute__((aligned(16))) unsigned char s_shared[kActB > kPhaseP ? kActB : kPhaseP];
-    auto& s_act = *reinterpret_cast<float (*)[2][AW_MAX_ROWS][AW_MAX_WIDTH]>(s_shared);
+    auto& s_act = *reinterpret_cast<float (*)[2][AW_MAX_ROWS][ANN_MAX_WIDTH]>(s_shared);
     auto& s_coef = *reinterpret_cast<double (*)[NPAD][4]>(s_shared);
     auto& s_elo = *reinterpret_cast<double (*)[64][RW]>(s_shared + kCoefB);
     auto& s_ehi = *reinterpret_cast<double (*)[64][RW]>(s_shared + kCoefB + kEdgeB);
@@ -110,107 +89,18 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
 
     if (tid < 4) s_u[tid < 2 ? tid : NPAD + tid] = 0.0;
 
-    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions --------
-    // Layer l on all 256 threads.  A thread owns 4 outputs (one 16-byte weight load per input k, no guards: the host pads
-    // W^T to [in4][ld]) and every KPw-th group of 4 inputs; lane = (input slice) * P + (output group), so that neighbouring
-    // lanes read neighbouring 16-byte chunks of a weight row.  NRT = rows compiled in.  Returns the buffer of the outputs.
+    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions (ann_layers).
+    // NRT = rows compiled in.  Returns the buffer of the outputs.
     auto mlp_impl = [&](auto nrt_c) __attribute__((always_inline)) -> int {
         constexpr int NRT = decltype(nrt_c)::value;
-        int cur = 0;
         if (tid < RW) {                                              // inputs padded with zeros to a multiple of 4
             s_act[0][0][tid] = tid < n ? (float)s_q[tid] : 0.0f;
 #pragma unroll
             for (int r = 1; r < NRT; ++r) s_act[0][r][tid] = (r - 1 == tid && tid < n) ? 1.0f : 0.0f;
         }
         __syncthreads();
-        for (int l = 0; l < a.nl; ++l) {
-            const int in4 = (a.width[l] + 3) & ~3, out = a.width[l + 1], ldw = (out + 7) & ~7, ogn = ldw >> 2;
-            int P = 1, pshift = 0;
-            while (4 * P < ogn) { P <<= 1; ++pshift; }                // output groups per wave (a power of two, <= 16)
-            int KPw = 64 >> pshift;                                   // input slices per wave ...
-            while (4 * KPw > in4 && KPw > 1) KPw >>= 1;               // ... at most one per group of 4 inputs (small layers)
-            const int kp = lane >> pshift, ogr = w * P + (lane & (P - 1));
-            const int og = ogr < ogn ? ogr : ogn - 1;                 // spare lanes redo the last group (no guarded loads)
-            const float* __restrict__ wp = a.wt[l] + 4 * og;
-            // the output this lane finishes after the fold (row rho of the wave: output rho of the thread's four)
-            const int o0 = 4 * og + (lane >> 4);
-            const float bias_0 = a.bias[l] ? a.bias[l][o0 < out ? o0 : out - 1] : 0.0f;
-            float acc[NRT][4];
-#pragma unroll
-            for (int r = 0; r < NRT; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] = 0.0f;
-            auto kload = [&](int kb, float4 (&wv)[4]) {
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) wv[kk] = *reinterpret_cast<const float4*>(wp + (size_t)(kb + kk) * ldw);
-            };
-            auto kfma = [&](int kb, const float4 (&wv)[4]) {
-#pragma unroll
-                for (int r = 0; r < NRT; ++r) {
-                    const float4 xv = *reinterpret_cast<const float4*>(&s_act[cur][r][kb]);
-                    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        acc[r][0] = __builtin_fmaf(xs[kk], wv[kk].x, acc[r][0]); acc[r][1] = __builtin_fmaf(xs[kk], wv[kk].y, acc[r][1]);
-                        acc[r][2] = __builtin_fmaf(xs[kk], wv[kk].z, acc[r][2]); acc[r][3] = __builtin_fmaf(xs[kk], wv[kk].w, acc[r][3]);
-                    }
-                }
-            };
-            // two slices per trip (8 weight loads in flight) where the registers allow it: at 18 and 21 rows that loop spills
-            const int kstride = 4 * KPw;
-            int kb = kp < KPw ? 4 * kp : in4;                         // lanes beyond the span hold zeros: the fold adds them
-            if constexpr (NRT <= 10) {
-                for (; kb + kstride < in4; kb += 2 * kstride) {
-                    float4 wa[4], wb[4];
-                    kload(kb, wa);
-                    kload(kb + kstride, wb);
-                    kfma(kb, wa);
-                    kfma(kb + kstride, wb);
-                }
-            }
-            for (; kb < in4; kb += kstride) {
-                float4 wa[4];
-                kload(kb, wa);
-                kfma(kb, wa);
-            }
-            // fold the input slices (lanes P apart): inside a row of 16 lanes with shifts towards the higher lanes, so the
-            // row total lands in its last P lanes ...
-            auto fold = [&](auto get) {
-#pragma unroll
-                for (int r = 0; r < NRT; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[r][c] += get(acc[r][c]);
-            };
-            if (P <= 1) fold([](float v) { return dpp_f32<0x111>(v); });      // row_shr:1
-            if (P <= 2) fold([](float v) { return dpp_f32<0x112>(v); });      // row_shr:2
-            if (P <= 4) fold([](float v) { return dpp_f32<0x114>(v); });      // row_shr:4
-            if (P <= 8) fold([](float v) { return dpp_f32<0x118>(v); });      // row_shr:8
-            // ... and across the four rows with v_permlane16_swap / v_permlane32_swap (VALU, not the LDS pipe).  One swap +
-            // add folds two values, paired so that row rho of the wave ends up with the total of output rho of the thread's
-            // four, for ALL rows: the value and its tangent rows meet in one lane, which applies bias, activation and
-            // derivative scaling in registers -- one barrier per layer.
-            float res[NRT];
-#pragma unroll
-            for (int r = 0; r < NRT; ++r) {
-                const float s01 = swap16_add(acc[r][0], acc[r][1]);
-                const float s23 = swap16_add(acc[r][2], acc[r][3]);
-                res[r] = swap32_add(s01, s23);
-            }
-            const int kind = a.act[l];
-            const float alpha = a.alpha[l];
-            if ((lane & 15) >= 16 - P && ogr < ogn) {
-                const bool real = o0 < out;
-                float av, d;                                         // bias, activation, derivative scaling
-                mlp_activate(kind, alpha, res[0] + (real ? bias_0 : 0.0f), av, d);
-                s_act[cur ^ 1][0][o0] = real ? av : 0.0f;            // the padding outputs feed the next layer's padded inputs
-#pragma unroll
-                for (int r = 1; r < NRT; ++r)
-                    s_act[cur ^ 1][r][o0] = real ? ((kind != BG_ACT_NONE) ? res[r] * d : res[r]) : 0.0f;
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-        return cur;
+        PhaseClock<false, 1> clk;
+        return ann_layers<NRT, 1, true, false>(a.m, s_act, tid, lane, w, clk);
     };
 
     __builtin_amdgcn_s_setprio(3);
@@ -251,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void rom_ann_wide_kernel(AnnWideArgs a)
                 const int nrt = !more ? 1 : (nr <= 10 ? 10 : (nr <= 18 ? 18 : AW_MAX_ROWS));
                 // the closure table of this pass: s_f[j] = N_j, s_J[j][c] = dN_j / dq_c (zero from c = n)
                 double (*__restrict__ s_J)[RW] = reinterpret_cast<double (*)[RW]>(s_shared + (cur ^ 1) * kActHalfB);
-                if (tid < AW_MAX_NBAR) s_f[tid] = tid < nbar ? (double)s_act[cur][0][tid] : 0.0;
+                if (tid < ANN_MAX_NBAR) s_f[tid] = tid < nbar ? (double)s_act[cur][0][tid] : 0.0;
                 if (more) {
                     for (int e = tid; e < nbar * RW; e += 256) {
                         const int j = e / RW, c = e - j * RW;
@@ -307,9 +197,9 @@ extern "C" {
 int bg_ann_rom_run_wide_limits(int* max_n, int* max_nbar, int* max_width, int* max_layers)
 {
     if (max_n) *max_n = AW_MAX_N;
-    if (max_nbar) *max_nbar = AW_MAX_NBAR;
-    if (max_width) *max_width = AW_MAX_WIDTH;
-    if (max_layers) *max_layers = AW_MAX_LAYERS;
+    if (max_nbar) *max_nbar = ANN_MAX_NBAR;
+    if (max_width) *max_width = ANN_MAX_WIDTH;
+    if (max_layers) *max_layers = ANN_MAX_LAYERS;
     return BG_OK;
 }
 
@@ -322,23 +212,15 @@ int bg_ann_rom_run_wide(int N, int B, int n, int nbar, int nsteps, int projectio
     if (N < 2 || B < 0 || n < 1 || nbar < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0) || n_layers < 1) return BG_ERR_BAD_ARG;
     if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
     if (N > AW_UT_LD) return BG_ERR_UNSUPPORTED_N;
-    if (n > AW_MAX_N || nbar > AW_MAX_NBAR || n_layers > AW_MAX_LAYERS) return BG_ERR_UNSUPPORTED_R;
-    if (!widths || !wt || !bias || !acts || !alphas) return BG_ERR_BAD_ARG;
-    if (widths[0] != n || widths[n_layers] != nbar) return BG_ERR_BAD_ARG;
-    AnnWideArgs a;
-    for (int l = 0; l < n_layers; ++l) {
-        if (widths[l + 1] < 1 || widths[l + 1] > AW_MAX_WIDTH) return BG_ERR_UNSUPPORTED_R;
-        if (!wt[l] || ((uintptr_t)wt[l] & 15)) return BG_ERR_BAD_ARG;
-        if (acts[l] != BG_ACT_NONE && acts[l] != BG_ACT_ELU && acts[l] != BG_ACT_RELU && acts[l] != BG_ACT_TANH) return BG_ERR_BAD_ARG;
-        a.wt[l] = wt[l]; a.bias[l] = bias[l]; a.act[l] = acts[l]; a.alpha[l] = alphas[l];
-    }
-    for (int l = 0; l <= n_layers; ++l) a.width[l] = widths[l];
+    AnnRunArgs a;
+    if (const int rc = ann_model_check(AW_MAX_N, n, nbar, n_layers, widths, wt, bias, acts, alphas, a.m)) return rc;
     if (B == 0) return BG_OK;
     if (!x || !UT || !u0 || !mu1 || !mu2 || !hist || !flags || !info || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
     if ((uintptr_t)UT & 15) return BG_ERR_BAD_ARG;       // 16-byte loads
     a.x = x; a.UT = UT; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags;
-    a.info = info; a.order = order; a.nl = n_layers; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.n = n; a.nbar = nbar;
+    a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.n = n; a.nbar = nbar;
     a.nsteps = nsteps; a.max_it = max_it; a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
+    a.no_reuse = 0;                                      // the tangent is not kept across time steps: nothing to switch off
     const int grid = persistent_grid(B, 2);          // two workgroups per CU: one's closure streams while the other projects
     hipStream_t st = (hipStream_t)stream;
     return dispatch_projection(projection, [&](auto p) {

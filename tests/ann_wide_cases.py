@@ -2,8 +2,8 @@
 the random closures, the bases, the cases the loop is tested at, and one cached oracle run per case and sample.  numpy only
 at import; torch and the oracle are imported where they are used.
 
-Closures: ``mlp(widths, act, bias, seed, scale)`` is _random_mlp of tests/test_ann_fused_gpu.py (torch.manual_seed(seed),
-every Linear.weight x 0.5) with the last layer's weight and bias multiplied by ``scale``.  At scale 0.02 a wrong tangent
+Closures: ``mlp(widths, act, bias, seed, scale)`` (torch.manual_seed(seed), every Linear.weight x 0.5, then the last
+layer's weight and bias multiplied by ``scale``) also serves tests/test_ann_fused_gpu.py.  At scale 0.02 a wrong tangent
 row moves the history by less than the float32 gate (a swap of columns 0 and 16 of the Jacobian: 8.3e-7 LSPG, 3.1e-7
 Galerkin), so those closures only exercise shapes; the tangent-sensitive cases use scale 3.0 (1.4e-4 / 5.2e-5)."""
 import functools

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import ann_wide_cases as aw
 from conftest import load_golden, mesh, rel_l2
 from oracle import burgers_ref as br
 
@@ -75,20 +76,6 @@ def test_ann_fused_equals_batched_path_and_oracle(hip, proj):
         assert rel_l2(fh[s].T, Uo) < TOL32 and np.abs(fi[s] - ito).max() <= 1
 
 
-def _random_mlp(widths, act, bias, seed):
-    import torch.nn as nn
-    torch.manual_seed(seed)
-    layers = []
-    for i in range(len(widths) - 1):
-        lin = nn.Linear(widths[i], widths[i + 1], bias=bias)
-        with torch.no_grad():
-            lin.weight.mul_(0.5)
-        layers.append(lin)
-        if i < len(widths) - 2:
-            layers.append(act())
-    return nn.Sequential(*layers).eval()
-
-
 @pytest.mark.parametrize("N,n,nbar,hidden,act,bias", [(512, 8, 128, [256, 33], "Tanh", True), (256, 3, 20, [7], "ReLU", False),
                                                      (255, 1, 5, [16, 16, 16, 16, 16, 16, 16], "ELU", True),
                                                      (100, 4, 12, [64], "ELU", True), (301, 6, 40, [130, 50], "Tanh", False)])
@@ -103,11 +90,7 @@ def test_ann_fused_shapes_and_activations(hip, N, n, nbar, hidden, act, bias):
     snap = fom.fom_run(X, np.ones(N), m1.ravel(), m2.ravel(), 0.05, 100)
     Phi = pod.pod_basis(pod.snapshot_matrix(snap.hist).contiguous(), n_modes=n + nbar)[0].cpu().numpy()
     U_p, U_s = Phi[:, :n], Phi[:, n:]
-    model = _random_mlp([n] + hidden + [nbar], getattr(nn, act), bias, seed=N + n)
-    with torch.no_grad():                                    # a gentle closure: O(1e-2) of the primary coordinates
-        list(model)[-1].weight.mul_(0.02)
-        if bias:
-            list(model)[-1].bias.mul_(0.02)
+    model = aw.mlp([n] + hidden + [nbar], act, bias, seed=N + n, scale=0.02)    # a gentle closure: O(1e-2) of the primary coordinates
     rng = np.random.default_rng(n)
     B, nT = 19, 5
     mu1 = rng.uniform(4.25, 5.5, B); mu2 = rng.uniform(0.015, 0.03, B)
@@ -173,9 +156,7 @@ def test_ann_fused_limits_and_edge_cases(hip):
     r = rom.pod_ann_run(X, np.ones(512), np.zeros(0), np.zeros(0), 0.05, 3, g["U_p"], g["U_s"], model)
     assert r.hist.shape == (0, 4, 512)
     # too wide a layer: the device-side loop declines, the host-driven path takes over
-    wide = _random_mlp([5, 300, 91], nn.ELU, True, 0)
-    with torch.no_grad():
-        list(wide)[-1].weight.mul_(0.01); list(wide)[-1].bias.mul_(0.01)
+    wide = aw.mlp([5, 300, 91], "ELU", True, 0, scale=0.01)
     assert rom.pod_ann_run_fused(X, np.ones(512), [4.5], [0.02], 0.05, 2, g["U_p"], g["U_s"], wide, rom.PROJ["lspg"]) is None
     r = rom.pod_ann_run(X, np.ones(512), [4.5], [0.02], 0.05, 2, g["U_p"], g["U_s"], wide)
     assert r.path == "host"
