@@ -1,7 +1,7 @@
 // abi_common.hpp -- what every translation unit of libburgers_hip.so shares at the C-ABI boundary:
 // the per-thread record of the last failed launch (read back by bg_last_hip_error) and the
 // cached per-device CU count (no other process-wide state exists in the library), and the launch idiom of the entry
-// points: the persistent grid, the projection as a compile-time tag, the fast-then-repair pair of launches.
+// points: the persistent grid, the projection and the rows per thread as compile-time tags, the fast-then-repair pair of launches.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +56,16 @@ auto dispatch_projection(int projection, F&& f)
 {
     if (projection == BG_PROJ_GALERKIN) return f(ProjectionTag<BG_PROJ_GALERKIN>{});
     return f(ProjectionTag<BG_PROJ_LSPG>{});
+}
+
+// Rows per thread as a compile-time constant: f(std::integral_constant<int, R>) for the first R of Rs... with
+// N <= THREADS * R (THREADS threads share one sample's N rows); BG_ERR_UNSUPPORTED_N when none is large enough.
+template <int THREADS, int... Rs, class F>
+int dispatch_rows(int N, F&& f)
+{
+    int rc = BG_ERR_UNSUPPORTED_N;
+    (void)(... || (N <= THREADS * Rs && ((rc = f(std::integral_constant<int, Rs>{})), true)));
+    return rc;
 }
 
 // The two launches of a loop with a repair kernel: the fast kernel (guarded pivot-free elimination, `fast_per_cu`

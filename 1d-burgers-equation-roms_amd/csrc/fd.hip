@@ -2,7 +2,8 @@
 //
 // Replaces FDBurgers.fom_burgers_newton with the analytical Jacobian (reference
 // FD/fd_burgers.py:59-107; residual :28-35, Jacobian :37-44, boundary values :19-22).
-// Same skeleton as the FEM kernel: one wavefront per (mu1, mu2) sample for the whole time loop,
+// Same skeleton as the FEM kernels: one body (fd_sample) over the topologies of fom_wide.hpp, one
+// wavefront (N <= 2048) or one workgroup (N <= 8192) per (mu1, mu2) sample for the whole time loop,
 // rows in registers, the tridiagonal Newton system solved by the Wang + PCR solver of
 // fom_device.hpp.  The Jacobian is diagonally dominant here (1/dt + 2 nu/dx^2 on the diagonal),
 // so pivot-free elimination is safe.
@@ -29,63 +30,6 @@ struct FdArgs {
     int32_t* flags;
     double dt, tol;
     int N, B, nsteps, max_it;
-};
-
-__device__ __forceinline__ double wave_max(double v)
-{
-    v = fmax(v, dpp_mov<0x111>(v));
-    v = fmax(v, dpp_mov<0x112>(v));
-    v = fmax(v, dpp_mov<0x114>(v));
-    v = fmax(v, dpp_mov<0x118>(v));
-    v = fmax(v, dpp_mov<0x142, 0xA>(v));
-    v = fmax(v, dpp_mov<0x143, 0xC>(v));
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-
-// Where neighbour values, maxima and the tridiagonal solve come from: one wavefront per sample (DPP inside the
-// wave) or one 256-thread workgroup per sample (LDS across its four waves, fom_wide.hpp).
-struct WaveTopo {
-    int g;                                           // index of this thread among the sample's threads (= lane)
-    __device__ __forceinline__ double below(double v) { return from_lane_below(v); }
-    __device__ __forceinline__ double above(double v) { return from_lane_above(v); }
-    __device__ __forceinline__ double gmax(double v) { return wave_max(v); }
-    template <int R>
-    __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
-    {
-        tridiag_solve<R>(lo, di, up, rhs);
-    }
-};
-
-struct WgTopo {
-    WideLds& s;
-    int g;
-    int par;                                         // alternating exchange buffers: one barrier per exchange
-    __device__ __forceinline__ double shift(double v, int d)
-    {
-        double* buf = par ? s.ulast : s.ufirst;
-        par ^= 1;
-        buf[g + WIDE_PAD] = v;
-        __syncthreads();
-        return buf[g + WIDE_PAD + d];
-    }
-    __device__ __forceinline__ double below(double v) { return shift(v, -1); }
-    __device__ __forceinline__ double above(double v) { return shift(v, +1); }
-    __device__ __forceinline__ double gmax(double v)
-    {
-        v = wave_max(v);
-        double* buf = s.nrm[par];
-        par ^= 1;
-        if ((g & 63) == 0) buf[g >> 6] = v;
-        __syncthreads();
-        return fmax(fmax(buf[0], buf[1]), fmax(buf[2], buf[3]));
-    }
-    template <int R>
-    __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
-    {
-        wide_tridiag_solve<R>(s, g, lo, di, up, rhs);
-    }
 };
 
 // boundary values of the reference's apply_dirichlet_bc: U[0] = mu1, U[-1] = U[-2]
@@ -210,28 +154,16 @@ extern "C" int bg_fd_run(int N, int B, int nsteps, const double* x, const double
     if (N < 3 || B < 0 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
     if (B == 0) return BG_OK;
     if (!x || !u0 || !mu1 || !mu2 || !hist || !flags || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
-    if (N > WIDE_THREADS * 32) return BG_ERR_UNSUPPORTED_N;
     FdArgs a{x, u0, mu1, mu2, hist, iters, flags, dt, tol, N, B, nsteps, max_it};
     const dim3 grid((B + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (N > 2048) {                                  // one workgroup per sample
-        const int rw = (N + WIDE_THREADS - 1) / WIDE_THREADS;
-        if (rw <= 12) hipLaunchKernelGGL((fd_wide_kernel<12>), dim3(B), dim3(WIDE_THREADS), 0, st, a);
-        else if (rw <= 16) hipLaunchKernelGGL((fd_wide_kernel<16>), dim3(B), dim3(WIDE_THREADS), 0, st, a);
-        else if (rw <= 24) hipLaunchKernelGGL((fd_wide_kernel<24>), dim3(B), dim3(WIDE_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((fd_wide_kernel<32>), dim3(B), dim3(WIDE_THREADS), 0, st, a);
+    if (N > 2048)                                    // one workgroup per sample; BG_ERR_UNSUPPORTED_N beyond 8192
+        return bg::dispatch_rows<WIDE_THREADS, 12, 16, 24, 32>(N, [&](auto rc) {
+            hipLaunchKernelGGL((fd_wide_kernel<decltype(rc)::value>), dim3(B), dim3(WIDE_THREADS), 0, st, a);
+            return bg::check_launch();
+        });
+    return bg::dispatch_rows<64, 1, 2, 4, 8, 12, 16, 24, 32>(N, [&](auto rc) {
+        hipLaunchKernelGGL((fd_fused_kernel<decltype(rc)::value>), grid, block, 0, st, a);
         return bg::check_launch();
-    }
-    const int r = (N + 63) / 64;
-#define BG_FD(RV) hipLaunchKernelGGL((fd_fused_kernel<RV>), grid, block, 0, st, a)
-    if (r <= 1) BG_FD(1);
-    else if (r <= 2) BG_FD(2);
-    else if (r <= 4) BG_FD(4);
-    else if (r <= 8) BG_FD(8);
-    else if (r <= 12) BG_FD(12);
-    else if (r <= 16) BG_FD(16);
-    else if (r <= 24) BG_FD(24);
-    else BG_FD(32);
-#undef BG_FD
-    return bg::check_launch();
+    });
 }

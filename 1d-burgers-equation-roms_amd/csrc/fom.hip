@@ -1,9 +1,13 @@
 // fom.hip -- fused batched FOM time-stepper for gfx950 and its C-ABI entry points.
 //
 // Replaces the body of FEMBurgers.fom_burgers (reference FEM/fem_burgers.py:646-707):
-// one wavefront integrates one (mu1, mu2) sample through all time steps and all Picard
-// iterations; the state never leaves registers between iterations, HBM sees one
-// coalesced row write per time step.
+// one wavefront (N <= 1536) or one 256-thread workgroup (N <= 8192) integrates one (mu1, mu2)
+// sample through all time steps and all Picard iterations; the state never leaves registers
+// between iterations, HBM sees one coalesced row write per time step.
+//
+// The time loop, the diagnostic assembly and the diagnostic solve are each written once, over a
+// topology (fom_sample, assemble_sample, solve_sample; WaveTopo / WgTopo of fom_wide.hpp).  The six
+// kernels only find their sample, build the topology and call the body.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -36,12 +40,13 @@ struct FomArgs {
 
 constexpr int WAVES_PER_WG = 4;
 
+// rows >= N read as `pad` (unless `full`: every row exists) and are not written
 template <int R>
 __device__ __forceinline__ void load_rows(const double* __restrict__ src, int N, int row0, bool full,
-                                          double (&u)[R])
+                                          double (&u)[R], double pad = 0.0)
 {
 #pragma unroll
-    for (int j = 0; j < R; ++j) u[j] = (full || row0 + j < N) ? src[row0 + j] : 0.0;
+    for (int j = 0; j < R; ++j) u[j] = (full || row0 + j < N) ? src[row0 + j] : pad;
 }
 
 template <int R>
@@ -53,28 +58,38 @@ __device__ __forceinline__ void store_rows(double* __restrict__ dst, int N, int 
         if (full || row0 + j < N) dst[row0 + j] = u[j];
 }
 
+// ---- one sample over a topology (WaveTopo / WgTopo, fom_wide.hpp); the kernels below only choose s and the topology ----
+// The whole time loop of sample s; every branch is uniform over the sample's threads (a wave or a workgroup), which
+// all see the same sums.
 // TRACE: also store error_U = ||dU|| / ||U1|| of every iteration (what the reference prints at :664); a separate
 // instantiation, so that the hot kernel carries no trace of it.
-template <int R, bool FULL, bool UNI = true, bool TRACE = false>
-__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs a)
+// PARK (workgroup form, uniform mesh, 32 rows per thread): g and hfs live in LDS (*park) instead of 128 VGPRs per thread.
+template <int R, bool FULL, bool UNI, bool TRACE, bool PARK, class Topo>
+__device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, WidePark<PARK ? R : 1>* park)
 {
-    const int lane = lane_id();
-    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
-    if (s >= a.B) return;                                   // wave-uniform
-    const int N = a.N;
-    const int row0 = lane * R;
+    static_assert(UNI || !PARK, "only the uniform assembly reads g and hfs through accessors");
+    const int N = a.N, t = tp.g, row0 = t * R;
     const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
     const MeshConst c = make_mesh_const(h, a.dt, a.E, a.supg);
     const double mu1 = a.mu1[s], mu2 = a.mu2[s];
 
-    double hfs[R], fdt[R], u[R], g[R];
+    double hfs[PARK ? 1 : R], fdt[R], u[R], g[PARK ? 1 : R];
     ElemGeom<UNI ? 0 : R> gm;
-    if constexpr (UNI) {
+    if constexpr (PARK) {
+        double hf[R];
+        forcing_setup<R>(a.x, N, row0, mu2, c.h, a.dt, hf, fdt);
+#pragma unroll
+        for (int j = 0; j < R; ++j) park->hfs[j][t] = hf[j];
+    } else if constexpr (UNI) {
         forcing_setup<R>(a.x, N, row0, mu2, c.h, a.dt, hfs, fdt);
     } else {
         geom_setup<R>(a.x, N, row0, a.dt, a.E, gm);
         forcing_setup_general<R>(a.x, N, row0, mu2, a.dt, hfs, fdt);
     }
+    // g and hfs of local row j, where they live
+    auto g_put = [&](int j, double v) { if constexpr (PARK) park->g[j][t] = v; else g[j] = v; };
+    auto g_at = [&](int j) { if constexpr (PARK) return park->g[j][t]; else return g[j]; };
+    auto hf_at = [&](int j) { if constexpr (PARK) return park->hfs[j][t]; else return hfs[j]; };
 
     double* hist = a.hist + (size_t)s * (size_t)(a.nsteps + 1) * (size_t)N;
     load_rows<R>(a.u0 + (size_t)s * N, N, row0, FULL, u);
@@ -82,15 +97,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs
 
     int flags = 0;
     for (int step = 0; step < a.nsteps; ++step) {
-        if constexpr (UNI) mass_rhs<R, FULL>(c, N, row0, u, fdt, g);
-        else mass_rhs_general<R>(gm, N, row0, u, fdt, g);
+        if constexpr (UNI) mass_rhs<R, FULL>(tp, c, N, u, fdt, g_put);
+        else mass_rhs_general<R>(tp, gm, N, u, fdt, g);
         int k = 0;
         bool more;
         do {
             double lo[R], di[R], up[R], rhs[R];
-            if constexpr (UNI) assemble<R, FULL>(c, N, row0, mu1, u, g, hfs, lo, di, up, rhs);
-            else assemble_general<R>(gm, a.dt, c.kap, N, row0, mu1, u, g, hfs, lo, di, up, rhs);
-            tridiag_solve<R>(lo, di, up, rhs);
+            if constexpr (UNI) assemble<R, FULL>(tp, c, N, mu1, u, g_at, hf_at, lo, di, up, rhs);
+            else assemble_general<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, hfs, lo, di, up, rhs);
+            tp.template solve<R>(lo, di, up, rhs);
             double nd = 0.0, nu = 0.0;
 #pragma unroll
             for (int j = 0; j < R; ++j) {
@@ -98,9 +113,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs
                 nd = __builtin_fma(rhs[j], rhs[j], nd);
                 nu = __builtin_fma(u[j], u[j], nu);
             }
-            wave_sum2(nd, nu, nd, nu);
+            tp.sum2(nd, nu, nd, nu);
             if constexpr (TRACE) {
-                if (lane == 0) a.errs[((size_t)s * a.nsteps + step) * a.max_it + k] = sqrt(nd) / sqrt(nu);
+                if (tp.first()) a.errs[((size_t)s * a.nsteps + step) * a.max_it + k] = sqrt(nd) / sqrt(nu);
             }
             ++k;
             // reference: error = ||dU|| / ||U1||; continue while error > tol and k < cap.
@@ -110,12 +125,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs
         } while (more);
         if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
         store_rows<R>(hist + (size_t)(step + 1) * N, N, row0, FULL, u);
-        if (lane == 0) a.iters[(size_t)s * a.nsteps + step] = k;
+        if (tp.first()) a.iters[(size_t)s * a.nsteps + step] = k;
     }
-    if (lane == 0) a.flags[s] = flags;
+    if (tp.first()) a.flags[s] = flags;
 }
 
-// ---- diagnostics kernels: one assembly / one solve ---------------------------------
+// ---- diagnostics: one assembly / one solve, the loop's own functions on given states ------------
 struct AsmArgs {
     const double *x, *uk, *un, *mu1, *mu2;
     double *lo, *di, *up, *rhs;
@@ -123,13 +138,10 @@ struct AsmArgs {
     int N, B, supg;
 };
 
-template <int R, bool FULL, bool UNI = true>
-__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_assemble_kernel(AsmArgs a)
+template <int R, bool FULL, bool UNI, class Topo>
+__device__ __forceinline__ void assemble_sample(const AsmArgs& a, Topo& tp, int s)
 {
-    const int lane = lane_id();
-    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
-    if (s >= a.B) return;
-    const int N = a.N, row0 = lane * R;
+    const int N = a.N, row0 = tp.g * R;
     const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
     const MeshConst c = make_mesh_const(h, a.dt, a.E, a.supg);
     double hfs[R], fdt[R], u[R], un[R], g[R], lo[R], di[R], up[R], rhs[R];
@@ -137,14 +149,17 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_assemble_kernel(AsmA
     load_rows<R>(a.uk + (size_t)s * N, N, row0, FULL, u);
     if constexpr (UNI) {
         forcing_setup<R>(a.x, N, row0, a.mu2[s], c.h, a.dt, hfs, fdt);
-        mass_rhs<R, FULL>(c, N, row0, un, fdt, g);
-        assemble<R, FULL>(c, N, row0, a.mu1[s], u, g, hfs, lo, di, up, rhs);
+        auto g_put = [&](int j, double v) { g[j] = v; };
+        auto g_at = [&](int j) { return g[j]; };
+        auto hf_at = [&](int j) { return hfs[j]; };
+        mass_rhs<R, FULL>(tp, c, N, un, fdt, g_put);
+        assemble<R, FULL>(tp, c, N, a.mu1[s], u, g_at, hf_at, lo, di, up, rhs);
     } else {
         ElemGeom<R> gm;
         geom_setup<R>(a.x, N, row0, a.dt, a.E, gm);
         forcing_setup_general<R>(a.x, N, row0, a.mu2[s], a.dt, hfs, fdt);
-        mass_rhs_general<R>(gm, N, row0, un, fdt, g);
-        assemble_general<R>(gm, a.dt, c.kap, N, row0, a.mu1[s], u, g, hfs, lo, di, up, rhs);
+        mass_rhs_general<R>(tp, gm, N, un, fdt, g);
+        assemble_general<R>(tp, gm, a.dt, c.kap, N, a.mu1[s], u, g, hfs, lo, di, up, rhs);
     }
     store_rows<R>(a.lo + (size_t)s * N, N, row0, FULL, lo);
     store_rows<R>(a.di + (size_t)s * N, N, row0, FULL, di);
@@ -158,137 +173,76 @@ struct SolveArgs {
     int N, B;
 };
 
-template <int R>
-__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void tridiag_solve_kernel(SolveArgs a)
+template <int R, class Topo>
+__device__ __forceinline__ void solve_sample(const SolveArgs& a, Topo& tp, int s)
 {
-    const int lane = lane_id();
-    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
-    if (s >= a.B) return;
-    const int N = a.N, row0 = lane * R;
+    const int N = a.N, row0 = tp.g * R;
     double lo[R], di[R], up[R], rhs[R];
     const size_t off = (size_t)s * N;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        const bool in = row0 + j < N;
-        lo[j] = in ? a.lo[off + row0 + j] : 0.0;
-        di[j] = in ? a.di[off + row0 + j] : 1.0;
-        up[j] = in ? a.up[off + row0 + j] : 0.0;
-        rhs[j] = in ? a.rhs[off + row0 + j] : 0.0;
-    }
-    tridiag_solve<R>(lo, di, up, rhs);
+    load_rows<R>(a.lo + off, N, row0, false, lo);
+    load_rows<R>(a.di + off, N, row0, false, di, 1.0);      // rows >= N are identity rows
+    load_rows<R>(a.up + off, N, row0, false, up);
+    load_rows<R>(a.rhs + off, N, row0, false, rhs);
+    tp.template solve<R>(lo, di, up, rhs);
     store_rows<R>(a.sol + off, N, row0, false, rhs);
 }
 
-// ---- workgroup-per-sample variants (2048 < N <= 8192), see fom_wide.hpp ---------------------
-// PARK (uniform mesh, 32 rows per thread): g and hfs live in LDS (WidePark) instead of 128 VGPRs per thread.
+// ---- one wavefront per sample (N <= 1536), four samples per workgroup ----------------------------
+template <int R, bool FULL, bool UNI = true, bool TRACE = false>
+__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs a)
+{
+    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
+    if (s >= a.B) return;                                   // wave-uniform
+    WaveTopo tp{lane_id()};
+    fom_sample<R, FULL, UNI, TRACE, false>(a, tp, s, nullptr);
+}
+
+template <int R, bool FULL, bool UNI = true>
+__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_assemble_kernel(AsmArgs a)
+{
+    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
+    if (s >= a.B) return;
+    WaveTopo tp{lane_id()};
+    assemble_sample<R, FULL, UNI>(a, tp, s);
+}
+
+template <int R>
+__global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void tridiag_solve_kernel(SolveArgs a)
+{
+    const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
+    if (s >= a.B) return;
+    WaveTopo tp{lane_id()};
+    solve_sample<R>(a, tp, s);
+}
+
+// ---- one workgroup per sample (N <= 8192), see fom_wide.hpp ---------------------------------------
 template <int R, bool UNI>
 __global__ __launch_bounds__(WIDE_THREADS, 1) void fom_wide_kernel(FomArgs a)
 {
     constexpr bool PARK = UNI && R >= 32;
     __shared__ WideLds lds;
     __shared__ WidePark<PARK ? R : 1> park;
-    const int g = threadIdx.x, s = blockIdx.x;              // one workgroup per sample
-    const int N = a.N, row0 = g * R;
-    wide_init(lds, g);
-    const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
-    const MeshConst c = make_mesh_const(h, a.dt, a.E, a.supg);
-    const double mu1 = a.mu1[s], mu2 = a.mu2[s];
-    double hfs[PARK ? 1 : R], fdt[R], u[R], gv[PARK ? 1 : R];
-    ElemGeom<UNI ? 0 : R> gm;
-    if constexpr (PARK) {
-        double hf[R];
-        forcing_setup<R>(a.x, N, row0, mu2, c.h, a.dt, hf, fdt);
-#pragma unroll
-        for (int j = 0; j < R; ++j) park.hfs[j][g] = hf[j];
-    } else if constexpr (UNI) {
-        forcing_setup<R>(a.x, N, row0, mu2, c.h, a.dt, hfs, fdt);
-    } else {
-        geom_setup<R>(a.x, N, row0, a.dt, a.E, gm);
-        forcing_setup_general<R>(a.x, N, row0, mu2, a.dt, hfs, fdt);
-    }
-    double* hist = a.hist + (size_t)s * (size_t)(a.nsteps + 1) * (size_t)N;
-    load_rows<R>(a.u0 + (size_t)s * N, N, row0, false, u);
-    store_rows<R>(hist, N, row0, false, u);
-    int flags = 0;
-    for (int step = 0; step < a.nsteps; ++step) {
-        if constexpr (PARK) wide_mass_rhs_uni_parked<R>(lds, park, g, c, N, u, fdt);
-        else if constexpr (UNI) wide_mass_rhs_uni<R>(lds, g, c, N, u, fdt, gv);
-        else wide_mass_rhs<R>(lds, g, gm, N, u, fdt, gv);
-        int k = 0;
-        bool more;                                          // workgroup-uniform: every thread sees the same sums
-        do {
-            double lo[R], di[R], up[R], rhs[R];
-            if constexpr (PARK) wide_assemble_uni_parked<R>(lds, park, g, c, N, mu1, u, lo, di, up, rhs);
-            else if constexpr (UNI) wide_assemble_uni<R>(lds, g, c, N, mu1, u, gv, hfs, lo, di, up, rhs);
-            else wide_assemble<R>(lds, g, gm, a.dt, c.kap, N, mu1, u, gv, hfs, lo, di, up, rhs);
-            wide_tridiag_solve<R>(lds, g, lo, di, up, rhs);
-            double nd = 0.0, nu = 0.0;
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                u[j] += rhs[j];
-                nd = __builtin_fma(rhs[j], rhs[j], nd);
-                nu = __builtin_fma(u[j], u[j], nu);
-            }
-            wide_sum2(lds, g, nd, nu, nd, nu);
-            ++k;
-            more = (nd > a.tol2 * nu) && (k < a.max_it);
-            flags |= uniform_nonfinite(nd, nu) ? BG_FLAG_NONFINITE : 0;
-        } while (more);
-        if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
-        store_rows<R>(hist + (size_t)(step + 1) * N, N, row0, false, u);
-        if (g == 0) a.iters[(size_t)s * a.nsteps + step] = k;
-    }
-    if (g == 0) a.flags[s] = flags;
+    wide_init(lds, threadIdx.x);
+    WgTopo tp{lds, (int)threadIdx.x, 0};
+    fom_sample<R, false, UNI, false, PARK>(a, tp, blockIdx.x, &park);
 }
 
 template <int R, bool UNI>
 __global__ __launch_bounds__(WIDE_THREADS, 1) void fom_assemble_wide_kernel(AsmArgs a)
 {
     __shared__ WideLds lds;
-    const int g = threadIdx.x, s = blockIdx.x;
-    const int N = a.N, row0 = g * R;
-    wide_init(lds, g);
-    const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
-    const MeshConst c = make_mesh_const(h, a.dt, a.E, a.supg);
-    double hfs[R], fdt[R], u[R], un[R], gv[R], lo[R], di[R], up[R], rhs[R];
-    load_rows<R>(a.un + (size_t)s * N, N, row0, false, un);
-    load_rows<R>(a.uk + (size_t)s * N, N, row0, false, u);
-    if constexpr (UNI) {
-        forcing_setup<R>(a.x, N, row0, a.mu2[s], c.h, a.dt, hfs, fdt);
-        wide_mass_rhs_uni<R>(lds, g, c, N, un, fdt, gv);
-        wide_assemble_uni<R>(lds, g, c, N, a.mu1[s], u, gv, hfs, lo, di, up, rhs);
-    } else {
-        ElemGeom<R> gm;
-        geom_setup<R>(a.x, N, row0, a.dt, a.E, gm);
-        forcing_setup_general<R>(a.x, N, row0, a.mu2[s], a.dt, hfs, fdt);
-        wide_mass_rhs<R>(lds, g, gm, N, un, fdt, gv);
-        wide_assemble<R>(lds, g, gm, a.dt, c.kap, N, a.mu1[s], u, gv, hfs, lo, di, up, rhs);
-    }
-    store_rows<R>(a.lo + (size_t)s * N, N, row0, false, lo);
-    store_rows<R>(a.di + (size_t)s * N, N, row0, false, di);
-    store_rows<R>(a.up + (size_t)s * N, N, row0, false, up);
-    store_rows<R>(a.rhs + (size_t)s * N, N, row0, false, rhs);
+    wide_init(lds, threadIdx.x);
+    WgTopo tp{lds, (int)threadIdx.x, 0};
+    assemble_sample<R, false, UNI>(a, tp, blockIdx.x);
 }
 
 template <int R>
 __global__ __launch_bounds__(WIDE_THREADS, 1) void tridiag_solve_wide_kernel(SolveArgs a)
 {
     __shared__ WideLds lds;
-    const int g = threadIdx.x, s = blockIdx.x;
-    const int N = a.N, row0 = g * R;
-    wide_init(lds, g);
-    double lo[R], di[R], up[R], rhs[R];
-    const size_t off = (size_t)s * N;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        const bool in = row0 + j < N;
-        lo[j] = in ? a.lo[off + row0 + j] : 0.0;
-        di[j] = in ? a.di[off + row0 + j] : 1.0;
-        up[j] = in ? a.up[off + row0 + j] : 0.0;
-        rhs[j] = in ? a.rhs[off + row0 + j] : 0.0;
-    }
-    wide_tridiag_solve<R>(lds, g, lo, di, up, rhs);
-    store_rows<R>(a.sol + off, N, row0, false, rhs);
+    wide_init(lds, threadIdx.x);
+    WgTopo tp{lds, (int)threadIdx.x, 0};
+    solve_sample<R>(a, tp, blockIdx.x);
 }
 
 // ---- batched transpose out[b][c][r] = in[b][r][c] ----------------------------------
@@ -316,15 +270,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
 }
 
 // ---- dispatch ------------------------------------------------------------------------
-constexpr int kRowsPerLane[] = {1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 16, 24};
-
-int rows_per_lane(int N)
-{
-    for (int r : kRowsPerLane)
-        if (N <= 64 * r) return r;
-    return 0;
-}
-
 // workgroup-per-sample kernels: 8, 12, 16, 24 or 32 rows per THREAD of a 256-thread workgroup
 // Measured (tools/time_wide.py, B = 1024): at 32 rows per lane the wave-per-sample kernel spills (N = 2048:
 // 1.1e8 steps/s, N = 1800: 3.4e7) and the workgroup kernel at 8 rows per thread wins (1.29e8 / 1.24e8); at 24
@@ -336,36 +281,32 @@ constexpr int kWaveMaxN = 64 * 24, kWideMaxN = WIDE_THREADS * 32;
 // reference's one-mu-per-call pattern, FEM/paper_training_stage.py:28-49), measured slower than the wavefront form
 // (see bg_fom_run) and therefore opt-in (BG_OPT_FOM_WIDE).
 template <typename F>
-int dispatch_wide(int N, F&& f)
+int dispatch_wide(int N, F&& f)                                  // (N <= 256: identity rows beyond N)
 {
-    if (N <= WIDE_THREADS * 2) return f(std::integral_constant<int, 2>{});     // (N <= 256: identity rows beyond N)
-    if (N <= WIDE_THREADS * 4) return f(std::integral_constant<int, 4>{});
-    if (N <= WIDE_THREADS * 8) return f(std::integral_constant<int, 8>{});
-    if (N <= WIDE_THREADS * 12) return f(std::integral_constant<int, 12>{});
-    if (N <= WIDE_THREADS * 16) return f(std::integral_constant<int, 16>{});
-    if (N <= WIDE_THREADS * 24) return f(std::integral_constant<int, 24>{});
-    if (N <= WIDE_THREADS * 32) return f(std::integral_constant<int, 32>{});
-    return BG_ERR_UNSUPPORTED_N;
+    return dispatch_rows<WIDE_THREADS, 2, 4, 8, 12, 16, 24, 32>(N, f);
 }
 
+// rows per lane of the wave-per-sample kernels
 template <typename F>
 int dispatch_r(int N, F&& f)
 {
-    switch (rows_per_lane(N)) {
-        case 1: return f(std::integral_constant<int, 1>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 9: return f(std::integral_constant<int, 9>{});
-        case 10: return f(std::integral_constant<int, 10>{});
-        case 12: return f(std::integral_constant<int, 12>{});
-        case 16: return f(std::integral_constant<int, 16>{});
-        case 24: return f(std::integral_constant<int, 24>{});
-        default: return BG_ERR_UNSUPPORTED_N;
-    }
+    return dispatch_rows<64, 1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 16, 24>(N, f);
+}
+
+// The checks of bg_fom_run and bg_fom_run_traced (`traced`: wave-per-sample sizes only, and errs is required) and the
+// kernels' argument block.  BG_OK with B == 0 means there is nothing to launch.
+int fom_args(FomArgs& a, bool traced, int N, int B, int nsteps, const double* x, const double* u0, const double* mu1,
+             const double* mu2, double dt, double E, double tol, int max_it, int supg, double* hist, int32_t* iters,
+             int32_t* flags, double* errs)
+{
+    if (N < 2 || B < 0 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
+    if (traced && N > kWaveMaxN) return BG_ERR_UNSUPPORTED_N;
+    if (B == 0) return BG_OK;
+    if (!x || !u0 || !mu1 || !mu2 || !hist || !flags || (traced && !errs) || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
+    a.x = x; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.errs = errs;
+    a.dt = dt; a.E = E; a.tol2 = tol * tol;
+    a.N = N; a.B = B; a.nsteps = nsteps; a.max_it = max_it; a.supg = supg & BG_OPT_SUPG;
+    return BG_OK;
 }
 
 }  // namespace
@@ -397,13 +338,9 @@ int bg_fom_run(int N, int B, int nsteps, const double* x, const double* u0, cons
                const double* mu2, double dt, double E, double tol, int max_it, int supg, double* hist,
                int32_t* iters, int32_t* flags, void* stream)
 {
-    if (N < 2 || B < 0 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
-    if (B == 0) return BG_OK;
-    if (!x || !u0 || !mu1 || !mu2 || !hist || !flags || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
     FomArgs a;
-    a.x = x; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.errs = nullptr;
-    a.dt = dt; a.E = E; a.tol2 = tol * tol;
-    a.N = N; a.B = B; a.nsteps = nsteps; a.max_it = max_it; a.supg = supg & BG_OPT_SUPG;
+    const int err = fom_args(a, false, N, B, nsteps, x, u0, mu1, mu2, dt, E, tol, max_it, supg, hist, iters, flags, nullptr);
+    if (err != BG_OK || B == 0) return err;
     const bool nonuniform = (supg & BG_OPT_NONUNIFORM) != 0;
     const dim3 grid((B + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
     hipStream_t st = (hipStream_t)stream;
@@ -441,14 +378,9 @@ int bg_fom_run_traced(int N, int B, int nsteps, const double* x, const double* u
                       double dt, double E, double tol, int max_it, int supg, double* hist, int32_t* iters, int32_t* flags,
                       double* errs, void* stream)
 {
-    if (N < 2 || B < 0 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
-    if (N > kWaveMaxN) return BG_ERR_UNSUPPORTED_N;         // the wave-per-sample kernels only
-    if (B == 0) return BG_OK;
-    if (!x || !u0 || !mu1 || !mu2 || !hist || !flags || !errs || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
     FomArgs a;
-    a.x = x; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.errs = errs;
-    a.dt = dt; a.E = E; a.tol2 = tol * tol;
-    a.N = N; a.B = B; a.nsteps = nsteps; a.max_it = max_it; a.supg = supg & BG_OPT_SUPG;
+    const int err = fom_args(a, true, N, B, nsteps, x, u0, mu1, mu2, dt, E, tol, max_it, supg, hist, iters, flags, errs);
+    if (err != BG_OK || B == 0) return err;
     const bool nonuniform = (supg & BG_OPT_NONUNIFORM) != 0;
     const dim3 grid((B + WAVES_PER_WG - 1) / WAVES_PER_WG), block(64 * WAVES_PER_WG);
     hipStream_t st = (hipStream_t)stream;

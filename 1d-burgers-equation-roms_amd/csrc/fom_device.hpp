@@ -1,8 +1,11 @@
-// fom_device.hpp -- per-wavefront building blocks of the Burgers FOM Picard iteration.
+// fom_device.hpp -- building blocks of the Burgers FOM Picard iteration.
 //
-// Row distribution: lane p of the wave owns the R consecutive mesh rows
-// [p*R, p*R+R), so N <= 64*R rows fit one wavefront; rows >= N are identity rows.
-// All per-row state lives in registers (fully unrolled, compile-time R).
+// Row distribution: thread p of a sample's threads owns the R consecutive mesh rows
+// [p*R, p*R+R); rows >= N are identity rows.  All per-row state lives in registers (fully
+// unrolled, compile-time R).  The forcing set-up, the mass right-hand side and the assembly are
+// written over a topology (fom_wide.hpp: one wavefront or one workgroup per sample) that supplies
+// the neighbours' values; the PCR and the tridiagonal solve below them are the one-wavefront form
+// (N <= 64*R), which the workgroup form of fom_wide.hpp builds on.
 //
 // Arithmetic restated from the reference (FEM/fem_burgers.py), closed form for
 // 2-node elements on a uniform mesh:
@@ -86,47 +89,38 @@ __device__ __forceinline__ void forcing_setup(const double* __restrict__ x, int 
     }
 }
 
-// g = M u^n + dt F  (constant over the Picard iterations of one time step).  uL / uR: u of the row below
-// this lane's first row / above its last row (0 outside the mesh).
+// Everything from here to the PCR is written over a topology `tp` (WaveTopo / WgTopo, fom_wide.hpp): tp.g is this thread's
+// index among the sample's threads, its rows are [tp.g*R, tp.g*R + R), and tp hands over the neighbours' values: uL / uR,
+// u of the row below this thread's first row / above its last row (0 outside the mesh), and seL, se of the element below.
+//
+// g = M u^n + dt F  (constant over the Picard iterations of one time step).
 // gstore(j, value): where row j of g goes (registers, or LDS when a kernel parks it there)
-template <int R, bool FULL, typename GStore>
-__device__ __forceinline__ void mass_rhs_core_to(const MeshConst& c, int N, int row0, const double (&u)[R], double uL,
-                                                 double uR, const double (&fdt)[R], GStore&& gstore)
+template <int R, bool FULL, class Topo, typename GStore>
+__device__ __forceinline__ void mass_rhs(Topo& tp, const MeshConst& c, int N, const double (&u)[R],
+                                         const double (&fdt)[R], GStore&& gstore)
 {
+    double uL, uR;
+    tp.halo(u[0], u[R - 1], uL, uR);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const double um = (j == 0) ? uL : u[j - 1];
         const double up = (j == R - 1) ? uR : u[j + 1];
-        const int i = row0 + j;
+        const int i = tp.g * R + j;
         double inner = __builtin_fma(4.0, u[j], um) + up;
         double last = __builtin_fma(2.0, u[j], um);
         double v = __builtin_fma(c.h6, (i == N - 1) ? last : inner, fdt[j]);
         gstore(j, (!FULL && i >= N) ? 0.0 : v);
     }
+    tp.halo_done();
 }
 
-template <int R, bool FULL>
-__device__ __forceinline__ void mass_rhs_core(const MeshConst& c, int N, int row0, const double (&u)[R], double uL,
-                                              double uR, const double (&fdt)[R], double (&g)[R])
-{
-    mass_rhs_core_to<R, FULL>(c, N, row0, u, uL, uR, fdt, [&](int j, double v) { g[j] = v; });
-}
-
-template <int R, bool FULL>
-__device__ __forceinline__ void mass_rhs(const MeshConst& c, int N, int row0, const double (&u)[R],
-                                         const double (&fdt)[R], double (&g)[R])
-{
-    mass_rhs_core<R, FULL>(c, N, row0, u, from_lane_below(u[R - 1]), from_lane_above(u[0]), fdt, g);
-}
-
-// One assembly: diagonals lo/di/up of A(u) and rhs = b - A u  (= -R of the reference), in two halves so that
-// the halo values can come from DPP (one wave per sample) or LDS (one workgroup per sample).
-// p1: off-diagonals and the SUPG element terms se[];  p2: diagonal, right-hand side, special rows.
-// `first` / `last_lane` mark the lanes that own global row 0 / (FULL only) the last row.
-// hf(j): hfs of local row j (a register array, or an LDS read when a kernel parks it there)
+// One assembly: diagonals lo/di/up of A(u) and rhs = b - A u  (= -R of the reference), in two halves around the
+// exchange of se.  p1: off-diagonals and the SUPG element terms se[];  p2: diagonal, right-hand side, special rows.
+// `first` / `last_lane` mark the threads that own global row 0 / (FULL only) the last row.
+// hf(j), g(j): hfs and g of local row j (a register array, or an LDS read when a kernel parks them there)
 template <int R, typename HF>
-__device__ __forceinline__ void assemble_p1_from(const MeshConst& c, const double (&u)[R], double uL, double uR,
-                                                 HF&& hf, double (&lo)[R], double (&up)[R], double (&se)[R])
+__device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u)[R], double uL, double uR,
+                                            HF&& hf, double (&lo)[R], double (&up)[R], double (&se)[R])
 {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -142,19 +136,11 @@ __device__ __forceinline__ void assemble_p1_from(const MeshConst& c, const doubl
     lo[0] = __builtin_fma(-c.dt6, __builtin_fma(2.0, u[0], uL), c.aoff);
 }
 
-template <int R>
-__device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u)[R], double uL, double uR,
-                                            const double (&hfs)[R], double (&lo)[R], double (&up)[R],
-                                            double (&se)[R])
-{
-    assemble_p1_from<R>(c, u, uL, uR, [&](int j) { return hfs[j]; }, lo, up, se);
-}
-
 template <int R, bool FULL, typename GF>
-__device__ __forceinline__ void assemble_p2_from(const MeshConst& c, int N, int row0, bool first, bool last_lane,
-                                                 double mu1, const double (&u)[R], double uL, double uR, double seL,
-                                                 GF&& g, const double (&se)[R], double (&lo)[R],
-                                                 double (&di)[R], double (&up)[R], double (&rhs)[R])
+__device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0, bool first, bool last_lane,
+                                            double mu1, const double (&u)[R], double uL, double uR, double seL,
+                                            GF&& g, const double (&se)[R], double (&lo)[R],
+                                            double (&di)[R], double (&up)[R], double (&rhs)[R])
 {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -194,29 +180,15 @@ __device__ __forceinline__ void assemble_p2_from(const MeshConst& c, int N, int 
     }
 }
 
-template <int R, bool FULL>
-__device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0, bool first, bool last_lane,
-                                            double mu1, const double (&u)[R], double uL, double uR, double seL,
-                                            const double (&g)[R], const double (&se)[R], double (&lo)[R],
-                                            double (&di)[R], double (&up)[R], double (&rhs)[R])
+template <int R, bool FULL, class Topo, typename GF, typename HF>
+__device__ __forceinline__ void assemble(Topo& tp, const MeshConst& c, int N, double mu1, const double (&u)[R], GF&& g,
+                                         HF&& hf, double (&lo)[R], double (&di)[R], double (&up)[R], double (&rhs)[R])
 {
-    assemble_p2_from<R, FULL>(c, N, row0, first, last_lane, mu1, u, uL, uR, seL, [&](int j) { return g[j]; }, se, lo, di,
-                              up, rhs);
-}
-
-template <int R, bool FULL>
-__device__ __forceinline__ void assemble(const MeshConst& c, int N, int row0, double mu1,
-                                         const double (&u)[R], const double (&g)[R],
-                                         const double (&hfs)[R], double (&lo)[R], double (&di)[R],
-                                         double (&up)[R], double (&rhs)[R])
-{
-    const int lane = lane_id();
-    const double uL = from_lane_below(u[R - 1]);
-    const double uR = from_lane_above(u[0]);
-    double se[R];
-    assemble_p1<R>(c, u, uL, uR, hfs, lo, up, se);
-    const double seL = from_lane_below(se[R - 1]);
-    assemble_p2<R, FULL>(c, N, row0, lane == 0, lane == 63, mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    double uL, uR, se[R];
+    tp.halo(u[0], u[R - 1], uL, uR);
+    assemble_p1<R>(c, u, uL, uR, hf, lo, up, se);
+    const double seL = tp.below_se(se[R - 1]);
+    assemble_p2<R, FULL>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 // ------------------------------------------------------------------------------------
@@ -271,33 +243,27 @@ __device__ __forceinline__ void forcing_setup_general(const double* __restrict__
     }
 }
 
-// core with the halo values passed in (uL = u of the row below this lane's first, uR = u of the row above its last)
-template <int R>
-__device__ __forceinline__ void mass_rhs_general_core(const ElemGeom<R>& gm, int N, int row0, const double (&u)[R],
-                                                      double uL, double uR, const double (&fdt)[R], double (&g)[R])
+template <int R, class Topo>
+__device__ __forceinline__ void mass_rhs_general(Topo& tp, const ElemGeom<R>& gm, int N, const double (&u)[R],
+                                                 const double (&fdt)[R], double (&g)[R])
 {
+    double uL, uR;
+    tp.halo(u[0], u[R - 1], uL, uR);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const double um = (j == 0) ? uL : u[j - 1];
         const double up = (j == R - 1) ? uR : u[j + 1];
-        const int i = row0 + j;
+        const int i = tp.g * R + j;
         // (M u)_i = h_{i-1}/6 (u_{i-1} + 2 u_i) + h_i/6 (2 u_i + u_{i+1}); h6 is 0 outside the mesh
         double v = gm.h6[j] * __builtin_fma(2.0, u[j], um);
         v = __builtin_fma(gm.h6[j + 1], __builtin_fma(2.0, u[j], up), v);
         g[j] = (i >= N) ? 0.0 : v + fdt[j];
     }
+    tp.halo_done();
 }
 
-template <int R>
-__device__ __forceinline__ void mass_rhs_general(const ElemGeom<R>& gm, int N, int row0, const double (&u)[R],
-                                                 const double (&fdt)[R], double (&g)[R])
-{
-    mass_rhs_general_core<R>(gm, N, row0, u, from_lane_below(u[R - 1]), from_lane_above(u[0]), fdt, g);
-}
-
-// assemble_general in two halves so that the halo values can come from anywhere (DPP inside one wave,
-// LDS across the waves of a workgroup).  p1: off-diagonals and the SUPG element terms se[];
-// p2: diagonal, right-hand side, special rows.  `first` marks the lane that owns global row 0.
+// assemble_general in the same two halves.  p1: off-diagonals and the SUPG element terms se[];
+// p2: diagonal, right-hand side, special rows.  `first` marks the thread that owns global row 0.
 template <int R>
 __device__ __forceinline__ void assemble_general_p1(const ElemGeom<R>& gm, double dt, const double (&u)[R], double uL,
                                                     double uR, const double (&hfs)[R], double (&lo)[R],
@@ -362,18 +328,17 @@ __device__ __forceinline__ void assemble_general_p2(const ElemGeom<R>& gm, doubl
     }
 }
 
-template <int R>
-__device__ __forceinline__ void assemble_general(const ElemGeom<R>& gm, double dt, double kap, int N, int row0,
+template <int R, class Topo>
+__device__ __forceinline__ void assemble_general(Topo& tp, const ElemGeom<R>& gm, double dt, double kap, int N,
                                                  double mu1, const double (&u)[R], const double (&g)[R],
                                                  const double (&hfs)[R], double (&lo)[R], double (&di)[R],
                                                  double (&up)[R], double (&rhs)[R])
 {
-    const double uL = from_lane_below(u[R - 1]);
-    const double uR = from_lane_above(u[0]);
-    double se[R];
+    double uL, uR, se[R];
+    tp.halo(u[0], u[R - 1], uL, uR);
     assemble_general_p1<R>(gm, dt, u, uL, uR, hfs, lo, up, se);
-    const double seL = from_lane_below(se[R - 1]);
-    assemble_general_p2<R>(gm, dt, kap, N, row0, lane_id() == 0, mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    const double seL = tp.below_se(se[R - 1]);
+    assemble_general_p2<R>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 // One PCR step on normalised equations A x[j-s] + x[j] + C x[j+s] = D; neighbours come from

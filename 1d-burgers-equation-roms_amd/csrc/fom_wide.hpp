@@ -1,6 +1,8 @@
 // fom_wide.hpp -- one WORKGROUP (4 wavefronts) per sample, for meshes beyond one wavefront's
-// registers (1536 < N <= 8192).  Same arithmetic as fom_device.hpp; what changes is where the
-// halo values come from and how the 256 interface equations of the Wang partition are solved.
+// registers (1536 < N <= 8192), and the two topologies (WaveTopo, WgTopo, at the end) over which
+// the FEM bodies of fom.hip and the FD body of fd.hip are written once.  Same arithmetic as
+// fom_device.hpp; what changes is where the halo values come from and how the 256 interface
+// equations of the Wang partition are solved.
 //
 // Row distribution: thread g = 64*wave + lane of the workgroup owns the R consecutive rows
 // [g*R, g*R + R), N <= 256*R.  Neighbour values travel through LDS arrays indexed by g with two
@@ -37,42 +39,6 @@ __device__ __forceinline__ void wide_init(WideLds& s, int tid)
     __syncthreads();
 }
 
-// u of the row below this thread's first row and above its last row (0 outside the mesh)
-template <int R>
-__device__ __forceinline__ void wide_halo_u(WideLds& s, int g, const double (&u)[R], double& uL, double& uR)
-{
-    s.ufirst[g + WIDE_PAD] = u[0];
-    s.ulast[g + WIDE_PAD] = u[R - 1];
-    __syncthreads();
-    uL = s.ulast[g + WIDE_PAD - 1];
-    uR = s.ufirst[g + WIDE_PAD + 1];
-}
-
-template <int R>
-__device__ __forceinline__ void wide_mass_rhs(WideLds& s, int g, const ElemGeom<R>& gm, int N, const double (&u)[R],
-                                              const double (&fdt)[R], double (&gv)[R])
-{
-    double uL, uR;
-    wide_halo_u<R>(s, g, u, uL, uR);
-    mass_rhs_general_core<R>(gm, N, g * R, u, uL, uR, fdt, gv);
-    __syncthreads();              // the assembly that follows refills ufirst/ulast
-}
-
-template <int R>
-__device__ __forceinline__ void wide_assemble(WideLds& s, int g, const ElemGeom<R>& gm, double dt, double kap, int N,
-                                              double mu1, const double (&u)[R], const double (&gv)[R],
-                                              const double (&hfs)[R], double (&lo)[R], double (&di)[R],
-                                              double (&up)[R], double (&rhs)[R])
-{
-    double uL, uR, se[R];
-    wide_halo_u<R>(s, g, u, uL, uR);
-    assemble_general_p1<R>(gm, dt, u, uL, uR, hfs, lo, up, se);
-    s.se[g + WIDE_PAD] = se[R - 1];
-    __syncthreads();
-    const double seL = s.se[g + WIDE_PAD - 1];
-    assemble_general_p2<R>(gm, dt, kap, N, g * R, g == 0, mu1, u, uL, uR, seL, gv, se, lo, di, up, rhs);
-}
-
 // Parked rows: at 32 rows per thread the per-row constants of a whole time step, g = M u^n + dt F and hfs, no longer fit
 // the register file beside the solver's working set (404 bytes of scratch per thread).  The uniform-mesh N > 6144 kernel
 // keeps them in LDS instead, row-major over threads (park[j][g]: consecutive threads, consecutive addresses) and reads
@@ -82,57 +48,6 @@ struct WidePark {
     double g[R][WIDE_THREADS];
     double hfs[R][WIDE_THREADS];
 };
-
-template <int R>
-__device__ __forceinline__ void wide_mass_rhs_uni_parked(WideLds& s, WidePark<R>& pk, int g, const MeshConst& c, int N,
-                                                         const double (&u)[R], const double (&fdt)[R])
-{
-    double uL, uR;
-    wide_halo_u<R>(s, g, u, uL, uR);
-    mass_rhs_core_to<R, false>(c, N, g * R, u, uL, uR, fdt, [&](int j, double v) { pk.g[j][g] = v; });
-    __syncthreads();
-}
-
-template <int R>
-__device__ __forceinline__ void wide_assemble_uni_parked(WideLds& s, const WidePark<R>& pk, int g, const MeshConst& c, int N,
-                                                         double mu1, const double (&u)[R], double (&lo)[R], double (&di)[R],
-                                                         double (&up)[R], double (&rhs)[R])
-{
-    double uL, uR, se[R];
-    wide_halo_u<R>(s, g, u, uL, uR);
-    assemble_p1_from<R>(c, u, uL, uR, [&](int j) { return pk.hfs[j][g]; }, lo, up, se);
-    s.se[g + WIDE_PAD] = se[R - 1];
-    __syncthreads();
-    const double seL = s.se[g + WIDE_PAD - 1];
-    assemble_p2_from<R, false>(c, N, g * R, g == 0, false, mu1, u, uL, uR, seL, [&](int j) { return pk.g[j][g]; }, se, lo,
-                               di, up, rhs);
-}
-
-// uniform-mesh variants (one element length: no per-element registers, fewer instructions)
-template <int R>
-__device__ __forceinline__ void wide_mass_rhs_uni(WideLds& s, int g, const MeshConst& c, int N, const double (&u)[R],
-                                                  const double (&fdt)[R], double (&gv)[R])
-{
-    double uL, uR;
-    wide_halo_u<R>(s, g, u, uL, uR);
-    mass_rhs_core<R, false>(c, N, g * R, u, uL, uR, fdt, gv);
-    __syncthreads();
-}
-
-template <int R>
-__device__ __forceinline__ void wide_assemble_uni(WideLds& s, int g, const MeshConst& c, int N, double mu1,
-                                                  const double (&u)[R], const double (&gv)[R],
-                                                  const double (&hfs)[R], double (&lo)[R], double (&di)[R],
-                                                  double (&up)[R], double (&rhs)[R])
-{
-    double uL, uR, se[R];
-    wide_halo_u<R>(s, g, u, uL, uR);
-    assemble_p1<R>(c, u, uL, uR, hfs, lo, up, se);
-    s.se[g + WIDE_PAD] = se[R - 1];
-    __syncthreads();
-    const double seL = s.se[g + WIDE_PAD - 1];
-    assemble_p2<R, false>(c, N, g * R, g == 0, false, mu1, u, uL, uR, seL, gv, se, lo, di, up, rhs);
-}
 
 // One PCR step of stride S on equation e, neighbours from the LDS copy `buf` of all equations.
 template <int S>
@@ -191,5 +106,96 @@ __device__ __forceinline__ void wide_sum2(WideLds& s, int g, double a, double b,
     sa = (s.nrm[0][0] + s.nrm[0][1]) + (s.nrm[0][2] + s.nrm[0][3]);
     sb = (s.nrm[1][0] + s.nrm[1][1]) + (s.nrm[1][2] + s.nrm[1][3]);
 }
+
+__device__ __forceinline__ double wave_max(double v)
+{
+    v = fmax(v, dpp_mov<0x111>(v));
+    v = fmax(v, dpp_mov<0x112>(v));
+    v = fmax(v, dpp_mov<0x114>(v));
+    v = fmax(v, dpp_mov<0x118>(v));
+    v = fmax(v, dpp_mov<0x142, 0xA>(v));
+    v = fmax(v, dpp_mov<0x143, 0xC>(v));
+    int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
+    int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+    return __hiloint2double(hi, lo);
+}
+
+// ---- the topology of a sample: what the FEM bodies (fom.hip) and the FD body (fd.hip) are written over ----
+// Thread g of the sample's threads owns the rows [g*R, g*R + R).  Where neighbour values, sums, maxima and the
+// tridiagonal solve come from: one wavefront per sample (DPP inside the wave, no barrier anywhere) or one 256-thread
+// workgroup per sample (LDS across its four waves).  Values from outside the sample's threads are 0.
+//   halo        uL / uR = `last` of thread g-1 / `first` of thread g+1, one exchange.  The workgroup form needs
+//               halo_done() before the next halo() (it refills ufirst / ulast); the wave form's is empty.
+//   below_se    v of thread g-1 through WideLds::se: once per Picard iteration, the solve's barriers lie between two uses
+//   below, above, gmax   the FD stepper's exchanges: alternating buffers, so one barrier each in any sequence
+struct WaveTopo {
+    int g;                                           // = lane
+    __device__ __forceinline__ bool first() const { return g == 0; }        // owns global row 0
+    __device__ __forceinline__ bool last() const { return g == 63; }        // owns the last row when N = 64 R (FULL)
+    __device__ __forceinline__ void halo(double first, double last, double& uL, double& uR)
+    {
+        uL = from_lane_below(last);
+        uR = from_lane_above(first);
+    }
+    __device__ __forceinline__ void halo_done() {}
+    __device__ __forceinline__ double below_se(double v) { return from_lane_below(v); }
+    __device__ __forceinline__ double below(double v) { return from_lane_below(v); }
+    __device__ __forceinline__ double above(double v) { return from_lane_above(v); }
+    __device__ __forceinline__ double gmax(double v) { return wave_max(v); }
+    __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wave_sum2(a, b, sa, sb); }
+    template <int R>
+    __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
+    {
+        tridiag_solve<R>(lo, di, up, rhs);
+    }
+};
+
+struct WgTopo {
+    WideLds& s;
+    int g;                                           // = threadIdx.x
+    int par;                                         // alternating exchange buffers: one barrier per exchange
+    __device__ __forceinline__ bool first() const { return g == 0; }
+    __device__ __forceinline__ bool last() const { return g == WIDE_THREADS - 1; }
+    __device__ __forceinline__ void halo(double first, double last, double& uL, double& uR)
+    {
+        s.ufirst[g + WIDE_PAD] = first;
+        s.ulast[g + WIDE_PAD] = last;
+        __syncthreads();
+        uL = s.ulast[g + WIDE_PAD - 1];
+        uR = s.ufirst[g + WIDE_PAD + 1];
+    }
+    __device__ __forceinline__ void halo_done() { __syncthreads(); }
+    __device__ __forceinline__ double below_se(double v)
+    {
+        s.se[g + WIDE_PAD] = v;
+        __syncthreads();
+        return s.se[g + WIDE_PAD - 1];
+    }
+    __device__ __forceinline__ double shift(double v, int d)
+    {
+        double* buf = par ? s.ulast : s.ufirst;
+        par ^= 1;
+        buf[g + WIDE_PAD] = v;
+        __syncthreads();
+        return buf[g + WIDE_PAD + d];
+    }
+    __device__ __forceinline__ double below(double v) { return shift(v, -1); }
+    __device__ __forceinline__ double above(double v) { return shift(v, +1); }
+    __device__ __forceinline__ double gmax(double v)
+    {
+        v = wave_max(v);
+        double* buf = s.nrm[par];
+        par ^= 1;
+        if ((g & 63) == 0) buf[g >> 6] = v;
+        __syncthreads();
+        return fmax(fmax(buf[0], buf[1]), fmax(buf[2], buf[3]));
+    }
+    __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wide_sum2(s, g, a, b, sa, sb); }
+    template <int R>
+    __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
+    {
+        wide_tridiag_solve<R>(s, g, lo, di, up, rhs);
+    }
+};
 
 }  // namespace bg

@@ -18,7 +18,7 @@ from oracle import burgers_ref as br
 from oracle import burgers_ref_c as bc
 
 TAU = 2.0 ** -31
-ROWS_PER_LANE = (1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 16, 24)       # kRowsPerLane of csrc/fom.hip
+ROWS_PER_LANE = (1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 16, 24)       # dispatch_r of csrc/fom.hip
 SIZES = (64, 100, 128, 1000, 1024, 1536)                       # one wavefront per system
 WIDE_SIZES = (2048, 4096)                                      # one workgroup per system
 FAMILIES = ("dominant", "skew", "half")
