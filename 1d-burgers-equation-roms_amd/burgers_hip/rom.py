@@ -134,19 +134,23 @@ def rom_reduce(c, W, U, G, proj, supg, active, Ar, br, wtu=None, colmajor=False,
     stride = 0 if W.dim() == 2 else c.N * r
     opts = (1 if supg else 0) | c.mesh_opt | (_lib.BG_OPT_W_COLMAJOR if colmajor else 0) | extra_opts
     if w_index is not None:
-        with torch.cuda.device(c.device):
-            rc = c.L.bg_rom_reduce_indexed(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(W), stride, _lib.ptr(w_index),
-                                           _lib.ptr(U), _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E, opts,
-                                           _lib.ptr(active), _lib.ptr(Ar), _lib.ptr(br), _lib.ptr(wtu), c.stream())
-        _lib.check(rc, "bg_rom_reduce_indexed")
-        return
+        _reduce_call(c, "bg_rom_reduce_indexed", r, proj, (_lib.ptr(W), stride, _lib.ptr(w_index), _lib.ptr(U)), G, opts,
+                     active, Ar, br, wtu)
+    else:
+        _reduce_call(c, "bg_rom_reduce", r, proj, (_lib.ptr(W), stride, _lib.ptr(U)), G, opts, active, Ar, br, wtu,
+                     r_limit=True)
+
+
+def _reduce_call(c, entry, r, proj, mid, G, opts, active, Ar, br, wtu, r_limit=False):
+    """One checked call of a bg_rom_reduce* entry point.  ``mid``: what its signature has between x and G (the basis or
+    tangent with its stride or index, and u or q).  ``r_limit``: BG_ERR_UNSUPPORTED_R raises the NotImplementedError that
+    names the kernels' limit on r."""
     with torch.cuda.device(c.device):
-        rc = c.L.bg_rom_reduce(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(W), stride, _lib.ptr(U), _lib.ptr(G),
-                               _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E, opts,
-                               _lib.ptr(active), _lib.ptr(Ar), _lib.ptr(br), _lib.ptr(wtu), c.stream())
-    if rc == _lib.BG_ERR_UNSUPPORTED_R:
+        rc = getattr(c.L, entry)(c.N, c.B, r, proj, _lib.ptr(c.X), *mid, _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1),
+                                 c.dt, c.E, opts, _lib.ptr(active), _lib.ptr(Ar), _lib.ptr(br), _lib.ptr(wtu), c.stream())
+    if r_limit and rc == _lib.BG_ERR_UNSUPPORTED_R:
         raise NotImplementedError(f"ROM kernels cover r <= {c.L.bg_rom_max_r()} (got {r})")
-    _lib.check(rc, "bg_rom_reduce")
+    _lib.check(rc, entry)
 
 
 def _rom_reduce_library(c, W, U, proj, supg, active, Ar, br, wtu):
@@ -188,15 +192,8 @@ def lu_solve(A, b, sign=1.0, active=None, x=None, info=None):
 
 def rom_reduce_lifted(c, Phi, q, U, G, proj, supg, active, Ar, br, wtu, extra_opts=0):
     """bg_rom_reduce with u = Phi q formed in-kernel (and stored to U)."""
-    r = Phi.shape[1]
-    with torch.cuda.device(c.device):
-        rc = c.L.bg_rom_reduce_lifted(c.N, c.B, r, proj, _lib.ptr(c.X), _lib.ptr(Phi), _lib.ptr(q), _lib.ptr(U),
-                                      _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E,
-                                      (1 if supg else 0) | c.mesh_opt | extra_opts, _lib.ptr(active), _lib.ptr(Ar),
-                                      _lib.ptr(br), _lib.ptr(wtu), c.stream())
-    if rc == _lib.BG_ERR_UNSUPPORTED_R:
-        raise NotImplementedError(f"ROM kernels cover r <= {c.L.bg_rom_max_r()} (got {r})")
-    _lib.check(rc, "bg_rom_reduce_lifted")
+    _reduce_call(c, "bg_rom_reduce_lifted", Phi.shape[1], proj, (_lib.ptr(Phi), _lib.ptr(q), _lib.ptr(U)), G,
+                 (1 if supg else 0) | c.mesh_opt | extra_opts, active, Ar, br, wtu, r_limit=True)
 
 
 def rom_lift(c, Phi, q, U, active=None):
@@ -979,10 +976,7 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
                 with torch.cuda.device(c.device):
                     _lib.check(c.L.bg_quad_tangent(c.N, c.B, n, _lib.ptr(Phid), _lib.ptr(H3p), _lib.ptr(qpad if NP != n else q),
                                                    _lib.ptr(st.active), _lib.ptr(Wf), c.stream()), "bg_quad_tangent")
-                    _lib.check(c.L.bg_rom_reduce_frag(c.N, c.B, n, proj, _lib.ptr(c.X), _lib.ptr(Wf), _lib.ptr(u),
-                                                      _lib.ptr(G), _lib.ptr(c.hfs), _lib.ptr(c.mu1), c.dt, c.E, c.mesh_opt,
-                                                      _lib.ptr(st.active), _lib.ptr(Ar), _lib.ptr(br), None, c.stream()),
-                               "bg_rom_reduce_frag")
+                _reduce_call(c, "bg_rom_reduce_frag", n, proj, (_lib.ptr(Wf), _lib.ptr(u)), G, c.mesh_opt, st.active, Ar, br, None)
             else:                                            # sizes beyond the fused kernels: library GEMM
                 T = torch.addmm(Phi_flat, q, H3t).reshape(c.B, c.N, n)
                 rom_reduce(c, T, u, G, proj, False, st.active, Ar, br, None)

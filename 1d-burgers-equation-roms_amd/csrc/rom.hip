@@ -4,8 +4,9 @@
 // (FEM/fem_burgers.py: pod_prom_burgers :709-785, pod_quadratic_manifold :1081-1175,
 // pod_ann_prom :1177-1251) is, per sample,
 //     assemble A(u), R(u)            -> fused into bg_rom_reduce (same arithmetic as the FOM)
-//     Ar = W^T A W | (A W)^T (A W)   -> bg_rom_reduce, fp64 MFMA 16x16x4, W = basis / tangent
-//     br = W^T R   | (A W)^T R       -> same kernel (extra B-operand column)
+//     Ar = W^T A W | (A W)^T (A W)   -> bg_rom_reduce, W = basis / tangent: one kernel frame over two fp64 MFMA shapes,
+//                                       4x4x4_4b for r <= 40 (Block4) and 16x16x4 for 41 <= r <= 47 (Tile16)
+//     br = W^T R   | (A W)^T R       -> same kernel (extra B-operand block / column)
 //     dq = solve(Ar, -br)            -> bg_lu_solve (partial pivoting, one wavefront per system)
 // The decode / tangent steps that differ between the three ROM families are plain dense
 // contractions over the whole batch and live on the host side (burgers_hip/rom.py).
@@ -61,13 +62,8 @@ __global__ __launch_bounds__(256) void mass_rhs_kernel(const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------
-// bg_rom_reduce: fused assembly + projection.
-//   workgroup = 4 wavefronts; wave w, lane (g = lane>>4, c = lane&15) owns the mesh rows
-//   i = (4w + g)*S + s, s = 0..S-1 as the K index of v_mfma_f64_16x16x4_f64 (k = g), so the
-//   rows i-1, i, i+1 needed by the tridiagonal apply Y = A W sit in the SAME lane's adjacent
-//   fragment registers.  Fragment t of step s holds W[i][16 t + c].  With a shared basis
-//   (w_stride == 0) the fragments are loaded once per workgroup and stay in registers
-//   while the workgroup walks over its samples.
+// bg_rom_reduce and its siblings: what one launch of the reduce kernel works on.  Each entry point names the fields it
+// has; the rest stay null / 0.
 // ------------------------------------------------------------------------------------
 struct ReduceArgs {
     const double* x;
@@ -84,175 +80,105 @@ struct ReduceArgs {
     const double* q_in;      // [B][r] or null: if given, u = W q is formed here and stored to Uout
     double* Uout;            // [B][N] (only with q_in)
     double dt, E;
-    int N, B, r, proj, supg, lift_only, nonuniform;
-    int w_frag;              // 1: W is in the fragment-major layout of bg_quad_tangent (rom_reduce4 only)
+    int N, B, r;
+    int supg;                // supg, nonuniform, w_colmajor: filled by reduce_launch from the options word
+    int lift_only, nonuniform;
+    int w_frag;              // 1: W is in the fragment-major layout of bg_quad_tangent (Block4 only)
     int w_colmajor;          // 1: W is [r][N] per sample (BG_OPT_W_COLMAJOR)
     const int32_t* w_index;  // [B] or null: sample b uses block w_index[b] of W (blocks w_stride apart)
 };
 
-template <int S, int NT, int PROJ>
-__global__ __launch_bounds__(256, 1) void rom_reduce_kernel(ReduceArgs a)
-{
-    constexpr int NPAD = 16 * S;
-    constexpr int RP = 16 * NT;             // padded reduced dimension
-    __shared__ double s_u[NPAD + 2];        // u with one halo entry on each side
-    __shared__ double s_coef[NPAD][4];      // lo, di, up, rhs(= -R) per row
-    __shared__ double s_red[4][RP][RP + 1]; // per-wave partial Ar | br
-    __shared__ double s_q[4][4][RP];        // per-wave, per-group partial W^T u
+template <int V>
+using ic = std::integral_constant<int, V>;
 
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int N = a.N, r = a.r;
-    const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
-    const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-    const int rowbase = (4 * w + g) * S;
+// ------------------------------------------------------------------------------------
+// The two MFMA shapes of the reduce kernel.  A shape says which mesh rows and which columns of W a lane holds, how a row's
+// partial products are summed over its lanes, and -- in Contract<PROJ, WTU> -- how one row step is contracted, where the
+// accumulators are parked in LDS for the sum over the four waves, and where br and W^T u are found there afterwards.
+// A shape object is one lane's coordinates, computed once at kernel entry: recomputing them from `lane` where they are used
+// costs the Block4 kernels registers and a split LDS read (profiles/reduce_shapes_isa.md).
+//
+// Tile16<S, NT>: v_mfma_f64_16x16x4_f64.  Wave w, lane (g = lane>>4, c = lane&15) owns the mesh rows (4w + g) S + s,
+//   s = 0..S-1, as the K index (k = g); fragment t holds W[row][16 t + c].  R rides in column r of the B operand (the
+//   padded width 16 NT covers r + 1 columns), W^T u is accumulated on the VALU.
+// ------------------------------------------------------------------------------------
+template <int S_, int NT>
+struct Tile16 {
+    static constexpr int S = S_, NF = NT, ROWS = 16 * S, RW = 16 * NT, MIRROR_SHIFT = 4;
+    static constexpr bool FRAG_MAJOR = false;
+    using Red = double[4][RW][RW + 1];      // per-wave partial Ar | br
+    using Wtu = double[4][4][RW];           // per-wave, per-group partial W^T u
 
-    double frag[NT][S + 2];                 // W[rowbase + s - 1][16 t + c], s = 0..S+1
-    bool have_frags = false;
-    int last_block = -1;
+    const int g, c, rowbase;
+    __device__ __forceinline__ Tile16(int w, int lane) : g(lane >> 4), c(lane & 15), rowbase((4 * w + g) * S) {}
+    __device__ __forceinline__ int col(int f) const { return 16 * f + c; }
+    __device__ __forceinline__ bool row_writer() const { return c == 15; }
+    static __device__ __forceinline__ int br_col(int r) { return r; }
+    static __device__ __forceinline__ double row_sum(double p)      // over the 16 lanes of the DPP row, into lane c == 15
+    {
+        p += dpp_mov<0x111>(p);
+        p += dpp_mov<0x112>(p);
+        p += dpp_mov<0x114>(p);
+        p += dpp_mov<0x118>(p);
+        return p;
+    }
 
-    for (int smp = blockIdx.x; smp < a.B; smp += gridDim.x) {
-        if (a.active && a.active[smp] == 0) continue;        // workgroup-uniform
-        // ---- basis / tangent fragments (kept across samples while the block of W stays the same) -------
-        const int wblock = a.w_stride == 0 ? 0 : (a.w_index ? a.w_index[smp] : smp);
-        if (!have_frags || wblock != last_block) {
-            last_block = wblock;
-            const double* Wp = a.W + (size_t)wblock * (size_t)a.w_stride;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = 16 * t + c;
-#pragma unroll
-                for (int s = 0; s < S + 2; ++s) {
-                    const int i = rowbase + s - 1;
-                    frag[t][s] = (i >= 0 && i < N && col < r)
-                                     ? (a.w_colmajor ? Wp[(size_t)col * N + i] : Wp[(size_t)i * r + col]) : 0.0;
-                }
-            }
-            have_frags = true;
-        }
-        // ---- stage u (from HBM, or lifted u = W q from the register-resident basis) ----------
-        if (a.q_in) {
-            double qv[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = 16 * t + c;
-                qv[t] = col < r ? a.q_in[(size_t)smp * r + col] : 0.0;
-            }
-            if (tid == 0) { s_u[0] = 0.0; s_u[NPAD + 1] = 0.0; }
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                double p = 0.0;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) p = __builtin_fma(frag[t][s + 1], qv[t], p);
-                p += dpp_mov<0x111>(p);            // sum over the 16 lanes of the DPP row
-                p += dpp_mov<0x112>(p);
-                p += dpp_mov<0x114>(p);
-                p += dpp_mov<0x118>(p);
-                if (c == 15) {
-                    const int i = rowbase + s;
-                    s_u[i + 1] = p;
-                    if (i < N) a.Uout[(size_t)smp * N + i] = p;
-                }
-            }
-        } else {
-            const double* up_ = a.U + (size_t)smp * N;
-            for (int i = tid; i < NPAD + 2; i += 256) {
-                const int gi = i - 1;
-                s_u[i] = (gi >= 0 && gi < N) ? up_[gi] : 0.0;
-            }
-        }
-        __syncthreads();
-        if (a.lift_only) continue;           // workgroup-uniform
-        const double mu1 = a.mu1[smp];
-        for (int i = tid; i < NPAD; i += 256) {
-            double lo, di, up, R;
-            const bool in = i < N;
-            rom_assemble_row(i, N, s_u[i], s_u[i + 1], s_u[i + 2], in ? a.G[(size_t)smp * N + i] : 0.0,
-                             (in && i > 0) ? a.hfs[(size_t)smp * N + i - 1] : 0.0,
-                             (in && i < N - 1) ? a.hfs[(size_t)smp * N + i] : 0.0, mu1, mc, a.nonuniform, a.x, a.dt, a.E,
-                             lo, di, up, R);
-            s_coef[i][0] = lo; s_coef[i][1] = di; s_coef[i][2] = up; s_coef[i][3] = R;
-        }
-        __syncthreads();
-        // ---- MFMA contraction over this wave's rows -------------------------------------------
-        f64x4 acc[NT][NT];
-#pragma unroll
-        for (int ta = 0; ta < NT; ++ta)
-#pragma unroll
-            for (int tb = 0; tb < NT; ++tb) acc[ta][tb] = f64x4{0.0, 0.0, 0.0, 0.0};
-        double qp[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) qp[t] = 0.0;
-        const bool rcol_lane = (c == r - 16 * (NT - 1));      // lane that carries column r (= R)
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int i = rowbase + s;
-            const double lo = s_coef[i][0], di = s_coef[i][1], up = s_coef[i][2], R = s_coef[i][3];
-            const double ui = s_u[i + 1];
-            double Y[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                double y = lo * frag[t][s];
-                y = __builtin_fma(di, frag[t][s + 1], y);
-                y = __builtin_fma(up, frag[t][s + 2], y);
-                Y[t] = y;
-                qp[t] = __builtin_fma(frag[t][s + 1], ui, qp[t]);
-            }
+    template <int PROJ, bool WTU>
+    struct Contract {
+        struct Acc {
+            f64x4 t[NT][NT];
+            double qp[NT];
+        };
+        static __device__ __forceinline__ void step(Acc& acc, const double (&frag)[NT][S + 2], int s, const double (&Y)[NT],
+                                                    double R, double ui, const Tile16& sh, int r)
+        {
             double Bf[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) Bf[t] = Y[t];
-            Bf[NT - 1] = rcol_lane ? R : Bf[NT - 1];
+            for (int t = 0; t < NT; ++t) {
+                Bf[t] = Y[t];
+                acc.qp[t] = __builtin_fma(frag[t][s + 1], ui, acc.qp[t]);
+            }
+            Bf[NT - 1] = (sh.c == r - 16 * (NT - 1)) ? R : Bf[NT - 1];      // the lane that carries column r
             if constexpr (PROJ == BG_PROJ_GALERKIN) {
 #pragma unroll
                 for (int ta = 0; ta < NT; ++ta)
 #pragma unroll
                     for (int tb = 0; tb < NT; ++tb)
-                        acc[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(frag[ta][s + 1], Bf[tb], acc[ta][tb], 0, 0, 0);
+                        acc.t[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(frag[ta][s + 1], Bf[tb], acc.t[ta][tb], 0, 0, 0);
             } else {
 #pragma unroll
                 for (int ta = 0; ta < NT; ++ta)
 #pragma unroll
                     for (int tb = ta; tb < NT; ++tb)
-                        acc[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Y[ta], Bf[tb], acc[ta][tb], 0, 0, 0);
+                        acc.t[ta][tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Y[ta], Bf[tb], acc.t[ta][tb], 0, 0, 0);
             }
         }
-        // ---- cross-wave reduction through LDS, then write Ar | br | W^T u ----------------------
+        static __device__ __forceinline__ void park(Red& s_red, Wtu& s_q, const Acc& acc, const Tile16& sh, int w, int)
+        {
+            const int g = sh.g, c = sh.c;
 #pragma unroll
-        for (int ta = 0; ta < NT; ++ta)
+            for (int ta = 0; ta < NT; ++ta)
 #pragma unroll
-            for (int tb = 0; tb < NT; ++tb)
+                for (int tb = 0; tb < NT; ++tb)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) s_red[w][16 * ta + g + 4 * k][16 * tb + c] = acc[ta][tb][k];
+                    for (int k = 0; k < 4; ++k) s_red[w][16 * ta + g + 4 * k][16 * tb + c] = acc.t[ta][tb][k];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) s_q[w][g][16 * t + c] = qp[t];
-        __syncthreads();
-        constexpr bool sym = PROJ != BG_PROJ_GALERKIN;
-        for (int e = tid; e < r * (r + 1); e += 256) {
-            const int row = e / (r + 1), col = e % (r + 1);
-            int rr = row, cc = col;
-            if (sym && col < r && (row >> 4) > (col >> 4)) { rr = col; cc = row; }   // mirror lower tiles
-            const double v = (s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc]);
-            if (col < r)
-                a.Ar[((size_t)smp * r + row) * r + col] = v;
-            else
-                a.br[(size_t)smp * r + row] = v;
+            for (int t = 0; t < NT; ++t) s_q[w][g][16 * t + c] = acc.qp[t];
         }
-        if (a.wtu) {
-            for (int j = tid; j < r; j += 256) {
-                double v = 0.0;
+        static __device__ __forceinline__ double wtu_sum(const Red&, const Wtu& s_q, int j)
+        {
+            double v = 0.0;
 #pragma unroll
-                for (int ww = 0; ww < 4; ++ww)
+            for (int ww = 0; ww < 4; ++ww)
 #pragma unroll
-                    for (int gg = 0; gg < 4; ++gg) v += s_q[ww][gg][j];
-                a.wtu[(size_t)smp * r + j] = v;
-            }
+                for (int gg = 0; gg < 4; ++gg) v += s_q[ww][gg][j];
+            return v;
         }
-        __syncthreads();
-    }
-}
+    };
+};
 
 // ------------------------------------------------------------------------------------
-// rom_reduce4_kernel: the same fused assembly + projection on v_mfma_f64_4x4x4_4b_f64.
+// Block4<S, NB>: v_mfma_f64_4x4x4_4b_f64, the product path (r <= 40 and every fragment-major call).
 //   Measured on gfx950 (tools/mfma_bench.hip): the 4-block 4x4x4 form issues every ~16 cycles
 //   (512 flop) = 31 flop/clk/SIMD, twice the rate of the 16x16x4 form (128 cycles, 2048 flop),
 //   and its 4-wide blocks waste no padding at r = 40.  Lane map found with one-hot operands
@@ -265,18 +191,131 @@ __global__ __launch_bounds__(256, 1) void rom_reduce_kernel(ReduceArgs a)
 //   B block [R, u, 0, 0] yields br and W^T u.  The four block partials of every pair are summed at
 //   the end with two DPP row shifts, the four waves through LDS.
 // ------------------------------------------------------------------------------------
-template <int NB, int PROJ, bool WTU>
-struct Pairs4 {
-    static constexpr int main_pairs = (PROJ == BG_PROJ_GALERKIN) ? NB * (NB + 1) : NB * (NB + 1) / 2 + NB;
-    static constexpr int total = main_pairs + ((PROJ != BG_PROJ_GALERKIN && WTU) ? NB : 0);
+template <int S_, int NB>
+struct Block4 {
+    static constexpr int S = S_, NF = NB, ROWS = 64 * S, RW = 4 * NB, MIRROR_SHIFT = 2;
+    static constexpr bool FRAG_MAJOR = true;
+    using Red = double[5][RW][RW + 4];      // per-wave  Ar | [br, W^T u (Galerkin), 0, 0]; [4] = dump for idle lanes
+    using Wtu = double[5][RW];              // per-wave  W^T u (LSPG); [4] = dump
+
+    const int t, owner, rowbase;
+    __device__ __forceinline__ Block4(int w, int lane) : t(lane & 3), owner(16 * w + (lane >> 2)), rowbase(owner * S) {}
+    __device__ __forceinline__ int col(int f) const { return 4 * f + t; }
+    __device__ __forceinline__ bool row_writer() const { return t == 0; }
+    static __device__ __forceinline__ int br_col(int) { return RW; }
+    static __device__ __forceinline__ double row_sum(double p)      // over the four t lanes, into all of them
+    {
+        p += dpp_mov<0xB1>(p);             // quad_perm [1,0,3,2]
+        p += dpp_mov<0x4E>(p);             // quad_perm [2,3,0,1]
+        return p;
+    }
+    // fragment-major: element (row o*S + s, col 4c + t) at ((c*S + s)*64 + o)*4 + t:
+    // every (c, s) is one coalesced 2 KB read for the workgroup; halos come from owners o -+ 1
+    __device__ __forceinline__ void load_frag_major(double (&frag)[NB][S + 2], const double* Wp, int N) const
+    {
+#pragma unroll
+        for (int c = 0; c < NB; ++c) {
+#pragma unroll
+            for (int s = 0; s < S + 2; ++s) {
+                const int i = rowbase + s - 1;
+                const int o = (s == 0) ? owner - 1 : ((s == S + 1) ? owner + 1 : owner);
+                const int ss = (s == 0) ? S - 1 : ((s == S + 1) ? 0 : s - 1);
+                frag[c][s] = (i >= 0 && i < N) ? Wp[((size_t)(c * S + ss) * 64 + o) * 4 + t] : 0.0;
+            }
+        }
+    }
+
+    template <int PROJ, bool WTU>
+    struct Contract {
+        static constexpr bool GAL = PROJ == BG_PROJ_GALERKIN;
+        static constexpr int NPAIR = (GAL ? NB * (NB + 1) : NB * (NB + 1) / 2 + NB) + ((!GAL && WTU) ? NB : 0);
+        struct Acc {
+            double p[NPAIR];
+        };
+        static __device__ __forceinline__ void step(Acc& acc, const double (&frag)[NB][S + 2], int s, const double (&Y)[NB],
+                                                    double R, double ui, const Block4& sh, int)
+        {
+            const double X = (sh.t == 0) ? R : ((sh.t == 1) ? ui : 0.0);      // extra B block [R, u, 0, 0]
+            int p = 0;
+            if constexpr (GAL) {
+#pragma unroll
+                for (int ca = 0; ca < NB; ++ca) {
+#pragma unroll
+                    for (int cb = 0; cb < NB; ++cb, ++p)
+                        acc.p[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], Y[cb], acc.p[p], 0, 0, 0);
+                    acc.p[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], X, acc.p[p], 0, 0, 0);
+                    ++p;
+                }
+            } else {
+#pragma unroll
+                for (int ca = 0; ca < NB; ++ca) {
+#pragma unroll
+                    for (int cb = ca; cb < NB; ++cb, ++p)
+                        acc.p[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(Y[ca], Y[cb], acc.p[p], 0, 0, 0);
+                    acc.p[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(Y[ca], X, acc.p[p], 0, 0, 0);
+                    ++p;
+                }
+                if constexpr (WTU) {
+#pragma unroll
+                    for (int ca = 0; ca < NB; ++ca, ++p)
+                        acc.p[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], X, acc.p[p], 0, 0, 0);
+                }
+            }
+            // Galerkin (110 accumulators): nothing moves across a row step -- otherwise the scheduler hoists later steps' operand
+            // loads and the register allocator answers with more scratch reloads inside the MFMA loop (412 -> 292 bytes per
+            // lane, 290 -> 266 us per 4096 samples; the LSPG forms are 3 % faster without it)
+            if constexpr (GAL) __builtin_amdgcn_sched_barrier(0);
+        }
+        // sum the four block partials of every pair (lanes differing in bits 2..3), then park them
+        static __device__ __forceinline__ void park(Red& s_red, Wtu& s_wtu, const Acc& acc, const Block4&, int w, int lane)
+        {
+            const int oi = lane >> 4, oj = lane & 3;
+            const bool writer = ((lane >> 2) & 3) == 3;
+            const int wslot = writer ? w : 4;            // idle lanes store into the dump slab: no branches
+            int p = 0;
+#pragma unroll
+            for (int ca = 0; ca < NB; ++ca) {
+#pragma unroll
+                for (int cb = (GAL ? 0 : ca); cb <= NB; ++cb, ++p) {
+                    double v = acc.p[p];
+                    v += dpp_mov<0x114>(v);          // row_shr:4
+                    v += dpp_mov<0x118>(v);          // row_shr:8 -> lanes with blk == 3 hold the sum
+                    s_red[wslot][4 * ca + oi][4 * cb + oj] = v;
+                }
+            }
+            if constexpr (!GAL && WTU) {
+#pragma unroll
+                for (int ca = 0; ca < NB; ++ca, ++p) {
+                    double v = acc.p[p];
+                    v += dpp_mov<0x114>(v);
+                    v += dpp_mov<0x118>(v);
+                    s_wtu[(writer && oj == 1) ? w : 4][4 * ca + oi] = v;
+                }
+            }
+        }
+        static __device__ __forceinline__ double wtu_sum(const Red& s_red, const Wtu& s_wtu, int j)
+        {
+            if constexpr (GAL)
+                return (s_red[0][j][RW + 1] + s_red[1][j][RW + 1]) + (s_red[2][j][RW + 1] + s_red[3][j][RW + 1]);
+            else if constexpr (WTU)
+                return (s_wtu[0][j] + s_wtu[1][j]) + (s_wtu[2][j] + s_wtu[3][j]);
+            else
+                return 0.0;
+        }
+    };
 };
 
-template <int S, int NB, int PROJ, bool WTU>
-__global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
+// ------------------------------------------------------------------------------------
+// bg_rom_reduce: fused assembly + projection, one frame for both shapes.
+//   workgroup = 4 wavefronts.  Every lane keeps the rows i-1, i, i+1 needed by the tridiagonal apply Y = A W in
+//   adjacent fragment registers (frag[f][s] = W[rowbase + s - 1][col(f)]).  While the block of W stays the same
+//   (always, with a shared basis) the fragments stay in registers as the workgroup walks over its samples.
+// ------------------------------------------------------------------------------------
+template <class Shape, int PROJ, bool WTU>
+__global__ __launch_bounds__(256, 1) void rom_reduce_kernel(ReduceArgs a)
 {
-    constexpr int NPAD = 64 * S;
-    constexpr int NPAIR = Pairs4<NB, PROJ, WTU>::total;
-    constexpr int RW = 4 * NB;                   // padded reduced dimension
+    using C = typename Shape::template Contract<PROJ, WTU>;
+    constexpr int S = Shape::S, NF = Shape::NF, NPAD = Shape::ROWS, RW = Shape::RW;
     constexpr bool GAL = PROJ == BG_PROJ_GALERKIN;
     // u, G, hfs of the current sample; double-buffered so that the NEXT sample's rows can stream in
     // with global_load_lds (no VGPRs, no wait) while this sample's MFMAs run.  u sits at offset 2
@@ -285,18 +324,18 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
     __shared__ __attribute__((aligned(16))) double s_g[2][NPAD];
     __shared__ __attribute__((aligned(16))) double s_h[2][NPAD];
     __shared__ __attribute__((aligned(16))) double s_qp[2][RW + 24];   // prefetched q (lifted mode), dword DMA
-    __shared__ double s_coef[NPAD][4];
-    __shared__ double s_red[5][RW][RW + 4];      // per-wave  Ar | [br, W^T u (Galerkin), 0, 0]; [4] = dump for idle lanes
-    __shared__ double s_wtu[5][RW];              // per-wave  W^T u (LSPG); [4] = dump
+    __shared__ double s_coef[NPAD][4];           // lo, di, up, rhs(= -R) per row
+    __shared__ typename Shape::Red s_red;
+    __shared__ typename Shape::Wtu s_wtu;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int t = lane & 3, owner = 16 * w + (lane >> 2);
     const int N = a.N, r = a.r;
     const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
     const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-    const int rowbase = owner * S;
+    const Shape sh(w, lane);
+    const int rowbase = sh.rowbase;
 
-    double frag[NB][S + 2];                      // W[rowbase + s - 1][4 c + t]
+    double frag[NF][S + 2];
     bool have_frags = false;
 
     for (int i = tid; i < 2 * (NPAD + 4); i += 256) (&s_u[0][0])[i] = 0.0;   // halos and padded rows stay finite
@@ -337,27 +376,16 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
         if (!have_frags || wblock != last_block) {     // fragments stay in registers while the block of W stays the same
             last_block = wblock;
             const double* Wp = a.W + (size_t)wblock * (size_t)a.w_stride;
-            if (a.w_frag) {
-                // fragment-major: element (row o*S + s, col 4c + t) at ((c*S + s)*64 + o)*4 + t:
-                // every (c, s) is one coalesced 2 KB read for the workgroup; halos come from owners o -+ 1
-#pragma unroll
-                for (int c = 0; c < NB; ++c) {
-#pragma unroll
-                    for (int s = 0; s < S + 2; ++s) {
-                        const int i = rowbase + s - 1;
-                        const int o = (s == 0) ? owner - 1 : ((s == S + 1) ? owner + 1 : owner);
-                        const int ss = (s == 0) ? S - 1 : ((s == S + 1) ? 0 : s - 1);
-                        frag[c][s] = (i >= 0 && i < N) ? Wp[((size_t)(c * S + ss) * 64 + o) * 4 + t] : 0.0;
-                    }
-                }
+            if (Shape::FRAG_MAJOR && a.w_frag) {
+                if constexpr (Shape::FRAG_MAJOR) sh.load_frag_major(frag, Wp, N);
             } else {
 #pragma unroll
-                for (int c = 0; c < NB; ++c) {
-                    const int col = 4 * c + t;
+                for (int f = 0; f < NF; ++f) {
+                    const int col = sh.col(f);
 #pragma unroll
                     for (int s = 0; s < S + 2; ++s) {
                         const int i = rowbase + s - 1;
-                        frag[c][s] = (i >= 0 && i < N && col < r)
+                        frag[f][s] = (i >= 0 && i < N && col < r)
                                          ? (a.w_colmajor ? Wp[(size_t)col * N + i] : Wp[(size_t)i * r + col]) : 0.0;
                     }
                 }
@@ -366,24 +394,23 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
         }
         // ---- stage u (from HBM, or lifted u = W q from the register-resident basis) ----------
         if (a.q_in) {
-            double qv[NB];
+            double qv[NF];
             if (pref) {                                          // q arrived by LDS DMA one sample ago
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
             }
 #pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                const int col = 4 * c + t;
-                qv[c] = col < r ? (pref ? s_qp[buf][col] : a.q_in[(size_t)smp * r + col]) : 0.0;
+            for (int f = 0; f < NF; ++f) {
+                const int col = sh.col(f);
+                qv[f] = col < r ? (pref ? s_qp[buf][col] : a.q_in[(size_t)smp * r + col]) : 0.0;
             }
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 double p = 0.0;
 #pragma unroll
-                for (int c = 0; c < NB; ++c) p = __builtin_fma(frag[c][s + 1], qv[c], p);
-                p += dpp_mov<0xB1>(p);             // quad_perm [1,0,3,2]: sum over the four t lanes
-                p += dpp_mov<0x4E>(p);             // quad_perm [2,3,0,1]
-                if (t == 0) {
+                for (int f = 0; f < NF; ++f) p = __builtin_fma(frag[f][s + 1], qv[f], p);
+                p = Shape::row_sum(p);
+                if (sh.row_writer()) {
                     const int i = rowbase + s;
                     s_u[buf][i + 2] = (i < N) ? p : 0.0;
                     if (i < N) a.Uout[(size_t)smp * N + i] = p;
@@ -396,7 +423,7 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this sample's LDS DMA has landed (every wave waits for its own)
         __syncthreads();
         if (a.lift_only) { smp = nxt; continue; }                // workgroup-uniform
-        // ---- assembly into LDS (same arithmetic as rom_reduce_kernel) -----------------------
+        // ---- assembly into LDS ------------------------------------------------------------------
         const double mu1 = a.mu1[smp];
         for (int i = tid; i < NPAD; i += 256) {
             double lo, di, up, R;
@@ -410,87 +437,32 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
         }
         __syncthreads();
         if (pref && nxt < a.B) prefetch(nxt, buf ^ 1);           // streams in under the MFMA phase
-        // ---- MFMA contraction: every step feeds 16 mesh rows per wave ---------------------------
-        double acc[NPAIR];
-#pragma unroll
-        for (int p = 0; p < NPAIR; ++p) acc[p] = 0.0;
+        // ---- MFMA contraction over this wave's rows ---------------------------------------------
+        typename C::Acc acc = {};
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const int i = rowbase + s;
             const double lo = s_coef[i][0], di = s_coef[i][1], up = s_coef[i][2], R = s_coef[i][3];
             const double ui = s_u[buf][i + 2];
-            double Y[NB];
+            double Y[NF];
 #pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                double y = lo * frag[c][s];
-                y = __builtin_fma(di, frag[c][s + 1], y);
-                y = __builtin_fma(up, frag[c][s + 2], y);
-                Y[c] = y;
+            for (int f = 0; f < NF; ++f) {
+                double y = lo * frag[f][s];
+                y = __builtin_fma(di, frag[f][s + 1], y);
+                y = __builtin_fma(up, frag[f][s + 2], y);
+                Y[f] = y;
             }
-            const double X = (t == 0) ? R : ((t == 1) ? ui : 0.0);      // extra B block [R, u, 0, 0]
-            int p = 0;
-            if constexpr (GAL) {
-#pragma unroll
-                for (int ca = 0; ca < NB; ++ca) {
-#pragma unroll
-                    for (int cb = 0; cb < NB; ++cb, ++p)
-                        acc[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], Y[cb], acc[p], 0, 0, 0);
-                    acc[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], X, acc[p], 0, 0, 0);
-                    ++p;
-                }
-            } else {
-#pragma unroll
-                for (int ca = 0; ca < NB; ++ca) {
-#pragma unroll
-                    for (int cb = ca; cb < NB; ++cb, ++p)
-                        acc[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(Y[ca], Y[cb], acc[p], 0, 0, 0);
-                    acc[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(Y[ca], X, acc[p], 0, 0, 0);
-                    ++p;
-                }
-                if constexpr (WTU) {
-#pragma unroll
-                    for (int ca = 0; ca < NB; ++ca, ++p)
-                        acc[p] = __builtin_amdgcn_mfma_f64_4x4x4f64(frag[ca][s + 1], X, acc[p], 0, 0, 0);
-                }
-            }
-            // Galerkin (110 accumulators): nothing moves across a row step -- otherwise the scheduler hoists later steps' operand
-            // loads and the register allocator answers with more scratch reloads inside the MFMA loop (412 -> 292 bytes per
-            // lane, 290 -> 266 us per 4096 samples; the LSPG forms are 3 % faster without it)
-            if constexpr (GAL) __builtin_amdgcn_sched_barrier(0);
+            C::step(acc, frag, s, Y, R, ui, sh, r);
         }
-        // ---- sum the four block partials of every pair (lanes differing in bits 2..3) -----------
-        {
-            const int oi = lane >> 4, oj = lane & 3;
-            const bool writer = ((lane >> 2) & 3) == 3;
-            const int wslot = writer ? w : 4;            // idle lanes store into the dump slab: no branches
-            int p = 0;
-#pragma unroll
-            for (int ca = 0; ca < NB; ++ca) {
-#pragma unroll
-                for (int cb = (GAL ? 0 : ca); cb <= NB; ++cb, ++p) {
-                    double v = acc[p];
-                    v += dpp_mov<0x114>(v);          // row_shr:4
-                    v += dpp_mov<0x118>(v);          // row_shr:8 -> lanes with blk == 3 hold the sum
-                    s_red[wslot][4 * ca + oi][4 * cb + oj] = v;
-                }
-            }
-            if constexpr (!GAL && WTU) {
-#pragma unroll
-                for (int ca = 0; ca < NB; ++ca, ++p) {
-                    double v = acc[p];
-                    v += dpp_mov<0x114>(v);
-                    v += dpp_mov<0x118>(v);
-                    s_wtu[(writer && oj == 1) ? w : 4][4 * ca + oi] = v;
-                }
-            }
-        }
+        // ---- cross-wave reduction through LDS, then write Ar | br | W^T u ----------------------
+        C::park(s_red, s_wtu, acc, sh, w, lane);
         __syncthreads();
         {   // thread (col = tid & 63, row phase = tid >> 6): no integer division, coalesced row stores
             const int col = tid & 63;
             if (col <= r) {
                 for (int row = tid >> 6; row < r; row += 4) {
-                    int rr = row, cc = (col < r) ? col : RW;             // br sits in column RW
-                    if (!GAL && col < r && (row >> 2) > (col >> 2)) { rr = col; cc = row; }   // mirror lower blocks
+                    int rr = row, cc = (col < r) ? col : Shape::br_col(r);
+                    if (!GAL && col < r && (row >> Shape::MIRROR_SHIFT) > (col >> Shape::MIRROR_SHIFT)) { rr = col; cc = row; }   // mirror the lower blocks
                     const double v = (s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc]);
                     if (col < r)
                         a.Ar[((size_t)smp * r + row) * r + col] = v;
@@ -500,16 +472,7 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
             }
         }
         if (a.wtu) {
-            for (int j = tid; j < r; j += 256) {
-                double v;
-                if constexpr (GAL)
-                    v = (s_red[0][j][RW + 1] + s_red[1][j][RW + 1]) + (s_red[2][j][RW + 1] + s_red[3][j][RW + 1]);
-                else if constexpr (WTU)
-                    v = (s_wtu[0][j] + s_wtu[1][j]) + (s_wtu[2][j] + s_wtu[3][j]);
-                else
-                    v = 0.0;
-                a.wtu[(size_t)smp * r + j] = v;
-            }
+            for (int j = tid; j < r; j += 256) a.wtu[(size_t)smp * r + j] = C::wtu_sum(s_red, s_wtu, j);
         }
         __syncthreads();
         smp = nxt;
@@ -520,7 +483,7 @@ __global__ __launch_bounds__(256, 1) void rom_reduce4_kernel(ReduceArgs a)
 // ------------------------------------------------------------------------------------
 // quad_tangent_kernel: T[b] = Phi + H3 . q[b]  (reference tangent(), FEM/fem_burgers.py:1120-1123,
 // with H3[i][a][c] = H[i][pair(a,c)] (1 + delta_ac) folding get_dQ_dq :292-312), written straight
-// into the fragment-major layout rom_reduce4_kernel reads.  Across the samples this is a GEMM per mesh row,
+// into the fragment-major layout the Block4 reduce kernel reads.  Across the samples this is a GEMM per mesh row,
 // T_i (n x B) = H3_i (n x n) . Q (n x B), and it runs on v_mfma_f64_4x4x4_4b: workgroup = one (column block c, row
 // slot s) and a chunk of 64 samples; MFMA block = one mesh row (owner), A = H3[row][4 columns][4 k] stationary in
 // registers (NKC doubles per lane and owner group), B = q[4 samples][4 k] from the chunk's copy in LDS (one 512-byte read
@@ -686,24 +649,29 @@ __global__ __launch_bounds__(256) void lu_solve_kernel(LuArgs a)
 template <typename F>
 int dispatch_lu(int n, F&& f)
 {
-    if (n <= 8) return f(std::integral_constant<int, 8>{});
-    if (n <= 16) return f(std::integral_constant<int, 16>{});
-    if (n <= 24) return f(std::integral_constant<int, 24>{});
-    if (n <= 32) return f(std::integral_constant<int, 32>{});
-    if (n <= 40) return f(std::integral_constant<int, 40>{});
-    if (n <= 48) return f(std::integral_constant<int, 48>{});
-    if (n <= 64) return f(std::integral_constant<int, 64>{});
+    if (n <= 8) return f(ic<8>{});
+    if (n <= 16) return f(ic<16>{});
+    if (n <= 24) return f(ic<24>{});
+    if (n <= 32) return f(ic<32>{});
+    if (n <= 40) return f(ic<40>{});
+    if (n <= 48) return f(ic<48>{});
+    if (n <= 64) return f(ic<64>{});
     return BG_ERR_UNSUPPORTED_R;
 }
 
-template <int V>
-using ic = std::integral_constant<int, V>;
+int launch_lu(const LuArgs& a, hipStream_t st)
+{
+    return dispatch_lu(a.n, [&](auto nc) {
+        hipLaunchKernelGGL((lu_solve_kernel<decltype(nc)::value>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+        return check_launch();
+    });
+}
 
 // The fragment shape of the 4x4x4 kernels: NB 4-column blocks cover r <= 40, every owner holds S rows of N <= 512.
 int frag_nb(int r) { return r <= 8 ? 2 : (r <= 16 ? 4 : (r <= 24 ? 6 : (r <= 32 ? 8 : 10))); }
 int frag_s(int N) { return N <= 256 ? 4 : 8; }
 
-// f(S, NB) for rom_reduce4_kernel and quad_tangent_kernel
+// f(S, NB) for Block4<S, NB> and quad_tangent_kernel
 template <typename F>
 int dispatch_frag(int N, int r, F&& f)
 {
@@ -718,7 +686,7 @@ int dispatch_frag(int N, int r, F&& f)
     return BG_ERR_UNSUPPORTED_R;
 }
 
-// f(S, NT) for rom_reduce_kernel: 16 S rows cover N <= 512, NT 16-column tiles r <= 47 and the extra column that carries R
+// f(S, NT) for Tile16<S, NT>: 16 S rows cover N <= 512, NT 16-column tiles r <= 47 and the extra column that carries R
 template <typename F>
 int dispatch_tiles(int N, int r, F&& f)
 {
@@ -731,6 +699,48 @@ int dispatch_tiles(int N, int r, F&& f)
     return BG_ERR_UNSUPPORTED_R;
 }
 
+// The checks and the dispatch shared by bg_rom_reduce, _indexed, _lifted, _frag and bg_rom_lift.
+int reduce_launch(ReduceArgs a, int projection, int options, void* stream)
+{
+    if (a.N < 2 || a.B < 0 || a.r < 1 || !(a.dt > 0.0)) return BG_ERR_BAD_ARG;
+    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
+    if (a.N > 512) return BG_ERR_UNSUPPORTED_N;
+    if (a.r > 47) return BG_ERR_UNSUPPORTED_R;
+    if (a.B == 0) return BG_OK;
+    if (!a.x || !a.W) return BG_ERR_BAD_ARG;
+    if (!a.lift_only && (!a.G || !a.hfs || !a.mu1 || !a.Ar || !a.br)) return BG_ERR_BAD_ARG;
+    if (a.q_in ? (!a.Uout || a.w_stride != 0) : !a.U) return BG_ERR_BAD_ARG;
+    a.supg = options & BG_OPT_SUPG;
+    a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
+    a.w_colmajor = (options & BG_OPT_W_COLMAJOR) ? 1 : 0;
+    const bool force16 = (options & BG_OPT_MFMA_16X16) != 0;
+    if (a.w_frag && (a.r > 40 || force16)) return BG_ERR_UNSUPPORTED_R;
+    const dim3 grid(persistent_grid(a.B, 1)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    // fast path: Block4, r <= 40 (accumulators and fragments must fit the register file)
+    if (a.r <= 40 && !force16)
+        return dispatch_frag(a.N, a.r, [&](auto s, auto nb) {
+            using Shape = Block4<decltype(s)::value, decltype(nb)::value>;
+            if (projection == BG_PROJ_GALERKIN)
+                hipLaunchKernelGGL((rom_reduce_kernel<Shape, BG_PROJ_GALERKIN, true>), grid, block, 0, st, a);
+            else if (a.wtu)
+                hipLaunchKernelGGL((rom_reduce_kernel<Shape, BG_PROJ_LSPG, true>), grid, block, 0, st, a);
+            else                              // LSPG without W^T u: NB accumulators fewer
+                hipLaunchKernelGGL((rom_reduce_kernel<Shape, BG_PROJ_LSPG, false>), grid, block, 0, st, a);
+            return check_launch();
+        });
+    return dispatch_tiles(a.N, a.r, [&](auto s, auto nt) {
+        return dispatch_projection(projection, [&](auto p) {
+            hipLaunchKernelGGL((rom_reduce_kernel<Tile16<decltype(s)::value, decltype(nt)::value>, decltype(p)::value, true>), grid,
+                               block, 0, st, a);
+            return check_launch();
+        });
+    });
+}
+
+// One workgroup row per sample; a grid's y extent ends at 65535 and the kernels stride over the rest.
+dim3 nodes_by_samples_grid(int N, int B) { return dim3((N + 255) / 256, B < 65535 ? B : 65535); }
+
 }  // namespace
 
 extern "C" {
@@ -741,8 +751,8 @@ int bg_forcing_setup(int N, int B, const double* x, const double* mu2, double dt
     if (N < 2 || B < 0) return BG_ERR_BAD_ARG;
     if (B == 0) return BG_OK;
     if (!x || !mu2 || !fdt || !hfs) return BG_ERR_BAD_ARG;
-    hipLaunchKernelGGL(forcing_setup_kernel, dim3((N + 255) / 256, B < 65535 ? B : 65535), dim3(256), 0, (hipStream_t)stream, x, mu2, N,
-                       B, dt, (options & BG_OPT_NONUNIFORM) ? 1 : 0, fdt, hfs);
+    hipLaunchKernelGGL(forcing_setup_kernel, nodes_by_samples_grid(N, B), dim3(256), 0, (hipStream_t)stream, x, mu2, N, B, dt,
+                       (options & BG_OPT_NONUNIFORM) ? 1 : 0, fdt, hfs);
     return check_launch();
 }
 
@@ -752,7 +762,7 @@ int bg_mass_rhs(int N, int B, const double* x, const double* un, const double* f
     if (N < 2 || B < 0) return BG_ERR_BAD_ARG;
     if (B == 0) return BG_OK;
     if (!x || !un || !fdt || !g) return BG_ERR_BAD_ARG;
-    hipLaunchKernelGGL(mass_rhs_kernel, dim3((N + 255) / 256, B < 65535 ? B : 65535), dim3(256), 0, (hipStream_t)stream, x, un, fdt, N, B,
+    hipLaunchKernelGGL(mass_rhs_kernel, nodes_by_samples_grid(N, B), dim3(256), 0, (hipStream_t)stream, x, un, fdt, N, B,
                        (options & BG_OPT_NONUNIFORM) ? 1 : 0, g);
     return check_launch();
 }
@@ -760,56 +770,13 @@ int bg_mass_rhs(int N, int B, const double* x, const double* un, const double* f
 int bg_rom_max_n(void) { return 512; }
 int bg_rom_max_r(void) { return 47; }
 
-static int rom_reduce_impl(int N, int B, int r, int projection, const double* x, const double* W, long long w_stride,
-                           const double* U, const double* G, const double* hfs, const double* mu1, double dt, double E,
-                           int supg, const int32_t* active, double* Ar, double* br, double* wtu, const double* q_in,
-                           double* Uout, int lift_only, void* stream, int w_frag = 0, const int32_t* w_index = nullptr)
-{
-    if (N < 2 || B < 0 || r < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
-    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
-    if (N > 512) return BG_ERR_UNSUPPORTED_N;
-    if (r > 47) return BG_ERR_UNSUPPORTED_R;
-    if (B == 0) return BG_OK;
-    if (!x || !W) return BG_ERR_BAD_ARG;
-    if (!lift_only && (!G || !hfs || !mu1 || !Ar || !br)) return BG_ERR_BAD_ARG;
-    if (q_in ? (!Uout || w_stride != 0) : !U) return BG_ERR_BAD_ARG;
-    ReduceArgs a;
-    a.x = x; a.W = W; a.w_stride = w_stride; a.U = U; a.G = G; a.hfs = hfs; a.mu1 = mu1; a.active = active;
-    a.Ar = Ar; a.br = br; a.wtu = wtu; a.dt = dt; a.E = E; a.N = N; a.B = B; a.r = r; a.proj = projection;
-    a.supg = supg & BG_OPT_SUPG; a.nonuniform = (supg & BG_OPT_NONUNIFORM) ? 1 : 0;
-    a.q_in = q_in; a.Uout = Uout; a.lift_only = lift_only; a.w_frag = w_frag;
-    a.w_colmajor = (supg & BG_OPT_W_COLMAJOR) ? 1 : 0;
-    a.w_index = w_index;
-    const bool force16 = (supg & BG_OPT_MFMA_16X16) != 0;
-    if (w_frag && (r > 40 || force16)) return BG_ERR_UNSUPPORTED_R;
-    const dim3 grid(persistent_grid(B, 1)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    // fast path: v_mfma_f64_4x4x4_4b kernel, r <= 40 (accumulators and fragments must fit the register file)
-    if (r <= 40 && !force16)
-        return dispatch_frag(N, r, [&](auto s, auto nb) {
-            constexpr int S = decltype(s)::value, NB = decltype(nb)::value;
-            if (projection == BG_PROJ_GALERKIN)
-                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_GALERKIN, true>), grid, block, 0, st, a);
-            else if (wtu)
-                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_LSPG, true>), grid, block, 0, st, a);
-            else                              // LSPG without W^T u: NB accumulators fewer
-                hipLaunchKernelGGL((rom_reduce4_kernel<S, NB, BG_PROJ_LSPG, false>), grid, block, 0, st, a);
-            return check_launch();
-        });
-    return dispatch_tiles(N, r, [&](auto s, auto nt) {
-        return dispatch_projection(projection, [&](auto p) {
-            hipLaunchKernelGGL((rom_reduce_kernel<decltype(s)::value, decltype(nt)::value, decltype(p)::value>), grid, block, 0, st, a);
-            return check_launch();
-        });
-    });
-}
-
 int bg_rom_reduce(int N, int B, int r, int projection, const double* x, const double* W, long long w_stride,
                   const double* U, const double* G, const double* hfs, const double* mu1, double dt, double E,
                   int supg, const int32_t* active, double* Ar, double* br, double* wtu, void* stream)
 {
-    return rom_reduce_impl(N, B, r, projection, x, W, w_stride, U, G, hfs, mu1, dt, E, supg, active, Ar, br, wtu,
-                           nullptr, nullptr, 0, stream);
+    return reduce_launch({.x = x, .W = W, .w_stride = w_stride, .U = U, .G = G, .hfs = hfs, .mu1 = mu1, .active = active,
+                          .Ar = Ar, .br = br, .wtu = wtu, .dt = dt, .E = E, .N = N, .B = B, .r = r},
+                         projection, supg, stream);
 }
 
 int bg_rom_reduce_indexed(int N, int B, int r, int projection, const double* x, const double* W, long long w_stride,
@@ -818,8 +785,9 @@ int bg_rom_reduce_indexed(int N, int B, int r, int projection, const double* x, 
                           void* stream)
 {
     if (B > 0 && (!w_index || w_stride == 0)) return BG_ERR_BAD_ARG;
-    return rom_reduce_impl(N, B, r, projection, x, W, w_stride, U, G, hfs, mu1, dt, E, supg, active, Ar, br, wtu,
-                           nullptr, nullptr, 0, stream, 0, w_index);
+    return reduce_launch({.x = x, .W = W, .w_stride = w_stride, .U = U, .G = G, .hfs = hfs, .mu1 = mu1, .active = active,
+                          .Ar = Ar, .br = br, .wtu = wtu, .dt = dt, .E = E, .N = N, .B = B, .r = r, .w_index = w_index},
+                         projection, supg, stream);
 }
 
 int bg_rom_reduce_lifted(int N, int B, int r, int projection, const double* x, const double* Phi, const double* q,
@@ -828,8 +796,9 @@ int bg_rom_reduce_lifted(int N, int B, int r, int projection, const double* x, c
 {
     if (B == 0) return BG_OK;
     if (!q || !U) return BG_ERR_BAD_ARG;
-    return rom_reduce_impl(N, B, r, projection, x, Phi, 0, nullptr, G, hfs, mu1, dt, E, supg, active, Ar, br, wtu, q,
-                           U, 0, stream);
+    return reduce_launch({.x = x, .W = Phi, .G = G, .hfs = hfs, .mu1 = mu1, .active = active, .Ar = Ar, .br = br, .wtu = wtu,
+                          .q_in = q, .Uout = U, .dt = dt, .E = E, .N = N, .B = B, .r = r},
+                         projection, supg, stream);
 }
 
 int bg_rom_frag_pad(int r) { return (r < 1 || r > 40) ? 0 : 4 * frag_nb(r); }
@@ -887,8 +856,9 @@ int bg_rom_reduce_frag(int N, int B, int r, int projection, const double* x, con
 {
     const long long per = bg_rom_frag_elems(N, r);
     if (per == 0) return (r > 40) ? BG_ERR_UNSUPPORTED_R : BG_ERR_UNSUPPORTED_N;
-    return rom_reduce_impl(N, B, r, projection, x, Wfrag, per, U, G, hfs, mu1, dt, E, supg, active, Ar, br, wtu,
-                           nullptr, nullptr, 0, stream, 1);
+    return reduce_launch({.x = x, .W = Wfrag, .w_stride = per, .U = U, .G = G, .hfs = hfs, .mu1 = mu1, .active = active,
+                          .Ar = Ar, .br = br, .wtu = wtu, .dt = dt, .E = E, .N = N, .B = B, .r = r, .w_frag = 1},
+                         projection, supg, stream);
 }
 
 int bg_rom_lift(int N, int B, int r, const double* x, const double* Phi, const double* q, const int32_t* active,
@@ -896,8 +866,8 @@ int bg_rom_lift(int N, int B, int r, const double* x, const double* Phi, const d
 {
     if (B == 0) return BG_OK;
     if (!q || !U) return BG_ERR_BAD_ARG;
-    return rom_reduce_impl(N, B, r, BG_PROJ_GALERKIN, x, Phi, 0, nullptr, nullptr, nullptr, nullptr, 1.0, 0.0, 0,
-                           active, nullptr, nullptr, nullptr, q, U, 1, stream);
+    return reduce_launch({.x = x, .W = Phi, .active = active, .q_in = q, .Uout = U, .dt = 1.0, .N = N, .B = B, .r = r, .lift_only = 1},
+                         BG_PROJ_GALERKIN, 0, stream);
 }
 
 int bg_lu_solve_update(int n, int B, const double* A, const double* b, int mode, const double* wtu, double* q,
@@ -907,13 +877,7 @@ int bg_lu_solve_update(int n, int B, const double* A, const double* b, int mode,
     if (n < 1 || B < 0 || mode < 1 || mode > 3) return BG_ERR_BAD_ARG;
     if (B == 0) return BG_OK;
     if (!A || !b || !q || !dq || !active || !iters || !flags || !counter || (mode == 1 && !wtu)) return BG_ERR_BAD_ARG;
-    LuArgs a{A, b, nullptr, dq, info, -1.0, n, B, mode, max_it, tol, wtu, q, active, iters, flags, counter};
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_lu(n, [&](auto nc) {
-        constexpr int NMAX = decltype(nc)::value;
-        hipLaunchKernelGGL((lu_solve_kernel<NMAX>), dim3((B + 3) / 4), dim3(256), 0, st, a);
-        return check_launch();
-    });
+    return launch_lu({A, b, nullptr, dq, info, -1.0, n, B, mode, max_it, tol, wtu, q, active, iters, flags, counter}, (hipStream_t)stream);
 }
 
 int bg_lu_solve(int n, int B, const double* A, const double* b, double sign, const int32_t* active, double* x,
@@ -922,13 +886,7 @@ int bg_lu_solve(int n, int B, const double* A, const double* b, double sign, con
     if (n < 1 || B < 0) return BG_ERR_BAD_ARG;
     if (B == 0) return BG_OK;
     if (!A || !b || !x) return BG_ERR_BAD_ARG;
-    LuArgs a{A, b, active, x, info, sign, n, B, 0, 0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_lu(n, [&](auto nc) {
-        constexpr int NMAX = decltype(nc)::value;
-        hipLaunchKernelGGL((lu_solve_kernel<NMAX>), dim3((B + 3) / 4), dim3(256), 0, st, a);
-        return check_launch();
-    });
+    return launch_lu({A, b, active, x, info, sign, n, B}, (hipStream_t)stream);      // mode 0: no update, the rest stays null
 }
 
 }  // extern "C"

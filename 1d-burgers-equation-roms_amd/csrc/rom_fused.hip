@@ -4,7 +4,7 @@
 // workgroup owns a sample for ALL time steps and ALL Picard iterations.  The basis fragments stay in registers (their halo
 // rows in LDS), u, g, the per-sample load constants, the reduced system and q stay in LDS; HBM sees the initial state
 // once and one N-row history write per time step.  Per iteration, with no kernel boundary and no host in between:
-//     assembly (2 rows per thread)  ->  fp64 MFMA projection (v_mfma_f64_4x4x4_4b, as rom_reduce4_kernel)
+//     assembly (2 rows per thread)  ->  fp64 MFMA projection (v_mfma_f64_4x4x4_4b, as rom_reduce_kernel on Block4)
 //     ->  r x r solve by all four waves (below)  ->  q = Phi^T u + dq, error, stopping test  ->  lift u = Phi q.
 //
 // The reduced solve.  np.linalg.solve (:767) is LU with partial pivoting.  On these systems (cond(Ar) < 10 on the

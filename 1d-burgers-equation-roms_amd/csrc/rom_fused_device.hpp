@@ -29,7 +29,7 @@ __device__ __forceinline__ void lds_add_f64(double* p, double v)
 }
 
 // ---- one MFMA pass over this wave's rows: pairs (ca, cb) with ca in [CA0, CA1) (LSPG) / cb in [CA0, CA1) (Galerkin) ----
-// Same operand layout and accumulation order as rom_reduce4_kernel (rom.hip).  frag[c][s] = Phi[rowbase + s][4 c + t]; the
+// Same operand layout and accumulation order as rom_reduce_kernel on Block4 (rom.hip).  frag[c][s] = Phi[rowbase + s][4 c + t]; the
 // two halo rows Phi[rowbase - 1], Phi[rowbase + S] of every column block come from `halo(side, c)` when the first / last
 // row step needs them (they are not kept in registers: 40 VGPRs fewer live across the whole kernel):
 //   HaloTable   one private LDS slot per thread (s_halo[side][c][tid], conflict-free 8-byte reads): rom_ann_fused, whose

@@ -165,8 +165,9 @@ int bg_mass_rhs(int N, int B, const double *x, const double *un, const double *f
  *   Ar       [B][r][r]: W^T A W (BG_PROJ_GALERKIN) or (A W)^T (A W) (BG_PROJ_LSPG)
  *   br       [B][r]:    W^T R   or (A W)^T R,  R = A u_k - b
  *   wtu      [B][r] or NULL: W^T u_k (the `Phi.T @ U0` of :770)
- *   Two kernels: v_mfma_f64_4x4x4_4b (r <= 40) and v_mfma_f64_16x16x4 (r <= 47).  BG_OPT_MFMA_16X16 in `supg`
- *   selects the second one for every r, for A/B timing and tests (no environment is read). */
+ *   One kernel over two MFMA shapes: v_mfma_f64_4x4x4_4b (r <= 40) and v_mfma_f64_16x16x4 (r <= 47); staging,
+ *   assembly, write-out and the order of every sum are shared.  BG_OPT_MFMA_16X16 in `supg` selects the second
+ *   shape for every r, for A/B timing and tests (no environment is read). */
 int bg_rom_reduce(int N, int B, int r, int projection, const double *x, const double *W,
                   long long w_stride, const double *U, const double *G, const double *hfs,
                   const double *mu1, double dt, double E, int supg, const int32_t *active,

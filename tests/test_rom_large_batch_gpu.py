@@ -3,7 +3,7 @@
 bg_rom_reduce* launches min(B, #CUs) workgroups; beyond that every workgroup walks over several
 samples with the basis fragments kept in registers, the per-sample rows double-buffered in LDS and
 the NEXT sample prefetched by LDS DMA under the current sample's MFMAs (csrc/rom.hip,
-rom_reduce4_kernel).  Every test here uses B >= 4 x 256 so that this loop really iterates, and checks
+rom_reduce_kernel).  Every test here uses B >= 4 x 256 so that this loop really iterates, and checks
   (i)  a strided subset of the samples against the oracle (oracle/burgers_ref.py), and
   (ii) ALL samples bit-for-bit against the same call split into chunks of <= 200 samples, i.e. the
        one-sample-per-workgroup path that tests/test_rom_gpu.py pins against the oracle.
@@ -130,10 +130,18 @@ def test_reduce_persistent_loop_shared_and_per_sample(hip, N, r, B, force16):
                 assert rel_l2(wtuh[b], Wb.T @ cs.U[b]) < 1e-13
 
 
-@pytest.mark.parametrize("N,r,B", [(512, 40, 1100), (300, 21, 1031), (511, 5, 1050)])
-def test_reduce_lifted_persistent_loop(hip, N, r, B):
-    """bg_rom_reduce_lifted (u = Phi q formed in-kernel, q prefetched by dword LDS DMA) and bg_rom_lift."""
+# B = 600: the smallest batch that still gives some of 256 workgroups a third sample (both LDS buffers reused); covers _holes' 300:340
+_ON_16X16 = [(130, 44, 600, False),      # default route = 16x16, three 16-column tiles; even N: LDS-DMA prefetch
+             (129, 47, 600, False),      # widest basis, odd N: plain staging
+             (130, 24, 600, True)]
+
+
+@pytest.mark.parametrize("N,r,B,force16", [(512, 40, 1100, False), (300, 21, 1031, False), (511, 5, 1050, False)] + _ON_16X16,
+                         ids=["512-40-1100", "300-21-1031", "511-5-1050", "130-44-600", "129-47-600", "130-24-600-force16"])
+def test_reduce_lifted_persistent_loop(hip, N, r, B, force16):
+    """bg_rom_reduce_lifted (u = Phi q formed in-kernel, q prefetched by dword LDS DMA) and bg_rom_lift, on both MFMA shapes."""
     from burgers_hip import rom
+    opts = hip.BG_OPT_MFMA_16X16 if force16 else 0
     cs = _Case(N, B, 77 * N + r)
     rng = cs.rng
     Phi = np.linalg.qr(rng.standard_normal((N, r)))[0]
@@ -145,13 +153,13 @@ def test_reduce_lifted_persistent_loop(hip, N, r, B):
     for pname, proj in (("galerkin", 0), ("lspg", 1)):
         Ar, brr, wtu = _outs(B, r)
         Uo = torch.full((B, N), -7.0, dtype=torch.float64, device="cuda")
-        rom.rom_reduce_lifted(cs.c, Phid, qd, Uo, cs.G, proj, True, actd, Ar, brr, wtu)
+        rom.rom_reduce_lifted(cs.c, Phid, qd, Uo, cs.G, proj, True, actd, Ar, brr, wtu, extra_opts=opts)
         Ar2, br2, wtu2 = _outs(B, r)
         Uo2 = torch.full((B, N), -7.0, dtype=torch.float64, device="cuda")
         for lo in range(0, B, CHUNK):
             hi = min(B, lo + CHUNK)
             rom.rom_reduce_lifted(cs.sub(lo, hi), Phid, qd[lo:hi], Uo2[lo:hi], cs.G[lo:hi], proj, True, actd[lo:hi],
-                                  Ar2[lo:hi], br2[lo:hi], wtu2[lo:hi])
+                                  Ar2[lo:hi], br2[lo:hi], wtu2[lo:hi], extra_opts=opts)
         torch.cuda.synchronize()
         assert torch.equal(Ar, Ar2) and torch.equal(brr, br2) and torch.equal(wtu, wtu2) and torch.equal(Uo, Uo2)
         Uh, Arh, brh = Uo.cpu().numpy(), Ar.cpu().numpy(), brr.cpu().numpy()
@@ -167,11 +175,14 @@ def test_reduce_lifted_persistent_loop(hip, N, r, B):
     assert np.abs(Uh[act == 1] - Ulift[act == 1]).max() < 1e-12 and (Uh[act == 0] == -7.0).all()
 
 
-@pytest.mark.parametrize("N,r,B", [(512, 30, 1100), (301, 16, 1040)])
-def test_reduce_indexed_mixed_blocks(hip, N, r, B):
+@pytest.mark.parametrize("N,r,B,force16", [(512, 30, 1100, False), (301, 16, 1040, False), (130, 44, 800, False), (301, 16, 1040, True)],
+                         ids=["512-30-1100", "301-16-1040", "130-44-800", "301-16-1040-force16"])
+def test_reduce_indexed_mixed_blocks(hip, N, r, B, force16):
     """bg_rom_reduce_indexed with a mixed w_index: runs of equal blocks (fragments kept) and changes of
-    block from one sample of a workgroup to its next (fragments reloaded), holes in between."""
+    block from one sample of a workgroup to its next (fragments reloaded), holes in between; on both MFMA shapes
+    (r = 44 takes the 16x16 one by default; B >= 768 for the pattern below)."""
     from burgers_hip import rom
+    opts = hip.BG_OPT_MFMA_16X16 if force16 else 0
     cs = _Case(N, B, 5 * N + r)
     rng = cs.rng
     C = 5
@@ -184,12 +195,12 @@ def test_reduce_indexed_mixed_blocks(hip, N, r, B):
     probe = [b for b in np.linspace(0, B - 1, 9).astype(int) if act[b]]
     for pname, proj in (("galerkin", 0), ("lspg", 1)):
         Ar, brr, wtu = _outs(B, r)
-        rom.rom_reduce(cs.c, stackd, cs.Ud, cs.G, proj, True, actd, Ar, brr, wtu, w_index=widxd)
+        rom.rom_reduce(cs.c, stackd, cs.Ud, cs.G, proj, True, actd, Ar, brr, wtu, w_index=widxd, extra_opts=opts)
         Ar2, br2, wtu2 = _outs(B, r)
         for lo in range(0, B, CHUNK):
             hi = min(B, lo + CHUNK)
             rom.rom_reduce(cs.sub(lo, hi), stackd, cs.Ud[lo:hi], cs.G[lo:hi], proj, True, actd[lo:hi], Ar2[lo:hi],
-                           br2[lo:hi], wtu2[lo:hi], w_index=widxd[lo:hi].contiguous())
+                           br2[lo:hi], wtu2[lo:hi], w_index=widxd[lo:hi].contiguous(), extra_opts=opts)
         torch.cuda.synchronize()
         assert torch.equal(Ar, Ar2) and torch.equal(brr, br2) and torch.equal(wtu, wtu2)
         Arh, brh = Ar.cpu().numpy(), brr.cpu().numpy()

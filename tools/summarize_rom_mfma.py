@@ -32,7 +32,8 @@ for k, disp in per.items():
     dur = sum(meta[(k, d)][1] for d in keep) / n
     mfma_busy, cu_busy = mean("SQ_VALU_MFMA_BUSY_CYCLES"), mean("SQ_BUSY_CU_CYCLES")
     mops = mean("SQ_INSTS_VALU_MFMA_MOPS_F64")
-    out.append({"kernel": (re.search(r"(rom_reduce\w*<[^>]*>|lu_solve_kernel<[^>]*>|rom_fused_kernel<[^>]*>)", k) or [k[:80]])[0], "launches": n, "avg_us": dur / 1e3,
+    # rom_reduce_kernel<(anonymous namespace)::Block4<8, 10>, 0, true>: the shape is a template argument with its own brackets
+    out.append({"kernel": (re.search(r"(rom_reduce\w*<(?:[^<>]|<[^<>]*>)*>|lu_solve_kernel<[^>]*>|rom_fused_kernel<[^>]*>)", k) or [k[:80]])[0], "launches": n, "avg_us": dur / 1e3,
                 "SQ_VALU_MFMA_BUSY_CYCLES": mfma_busy, "SQ_BUSY_CU_CYCLES": cu_busy,
                 "MfmaUtil": mfma_busy / (4.0 * cu_busy) if cu_busy else None,
                 "SQ_INSTS_VALU_MFMA_MOPS_F64": mops, "SQ_INSTS_VALU_MFMA_F64": mean("SQ_INSTS_VALU_MFMA_F64"),
