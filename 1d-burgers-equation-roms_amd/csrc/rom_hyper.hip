@@ -19,6 +19,14 @@
 // Then the system is parked over the dead slabs and solved by rom_fused_device.hpp's r <= 40 routines, q <- q + dq (equal to
 // the reference's Phi^T u_k + dq for an orthonormal basis, since u_k = Phi q), the stopping test |dq| / |q|.  There is no
 // lift-only sweep: the output is q itself, [B][nsteps + 1][r].  Pivoting is repaired inside the call as in bg_rom_run_long.
+//
+// The arithmetic of an iteration is the full loops' own code: the lift of a row and the operands Y, P of a row step are
+// rom_stream_device.hpp's stream_lift_rows and stream_row_operands (there the three rows are neighbours in the slab, here
+// 3 j .. 3 j + 2 of it), the matrix steps and the parking its stream_step_mfma and stream_park, the solve
+// rom_long_device.hpp's LongLayout::solve_add (dq added to q, where the streaming loops add it to the parked Phi^T u),
+// mass row and assembly rom_device.hpp's rom_mass_rhs_node and rom_assemble_row, reading the stencil coordinates xs as a
+// mesh x.  This file's own: the contiguous slab DMA, the weights, the start from u0s, the frame of the loop, and the
+// per-sample forcing loads (hyper_row_forcing, which says why).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -57,36 +65,13 @@ struct HyperLds {
     int* row;                                                        // [HMMAX] mesh row (N beyond m: an identity row with weight 0)
 };
 
-// The description of rom_stream_device.hpp's items, matrix steps and parking, and the solve of rom_long_device.hpp with
-// the one difference of this loop: the update adds dq to q itself (L.q), not to a projected Phi^T u.
-struct HyperPod : LongLayout {
-    template <bool GAL, bool PIV, int W>
-    static __device__ __forceinline__ void solve_update(const StreamLds& L, int r, int lane, bool& aborted, int& info_out,
-                                                        double& nd, double& nq)
-    {
-        const double* S = L.slab;
-        const double qk = (lane < r) ? L.q[lane] : 0.0;                            // read before the solve's first barrier
-        auto entry = [&](int i, int j) -> double { return S[i * LSW + j]; };      // (Ar | br)[i][j]
-        double xout;
-        if constexpr (PIV) {
-            if (W == 0) fused::pivoted_solve_of<LNB>(entry, L.x, &L.bad[4], lane, r);
-            __syncthreads();
-            xout = (lane < LR) ? L.x[lane] : 0.0;
-            if (L.bad[4] != 0 && info_out == 0) info_out = L.bad[4];
-        } else {
-            bool tripped;
-            xout = fused::coop_gj_solve_of<LNB>(entry, reinterpret_cast<double (*)[4][64]>(L.m), L.diag, L.y, L.bad, W, lane, r, tripped);
-            if (tripped) aborted = true;
-        }
-        const double dq = (lane < r) ? xout : 0.0;
-        const double qn = qk + dq;
-        wave_sum2(dq * dq, qn * qn, nd, nq);
-        if (W == 0 && lane < LR) L.q[lane] = qn;
-    }
-};
-
-// Loads of the forcing term at a sampled row with the stencil coordinates xm, x0, xp (rom_nodal_forcing's arithmetic):
-// dt F_i, and h_e (f(gp1) + f(gp2)) of the left and right element; 0 where the mesh has no such element.
+// Loads of the forcing term at a sampled row with the stencil coordinates xm, x0, xp: dt F_i, and h_e (f(gp1) + f(gp2)) of
+// the left and right element; 0 where the mesh has no such element.  The formulas are rom_nodal_forcing's (rom_device.hpp);
+// the last bit is not.  Both functions leave sums of two products (`GP_A * xm + GP_B * x0`, `f1 * GP_B + f2 * GP_A`) to the
+// compiler's contraction: here it fuses the product with x0 in both elements, there the product with the element's left
+// node, and in the full loops it leaves frPrev unfused (profiles/hyper_stream_isa.md).  Calling rom_nodal_forcing from here
+// changed q in its last bits in every all-rows run (profiles/hyper_stream_ab.md).  One routine for both needs the fused
+// product spelled with __builtin_fma, and that changes one side's results.
 __device__ __forceinline__ void hyper_row_forcing(double xm, double x0, double xp, int i, int N, double mu2, double h, int nonuniform,
                                                   double dt, double& fdt, double& hl, double& hr)
 {
@@ -110,11 +95,12 @@ __device__ __forceinline__ void hyper_row_forcing(double xm, double x0, double x
 }
 
 // The body for wave W of the workgroup (a template parameter of the whole body, as in rom_stream_body: every wave keeps
-// its own quarter of the block pairs in accumulators that never change registers).
+// its own quarter of the block pairs in accumulators that never change registers).  The description K is LongLayout as it
+// stands: the items, matrix steps, parking and solve of the r <= 40 streaming loops.
 template <bool GAL, bool PIV, int W>
 __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLds& L, const HyperLds& H)
 {
-    using K = HyperPod;
+    using K = LongLayout;
     constexpr int NB = LNB, R = LR, PS = LPS;
     constexpr int NACC = StreamItems<K, GAL>::per_wave;
     constexpr int w = W;
@@ -196,23 +182,8 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
                     if (q4 < HS) {                                            // (wave-uniform: the first HS / 16 waves)
                         const int j = slab * HS + q4;
                         double um, u0, ur;
-                        if (lift) {
-                            const double* prow = s_P + 3 * q4 * PS + NB * pt;
-                            double sm = 0.0, s0 = 0.0, sr = 0.0;
-#pragma unroll
-                            for (int c2 = 0; c2 < NB / 2; ++c2) {
-                                const double2 qv = *reinterpret_cast<const double2*>(&s_q[NB * pt + 2 * c2]);
-                                const double2 pm = *reinterpret_cast<const double2*>(prow + 2 * c2);
-                                const double2 p0 = *reinterpret_cast<const double2*>(prow + PS + 2 * c2);
-                                const double2 pr = *reinterpret_cast<const double2*>(prow + 2 * PS + 2 * c2);
-                                sm = __builtin_fma(pm.x, qv.x, sm); sm = __builtin_fma(pm.y, qv.y, sm);
-                                s0 = __builtin_fma(p0.x, qv.x, s0); s0 = __builtin_fma(p0.y, qv.y, s0);
-                                sr = __builtin_fma(pr.x, qv.x, sr); sr = __builtin_fma(pr.y, qv.y, sr);
-                            }
-                            sm += dpp_mov<0xB1>(sm); sm += dpp_mov<0x4E>(sm);          // quad sums
-                            s0 += dpp_mov<0xB1>(s0); s0 += dpp_mov<0x4E>(s0);
-                            sr += dpp_mov<0xB1>(sr); sr += dpp_mov<0x4E>(sr);
-                            um = sm; u0 = s0; ur = sr;                                 // rows outside the mesh are zero rows of PhiS
+                        if (lift) {                                            // rows outside the mesh are zero rows of PhiS
+                            stream_lift_rows<NB, PS>(s_P + 3 * q4 * PS + NB * pt, s_q + NB * pt, um, u0, ur);
                         } else {
                             um = u0 = ur = 0.0;
                             if (pt == 0 && j < m) { um = u0s[3 * j]; u0 = u0s[3 * j + 1]; ur = u0s[3 * j + 2]; }
@@ -248,17 +219,8 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
                         const int rl = 16 * st + 4 * pk + pblk;
                         const double2 c01 = *reinterpret_cast<const double2*>(&s_cf[rl][0]);
                         const double2 c23 = *reinterpret_cast<const double2*>(&s_cf[rl][2]);
-                        const double* pb = s_P + 3 * rl * PS + NB * pt;
                         double Y[NB], P[NB];
-#pragma unroll
-                        for (int c2 = 0; c2 < NB / 2; ++c2) {
-                            const double2 tb = *reinterpret_cast<const double2*>(pb + 2 * c2);
-                            const double2 tm = *reinterpret_cast<const double2*>(pb + PS + 2 * c2);
-                            const double2 ta = *reinterpret_cast<const double2*>(pb + 2 * PS + 2 * c2);
-                            P[2 * c2] = tm.x; P[2 * c2 + 1] = tm.y;
-                            Y[2 * c2] = __builtin_fma(c23.x, ta.x, __builtin_fma(c01.y, tm.x, c01.x * tb.x));
-                            Y[2 * c2 + 1] = __builtin_fma(c23.x, ta.y, __builtin_fma(c01.y, tm.y, c01.x * tb.y));
-                        }
+                        stream_row_operands<NB, PS>(s_P + 3 * rl * PS + NB * pt, c01, c23, Y, P);
                         const double X = (pt == 0) ? c23.y : 0.0;             // extra B block [R, 0, 0, 0] (no Phi^T u here)
                         stream_step_mfma<K, GAL, W>(Y, P, X, acc);
                     }
@@ -268,7 +230,8 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
                 __syncthreads();
                 // ---- solve(Ar, -br) (:767), q <- q + dq, err = |dq| / |q|  (:770-776) -------------------------------------------
                 double nd, nq;
-                K::template solve_update<GAL, PIV, W>(L, a.r, lane, aborted, info_out, nd, nq);
+                const double qk = (lane < a.r) ? s_q[lane] : 0.0;                 // read before the solve's first barrier
+                K::template solve_add<PIV, W>(L, a.r, lane, qk, aborted, info_out, nd, nq);
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;

@@ -2,7 +2,8 @@
 // bg_rom_run_long (rom_long.hip, POD) and bg_local_rom_run_long (rom_local_long.hip, local POD).  The loop itself is
 // rom_stream_device.hpp's; here are the layout constants, the part of the description K both use (LongLayout: the reduced
 // system parked WHOLE in LDS over the dead slabs and solved by rom_fused_device.hpp's routines) and the kernel body with
-// its LDS arrays (BG_LONG_KERNEL_BODY).
+// its LDS arrays (BG_LONG_KERNEL_BODY).  The hyper-reduced loop (rom_hyper.hip) has a body of its own over the same
+// LongLayout: its items, parking and solve are these.
 // LDS: 8 B per mesh row for each of u, g, h_f, dt F (32 KB at 1024 rows), the coefficients of ONE slab (2 KB), two slabs
 // of 66 x 42 doubles (43.3 KB) -- 77.7 KB, so two workgroups share a compute unit (local POD: + 64 doubles for q_g).
 #pragma once
@@ -35,12 +36,14 @@ struct LongLayout {
     // r: the live unknowns of this step.  Both solves put a unit diagonal and a zero right-hand side on the unknowns at and
     // beyond r (coop_gj_solve_of, pivoted_solve_of), so their correction is exactly zero and q is zero there: what local POD
     // needs when the step's cluster is narrower than the padded 40.
-    template <bool GAL, bool PIV, int W, class Lap>
-    static __device__ __forceinline__ void solve_update(const StreamRunArgs&, const StreamLds& L, int r, int lane, bool& aborted,
-                                                        int& info_out, double& nd, double& nq, const Lap&)
+    // solve_add: q = base + dq into L.q, |dq|^2 and |q|^2; `base` is this lane's value (0 at and beyond r), read by the caller
+    // before the solve's first barrier.  The streaming loops add dq to the parked Phi^T u (solve_update), the hyper-reduced
+    // loop (rom_hyper.hip) to q itself.
+    template <bool PIV, int W>
+    static __device__ __forceinline__ void solve_add(const StreamLds& L, int r, int lane, double base, bool& aborted, int& info_out,
+                                                     double& nd, double& nq)
     {
         const double* S = L.slab;
-        const double wtu = (lane < r) ? S[lane * LSW + LR + 1] : 0.0;            // Phi^T u
         auto entry = [&](int i, int j) -> double { return S[i * LSW + j]; };      // (Ar | br)[i][j]
         double xout;
         if constexpr (PIV) {
@@ -54,9 +57,17 @@ struct LongLayout {
             if (tripped) aborted = true;
         }
         const double dq = (lane < r) ? xout : 0.0;
-        const double qn = wtu + dq;
+        const double qn = base + dq;
         wave_sum2(dq * dq, qn * qn, nd, nq);
         if (W == 0 && lane < LR) L.q[lane] = qn;
+    }
+
+    template <bool GAL, bool PIV, int W, class Lap>
+    static __device__ __forceinline__ void solve_update(const StreamRunArgs&, const StreamLds& L, int r, int lane, bool& aborted,
+                                                        int& info_out, double& nd, double& nq, const Lap&)
+    {
+        const double wtu = (lane < r) ? L.slab[lane * LSW + LR + 1] : 0.0;       // Phi^T u
+        solve_add<PIV, W>(L, r, lane, wtu, aborted, info_out, nd, nq);
     }
 };
 

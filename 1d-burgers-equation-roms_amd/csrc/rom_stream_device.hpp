@@ -217,6 +217,47 @@ __device__ __forceinline__ void stream_park(const double (&acc)[StreamItems<K, G
     }
 }
 
+// The two row routines of a slab, for this loop and for the hyper-reduced one (rom_hyper.hip), which keeps the three stencil
+// rows of a sampled row side by side: `rows` is the first of three LDS rows PS doubles apart (basis rows i - 1, i, i + 1),
+// already at this lane's columns NB t .. NB t + NB - 1.
+// The lift u_{i-1}, u_i, u_{i+1} = Phi q of one row by its four lanes: qs = this lane's slice of q (s_q + NB t).  After the
+// two quad sums every lane of the quad holds the three values.
+template <int NB, int PS>
+__device__ __forceinline__ void stream_lift_rows(const double* rows, const double* qs, double& um, double& u0, double& ur)
+{
+    double sm = 0.0, s0 = 0.0, sr = 0.0;
+#pragma unroll
+    for (int c2 = 0; c2 < NB / 2; ++c2) {
+        const double2 qv = *reinterpret_cast<const double2*>(qs + 2 * c2);
+        const double2 pm = *reinterpret_cast<const double2*>(rows + 2 * c2);
+        const double2 p0 = *reinterpret_cast<const double2*>(rows + PS + 2 * c2);
+        const double2 pr = *reinterpret_cast<const double2*>(rows + 2 * PS + 2 * c2);
+        sm = __builtin_fma(pm.x, qv.x, sm); sm = __builtin_fma(pm.y, qv.y, sm);
+        s0 = __builtin_fma(p0.x, qv.x, s0); s0 = __builtin_fma(p0.y, qv.y, s0);
+        sr = __builtin_fma(pr.x, qv.x, sr); sr = __builtin_fma(pr.y, qv.y, sr);
+    }
+    sm += dpp_mov<0xB1>(sm); sm += dpp_mov<0x4E>(sm);
+    s0 += dpp_mov<0xB1>(s0); s0 += dpp_mov<0x4E>(s0);
+    sr += dpp_mov<0xB1>(sr); sr += dpp_mov<0x4E>(sr);
+    um = sm; u0 = s0; ur = sr;
+}
+
+// The operands of one row of a 16-row step: Y = lo Phi[i-1] + di Phi[i] + up Phi[i+1] (c01 = lo, di; c23 = up, R) and
+// P = Phi[i], this lane's NB columns of each.
+template <int NB, int PS>
+__device__ __forceinline__ void stream_row_operands(const double* rows, double2 c01, double2 c23, double (&Y)[NB], double (&P)[NB])
+{
+#pragma unroll
+    for (int c2 = 0; c2 < NB / 2; ++c2) {
+        const double2 tb = *reinterpret_cast<const double2*>(rows + 2 * c2);
+        const double2 tm = *reinterpret_cast<const double2*>(rows + PS + 2 * c2);
+        const double2 ta = *reinterpret_cast<const double2*>(rows + 2 * PS + 2 * c2);
+        P[2 * c2] = tm.x; P[2 * c2 + 1] = tm.y;
+        Y[2 * c2] = __builtin_fma(c23.x, ta.x, __builtin_fma(c01.y, tm.x, c01.x * tb.x));
+        Y[2 * c2 + 1] = __builtin_fma(c23.x, ta.y, __builtin_fma(c01.y, tm.y, c01.x * tb.y));
+    }
+}
+
 // The body of the kernel for wave W of the workgroup.  The wave number is a template parameter of the WHOLE body (the kernel
 // branches once, at its top): every wave runs its own quarter of the block pairs with accumulators that never change
 // registers.  A `switch (w)` around the matrix instructions of each row step instead cost 340 accumulator moves per
@@ -335,22 +376,7 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                         const int q4 = tid_i >> 2, i = r0 + q4;
                         double um, u0, ur;
                         if (lift) {
-                            const double* prow = s_P + q4 * PS + NB * pt;
-                            double sm = 0.0, s0 = 0.0, sr = 0.0;
-#pragma unroll
-                            for (int c2 = 0; c2 < NB / 2; ++c2) {
-                                const double2 qv = *reinterpret_cast<const double2*>(&s_q[NB * pt + 2 * c2]);
-                                const double2 pm = *reinterpret_cast<const double2*>(prow + 2 * c2);
-                                const double2 p0 = *reinterpret_cast<const double2*>(prow + PS + 2 * c2);
-                                const double2 pr = *reinterpret_cast<const double2*>(prow + 2 * PS + 2 * c2);
-                                sm = __builtin_fma(pm.x, qv.x, sm); sm = __builtin_fma(pm.y, qv.y, sm);
-                                s0 = __builtin_fma(p0.x, qv.x, s0); s0 = __builtin_fma(p0.y, qv.y, s0);
-                                sr = __builtin_fma(pr.x, qv.x, sr); sr = __builtin_fma(pr.y, qv.y, sr);
-                            }
-                            sm += dpp_mov<0xB1>(sm); sm += dpp_mov<0x4E>(sm);          // quad sums: every lane of the quad holds the three values
-                            s0 += dpp_mov<0xB1>(s0); s0 += dpp_mov<0x4E>(s0);
-                            sr += dpp_mov<0xB1>(sr); sr += dpp_mov<0x4E>(sr);
-                            um = sm; u0 = s0; ur = sr;                                 // rows outside the mesh are zero rows of PhiP
+                            stream_lift_rows<NB, PS>(s_P + q4 * PS + NB * pt, s_q + NB * pt, um, u0, ur);      // rows outside the mesh are zero rows of PhiP
                             if (pt == 0) s_u[i + 2] = u0;
                         } else {
                             um = s_u[i + 1]; u0 = s_u[i + 2]; ur = s_u[i + 3];
@@ -375,17 +401,8 @@ __device__ __forceinline__ void rom_stream_body(const typename K::Args& a, const
                             const int rl = 16 * st + 4 * pk + pblk;
                             const double2 c01 = *reinterpret_cast<const double2*>(&s_cf[cf0 + rl][0]);
                             const double2 c23 = *reinterpret_cast<const double2*>(&s_cf[cf0 + rl][2]);
-                            const double* pb = s_P + rl * PS + NB * pt;           // the row below (local row rl = mesh row r0 - 1 + rl)
-                            double Y[NB], P[NB];
-#pragma unroll
-                            for (int c2 = 0; c2 < NB / 2; ++c2) {
-                                const double2 tb = *reinterpret_cast<const double2*>(pb + 2 * c2);
-                                const double2 tm = *reinterpret_cast<const double2*>(pb + PS + 2 * c2);
-                                const double2 ta = *reinterpret_cast<const double2*>(pb + 2 * PS + 2 * c2);
-                                P[2 * c2] = tm.x; P[2 * c2 + 1] = tm.y;
-                                Y[2 * c2] = __builtin_fma(c23.x, ta.x, __builtin_fma(c01.y, tm.x, c01.x * tb.x));
-                                Y[2 * c2 + 1] = __builtin_fma(c23.x, ta.y, __builtin_fma(c01.y, tm.y, c01.x * tb.y));
-                            }
+                            double Y[NB], P[NB];                                  // from the row below (local row rl = mesh row r0 - 1 + rl) on
+                            stream_row_operands<NB, PS>(s_P + rl * PS + NB * pt, c01, c23, Y, P);
                             const double ui = s_u[r0 + rl + 2];
                             const double X = (pt == 0) ? c23.y : ((pt == 1) ? ui : 0.0);      // extra B block [R, u, 0, 0]
                             stream_step_mfma<K, GAL, W>(Y, P, X, acc);
