@@ -123,6 +123,11 @@ _SIGNATURES = {
     "bg_hyper_rom_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     # N, B, r, m, nsteps, projection, rows, xi, xs, PhiS, q0, u0s, mu1, mu2, the step, the outputs (qhist for hist)
     "bg_hyper_rom_run": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),
+    "bg_hyper_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 6),
+    "bg_hyper_ann_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
+    # N, B, n, nbar, m, nodes, nsteps, projection, node, xn, pos, xi, UTn, q0, u0n, mu1, mu2, the MLP, the step, qhist, qshist, ...
+    "bg_hyper_ann_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_int_p, c_double_p, c_int_p] + [c_double_p] * 6 + _ANN_MLP +
+                             _LOOP_STEP + [c_double_p] + _LOOP_OUT),
     "bg_rom_run_long_wide_max_n": (ctypes.c_int, []),
     "bg_rom_run_long_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_long_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),

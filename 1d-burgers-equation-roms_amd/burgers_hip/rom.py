@@ -64,6 +64,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
+    _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
 )}
 
 
@@ -1186,30 +1187,44 @@ def _ann_fused_plan(model, n, nbar, N, dtype, device, limits="bg_ann_rom_limits"
     """The closure as bg_ann_rom_run and bg_ann_rom_run_wide want it (``args``: its part of the argument list; ``keep``:
     the device copies those pointers refer to), or None when the device-side loop does not apply (not a plain fp32 MLP
     the evaluator recognises, or beyond ``limits``, the entry point's own ``*_limits`` symbol)."""
-    import ctypes
     if dtype != torch.float32 or N > 512:
         return None
-    ann = AnnEvaluator(model, n, dtype)
+    layers = _ann_model_layers(model, n, nbar, limits)
+    return None if layers is None else _ann_model_pack(layers, device)
+
+
+def _ann_model_layers(model, n, nbar, limits, count=4):
+    """The [(Linear, activation)] of a float32 ``model`` the evaluator recognises as a plain MLP (n) -> (nbar) inside the
+    first four of the ``count`` ints of the ``limits`` symbol (n, nbar, width, layers), or None.  Touches no device but
+    the model's own."""
+    ann = AnnEvaluator(model, n, torch.float32)
     if ann.layers is None:
         return None
-    max_n, max_nbar, max_w, max_l = _lib.limits(limits, 4)
+    max_n, max_nbar, max_w, max_l = _lib.limits(limits, count)[:4]
     widths = [ann.layers[0][0].in_features] + [lin.out_features for lin, _ in ann.layers]
     if (n > max_n or nbar > max_nbar or len(ann.layers) > max_l or max(widths[1:]) > max_w or widths[0] != n
             or widths[-1] != nbar or any(type(act) not in _ACT_KINDS for _, act in ann.layers)):
         return None
+    return ann.layers
+
+
+def _ann_model_pack(layers, device):
+    """``args`` and ``keep`` of _ann_fused_plan for the layers _ann_model_layers returned, packed on ``device``."""
+    import ctypes
+    widths = [layers[0][0].in_features] + [lin.out_features for lin, _ in layers]
     f32 = dict(dtype=torch.float32, device=device)
     # W^T zero-padded to [in rounded up to 4][out rounded up to 8]: a thread fetches the weights of 8 outputs of one input
     # as two 16-byte loads, four inputs at a time, with no bounds checks in the kernel
     wts = [torch.nn.functional.pad(lin.weight.detach().to(**f32).t(), (0, -lin.out_features % 8, 0, -lin.in_features % 4)).contiguous()
-           for lin, _ in ann.layers]
-    biases = [None if lin.bias is None else lin.bias.detach().to(**f32).contiguous() for lin, _ in ann.layers]
+           for lin, _ in layers]
+    biases = [None if lin.bias is None else lin.bias.detach().to(**f32).contiguous() for lin, _ in layers]
     nl = len(wts)
     return SimpleNamespace(keep=(wts, biases), args=(
         nl, (ctypes.c_int * (nl + 1))(*widths),
         (ctypes.c_void_p * nl)(*[w.data_ptr() for w in wts]),
         (ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in biases]),
-        (ctypes.c_int * nl)(*[_ACT_KINDS[type(act)] for _, act in ann.layers]),
-        (ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in ann.layers])))
+        (ctypes.c_int * nl)(*[_ACT_KINDS[type(act)] for _, act in layers]),
+        (ctypes.c_float * nl)(*[float(getattr(act, "alpha", 1.0)) for _, act in layers])))
 
 
 def _ann_device_loop(route, limits, ut_rows, X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device,
@@ -1257,6 +1272,138 @@ def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, 
                             X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
+class HyperAnnPlan:
+    """What bg_hyper_ann_rom_run reads besides the batch, built once per bases, closure, sampling and mesh
+    (include/burgers_hip.h): the table of the sorted distinct stencil nodes of the sampled rows (``nodes``, at most 3 m),
+    their coordinates ``xn``, the table position ``pos`` of every sampled row, the weights ``xi``, UTn = [U_p^T; U_s^T]
+    restricted to the table nodes, and the packed closure.  ``sampling``: a pod.RowSampling (pod.build_ann_row_sampling);
+    ``model``: a plain float32 MLP.  Everything the shapes, the sampling, the model and the bases decide is refused with a
+    ValueError before the device is touched -- also bases with |[U_p U_s]^T [U_p U_s] - I|_max > 1e-8: the loop carries q_p
+    from step to step instead of re-projecting U_p^T u^n, which is exact only for orthonormal bases."""
+
+    def __init__(self, U_p, U_s, model, sampling, X, device):
+        route = _ROUTES["bg_hyper_ann_rom_run"]
+        Up, Us = (np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64) for A in (U_p, U_s))
+        if Up.ndim != 2 or Us.ndim != 2 or Up.shape[0] != Us.shape[0] or Up.shape[1] < 1 or Us.shape[1] < 1:
+            raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
+        N, n, nbar = Up.shape[0], Up.shape[1], Us.shape[1]
+        Xh = check_mesh(X)
+        if N < route.min_n or N > _limit(route.max_n) or len(Xh) != N:
+            raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of U_p and U_s per mesh node")
+        max_n, max_nbar, max_w, max_l, max_m, max_nodes = _lib.limits("bg_hyper_ann_rom_limits", 6)
+        if n > max_n or nbar > max_nbar:
+            raise ValueError(f"{route.entry} covers n <= {max_n} and nbar <= {max_nbar} (got {n}, {nbar})")
+        rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
+        xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
+        m = len(rows)
+        if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
+            raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
+        if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
+            raise ValueError("the weights must be finite and >= 0")
+        if m > max_m:
+            raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+        if not isinstance(model, nn.Module) or any(p.dtype != torch.float32 for p in model.parameters()):
+            raise ValueError("the closure must be a plain float32 MLP (torch.nn.Module)")
+        layers = _ann_model_layers(model, n, nbar, "bg_hyper_ann_rom_limits", 6)
+        if layers is None:
+            raise ValueError(f"the closure must be a plain float32 MLP ({n}) -> ({nbar}) of Linear / ELU / ReLU / Tanh layers with "
+                             f"widths <= {max_w} and at most {max_l} layers")
+        U = np.concatenate([Up, Us], axis=1)
+        if not np.isfinite(U).all() or np.abs(U.T @ U - np.eye(n + nbar)).max() > 1e-8:
+            raise ValueError("[U_p U_s] must have orthonormal columns (to 1e-8): the loop does not re-project U_p^T u^n")
+        nodes = np.unique(np.clip(rows[:, None] + np.arange(-1, 2)[None, :], 0, N - 1))
+        if len(nodes) > max_nodes:
+            raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
+        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        device = _lib.require_device(device)
+        self.N, self.n, self.nbar, self.m, self.n_nodes, self.Xh = N, n, nbar, m, len(nodes), Xh.copy()
+        self.sampling = sampling
+        self.wg_per_cu = _lib.load().bg_hyper_ann_rom_workgroups_per_cu(len(nodes))
+        self.Up, self.Us = _as_dev(Up, device), _as_dev(Us, device)
+        self.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
+        self.node = self.nodes.to(torch.int32)
+        self.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
+        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+        self.xn = _as_dev(Xh[nodes], device)
+        UTn = np.zeros((-(-(n + nbar) // 8) * 8, len(nodes)))
+        UTn[:n + nbar] = U[nodes].T
+        self.UTn = _as_dev(UTn, device)
+        self.model = _ann_model_pack(layers, device)
+
+
+class HyperAnnRomResult:
+    """Result of pod_ann_run_hyper: the primary coordinates ``q`` (B, nT+1, n) and the closure values ``q_s`` (B, nT+1, nbar)
+    of every step's decode (column 0: U_p^T u0, and zeros: no closure value belongs to u0), ``iters``, ``flags``, ``info``
+    and the ``plan``.  ``hist``
+    (B, nT+1, N) is decoded on demand, U = U_p q + U_s q_s as one batched product -- the kernel's own decode, not a second
+    evaluation of the closure -- with u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
+    (B, N, nT+1) layout."""
+
+    def __init__(self, res, plan, u0d, q_s):
+        self.q, self.q_s, self.iters, self.flags, self.info, self.path = res.hist, q_s, res.iters, res.flags, res.info, res.path
+        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
+
+    @property
+    def hist(self):
+        if self._hist is None:
+            self._hist = torch.matmul(torch.cat([self.q, self.q_s], dim=2), torch.cat([self.plan.Up, self.plan.Us], dim=1).t())
+            self._hist[:, 0] = self._u0
+        return self._hist
+
+    def snapshots(self):
+        return FomResult(self.hist, self.iters, self.flags).snapshots()
+
+    @property
+    def newton_steps(self):
+        return int(self.iters.sum().item())
+
+
+def _project_rows(u, P, chunk=256):
+    """u (B, N) times P (N, n), every ``chunk`` rows as one product-and-sum of one fixed shape (the last chunk padded with
+    zero rows): a row's result does not depend on the batch around it, which a GEMM over the whole batch does not promise."""
+    B, N = u.shape
+    out = torch.empty((B, P.shape[1]), dtype=u.dtype, device=u.device)
+    for b0 in range(0, B, chunk):
+        rows = u[b0:b0 + chunk]
+        if rows.shape[0] < chunk:
+            rows = torch.cat([rows, rows.new_zeros((chunk - rows.shape[0], N))])
+        out[b0:b0 + chunk] = (rows[:, :, None] * P[None]).sum(dim=1)[:min(chunk, B - b0)]
+    return out
+
+
+def pod_ann_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=50,
+                      device=None, options=0, balance=True):
+    """``pod_ann_prom`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_ann_rom_run): both projections are
+    assembled from the sampled mesh rows of a pod.RowSampling (pod.build_ann_row_sampling) with their weights, on the table
+    of their stencil nodes, so an iteration costs the same whatever the mesh: N up to bg_fom_max_n(), n <= 8, m <= 256
+    (bg_hyper_ann_rom_limits).  q_p carries over from step to step (no U_p^T u^n: the bases must be orthonormal).
+    ``sampling_or_plan``: the sampling, or a HyperAnnPlan of these bases, closure, sampling and mesh to reuse across calls
+    (``res.plan``; ``U_p``, ``U_s`` and ``model`` are then not looked at).  A sampling trained for the other projection is
+    refused.  Nothing is synchronised.  Returns a HyperAnnRomResult."""
+    Xh = check_mesh(X)
+    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperAnnPlan) else HyperAnnPlan(U_p, U_s, model, sampling_or_plan, Xh, device)
+    device = _lib.require_device(device)
+    if plan.Up.device != device:
+        raise ValueError("the plan was built on another device")
+    if not np.array_equal(plan.Xh, Xh):
+        raise ValueError("the plan was built for another mesh")
+    if plan.projection != proj:
+        raise ValueError("the row sampling was trained for the other projection")
+    route = _ROUTES["bg_hyper_ann_rom_run"]
+    u0d, mu1d, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
+    B = mu1d.numel()
+    q0 = _project_rows(u0d, plan.Up)
+    u0n = u0d[:, plan.nodes].contiguous()
+    q_s = torch.empty((B, nsteps + 1, plan.nbar), dtype=torch.float64, device=device)
+    res = _device_loop(route, Xh, u0d, mu1, mu2, nsteps, device, options, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.n, plan.nbar, plan.m, plan.n_nodes, int(nsteps), proj, _lib.ptr(plan.node), _lib.ptr(plan.xn),
+                           _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn), _lib.ptr(q0), _lib.ptr(u0n), *inputs[1:],
+                           *plan.model.args, float(dt), float(E), float(tol), int(max_it), opts, outputs[0], _lib.ptr(q_s),
+                           *outputs[1:]), keep=(plan, q0, u0n, q_s), slots=plan.wg_per_cu * _cu_count(device), cols=plan.n)
+    return HyperAnnRomResult(res, plan, u0d, q_s)
+
+
 def _ann_route(n, fused=True, wide=False):
     """The device-side loops pod_ann_run tries, in order: bg_ann_rom_run_wide first only for an opted-in model with more
     primary modes than bg_ann_rom_run takes."""
@@ -1266,15 +1413,22 @@ def _ann_route(n, fused=True, wide=False):
 
 
 def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG", E=0.0, tol=1e-6, max_it=50,
-                device=None, ann_dtype=torch.float32, fused=True, wide=False):
+                device=None, ann_dtype=torch.float32, fused=True, wide=False, hyper=None):
     """Batched ``pod_ann_prom``.  The MLP and its Jacobian are evaluated in ``ann_dtype`` (the
     reference uses float32, :1219,:1241); everything else is fp64.  ``fused`` (default): the device-side time loop
     bg_ann_rom_run when the closure is a plain float32 MLP within bg_ann_rom_limits; otherwise, or with
     ``fused=False``, the batched iteration driven from the host (MLP layers as GEMMs through PyTorch-ROCm).
     ``wide`` (opt-in, with ``fused`` and float32): a model with more primary modes than bg_ann_rom_limits allows that is
     inside bg_ann_rom_run_wide_limits (n <= 20) takes the device-side loop bg_ann_rom_run_wide instead of the host-driven
-    iteration; every other model routes as without the flag."""
+    iteration; every other model routes as without the flag.
+    ``hyper`` (opt-in): a pod.RowSampling (pod.build_ann_row_sampling) or a HyperAnnPlan sends the call through the
+    hyper-reduced loop pod_ann_run_hyper, which assembles both projections from the sampled mesh rows only; models, bases
+    and sizes it does not cover are refused, not rerouted."""
     proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
+    if hyper is not None:
+        if ann_dtype != torch.float32:
+            raise ValueError("the hyper-reduced POD-ANN loop evaluates the closure in float32")
+        return check_singular(pod_ann_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, hyper, proj, E, tol, max_it, device))
     if ann_dtype == torch.float32:
         for entry in _ann_route(np.shape(U_p)[1], fused, wide):
             run = pod_ann_run_wide if entry == "bg_ann_rom_run_wide" else pod_ann_run_fused

@@ -1,0 +1,535 @@
+// rom_ann_loop_device.hpp -- the POD-ANN PROM time loop of one sample on one 256-thread workgroup, as a body two kernels
+// instantiate: rom_ann_fused.hip (bg_ann_rom_run: the mesh itself, N <= 512) and rom_hyper_ann.hip (bg_hyper_ann_rom_run: the
+// compacted mesh of a row sampling's stencil nodes, any N).  The phases of an iteration and what they cost are described in
+// rom_ann_fused.hip; this file holds the sweep and its table s_dN, the input set-up (s_qlast), pivoted_gj8, the LDS overlay
+// and the loop.  The closure MLP is rom_ann_device.hpp's.
+//
+// The hyper-reduced form (Args = HyperAnnRunArgs).  Both projections are sums over mesh rows, Ar = sum_i w_i^T y_i and
+// br = sum_i w_i^T R_i, and row i needs the state, the tangent and the coordinates at nodes i - 1, i, i + 1 only.  The caller
+// packs the sorted distinct stencil nodes of the m sampled rows (node[k], k < nodes <= 3 m) with their coordinates and the
+// rows of [U_p | U_s] at them; the three stencil nodes of a sampled row are consecutive integers and therefore consecutive
+// table entries, so the table is a mesh on which a sampled row's neighbours are its table neighbours, and the whole body
+// runs on it with `nodes` for N: the sweep forms tangent and decode at the table nodes, forcing and mass row read the table
+// coordinates as a non-uniform mesh x.  What differs:
+//   - a table node that is only a neighbour assembles as a row outside the mesh (an identity row) and every coefficient is
+//     multiplied by the row's weight xi (Galerkin) or sqrt(xi) (LSPG), 0 there -- its row vanishes from both sums; whether a
+//     sampled row is the Dirichlet row or the last row is decided by node[k] (a sampled row 0 is table node 0 and a sampled
+//     row N - 1 the last table node, so forcing and mass row may ask the table index);
+//   - the run starts from q_p = q0 and u0 gathered at the table nodes, and q_p carries over from step to step: there is no
+//     U_p^T u^n (equal to q_p for orthonormal [U_p U_s]), so the first pass of a step always meets the float32 input of the
+//     previous evaluation and reuses its tangent;
+//   - the outputs are q_p and the closure value q_s = N(q_p) of every step's decode; no vector of mesh length is touched.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "../../include/burgers_hip.h"
+#include "abi_common.hpp"
+#include "rom_ann_device.hpp"
+
+namespace bg {
+namespace fused {
+
+// bg_hyper_ann_rom_run: x, UT, u0 are the table's xn [nodes], UTn [m8][nodes], u0n [B][nodes]; hist is qhist [B][nsteps+1][n];
+// N is the mesh's node count (it decides the last row), nonuniform is not read (the table is a non-uniform mesh)
+struct HyperAnnRunArgs : AnnRunArgs {
+    const int32_t* node;    // [nodes] ascending mesh nodes of the table
+    const int32_t* pos;     // [nrows] table position of every sampled row
+    const double* xi;       // [nrows] weights
+    const double* q0;       // [B][n]
+    double* qshist;         // [B][nsteps+1][nbar]
+    int nodes, nrows;
+};
+
+// rows of the mesh the body works on
+__device__ __forceinline__ int ann_loop_rows(const AnnRunArgs& a) { return a.N; }
+__device__ __forceinline__ int ann_loop_rows(const HyperAnnRunArgs& a) { return a.nodes; }
+// ... and whether its element lengths come from x (the table always is a non-uniform mesh)
+__device__ __forceinline__ int ann_loop_nonuniform(const AnnRunArgs& a) { return a.nonuniform; }
+__device__ __forceinline__ int ann_loop_nonuniform(const HyperAnnRunArgs&) { return 1; }
+
+// Issue priority of the phases (see rom_fused.hip): 3 by default, 0 in the phases named by this bit mask -- 1 the sweep
+// over [U_p | U_s], 2 the closure MLP, 4 the projection.  Measured (B = 2048): 0 (no priorities) 1.312e7, 1: 1.322e7,
+// 3: 1.329e7, 5 / 7: 1.327e7 -- the solve, assembly and update chains of one workgroup no longer queue behind the other's bulk phases.
+#ifndef BG_ANN_PRIO
+#define BG_ANN_PRIO 3
+#endif
+constexpr int ANN_MAX_N = 8;            // reduced coordinates: two 4-column MFMA blocks
+constexpr int ANN_MAX_ROWS = 1 + ANN_MAX_N;
+
+// value of lane `src` (any lane), two ds_bpermute
+__device__ __forceinline__ double lane_f64(double v, int src)
+{
+    const int lo = __builtin_amdgcn_ds_bpermute(4 * src, __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute(4 * src, __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// x = solve(Ar, -br) for n <= 8 with np.linalg.solve's pivot choice (the not-yet-used row with the largest |a[k]|, ties
+// to the lowest row, as lu_pivoted_wave), one wavefront, the WHOLE system spread over the lanes: lane 8 i + j holds
+// a[i][j] and a copy of b[i].  Per step: the column entry of the own row and the pivot row's entry of the own column by
+// ds_bpermute, one rank-1 update of all 64 entries; the rows above the pivot are eliminated too (Gauss-Jordan), so what is
+// left is diagonal and there is no back substitution.  lu_pivoted_wave<8> (lane = row, eight serial steps whatever n is,
+// a readlane pair per entry, then eight dependent back-substitution steps) took 10.8 k clocks per call here.
+template <bool GAL>
+__device__ __forceinline__ void pivoted_gj8(const double (*__restrict__ s_red)[8][12], double* __restrict__ s_x,
+                                            int* __restrict__ s_info, int lane, int n)
+{
+    const int i = lane >> 3, j = lane & 7;
+    auto entry = [&](int r, int c) -> double {               // (Ar | br)[r][c], c <= 8; LSPG: mirror the lower blocks
+        int rr = r, cc = c;
+        if (!GAL && c < 8 && (r >> 2) > (c >> 2)) { rr = c; cc = r; }
+        return (s_red[0][rr][cc] + s_red[1][rr][cc]) + (s_red[2][rr][cc] + s_red[3][rr][cc]);
+    };
+    double A = (i < n && j < n) ? entry(i, j) : (i == j ? 1.0 : 0.0);
+    double rb = (i < n) ? -entry(i, 8) : 0.0;
+    bool used = false;
+    int my_step = -1, info = 0;
+    if (lane < 8) s_x[lane] = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const double ck = lane_f64(A, (lane & ~7) | k);                      // a[i][k]
+        const unsigned key = used ? 0u : (((unsigned)__double2hiint(ck) & 0x7fffffffu) + 1u);
+        const unsigned best = wave_max_u32(key);
+        const unsigned long long m = __ballot(key == best && !used);
+        const int p = __builtin_ctzll(m) >> 3;                               // lowest candidate row
+        const double piv = readlane_f64(A, 8 * p + k);
+        if (piv == 0.0 && info == 0) info = k + 1;
+        const double rp = rcp(piv);
+        const double prow = lane_f64(A, 8 * p + j);                          // a[p][j]
+        const double pb = readlane_f64(rb, 8 * p);
+        const double mult = (i == p) ? 0.0 : ck * rp;
+        A = __builtin_fma(-mult, prow, A);
+        rb = __builtin_fma(-mult, pb, rb);
+        if (i == p) { used = true; my_step = k; }
+    }
+    if (j == my_step) s_x[my_step] = rb * rcp(A);                            // the row that pivoted at step k holds x_k
+    if (lane == 0) *s_info = info;
+}
+
+}  // namespace fused
+}  // namespace bg
+
+namespace {
+
+using namespace bg;
+using namespace bg::fused;
+
+// WG: workgroups resident per compute unit (the register budget)
+template <int S, int PROJ, int WG, class Args>
+__global__ __launch_bounds__(256, WG) void ann_loop_kernel(Args a)
+{
+    constexpr bool HYPER = std::is_same<Args, HyperAnnRunArgs>::value;
+    constexpr int NB = 2;
+    constexpr int NPAD = 64 * S;
+    constexpr int RW = 4 * NB;
+    constexpr bool GAL = PROJ == BG_PROJ_GALERKIN;
+    __shared__ double s_u[NPAD + 4];             // u at offset 2, zero halo on each side
+    __shared__ double s_g[NPAD], s_h[NPAD];
+    __shared__ __attribute__((aligned(16))) double s_W[NPAD + 2][RW];      // tangent rows, row i at [i + 1]; zero rows around and beyond N
+    __shared__ double s_wtu[4][RW];
+    __shared__ double s_q[RW], s_x[RW];
+    __shared__ float s_qlast[RW];                // float32 input of the latest full closure evaluation (see the step start)
+    __shared__ double s_part[4][RW];             // per-wave partial sums of U_p^T u
+    __shared__ int s_info;
+    // The two halves of an iteration never overlap in time and share one block of LDS (two workgroups per CU need
+    // <= 80 KB each):  projection + solve: s_coef, s_halo, s_red   |   closure: s_act, s_dN
+    constexpr int kCoefB = NPAD * 4 * 8, kHaloB = 2 * NB * 256 * 8, kRedB = 4 * RW * (RW + 4) * 8;
+    constexpr int kSweepDepth = 3;                 // register buffers of the sweep (groups of 4 modes in flight + 1); 6 measured slower
+    constexpr int kModes = ANN_MAX_NBAR + ANN_MAX_N + 4 * kSweepDepth;   // secondary + primary modes of the sweep + zero modes that round its trip count up
+    constexpr int kBW = 12;                        // columns of the sweep's right-hand matrix: n derivatives + 1 coefficient, padded to 3 blocks of 4
+    constexpr int kBS = 13;                        // its row stride in doubles (odd: the row-per-lane writes spread over the banks)
+    constexpr int kActB = 2 * ANN_MAX_ROWS * ANN_MAX_WIDTH * 4, kDnB = kModes * kBS * 8;
+    constexpr int kPhaseA = kCoefB + kHaloB + kRedB, kPhaseB = kActB + kDnB;
+    __shared__ __attribute__((aligned(16))) unsigned char s_shared[kPhaseA > kPhaseB ? kPhaseA : kPhaseB];
+    auto& s_coef = *reinterpret_cast<double (*)[NPAD][4]>(s_shared);
+    auto& s_halo = *reinterpret_cast<double (*)[2][NB][256]>(s_shared + kCoefB);
+    auto& s_red = *reinterpret_cast<double (*)[4][RW][RW + 4]>(s_shared + kCoefB + kHaloB);
+    auto& s_act = *reinterpret_cast<float (*)[2][ANN_MAX_ROWS][ANN_MAX_WIDTH]>(s_shared);   // MLP activations: value row + n tangent rows
+    auto& s_dN = *reinterpret_cast<double (*)[kModes][kBS]>(s_shared + kActB);              // mode j of the sweep: [d(coefficient j)/dq_p | coefficient j | 0]
+
+    // The thread-index family is re-derived from an opaque copy at the top of every Gauss-Newton pass (see the time loop):
+    // per-lane addresses are loop invariants of the whole kernel, and hoisted out of the loops by the dozen they end up in
+    // scratch (round 3: the same measure took bg_rom_run's kernels from 160 / 280 to 12 / 152 bytes).
+    int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction
+    int t = lane & 3, owner = 16 * w + (lane >> 2);
+    const int N = ann_loop_rows(a), n = a.n, nbar = a.nbar, nr = 1 + a.n, m8 = (a.n + a.nbar + 7) & ~7;
+    const double h = HYPER ? 1.0 : (a.x[N - 1] - a.x[0]) / (double)(N - 1);      // (not read on a non-uniform mesh)
+    int rowbase = owner * S;
+    auto rederive = [&]() {
+        int v = threadIdx.x;
+        asm volatile("" : "+v"(v));
+        tid = v; lane = v & 63; t = lane & 3; owner = 16 * w + (lane >> 2); rowbase = owner * S;
+    };
+
+#ifdef BG_ANN_LDS_PAD                              // timing builds only: extra LDS, so that one workgroup fills a CU
+    __shared__ volatile int s_pad[BG_ANN_LDS_PAD / 4];
+    if (a.B < 0) s_pad[threadIdx.x] = 1;
+#endif
+    if (tid < 4) s_u[tid < 2 ? tid : NPAD + tid] = 0.0;
+    for (int e = tid; e < (NPAD + 2) * RW; e += 256) (&s_W[0][0])[e] = 0.0;
+    if (tid < RW) s_q[tid] = 0.0;
+
+    using Clock = PhaseClock<kTiming || kPhaseClock, 16>;        // diagnostic builds (tools/time_ann_fused.py): one per sample
+    // ---- N(q_p) and dN/dq_p at q_p = s_q, float32 forward mode: rows 0 = value, 1 .. n = tangent directions (ann_layers),
+    // then the sweep's table.  NRT = rows compiled in.
+    auto mlp_impl = [&](auto nrt_c, Clock& clk) __attribute__((always_inline)) {
+        constexpr int NRT = decltype(nrt_c)::value;
+        if (tid < RW) {                                              // inputs padded with zeros to a multiple of 4
+            s_act[0][0][tid] = tid < n ? (float)s_q[tid] : 0.0f;
+            s_qlast[tid] = tid < n ? (float)s_q[tid] : 0.0f;
+#pragma unroll
+            for (int r = 1; r < ANN_MAX_ROWS; ++r) s_act[0][r][tid] = (r - 1 == tid && tid < n) ? 1.0f : 0.0f;
+        }
+        __syncthreads();
+        clk.lap(14);
+        const int cur = ann_layers<NRT, 2, NRT == 6 || NRT == 1, true>(a.m, s_act, tid, lane, w, clk);
+        // the sweep's right-hand matrix: row j = mode j = [d c_j / d q_p (n columns) | c_j | zeros]; modes 0 .. n-1 are the
+        // primary ones (c = q_p, derivative = identity), modes n .. n+nbar-1 the closure outputs, the rest (up to m8) zero
+        // (all reads unconditional, all choices selects: the branchy form of this table took 4.7 k clocks)
+        if (tid < m8 + 4 * kSweepDepth) {
+            const int j = tid - n;
+            const bool prim = tid < n, sec = j >= 0 && j < nbar;
+            const int jj = sec ? j : 0;
+            float rv[NRT];
+#pragma unroll
+            for (int r = 0; r < NRT; ++r) rv[r] = s_act[cur][r][jj];
+            const double qv = s_q[tid & (RW - 1)];
+            const double cv = prim ? qv : (sec ? (double)rv[0] : 0.0);
+#pragma unroll
+            for (int c = 0; c < kBW; ++c) {
+                double dv = 0.0;
+                if (c < ANN_MAX_N && 1 + c < NRT) {                      // compile-time
+                    const double d = prim ? (tid == c ? 1.0 : 0.0) : (sec ? (double)rv[(1 + c < NRT) ? 1 + c : 0] : 0.0);
+                    dv = c < n ? d : 0.0;
+                }
+                dv = (c == n) ? cv : dv;
+                s_dN[tid][c] = dv;
+            }
+        }
+        __syncthreads();
+        clk.lap(11);
+    };
+    // value_only: an evaluation that feeds the decode alone leaves the n tangent rows -- 5/6 of the layer arithmetic at n = 5 --
+    // out; row 0 is computed by the same operations in the same order either way (same slices, same fold).
+    auto mlp = [&](bool value_only, Clock& clk) __attribute__((always_inline)) {
+        if (value_only) mlp_impl(std::integral_constant<int, 1>{}, clk);
+        else if (nr <= 6) mlp_impl(std::integral_constant<int, 6>{}, clk);
+        else mlp_impl(std::integral_constant<int, ANN_MAX_ROWS>{}, clk);
+    };
+
+    // ---- one sweep over [U_p | U_s]: T = U . B with B = s_dN gives the tangent W = U_p + U_s dN (columns 0 .. n-1, into
+    // s_W) and the decode u = U_p q_p + U_s N(q_p) (column n, into s_u) together, on v_mfma_f64_4x4x4_4b: block = 4 mesh
+    // rows, A = U^T[4 modes][those rows] straight from L2 (one double per lane), B = 4 modes x 4 columns from LDS -- one
+    // 512-byte read per (4 modes, 4 columns) for the whole wave instead of a broadcast 16-byte read per lane, mode and
+    // column pair, which made the LDS pipe the limit of the VALU form of this sweep (2.1 k clocks per 8 modes).
+    auto closure_impl = [&](auto ncb_c, auto full_c, bool decode) __attribute__((always_inline)) {
+        constexpr int NCB = decltype(ncb_c)::value;                            // column blocks compiled in: n derivatives + 1 coefficient
+        constexpr bool FULL = decltype(full_c)::value;                         // N == NPAD: no ragged last lanes
+        const int ak = lane >> 4, ablk = (lane >> 2) & 3, aij = lane & 3;      // A / B operand lane: 16 k + 4 blk + (i | j)
+        const int wrow = 16 * S * w;                                           // first mesh row of this wave
+        // MFMA number tl of a trip works on the rows wrow + S (4 blk + i) + tl: a lane's S rows are consecutive, so its share
+        // of 4 modes x 16 S rows is S / 2 16-byte loads, and 16 neighbouring lanes read 128 S contiguous bytes of a mode
+        const int lrow = wrow + S * (4 * ablk + aij);
+        auto fetch = [&](int kc, double (&dst)[S]) {
+            const double* src = a.UT + (size_t)(4 * kc + ak) * N;
+            if constexpr (FULL) {
+#pragma unroll
+                for (int tl = 0; tl < S; tl += 2) {
+                    const double2 v = *reinterpret_cast<const double2*>(src + lrow + tl);
+                    dst[tl] = v.x; dst[tl + 1] = v.y;
+                }
+            } else {
+#pragma unroll
+                for (int tl = 0; tl < S; ++tl) dst[tl] = src[lrow + tl < N ? lrow + tl : N - 1];   // dropped below
+            }
+        };
+        double acc[S][NCB];
+#pragma unroll
+        for (int tl = 0; tl < S; ++tl)
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) acc[tl][cb] = 0.0;
+        auto mma = [&](int kc, const double (&av)[S]) {
+            double bv[NCB];
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) bv[cb] = s_dN[4 * kc + ak][4 * cb + aij];
+#pragma unroll
+            for (int tl = 0; tl < S; ++tl)
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) acc[tl][cb] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[tl], bv[cb], acc[tl][cb], 0, 0, 0);
+        };
+        // groups of 4 modes, a ring of DEPTH register buffers: DEPTH - 1 groups in flight while one is multiplied.  Three
+        // is enough: the sweep moves 393 KB per evaluation at 24 B/clk per workgroup, with two workgroups on the CU close to
+        // what the 64 B/clk vector-memory return path gives; six buffers measured 7 % slower.  The trip count is rounded up to a multiple of DEPTH (the extra groups meet zero rows of B; their fetches
+        // are clamped to the last real group): no guards anywhere in the loop.
+        constexpr int DEPTH = kSweepDepth;
+        const int kcn = skip(256) ? 0 : m8 / 4;                                // (256: timing builds only)
+        const int kcl = kcn - 1;
+        double ab[DEPTH][S];
+        if (kcn > 0) {
+#pragma unroll
+            for (int d = 0; d < DEPTH - 1; ++d) fetch(d < kcl ? d : kcl, ab[d]);
+        }
+        for (int kc = 0; kc < kcn; kc += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; ++d) {
+                const int nx = kc + d + DEPTH - 1;
+                fetch(nx < kcl ? nx : kcl, ab[(d + DEPTH - 1) % DEPTH]);
+                mma(kc + d, ab[d]);
+            }
+        }
+        // result lane: 16 i + 4 blk + j holds T[row S (4 blk + i) + tl][column 4 cb + j]
+        const int di = lane >> 4, dblk = (lane >> 2) & 3, dj = lane & 3;
+#pragma unroll
+        for (int tl = 0; tl < S; ++tl) {
+            const int row = wrow + S * (4 * dblk + di) + tl;
+            const bool in = row < N;
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {
+                const int col = 4 * cb + dj;
+                const double v = in ? acc[tl][cb] : 0.0;
+                if (col < n) s_W[row + 1][col] = v;
+                if (col == n && decode) s_u[row + 2] = v;
+            }
+        }
+        __syncthreads();
+    };
+    auto closure = [&](bool decode) __attribute__((always_inline)) {
+        using T = std::true_type; using F = std::false_type;
+        if (n <= 7) { if (N == NPAD) closure_impl(std::integral_constant<int, 2>{}, T{}, decode); else closure_impl(std::integral_constant<int, 2>{}, F{}, decode); }
+        else { if (N == NPAD) closure_impl(std::integral_constant<int, 3>{}, T{}, decode); else closure_impl(std::integral_constant<int, 3>{}, F{}, decode); }
+    };
+
+    // ---- hyper-reduced form: the mesh row (a.N: not sampled, an identity row) and the weight factor of this thread's table
+    // nodes i = tid (+ 256), the same for every sample; scattered from pos / xi through the LDS the phases share
+    int hnode[S / 4];
+    double hmul[S / 4];
+    if constexpr (HYPER) {
+        int* s_smp = reinterpret_cast<int*>(s_shared);          // [NPAD]: 1 + the sampled row at this table node, or 0
+        static_assert(NPAD * 4 <= sizeof(s_shared), "the scatter table fits the shared block");
+        for (int k = tid; k < NPAD; k += 256) s_smp[k] = 0;
+        __syncthreads();
+        for (int j = tid; j < a.nrows; j += 256) {
+            const int p = a.pos[j];
+            if ((unsigned)p < (unsigned)N) s_smp[p] = j + 1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ii = 0; ii < S / 4; ++ii) {
+            const int k = tid + 256 * ii;
+            int j = s_smp[k];
+            const int ir = j ? a.node[k] : a.N;
+            // (a sampled row whose neighbour the table does not hold -- not a table the contract allows -- is left out)
+            if ((unsigned)ir >= (unsigned)a.N || (ir > 0 && k == 0) || (ir < a.N - 1 && k == N - 1)) j = 0;
+            const double xi = j ? a.xi[j - 1] : 0.0;
+            hnode[ii] = j ? ir : a.N;
+            hmul[ii] = GAL ? xi : sqrt(xi);
+        }
+    }
+#if BG_ANN_PRIO
+    __builtin_amdgcn_s_setprio(3);
+#endif
+    for (int slot = blockIdx.x; slot < a.B; slot += gridDim.x) {
+        const int smp = a.order ? a.order[slot] : slot;
+        if constexpr (HYPER) {
+            if ((unsigned)smp >= (unsigned)a.B) continue;        // workgroup-uniform
+        }
+        const double mu1 = a.mu1[smp], mu2 = a.mu2[smp];
+        Clock clk;
+        double* hist = a.hist + (size_t)smp * (size_t)(a.nsteps + 1) * (size_t)(HYPER ? n : N);      // HYPER: q_p of every step
+        __syncthreads();
+        // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
+        double fdt[S / 4];                          // dt F of this thread's rows i = tid (+ 256)
+#pragma unroll
+        for (int ii = 0; ii < S / 4; ++ii) {
+            const int i = tid + 256 * ii;
+            double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
+            if (i < N) {
+                rom_nodal_forcing(a.x, i, N, mu2, h, ann_loop_nonuniform(a), frPrev, fl, hf);
+                u = a.u0[(size_t)smp * N + i];
+                if constexpr (!HYPER) hist[i] = u;
+            }
+            fdt[ii] = a.dt * (frPrev + fl);
+            s_h[i] = hf;
+            s_u[i + 2] = u;
+        }
+        if constexpr (HYPER) {                      // q_p = q0 (the caller's U_p^T u0); no closure value belongs to u0
+            const HyperAnnRunArgs& ha = a;
+            if (tid < RW) {
+                const double q = tid < n ? ha.q0[(size_t)smp * n + tid] : 0.0;
+                s_q[tid] = q;
+                if (tid < n) hist[tid] = q;
+            }
+            for (int j = tid; j < nbar; j += 256) ha.qshist[(size_t)smp * (size_t)(a.nsteps + 1) * (size_t)nbar + j] = 0.0;
+        }
+        __syncthreads();
+
+        int flags = 0, info_out = 0;
+        bool have_tangent = false;                 // s_W holds U_p + U_s dN at the float32 input s_qlast
+        for (int step = 0; step < a.nsteps && info_out == 0; ++step) {
+            // ---- g = M u^n + dt F (:1214) and q_p = U_p^T u^n (:1197); HYPER: g at the table nodes, q_p carries over ---------
+            if constexpr (HYPER) {
+#pragma unroll
+                for (int ii = 0; ii < S / 4; ++ii) {
+                    const int i = tid + 256 * ii;
+                    s_g[i] = i < N ? rom_mass_rhs_node(a.x, i, N, s_u[i + 1], s_u[i + 2], s_u[i + 3], fdt[ii], h, ann_loop_nonuniform(a)) : 0.0;
+                }
+                __syncthreads();                    // the previous step's history rows have been read from s_dN
+            } else {
+                double part[ANN_MAX_N];
+#pragma unroll
+                for (int c = 0; c < ANN_MAX_N; ++c) part[c] = 0.0;
+#pragma unroll
+                for (int ii = 0; ii < S / 4; ++ii) {
+                    const int i = tid + 256 * ii;
+                    double g = 0.0;
+                    if (i < N) {
+                        const double uc = s_u[i + 2];
+                        g = rom_mass_rhs_node(a.x, i, N, s_u[i + 1], uc, s_u[i + 3], fdt[ii], h, ann_loop_nonuniform(a));
+#pragma unroll
+                        for (int c = 0; c < ANN_MAX_N; ++c)
+                            if (c < n) part[c] = __builtin_fma(a.UT[(size_t)c * N + i], uc, part[c]);
+                    }
+                    s_g[i] = g;
+                }
+#pragma unroll
+                for (int c = 0; c < ANN_MAX_N; ++c) {
+                    if (c < n) {
+                        const double sm = wave_sum(part[c]);
+                        if (lane == 0) s_part[w][c] = sm;
+                    }
+                }
+                __syncthreads();
+                if (tid < RW) s_q[tid] = (tid < n) ? (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]) : 0.0;
+                __syncthreads();
+            }
+            // The tangent of the first pass is dN at (float) U_p^T u^n (:1197, :1219).  u^n is the decode of the previous
+            // step's last q_p, so U_p^T u^n is that q_p up to 1e-15 and its float32 image is, as a rule, the very input of the
+            // previous step's last evaluation -- whose tangent is still in s_W.  When the eight floats are bitwise equal the
+            // evaluation would reproduce it bit for bit and is skipped; otherwise (first step, a rounding boundary) it runs.
+            bool skip_eval = have_tangent && !kTiming && !a.no_reuse;
+#pragma unroll
+            for (int c = 0; c < RW; ++c) skip_eval = skip_eval && ((c < n ? (float)s_q[c] : 0.0f) == s_qlast[c]);
+            clk.lap(13);
+            int k = 0;
+            bool more = true, decode = false;
+            while (true) {
+                rederive();
+                // ---- closure at the current q_p (one call site: the code is inlined once).  First pass of a time step:
+                // dN at the first guess (:1219), tangent only, U0 stays u^n.  Later passes: q_s = N(q_p) for the decode
+                // (:1241-1242) and dN for the next projection (:1219-1224).
+                clk.lap(2);
+                if (!skip_eval) {
+                    // the last evaluation of the last step feeds the decode alone: value only
+                    const bool value_only = !more && step == a.nsteps - 1 && !kTiming;
+#if BG_ANN_PRIO & 2
+                    __builtin_amdgcn_s_setprio(0);
+#endif
+                    mlp(value_only, clk);
+#if BG_ANN_PRIO & 1
+                    __builtin_amdgcn_s_setprio(0);
+#endif
+                    closure(decode);
+#if BG_ANN_PRIO
+                    __builtin_amdgcn_s_setprio(3);
+#endif
+                    have_tangent = !value_only;
+                }
+                skip_eval = false;
+                clk.lap(12);
+                if (!more) break;
+                decode = true;
+                // ---- assembly: A(u_k), R(u_k) per row into LDS ----------------------------------------------------
+                if constexpr (HYPER) {
+                    // table node i as mesh row hnode (a.N where the node is only a neighbour: an identity row, weight 0), the
+                    // table coordinates as the x[ir - 1], x[ir], x[ir + 1] of the row routine, the weight in the coefficients
+#pragma unroll
+                    for (int ii = 0; ii < S / 4; ++ii) {
+                        const int i = tid + 256 * ii, ir = hnode[ii];
+                        double lo, di, up, R;
+                        const bool in = ir < a.N;
+                        const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
+                        rom_assemble_row(ir, a.N, s_u[i + 1], s_u[i + 2], s_u[i + 3], in ? s_g[i] : 0.0,
+                                         (in && ir > 0) ? s_h[i - 1] : 0.0, (in && ir < a.N - 1) ? s_h[i] : 0.0, mu1, mc,
+                                         ann_loop_nonuniform(a), a.x + (in ? i - ir : 0), a.dt, a.E, lo, di, up, R);
+                        const double wm = hmul[ii];
+                        s_coef[i][0] = wm * lo; s_coef[i][1] = wm * di; s_coef[i][2] = wm * up; s_coef[i][3] = wm * R;
+                    }
+                } else
+                for (int i = tid; i < (skip(16) ? 0 : NPAD); i += 256) {
+                    double lo, di, up, R;
+                    const bool in = i < N;
+                    const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
+                    rom_assemble_row(i, N, s_u[i + 1], s_u[i + 2], (i + 1 < N) ? s_u[i + 3] : 0.0, in ? s_g[i] : 0.0,
+                                     (in && i > 0) ? s_h[i - 1] : 0.0, (in && i < N - 1) ? s_h[i] : 0.0, mu1, mc,
+                                     ann_loop_nonuniform(a), a.x, a.dt, a.E, lo, di, up, R);
+                    s_coef[i][0] = lo; s_coef[i][1] = di; s_coef[i][2] = up; s_coef[i][3] = R;
+                }
+                // ---- tangent fragments of this lane from LDS (the tangent changes every iteration) ----------------
+                double frag[NB][S];
+#pragma unroll
+                for (int c = 0; c < NB; ++c) {
+#pragma unroll
+                    for (int s = 0; s < S; ++s) frag[c][s] = s_W[rowbase + s + 1][4 * c + t];
+                    s_halo[0][c][tid] = s_W[rowbase][4 * c + t];
+                    s_halo[1][c][tid] = s_W[rowbase + S + 1][4 * c + t];
+                }
+                __syncthreads();
+                clk.lap(0);
+#if BG_ANN_PRIO & 4
+                __builtin_amdgcn_s_setprio(0);
+#endif
+                if constexpr (!skip(1))
+                    mfma_pass<S, NB, GAL, 0, NB, true, RW>(frag, HaloTable<NB>{s_halo, tid}, s_coef, s_u, rowbase, t, w, lane, s_red, s_wtu);
+#if BG_ANN_PRIO & 4
+                __builtin_amdgcn_s_setprio(3);
+#endif
+                __syncthreads();
+                clk.lap(1);
+                // ---- reduced solve -------------------------------------------------------------------------------
+                // np.linalg.solve's partial-pivoting elimination by wave 0 (pivoted_gj8).  The guarded pivot-free
+                // elimination of bg_rom_run does not apply here: the columns of U_p + U_s dN are far from orthonormal, the
+                // multipliers exceed 1 in nearly every system, and LAPACK does leave the diagonal.
+                if (tid == 0) s_info = 0;
+                __syncthreads();
+                if (w == 0 && !skip(2)) pivoted_gj8<GAL>(s_red, s_x, &s_info, lane, n);
+                __syncthreads();
+                const double xout = (lane < RW) ? s_x[lane] : 0.0;
+                if (s_info != 0 && info_out == 0) info_out = s_info;
+                // ---- q_p += dq, err = |dq| / (|q_p| + 1e-14)  (:1238-1244) -----------------------------------------
+                const double dq = (lane < n) ? xout : 0.0;
+                const double qn = (lane < n) ? s_q[lane] + dq : 0.0;
+                double nd, nq;
+                wave_sum2(dq * dq, qn * qn, nd, nq);
+                nd = sqrt(nd); nq = sqrt(nq);
+                const double err = nd / (nq + 1e-14);
+                ++k;
+                clk.pass();
+                more = (err > a.tol) && (k < a.max_it) && info_out == 0;
+                if (kTiming) more = k < 5;
+                if (!(err - err == 0.0)) flags |= BG_FLAG_NONFINITE;
+                if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
+                __syncthreads();                                   // every wave has read s_q
+                if (w == 0 && lane < RW) s_q[lane] = qn;
+                __syncthreads();
+            }
+            if constexpr (HYPER) {                  // q_p and the closure value of the decode: s_dN is the last evaluation's
+                if (tid < n) hist[(size_t)(step + 1) * n + tid] = s_q[tid];
+                double* qs = a.qshist + ((size_t)smp * (size_t)(a.nsteps + 1) + (size_t)(step + 1)) * (size_t)nbar;
+                for (int j = tid; j < nbar; j += 256) qs[j] = s_dN[n + j][n];
+            } else {
+                double* hrow = hist + (size_t)(step + 1) * N;
+                for (int i = tid; i < N; i += 256) hrow[i] = s_u[i + 2];
+            }
+            if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
+        }
+        if (tid == 0) {
+            a.flags[smp] = flags;
+            a.info[smp] = info_out;
+            clk.store(a.iters + (size_t)smp * a.nsteps, a.nsteps);
+        }
+    }
+}
+
+}  // namespace

@@ -127,15 +127,18 @@ class FEMBurgers:
         return self._finish(res, batched)
 
     # --------------------------------------------------------------------------- POD-ANN
-    def pod_ann_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, model, projection="LSPG", wide=False):
+    def pod_ann_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, model, projection="LSPG", wide=False, hyper=None):
         """POD-ANN PROM (reference :1177-1251).  ``model`` is any torch.nn.Module mapping
         (., n) -> (., nbar); it is borrowed and evaluated in float32 like the reference.  ``wide``: a plain MLP with
-        9 .. 20 primary modes takes the device-side loop bg_ann_rom_run_wide instead of the host-driven iteration."""
+        9 .. 20 primary modes takes the device-side loop bg_ann_rom_run_wide instead of the host-driven iteration.
+        ``hyper``: a row sampling (burgers_hip.pod.build_ann_row_sampling) or a rom.HyperAnnPlan sends the call through the
+        hyper-reduced device-side loop bg_hyper_ann_rom_run, which assembles both projections from the sampled mesh rows
+        only (any mesh the FOM takes, a plain float32 MLP with at most 8 primary modes, at most 256 rows)."""
         import copy
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_ann_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                np.asarray(U_p, dtype=np.float64), np.asarray(U_s, dtype=np.float64),
-                               copy.deepcopy(model), projection=projection, E=E, wide=wide)
+                               copy.deepcopy(model), projection=projection, E=E, wide=wide, hyper=hyper)
         return self._finish(res, batched)
 
     # --------------------------------------------------------------------------- POD-RBF

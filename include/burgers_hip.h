@@ -355,6 +355,48 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
                      const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
                      int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_hyper_ann_rom_run -- the POD-ANN PROM time loop HYPER-REDUCED: both projections of pod_ann_prom are assembled from m
+ *   sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j with the tangent
+ *   W = U_p + U_s dN(q_p), y_j = (A W)[i_j], R_j = (A u - b)[i_j], w_j = W[i_j] (Galerkin) or y_j (LSPG).
+ *   3 <= N <= bg_fom_max_n(): the kernel never touches a vector of mesh length.  reference: FEM/fem_burgers.py:1177-1251
+ *   with the sums over mesh rows restricted and weighted and without the re-projection q_p = U_p^T u^n at the start of a
+ *   step (below).  Opt-in: nothing routes here unless asked (burgers_hip/rom.py, pod_ann_run_hyper; hyper= of pod_ann_run
+ *   and of the facade).  The caller packs once per bases, sampling and mesh:
+ *   node   [nodes] int32: the sorted distinct stencil nodes i - 1, i, i + 1 (inside the mesh) of the sampled rows, m <= nodes
+ *          <= 3 m.  The stencil nodes of a sampled row are consecutive table entries: the table is a compacted mesh;
+ *   xn     [nodes] their coordinates;
+ *   pos    [m] int32: the table position of every sampled row (node[pos[j]] is the mesh row; distinct; entries outside
+ *          [0, nodes) are skipped);   xi  [m] the weights, finite, >= 0;
+ *   UTn    [m8][nodes], m8 = n + nbar rounded up to 8, 16-byte aligned: the rows of bg_ann_rom_run's UT = [U_p^T; U_s^T]
+ *          restricted to the table nodes, zero rows from n + nbar;
+ *   q0     [B][n] = U_p^T u0;   u0n  [B][nodes] u0 at the table nodes;
+ *   the closure: n_layers, widths, wt, bias, acts, alphas exactly as bg_ann_rom_run takes them;
+ *   qhist  [B][nsteps+1][n] q_p of every step, row 0 = q0;  qshist [B][nsteps+1][nbar] the closure value q_s = N(q_p) of
+ *          every step's decode (row 0: zeros), so that U = U_p q_p + U_s q_s is the kernel's own decode;
+ *   iters, flags, info, options (BG_OPT_SUPG, BG_OPT_NO_TANGENT_REUSE; the table is always read as a non-uniform mesh):
+ *          as bg_ann_rom_run; order: as bg_rom_run, entries outside [0, B) are skipped.
+ *   The first pass of the run assembles at u0n itself with the tangent at q0.  Afterwards q_p carries over from step to
+ *   step: for orthonormal [U_p U_s] it equals the reference's U_p^T u^n, and the first pass of a step reuses the tangent
+ *   of the previous evaluation.  Row 0 is the Dirichlet row, row N - 1 has no right element: decided by node[], so a table
+ *   node that is only a neighbour contributes nothing.
+ *   Limits (bg_hyper_ann_rom_limits): n <= 8, nbar <= 128, widths <= 256, layers <= 8, m <= 256, nodes <= 768.
+ *   Errors: N < 3, n, nbar, m, nodes or n_layers < 1, B or nsteps < 0, max_it < 1, dt <= 0, m > N, nodes outside
+ *   [m, min(3 m, N)], a null operand or output with B > 0, UTn not 16-byte aligned, a model that does not fit its widths:
+ *   BG_ERR_BAD_ARG; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; m, nodes or the model beyond the limits:
+ *   BG_ERR_UNSUPPORTED_R; an unknown projection: BG_ERR_PROJECTION; B = 0: BG_OK with nothing launched.  Sizes the
+ *   kernel does not cover are refused, never rerouted.
+ *   One 256-thread workgroup per sample runs bg_ann_rom_run's loop on the table (csrc/rom_ann_loop_device.hpp,
+ *   csrc/rom_hyper_ann.hip), instantiated for nodes <= 256, <= 512 and <= 768;
+ *   bg_hyper_ann_rom_workgroups_per_cu(nodes) of them are resident per CU (0: no such table). */
+int bg_hyper_ann_rom_limits(int *max_n, int *max_nbar, int *max_width, int *max_layers, int *max_m, int *max_nodes);
+int bg_hyper_ann_rom_workgroups_per_cu(int nodes);
+int bg_hyper_ann_rom_run(int N, int B, int n, int nbar, int m, int nodes, int nsteps, int projection, const int32_t *node,
+                         const double *xn, const int32_t *pos, const double *xi, const double *UTn, const double *q0,
+                         const double *u0n, const double *mu1, const double *mu2, int n_layers, const int *widths,
+                         const float *const *wt, const float *const *bias, const int *acts, const float *alphas, double dt,
+                         double E, double tol, int max_it, int options, double *qhist, double *qshist, int32_t *iters,
+                         int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
 /* bg_rom_run_long_wide -- bg_rom_run_wide for long meshes: 3 <= N <= 1024 (bg_rom_run_long_wide_max_n; meant for N > 512,
  *   where bg_rom_run_wide ends), r <= 96 (bg_rom_run_long_wide_max_r; meant for r > 40, where bg_rom_run_long ends).
  *   reference: FEM/fem_burgers.py:709-785.
