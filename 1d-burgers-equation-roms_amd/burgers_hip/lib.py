@@ -128,6 +128,13 @@ _SIGNATURES = {
     # N, B, n, nbar, m, nodes, nsteps, projection, node, xn, pos, xi, UTn, q0, u0n, mu1, mu2, the MLP, the step, qhist, qshist, ...
     "bg_hyper_ann_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_int_p, c_double_p, c_int_p] + [c_double_p] * 6 + _ANN_MLP +
                              _LOOP_STEP + [c_double_p] + _LOOP_OUT),
+    "bg_hyper_rbf_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 5),
+    "bg_hyper_rbf_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
+    "bg_hyper_rbf_rom_ut_ld": (ctypes.c_int, [ctypes.c_int]),
+    # N, B, n, nbar, Ns, m, nodes, nsteps, projection, kind, node, xn, pos, xi, UTn, XtT, Wd, bias, x_min, dx, eps, q0, u0n, mu1,
+    # mu2, the step, qhist, qshist, ...
+    "bg_hyper_rbf_rom_run": (ctypes.c_int, [ctypes.c_int] * 10 + [c_int_p, c_double_p, c_int_p] + [c_double_p] * 7 +
+                             [ctypes.c_double] + [c_double_p] * 4 + _LOOP_STEP + [c_double_p] + _LOOP_OUT),
     "bg_rom_run_long_wide_max_n": (ctypes.c_int, []),
     "bg_rom_run_long_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_long_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),

@@ -65,6 +65,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
+    _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
 )}
 
 
@@ -1272,17 +1273,12 @@ def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, 
                             X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
-class HyperAnnPlan:
-    """What bg_hyper_ann_rom_run reads besides the batch, built once per bases, closure, sampling and mesh
-    (include/burgers_hip.h): the table of the sorted distinct stencil nodes of the sampled rows (``nodes``, at most 3 m),
-    their coordinates ``xn``, the table position ``pos`` of every sampled row, the weights ``xi``, UTn = [U_p^T; U_s^T]
-    restricted to the table nodes, and the packed closure.  ``sampling``: a pod.RowSampling (pod.build_ann_row_sampling);
-    ``model``: a plain float32 MLP.  Everything the shapes, the sampling, the model and the bases decide is refused with a
-    ValueError before the device is touched -- also bases with |[U_p U_s]^T [U_p U_s] - I|_max > 1e-8: the loop carries q_p
-    from step to step instead of re-projecting U_p^T u^n, which is exact only for orthonormal bases."""
+class _HyperClosurePlan:
+    """What HyperAnnPlan and HyperRbfPlan share: the checks of bases, mesh and sampling on the host, and the table of the
+    sorted distinct stencil nodes of the sampled rows on the device (include/burgers_hip.h, bg_hyper_ann_rom_run)."""
 
-    def __init__(self, U_p, U_s, model, sampling, X, device):
-        route = _ROUTES["bg_hyper_ann_rom_run"]
+    def _check_sizes(self, route, U_p, U_s, sampling, X, max_n, max_nbar, max_m):
+        """Bases, mesh and sampling against each other and the limits; returns the host copies (Up, Us, Xh, rows, xi)."""
         Up, Us = (np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64) for A in (U_p, U_s))
         if Up.ndim != 2 or Us.ndim != 2 or Up.shape[0] != Us.shape[0] or Up.shape[1] < 1 or Us.shape[1] < 1:
             raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
@@ -1290,7 +1286,6 @@ class HyperAnnPlan:
         Xh = check_mesh(X)
         if N < route.min_n or N > _limit(route.max_n) or len(Xh) != N:
             raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of U_p and U_s per mesh node")
-        max_n, max_nbar, max_w, max_l, max_m, max_nodes = _lib.limits("bg_hyper_ann_rom_limits", 6)
         if n > max_n or nbar > max_nbar:
             raise ValueError(f"{route.entry} covers n <= {max_n} and nbar <= {max_nbar} (got {n}, {nbar})")
         rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
@@ -1302,12 +1297,13 @@ class HyperAnnPlan:
             raise ValueError("the weights must be finite and >= 0")
         if m > max_m:
             raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
-        if not isinstance(model, nn.Module) or any(p.dtype != torch.float32 for p in model.parameters()):
-            raise ValueError("the closure must be a plain float32 MLP (torch.nn.Module)")
-        layers = _ann_model_layers(model, n, nbar, "bg_hyper_ann_rom_limits", 6)
-        if layers is None:
-            raise ValueError(f"the closure must be a plain float32 MLP ({n}) -> ({nbar}) of Linear / ELU / ReLU / Tanh layers with "
-                             f"widths <= {max_w} and at most {max_l} layers")
+        return Up, Us, Xh, rows, xi
+
+    def _pack_table(self, route, Up, Us, Xh, rows, xi, sampling, max_nodes, device, workgroups_per_cu, ut_shape):
+        """The remaining refusals (orthonormal bases, the table's size, the sampling's projection), then the device: the
+        table, ``wg_per_cu`` from ``workgroups_per_cu(nodes)`` and UTn of shape ``ut_shape(nodes)``, zero outside
+        [n + nbar][nodes].  Returns the device."""
+        N, n, nbar = Up.shape[0], Up.shape[1], Us.shape[1]
         U = np.concatenate([Up, Us], axis=1)
         if not np.isfinite(U).all() or np.abs(U.T @ U - np.eye(n + nbar)).max() > 1e-8:
             raise ValueError("[U_p U_s] must have orthonormal columns (to 1e-8): the loop does not re-project U_p^T u^n")
@@ -1316,25 +1312,51 @@ class HyperAnnPlan:
             raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
         self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
         device = _lib.require_device(device)
-        self.N, self.n, self.nbar, self.m, self.n_nodes, self.Xh = N, n, nbar, m, len(nodes), Xh.copy()
+        self.N, self.n, self.nbar, self.m, self.n_nodes, self.Xh = N, n, nbar, len(rows), len(nodes), Xh.copy()
         self.sampling = sampling
-        self.wg_per_cu = _lib.load().bg_hyper_ann_rom_workgroups_per_cu(len(nodes))
+        self.wg_per_cu = workgroups_per_cu(len(nodes))
         self.Up, self.Us = _as_dev(Up, device), _as_dev(Us, device)
         self.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
         self.node = self.nodes.to(torch.int32)
         self.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
         self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
         self.xn = _as_dev(Xh[nodes], device)
-        UTn = np.zeros((-(-(n + nbar) // 8) * 8, len(nodes)))
-        UTn[:n + nbar] = U[nodes].T
+        UTn = np.zeros(ut_shape(len(nodes)))
+        UTn[:n + nbar, :len(nodes)] = U[nodes].T
         self.UTn = _as_dev(UTn, device)
+        return device
+
+
+class HyperAnnPlan(_HyperClosurePlan):
+    """What bg_hyper_ann_rom_run reads besides the batch, built once per bases, closure, sampling and mesh
+    (include/burgers_hip.h): the table of the sorted distinct stencil nodes of the sampled rows (``nodes``, at most 3 m),
+    their coordinates ``xn``, the table position ``pos`` of every sampled row, the weights ``xi``, UTn = [U_p^T; U_s^T]
+    restricted to the table nodes, and the packed closure.  ``sampling``: a pod.RowSampling (pod.build_ann_row_sampling);
+    ``model``: a plain float32 MLP.  Everything the shapes, the sampling, the model and the bases decide is refused with a
+    ValueError before the device is touched -- also bases with |[U_p U_s]^T [U_p U_s] - I|_max > 1e-8: the loop carries q_p
+    from step to step instead of re-projecting U_p^T u^n, which is exact only for orthonormal bases."""
+
+    def __init__(self, U_p, U_s, model, sampling, X, device):
+        route = _ROUTES["bg_hyper_ann_rom_run"]
+        max_n, max_nbar, max_w, max_l, max_m, max_nodes = _lib.limits("bg_hyper_ann_rom_limits", 6)
+        Up, Us, Xh, rows, xi = self._check_sizes(route, U_p, U_s, sampling, X, max_n, max_nbar, max_m)
+        n, nbar = Up.shape[1], Us.shape[1]
+        if not isinstance(model, nn.Module) or any(p.dtype != torch.float32 for p in model.parameters()):
+            raise ValueError("the closure must be a plain float32 MLP (torch.nn.Module)")
+        layers = _ann_model_layers(model, n, nbar, "bg_hyper_ann_rom_limits", 6)
+        if layers is None:
+            raise ValueError(f"the closure must be a plain float32 MLP ({n}) -> ({nbar}) of Linear / ELU / ReLU / Tanh layers with "
+                             f"widths <= {max_w} and at most {max_l} layers")
+        device = self._pack_table(route, Up, Us, Xh, rows, xi, sampling, max_nodes, device,
+                                  lambda k: _lib.load().bg_hyper_ann_rom_workgroups_per_cu(k),
+                                  lambda k: (-(-(n + nbar) // 8) * 8, k))
         self.model = _ann_model_pack(layers, device)
 
 
-class HyperAnnRomResult:
-    """Result of pod_ann_run_hyper: the primary coordinates ``q`` (B, nT+1, n) and the closure values ``q_s`` (B, nT+1, nbar)
-    of every step's decode (column 0: U_p^T u0, and zeros: no closure value belongs to u0), ``iters``, ``flags``, ``info``
-    and the ``plan``.  ``hist``
+class HyperClosureRomResult:
+    """Result of pod_ann_run_hyper and pod_rbf_run_hyper: the primary coordinates ``q`` (B, nT+1, n) and the closure values
+    ``q_s`` (B, nT+1, nbar) of every step's decode (column 0: U_p^T u0, and zeros: no closure value belongs to u0),
+    ``iters``, ``flags``, ``info`` and the ``plan``.  ``hist``
     (B, nT+1, N) is decoded on demand, U = U_p q + U_s q_s as one batched product -- the kernel's own decode, not a second
     evaluation of the closure -- with u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
     (B, N, nT+1) layout."""
@@ -1356,6 +1378,10 @@ class HyperAnnRomResult:
     @property
     def newton_steps(self):
         return int(self.iters.sum().item())
+
+
+HyperAnnRomResult = HyperClosureRomResult        # the name pod_ann_run_hyper's result has had
+HyperRbfRomResult = HyperClosureRomResult
 
 
 def _project_rows(u, P, chunk=256):
@@ -1382,6 +1408,17 @@ def pod_ann_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_
     refused.  Nothing is synchronised.  Returns a HyperAnnRomResult."""
     Xh = check_mesh(X)
     plan = sampling_or_plan if isinstance(sampling_or_plan, HyperAnnPlan) else HyperAnnPlan(U_p, U_s, model, sampling_or_plan, Xh, device)
+    return _hyper_closure_run(_ROUTES["bg_hyper_ann_rom_run"], plan, Xh, u0, mu1, mu2, nsteps, proj, device, options, balance,
+                              lambda N, B, nsteps, proj, q0, u0n, inputs: (
+                                  N, B, plan.n, plan.nbar, plan.m, plan.n_nodes, nsteps, proj, _lib.ptr(plan.node), _lib.ptr(plan.xn),
+                                  _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn), q0, u0n, *inputs[1:], *plan.model.args,
+                                  float(dt), float(E), float(tol), int(max_it)))
+
+
+def _hyper_closure_run(route, plan, Xh, u0, mu1, mu2, nsteps, proj, device, options, balance, head):
+    """What pod_ann_run_hyper and pod_rbf_run_hyper share: the plan against the call (device, mesh, projection), q0 and u0
+    at the table nodes, the launch through _device_loop and the result.  ``head(N, B, nsteps, proj, q0, u0n, inputs)``: the
+    entry point's argument list up to max_it; options, qhist, qshist and the other outputs follow it."""
     device = _lib.require_device(device)
     if plan.Up.device != device:
         raise ValueError("the plan was built on another device")
@@ -1389,19 +1426,15 @@ def pod_ann_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_
         raise ValueError("the plan was built for another mesh")
     if plan.projection != proj:
         raise ValueError("the row sampling was trained for the other projection")
-    route = _ROUTES["bg_hyper_ann_rom_run"]
     u0d, mu1d, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
-    B = mu1d.numel()
     q0 = _project_rows(u0d, plan.Up)
     u0n = u0d[:, plan.nodes].contiguous()
-    q_s = torch.empty((B, nsteps + 1, plan.nbar), dtype=torch.float64, device=device)
+    q_s = torch.empty((mu1d.numel(), nsteps + 1, plan.nbar), dtype=torch.float64, device=device)
     res = _device_loop(route, Xh, u0d, mu1, mu2, nsteps, device, options, balance,
                        lambda f, N, B, x, inputs, opts, outputs: f(
-                           N, B, plan.n, plan.nbar, plan.m, plan.n_nodes, int(nsteps), proj, _lib.ptr(plan.node), _lib.ptr(plan.xn),
-                           _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn), _lib.ptr(q0), _lib.ptr(u0n), *inputs[1:],
-                           *plan.model.args, float(dt), float(E), float(tol), int(max_it), opts, outputs[0], _lib.ptr(q_s),
+                           *head(N, B, int(nsteps), proj, _lib.ptr(q0), _lib.ptr(u0n), inputs), opts, outputs[0], _lib.ptr(q_s),
                            *outputs[1:]), keep=(plan, q0, u0n, q_s), slots=plan.wg_per_cu * _cu_count(device), cols=plan.n)
-    return HyperAnnRomResult(res, plan, u0d, q_s)
+    return HyperClosureRomResult(res, plan, u0d, q_s)
 
 
 def _ann_route(n, fused=True, wide=False):
@@ -1611,6 +1644,69 @@ def pod_rbf_run_long(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon,
                             options)
 
 
+class HyperRbfPlan(_HyperClosurePlan):
+    """What bg_hyper_rbf_rom_run reads besides the batch, built once per bases, closure, sampling and mesh
+    (include/burgers_hip.h): the table HyperAnnPlan holds (``nodes``, ``node``, ``pos``, ``xi``, ``xn``), UTn = [U_p^T; U_s^T]
+    restricted to the table nodes with the row stride bg_hyper_rbf_rom_ut_ld gives, ``wg_per_cu`` from the library, and the
+    closure operands of RbfFusedPlan: ``XtT``, ``Wd`` and ``bias`` padded to 128 columns, ``x_min``, ``dx``, ``kind``,
+    ``eps``.  ``sampling``: a pod.RowSampling (pod.build_rbf_row_sampling).  Everything the shapes, the limits, the
+    sampling, the kernel name and the bases decide is refused with a ValueError before the device is touched -- also bases
+    with |[U_p U_s]^T [U_p U_s] - I|_max > 1e-8: the loop carries q_p over instead of re-projecting U_p^T U0, which is exact
+    only for orthonormal bases."""
+
+    def __init__(self, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, sampling, X, device):
+        route = _ROUTES["bg_hyper_rbf_rom_run"]
+        max_n, max_nbar, max_ns, max_m, max_nodes = _lib.limits("bg_hyper_rbf_rom_limits", 5)
+        Up, Us, Xh, rows, xi = self._check_sizes(route, U_p, U_s, sampling, X, max_n, max_nbar, max_m)
+        n, nbar = Up.shape[1], Us.shape[1]
+        host = lambda a: np.array(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+        Xt, Wm = host(X_train), host(W)
+        if Xt.ndim != 2 or Wm.ndim != 2 or Xt.shape[1] != n or Wm.shape != (Xt.shape[0], nbar) or Xt.shape[0] < 1:
+            raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
+        scal = {}
+        for name, v, k in (("x_min", x_min, n), ("x_max", x_max, n), ("y_min", y_min, nbar), ("y_max", y_max, nbar)):
+            scal[name] = host(v)
+            if scal[name].shape != (k,):
+                raise ValueError(f"{name} must have {k} entries")
+        if Xt.shape[0] > max_ns:
+            raise ValueError(f"{route.entry} covers at most {max_ns} centres (got {Xt.shape[0]})")
+        self.kind = _pod._rbf_kind(kernel)                             # refuses an unknown name
+        self.Ns, self.eps = Xt.shape[0], float(epsilon)
+        L = _lib.load()
+        device = self._pack_table(route, Up, Us, Xh, rows, xi, sampling, max_nodes, device,
+                                  L.bg_hyper_rbf_rom_workgroups_per_cu, lambda k: (n + nbar, L.bg_hyper_rbf_rom_ut_ld(k)))
+        dx, dy = _pod._rbf_range(scal["x_min"], scal["x_max"]), _pod._rbf_range(scal["y_min"], scal["y_max"])
+        self.XtT = _as_dev(np.ascontiguousarray(Xt.T), device)         # (n, Ns): centre index fastest
+        Wd, bias = np.zeros((self.Ns, 128)), np.zeros(128)
+        Wd[:, :nbar] = Wm * (0.5 * dy)                                 # output scaling folded into the weights (RbfClosure)
+        bias[:nbar] = 0.5 * dy + scal["y_min"]
+        self.Wd, self.bias = _as_dev(Wd, device), _as_dev(bias, device)
+        self.x_min, self.dx = _as_dev(scal["x_min"], device), _as_dev(dx, device)
+
+
+def pod_rbf_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
+                      sampling_or_plan, proj, kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None, options=0,
+                      balance=True):
+    """``pod_rbf_prom`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_rbf_rom_run): both projections are
+    assembled from the sampled mesh rows of a pod.RowSampling (pod.build_rbf_row_sampling) with their weights, on the table
+    of their stencil nodes, so the mesh side of an iteration costs the same whatever the mesh: N up to bg_fom_max_n(),
+    n <= 20, nbar <= 128, m <= 256 (bg_hyper_rbf_rom_limits).  q_p carries over between iterations and steps (no U_p^T U0:
+    the bases must be orthonormal).  ``sampling_or_plan``: the sampling, or a HyperRbfPlan of these bases, closure,
+    sampling and mesh to reuse across calls (``res.plan``; the bases and the closure arguments are then not looked at).
+    ``proj``: BG_PROJ_GALERKIN or BG_PROJ_LSPG (PROJ); a sampling trained for the other projection is refused.  Nothing is
+    synchronised.  Returns a HyperRbfRomResult."""
+    Xh = check_mesh(X)
+    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperRbfPlan) else HyperRbfPlan(
+        U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, sampling_or_plan, Xh, device)
+    return _hyper_closure_run(_ROUTES["bg_hyper_rbf_rom_run"], plan, Xh, u0, mu1, mu2, nsteps, proj, device, options, balance,
+                              lambda N, B, nsteps, proj, q0, u0n, inputs: (
+                                  N, B, plan.n, plan.nbar, plan.Ns, plan.m, plan.n_nodes, nsteps, proj, plan.kind,
+                                  _lib.ptr(plan.node), _lib.ptr(plan.xn), _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn),
+                                  _lib.ptr(plan.XtT), _lib.ptr(plan.Wd), _lib.ptr(plan.bias), _lib.ptr(plan.x_min),
+                                  _lib.ptr(plan.dx), plan.eps, q0, u0n, *inputs[1:], float(dt), float(E), float(tol_newton),
+                                  int(max_newton)))
+
+
 def _rbf_route(N, fused=False, long_mesh=False):
     """The device loops pod_rbf_run tries for a mesh of N nodes, in this order; each is taken if the RbfFusedPlan of the
     closure for it is ``ok`` (inside its limits), and "host" is what is left."""
@@ -1621,13 +1717,19 @@ def _rbf_route(N, fused=False, long_mesh=False):
 
 def pod_rbf_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,
                 projection="LSPG", kernel="gaussian", E=0.0, tol_newton=1e-6, max_newton=30, device=None, fused=False,
-                long_mesh=False):
+                long_mesh=False, hyper=None):
     """Batched ``pod_rbf_prom`` (FEM/fem_burgers.py:1278-1398).  Default: the batched iteration driven from the host.
     ``fused``: the device-side time loop bg_rbf_rom_run (pod_rbf_run_fused) when the closure is within bg_rbf_rom_limits,
     otherwise the host-driven iteration as well.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= 1024 whose closure is inside bg_rbf_rom_run_long_limits
-    take the device-side loop bg_rbf_rom_run_long (pod_rbf_run_long) instead of the host-driven iteration."""
+    take the device-side loop bg_rbf_rom_run_long (pod_rbf_run_long) instead of the host-driven iteration.
+    ``hyper`` (opt-in): a pod.RowSampling (pod.build_rbf_row_sampling) or a HyperRbfPlan sends the call through the
+    hyper-reduced loop pod_rbf_run_hyper, which assembles both projections from the sampled mesh rows only; closures, bases
+    and sizes it does not cover are refused, not rerouted."""
     proj = _projection(projection, "projection must be 'LSPG' or 'Galerkin'.")
+    if hyper is not None:
+        return check_singular(pod_rbf_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min,
+                                                y_max, hyper, proj, kernel, E, tol_newton, max_newton, device))
     tries = _rbf_route(np.shape(X)[0], fused, long_mesh)
     if "bg_rbf_rom_run_long" in tries:
         res = pod_rbf_run_long(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max,

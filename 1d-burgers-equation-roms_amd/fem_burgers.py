@@ -144,15 +144,18 @@ class FEMBurgers:
     # --------------------------------------------------------------------------- POD-RBF
     def pod_rbf_prom(self, At, nTimeSteps, u0, mu1, E, mu2, U_p, U_s, X_train, W, epsilon,
                      x_min, x_max, y_min, y_max, projection="LSPG", kernel="gaussian",
-                     tol_newton=1e-6, max_newton=30, fused=False, long_mesh=False):
+                     tol_newton=1e-6, max_newton=30, fused=False, long_mesh=False, hyper=None):
         """POD-RBF PROM with the scaled Gaussian / IMQ closure (reference :1278-1398).  ``fused``: the whole time loop
         on the device (bg_rbf_rom_run) when the closure is within its limits; the default is the host-driven iteration.
-        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_rbf_rom_run_long."""
+        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_rbf_rom_run_long.
+        ``hyper``: a row sampling (burgers_hip.pod.build_rbf_row_sampling) or a rom.HyperRbfPlan sends the call through the
+        hyper-reduced device-side loop bg_hyper_rbf_rom_run, which assembles both projections from the sampled mesh rows
+        only (any mesh the FOM takes, n <= 20, nbar <= 128, at most 256 rows)."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_rbf_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps), U_p, U_s,
                                X_train, W, epsilon, x_min, x_max, y_min, y_max, projection=projection,
                                kernel=kernel, E=E, tol_newton=tol_newton, max_newton=max_newton, fused=fused,
-                               long_mesh=long_mesh)
+                               long_mesh=long_mesh, hyper=hyper)
         return self._finish(res, batched)
 
     # ------------------------------------------------------------------------- local POD

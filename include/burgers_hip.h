@@ -397,6 +397,48 @@ int bg_hyper_ann_rom_run(int N, int B, int n, int nbar, int m, int nodes, int ns
                          double E, double tol, int max_it, int options, double *qhist, double *qshist, int32_t *iters,
                          int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_hyper_rbf_rom_run -- the POD-RBF PROM time loop HYPER-REDUCED: both projections of pod_rbf_prom are assembled from m
+ *   sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j with the tangent
+ *   W = U_p + U_s J(q_p), y_j = (A W)[i_j], R_j = (A u - b)[i_j], w_j = W[i_j] (Galerkin) or y_j (LSPG).
+ *   3 <= N <= bg_fom_max_n(): the kernel never touches a vector of mesh length; the mesh side of an iteration costs what
+ *   the table costs, the closure evaluation (Ns nbar n) what it costs in bg_rbf_rom_run.  reference:
+ *   FEM/fem_burgers.py:1278-1398 with the sums over mesh rows restricted and weighted and without the re-projection
+ *   q_p = U_p^T U0 of every iteration (below).  Opt-in: nothing routes here unless asked (burgers_hip/rom.py,
+ *   pod_rbf_run_hyper; hyper= of pod_rbf_run and of the facade).  The caller packs once per bases, closure, sampling and mesh:
+ *   node, xn, pos, xi: the table of the sorted distinct stencil nodes of the sampled rows, exactly as bg_hyper_ann_rom_run
+ *          takes it (m <= nodes <= 3 m; pos entries outside [0, nodes) are skipped; a sampled row whose neighbour the
+ *          table does not hold is left out);
+ *   UTn    [n + nbar][ut_ld], ut_ld = bg_hyper_rbf_rom_ut_ld(nodes) (512 up to 512 nodes, 1024 beyond), 16-byte aligned:
+ *          the rows of bg_rbf_rom_run's UT = [U_p^T; U_s^T] restricted to the table nodes, zero columns from nodes;
+ *   XtT, Wd, bias, x_min, dx, eps, kind: the closure exactly as bg_rbf_rom_run takes it;
+ *   q0     [B][n] = U_p^T u0;   u0n  [B][nodes] u0 at the table nodes;
+ *   qhist  [B][nsteps+1][n] q_p of every step, row 0 = q0;  qshist [B][nsteps+1][nbar] the closure value f(q_p) of every
+ *          step's decode (row 0: zeros), so that U = U_p q_p + U_s q_s is the kernel's own decode;
+ *   iters, flags, info, options (BG_OPT_SUPG; the table is always read as a non-uniform mesh): as bg_rbf_rom_run;
+ *          order: as bg_rom_run, entries outside [0, B) are skipped.
+ *   The first iteration of the run assembles at u0n itself.  q_p carries over between iterations and steps: for
+ *   orthonormal [U_p U_s] it equals the reference's U_p^T U0.  The stopping rule is bg_rbf_rom_run's (|dq| / |q_new|, |dq|
+ *   when |q_new| = 0).  Row 0 is the Dirichlet row, row N - 1 has no right element: decided by node[], so a table node
+ *   that is only a neighbour contributes nothing.
+ *   Limits (bg_hyper_rbf_rom_limits): n <= 20, nbar <= 128, Ns <= 65536, m <= 256, nodes <= 768.
+ *   Checked in this order: N < 3, n, nbar, Ns, m or nodes < 1, B or nsteps < 0, max_it < 1, dt <= 0: BG_ERR_BAD_ARG; an
+ *   unknown kind: BG_ERR_BAD_ARG; an unknown projection: BG_ERR_PROJECTION; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; n,
+ *   nbar, Ns, m or nodes beyond the limits: BG_ERR_UNSUPPORTED_R; m > N or nodes outside [m, min(3 m, N)]: BG_ERR_BAD_ARG;
+ *   B = 0: BG_OK with nothing launched; a null operand or output, UTn or Wd not 16-byte aligned: BG_ERR_BAD_ARG.  Sizes
+ *   the kernel does not cover are refused, never rerouted.
+ *   One workgroup per sample runs bg_rbf_rom_run's loop on the table (csrc/rom_rbf_loop_device.hpp,
+ *   csrc/rom_hyper_rbf.hip): 256 threads for nodes <= 256 and <= 512, 512 threads (the bg_rbf_rom_run_long profile) for
+ *   nodes <= 768; bg_hyper_rbf_rom_workgroups_per_cu(nodes) of them are resident per CU (2, 1; 0: no such table). */
+int bg_hyper_rbf_rom_limits(int *max_n, int *max_nbar, int *max_ns, int *max_m, int *max_nodes);
+int bg_hyper_rbf_rom_workgroups_per_cu(int nodes);
+int bg_hyper_rbf_rom_ut_ld(int nodes);
+int bg_hyper_rbf_rom_run(int N, int B, int n, int nbar, int Ns, int m, int nodes, int nsteps, int projection, int kind,
+                         const int32_t *node, const double *xn, const int32_t *pos, const double *xi, const double *UTn,
+                         const double *XtT, const double *Wd, const double *bias, const double *x_min, const double *dx,
+                         double eps, const double *q0, const double *u0n, const double *mu1, const double *mu2, double dt,
+                         double E, double tol, int max_it, int options, double *qhist, double *qshist, int32_t *iters,
+                         int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
 /* bg_rom_run_long_wide -- bg_rom_run_wide for long meshes: 3 <= N <= 1024 (bg_rom_run_long_wide_max_n; meant for N > 512,
  *   where bg_rom_run_wide ends), r <= 96 (bg_rom_run_long_wide_max_r; meant for r > 40, where bg_rom_run_long ends).
  *   reference: FEM/fem_burgers.py:709-785.
