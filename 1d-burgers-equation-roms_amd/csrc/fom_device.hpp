@@ -106,12 +106,43 @@ __device__ __forceinline__ void mass_rhs(Topo& tp, const MeshConst& c, int N, co
         const double um = (j == 0) ? uL : u[j - 1];
         const double up = (j == R - 1) ? uR : u[j + 1];
         const int i = tp.g * R + j;
-        double inner = __builtin_fma(4.0, u[j], um) + up;
-        double last = __builtin_fma(2.0, u[j], um);
-        double v = __builtin_fma(c.h6, (i == N - 1) ? last : inner, fdt[j]);
+        double m = __builtin_fma(4.0, u[j], um) + up;
+        // the last real row has no right element; with FULL it can only be row R-1 of the last thread (as in assemble_p2)
+        if (FULL ? (j == R - 1) : true) {
+            const bool is_last = FULL ? tp.last() : (i == N - 1);
+            m = is_last ? __builtin_fma(2.0, u[j], um) : m;
+        }
+        double v = __builtin_fma(c.h6, m, fdt[j]);
         gstore(j, (!FULL && i >= N) ? 0.0 : v);
     }
     tp.halo_done();
+}
+
+// SUPG element terms se[j] = t[j] / mx[j], mx[j] = max(|w_j|, 2e-10) >= 2e-10.  The R quotients of a thread do not depend on one
+// another, so every full group of four shares ONE reciprocal (v_rcp_f64 is quarter rate: 16.4 cycles against 4.3 for a
+// multiply) through a product tree:
+//   r = 1 / (m0 m1 m2 m3),  r01 = r (m2 m3) = 1 / (m0 m1),  r23 = r (m0 m1),  1/m0 = r01 m1,  1/m1 = r01 m0,  ...
+// 16 instructions per group, as many as four rcp1 with their multiplies, three of them no longer reciprocals.  The R % 4
+// elements left over keep t * rcp1(mx).  Four roundings on top of rcp1's 2.1e-15: under 2.6e-15 relative.
+// Range: the product of a group must stay finite, which every mx <= 1e77 (|u| <~ 5e76) guarantees; it cannot underflow
+// (>= 1.6e-39).  Past that the group's reciprocal is 0, its Newton step NaN, and the sample ends flagged
+// BG_FLAG_NONFINITE like any other non-finite state (include/burgers_hip.h, bg_fom_run).
+template <int R>
+__device__ __forceinline__ void supg_terms(const double (&mx)[R], const double (&t)[R], double (&se)[R])
+{
+    constexpr int G = R / 4 * 4;
+#pragma unroll
+    for (int j = 0; j < G; j += 4) {
+        const double p01 = mx[j] * mx[j + 1], p23 = mx[j + 2] * mx[j + 3];
+        const double r = BG_RCP(p01 * p23);
+        const double r01 = r * p23, r23 = r * p01;
+        se[j] = t[j] * (r01 * mx[j + 1]);
+        se[j + 1] = t[j + 1] * (r01 * mx[j]);
+        se[j + 2] = t[j + 2] * (r23 * mx[j + 3]);
+        se[j + 3] = t[j + 3] * (r23 * mx[j + 2]);
+    }
+#pragma unroll
+    for (int j = G; j < R; ++j) se[j] = t[j] * BG_RCP(mx[j]);
 }
 
 // One assembly: diagonals lo/di/up of A(u) and rhs = b - A u  (= -R of the reference), in two halves around the
@@ -122,6 +153,7 @@ template <int R, typename HF>
 __device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u)[R], double uL, double uR,
                                             HF&& hf, double (&lo)[R], double (&up)[R], double (&se)[R])
 {
+    double mx[R], t[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const double ur = (j == R - 1) ? uR : u[j + 1];
@@ -129,10 +161,10 @@ __device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u
         const double dif = ur - u[j];
         up[j] = __builtin_fma(c.dt6, w + u[j], c.aoff);
         if (j + 1 < R) lo[j + 1] = __builtin_fma(-c.dt6, w + ur, c.aoff);
-        const double mx = fmax(fabs(w), 2.0e-10);
-        const double t = __builtin_fma(w, dif, -hf(j));
-        se[j] = t * BG_RCP(mx);
+        mx[j] = fmax(fabs(w), 2.0e-10);
+        t[j] = __builtin_fma(w, dif, -hf(j));
     }
+    supg_terms<R>(mx, t, se);
     lo[0] = __builtin_fma(-c.dt6, __builtin_fma(2.0, u[0], uL), c.aoff);
 }
 
@@ -270,6 +302,7 @@ __device__ __forceinline__ void assemble_general_p1(const ElemGeom<R>& gm, doubl
                                                     double (&up)[R], double (&se)[R])
 {
     const double dt6 = dt / 6.0;
+    double mx[R], t[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const double ur = (j == R - 1) ? uR : u[j + 1];
@@ -278,10 +311,10 @@ __device__ __forceinline__ void assemble_general_p1(const ElemGeom<R>& gm, doubl
         const double aoff = gm.h6[j + 1] - gm.eh[j + 1];
         up[j] = __builtin_fma(dt6, w + u[j], aoff);
         if (j + 1 < R) lo[j + 1] = __builtin_fma(-dt6, w + ur, aoff);
-        const double mx = fmax(fabs(w), 2.0e-10);
-        const double t = __builtin_fma(w, dif, -hfs[j]);
-        se[j] = t * BG_RCP(mx);
+        mx[j] = fmax(fabs(w), 2.0e-10);
+        t[j] = __builtin_fma(w, dif, -hfs[j]);
     }
+    supg_terms<R>(mx, t, se);
     lo[0] = __builtin_fma(-dt6, __builtin_fma(2.0, u[0], uL), gm.h6[0] - gm.eh[0]);
 }
 

@@ -94,6 +94,12 @@ int bg_fom_max_n(void);
  *   flags  [B]               BG_FLAG_* bits
  *   tol, max_it              the reference hard-codes 1e-6 and 20 (:663)
  *   supg                     option bits: BG_OPT_SUPG (fom_burgers has it) | BG_OPT_NONUNIFORM
+ *
+ *   Range of the state: the SUPG quotients t_e / max(|u_e + u_{e+1}|, 2e-10) of four neighbouring elements share
+ *   one reciprocal of the product of their denominators, which must stay below 1.8e308: every |u| <~ 5e76 is safe
+ *   (the product cannot underflow).  Beyond that the reciprocal is 0 and its Newton step NaN: the sample turns
+ *   non-finite, BG_FLAG_NONFINITE is set and its Picard loops end as for any NaN state; it is never silently wrong.
+ *   bg_fom_run_traced and bg_fom_assemble share the assembly and the limit.
  * --------------------------------------------------------------------------------- */
 int bg_fom_run(int N, int B, int nsteps, const double *x, const double *u0, const double *mu1,
                const double *mu2, double dt, double E, double tol, int max_it, int supg,
