@@ -66,6 +66,20 @@ __device__ __forceinline__ void fd_sample(const FdArgs& a, Topo& tp, int s)
     for (int j = 0; j < R; ++j)
         if (row0 + j < N) hist[row0 + j] = u[j];
 
+    // The three maxima of an iteration are np.max's in the reference: NaN when an entry is, and both stopping tests then
+    // fail.  fmax drops a NaN operand, so the NaN is carried beside the maxima, without a test per row and solve:
+    //   unan   "an interior row of u is NaN", uniform over the sample.  From u0 here; afterwards u changes only by the
+    //          solution of a solve, and a NaN never leaves u.
+    //   a solve (wang_reduce, the PCR, wang_finish of fom_device.hpp) multiplies whatever NaN enters a thread's rows or
+    //          coefficients into that thread's interface unknown, its last row, and from there into all its rows; only
+    //          interior rows have coefficients that can be NaN.  So "the update has a NaN" is one test per thread.
+    //   a NaN residual on a finite state (src, or inf - inf) fails the residual test where that test would pass.
+    bool u0nan = false;
+#pragma unroll
+    for (int j = 0; j < R; ++j) u0nan |= (row0 + j >= 1) && (row0 + j <= N - 2) && (u[j] != u[j]);
+    bool unan = tp.gmax(u0nan ? 1.0 : 0.0) > 0.0;
+    const double nan = __builtin_nan("");
+
     int flags = 0;
     for (int step = 0; step < a.nsteps; ++step) {
         double uprev[R];
@@ -83,8 +97,10 @@ __device__ __forceinline__ void fd_sample(const FdArgs& a, Topo& tp, int s)
                 const int i = row0 + j;
                 mloc = (i >= 1 && i <= N - 2) ? fmax(mloc, fabs(u[j])) : mloc;
             }
-            const double umax_int = tp.gmax(mloc);                  // max |U_guess[1:-1]|
-            const double nu = 0.25 * dx * fmax(umax_int, fabs(mu1));  // max over ALL entries (U[-1] = U[-2])
+            const double mglob = tp.gmax(mloc);
+            const double umax_int = unan ? nan : mglob;             // max |U_guess[1:-1]|
+            const double uall = (unan || mu1 != mu1) ? nan : fmax(umax_int, fabs(mu1));
+            const double nu = 0.25 * dx * uall;                     // max over ALL entries (U[-1] = U[-2])
             const double nud = nu * idx2;
             double lo[R], di[R], up[R], rhs[R];
             double rloc = 0.0;
@@ -103,8 +119,15 @@ __device__ __forceinline__ void fd_sample(const FdArgs& a, Topo& tp, int s)
                 di[j] = interior ? (idt + 2.0 * nud) : 1.0;
                 rhs[j] = interior ? -Ri : 0.0;
             }
-            const double res = tp.gmax(rloc);
-            if (res < a.tol) { converged = true; break; }
+            const double rglob = tp.gmax(rloc);
+            const double res = unan ? nan : rglob;                  // a NaN state has a NaN nu, hence a NaN residual
+            if (res < a.tol) {
+                // about to leave: once per step at the most, look for a NaN the maximum has dropped (rhs = -Ri or 0)
+                bool rnan = false;
+#pragma unroll
+                for (int j = 0; j < R; ++j) rnan |= (rhs[j] != rhs[j]);
+                if (!(tp.gmax(rnan ? 1.0 : 0.0) > 0.0)) { converged = true; break; }
+            }
             tp.template solve<R>(lo, di, up, rhs);
             double dloc = 0.0;
 #pragma unroll
@@ -112,7 +135,10 @@ __device__ __forceinline__ void fd_sample(const FdArgs& a, Topo& tp, int s)
                 dloc = fmax(dloc, fabs(rhs[j]));
                 u[j] += rhs[j];
             }
-            const double rel = tp.gmax(dloc) / fmax(umax_int, 1e-15);
+            const double dmax = tp.gmax_nan(dloc, rhs[R - 1] != rhs[R - 1]);
+            unan |= (dmax != dmax);
+            // a NaN umax_int stays NaN: Python's max(nan, 1e-15) is nan
+            const double rel = dmax / (unan ? nan : fmax(umax_int, 1e-15));
             ++k;
             if (uniform_nonfinite(rel)) flags |= BG_FLAG_NONFINITE;
             if (rel < a.tol) { converged = true; break; }

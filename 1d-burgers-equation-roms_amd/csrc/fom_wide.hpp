@@ -120,6 +120,14 @@ __device__ __forceinline__ double wave_max(double v)
     return __hiloint2double(hi, lo);
 }
 
+// wave_max of v >= 0 as np.max has it: NaN when `nan` holds in any lane (fmax alone drops a NaN operand).  `nan` is one
+// bit per lane, so it rides on a ballot beside the reduction that is there anyway.
+__device__ __forceinline__ double wave_max_nan(double v, bool nan)
+{
+    const double m = wave_max(v);
+    return __builtin_amdgcn_ballot_w64(nan) ? __builtin_nan("") : m;
+}
+
 // ---- the topology of a sample: what the FEM bodies (fom.hip) and the FD body (fd.hip) are written over ----
 // Thread g of the sample's threads owns the rows [g*R, g*R + R).  Where neighbour values, sums, maxima and the
 // tridiagonal solve come from: one wavefront per sample (DPP inside the wave, no barrier anywhere) or one 256-thread
@@ -127,7 +135,8 @@ __device__ __forceinline__ double wave_max(double v)
 //   halo        uL / uR = `last` of thread g-1 / `first` of thread g+1, one exchange.  The workgroup form needs
 //               halo_done() before the next halo() (it refills ufirst / ulast); the wave form's is empty.
 //   below_se    v of thread g-1 through WideLds::se: once per Picard iteration, the solve's barriers lie between two uses
-//   below, above, gmax   the FD stepper's exchanges: alternating buffers, so one barrier each in any sequence
+//   below, above, gmax, gmax_nan   the FD stepper's exchanges: alternating buffers, so one barrier each in any sequence.
+//               gmax_nan(v, nan): gmax of v >= 0, NaN when `nan` holds in any of the sample's threads (np.max, not fmax)
 struct WaveTopo {
     int g;                                           // = lane
     __device__ __forceinline__ bool first() const { return g == 0; }        // owns global row 0
@@ -142,6 +151,7 @@ struct WaveTopo {
     __device__ __forceinline__ double below(double v) { return from_lane_below(v); }
     __device__ __forceinline__ double above(double v) { return from_lane_above(v); }
     __device__ __forceinline__ double gmax(double v) { return wave_max(v); }
+    __device__ __forceinline__ double gmax_nan(double v, bool nan) { return wave_max_nan(v, nan); }
     __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wave_sum2(a, b, sa, sb); }
     template <int R>
     __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
@@ -189,6 +199,17 @@ struct WgTopo {
         if ((g & 63) == 0) buf[g >> 6] = v;
         __syncthreads();
         return fmax(fmax(buf[0], buf[1]), fmax(buf[2], buf[3]));
+    }
+    __device__ __forceinline__ double gmax_nan(double v, bool nan)
+    {
+        v = wave_max_nan(v, nan);
+        double* buf = s.nrm[par];
+        par ^= 1;
+        if ((g & 63) == 0) buf[g >> 6] = v;
+        __syncthreads();
+        const double b0 = buf[0], b1 = buf[1], b2 = buf[2], b3 = buf[3];
+        const double m = fmax(fmax(b0, b1), fmax(b2, b3));
+        return ((b0 != b0) | (b1 != b1) | (b2 != b2) | (b3 != b3)) ? __builtin_nan("") : m;
     }
     __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wide_sum2(s, g, a, b, sa, sb); }
     template <int R>

@@ -25,8 +25,10 @@ __global__ __launch_bounds__(256) void mlp_act_jvp_kernel(float* __restrict__ z,
         const float v = p[0] + (bias ? bias[j] : 0.0f);
         float a = v, d = 1.0f;
         if (ACT == BG_ACT_ELU) {
+            // the value as torch's ELU has it, alpha expm1(v), rounded once: e - alpha cancels for small negative v (an
+            // absolute error of eps32 alpha / 2 on a value of size |v|).  expf(100) = inf stays in the arm not taken.
             const float e = alpha * expf(v);
-            a = v > 0.0f ? v : e - alpha;
+            a = v > 0.0f ? v : (float)((double)alpha * expm1((double)v));
             d = v > 0.0f ? 1.0f : e;
         } else if (ACT == BG_ACT_RELU) {
             a = v > 0.0f ? v : 0.0f;

@@ -148,7 +148,8 @@ __device__ __forceinline__ float swap32_add(float a, float b)
 }
 
 // ---- MLP activation of the pre-activation v (bias added): value av and derivative d, the arithmetic of bg_mlp_act_jvp
-// (csrc/mlp.hip); BG_ACT_NONE: av = v, d = 1
+// (csrc/mlp.hip) but for the ELU value below 0: e - alpha here, alpha expm1(v) there, eps32 alpha / 2 apart at the most, which
+// is 1e-8 of the closure where the loops are held to 5e-6 (tests/test_mlp_stage_gpu.py).  BG_ACT_NONE: av = v, d = 1
 __device__ __forceinline__ void mlp_activate(int kind, float alpha, float v, float& av, float& d)
 {
     av = v; d = 1.0f;

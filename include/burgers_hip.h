@@ -190,8 +190,10 @@ int bg_rom_reduce_indexed(int N, int B, int r, int projection, const double *x, 
 
 /* bg_lu_solve -- x[b] = solve(A[b], sign * rhs[b]), partial pivoting, n <= 64
  *   reference: np.linalg.solve(Ar, -br) at FEM/fem_burgers.py:767 / :1161 / :1237
- *   (LAPACK gesv).  info[b] = 0, or k+1 when the pivot of step k is exactly zero
- *   (numpy raises LinAlgError("Singular matrix") there). */
+ *   (LAPACK gesv).  info[b] = 0, or k+1 when the pivot of step k is exactly zero (the first such step;
+ *   numpy raises LinAlgError("Singular matrix") there).  info (may be NULL) is only ever written with a non-zero
+ *   value: the caller zeroes it, and a system that is healthy or skipped leaves its entry as it was.  The same
+ *   holds for the info of bg_lu_solve_update, which so keeps a singular system's mark across iterations. */
 int bg_lu_solve(int n, int B, const double *A, const double *rhs, double sign, const int32_t *active,
                 double *x, int32_t *info, void *stream);
 
@@ -478,7 +480,9 @@ int bg_rom_run_long_wide(int N, int B, int r, int nsteps, int projection, const 
  *   boundary values :19-22 (U[0] = mu1, U[-1] = U[-2]).  Central differences with the lagged
  *   artificial viscosity nu = 0.25 dx max|U|; stop on max|R| < tol or max|dU|/max|U| < tol.
  *   Arrays as in bg_fom_run; x must be the linspace(a, b, N) of the reference; N <= 8192.
- *   iters[b][t] = Newton solves taken in step t; flags: BG_FLAG_HIT_CAP when max_it ran out.
+ *   iters[b][t] = Newton solves taken in step t; flags: BG_FLAG_HIT_CAP when max_it ran out in some step,
+ *   BG_FLAG_NONFINITE when a sample's state went non-finite: the three maxima are NaN when an entry is, as the
+ *   reference's np.max, so such a sample takes max_it solves in every later step and is never reported as converged.
  * ================================================================================= */
 int bg_fd_run(int N, int B, int nsteps, const double *x, const double *u0, const double *mu1,
               const double *mu2, double dt, double tol, int max_it, double *hist, int32_t *iters,
