@@ -95,6 +95,26 @@ __device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, Wi
     load_rows<R>(a.u0 + (size_t)s * N, N, row0, FULL, u);
     store_rows<R>(hist, N, row0, FULL, u);
 
+    // ROT (BG_PICARD_ROTATE, topologies with rotates_picard): the loop is rotated by half an assembly.  assemble_head of an
+    // iterate (halo, off-diagonals, SUPG terms) reads u, hfs and the mesh constants only, so it is formed right after the
+    // update that makes the iterate, in the block of sum2 and the stopping test: with one wave per SIMD nothing else can
+    // issue between the reduction's dependent rounds (on a uniform mesh the two are woven by hand, below; a graded mesh
+    // has the head, then sum2).  Whichever way the test goes the head is the one needed next, by the next iteration or,
+    // with the new g, by the first iteration of the next time step, which starts from the same u; only the head after a
+    // sample's last step is dropped.  Every value is formed by the same operations in the same order as without the
+    // rotation: histories, counts and flags are bit for bit those of -DBG_PICARD_ROTATE=0.  The TRACE instantiations
+    // take the same form.
+    constexpr bool ROT = BG_PICARD_ROTATE && Topo::rotates_picard;
+    static_assert(!ROT || !PARK, "the parked form belongs to the workgroup topology");
+    double huL, huR, hse[ROT ? R : 1], hlo[ROT ? R : 1], hup[ROT ? R : 1];   // ROT: the head of the coming iteration
+    auto head = [&]() {
+        if constexpr (ROT) {
+            if constexpr (UNI) assemble_head<R>(tp, c, u, hf_at, huL, huR, hse, hlo, hup);
+            else assemble_general_head<R>(tp, gm, a.dt, u, hfs, huL, huR, hse, hlo, hup);
+        }
+    };
+    head();
+
     int flags = 0;
     for (int step = 0; step < a.nsteps; ++step) {
         if constexpr (UNI) mass_rhs<R, FULL>(tp, c, N, u, fdt, g_put);
@@ -103,8 +123,15 @@ __device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, Wi
         bool more;
         do {
             double lo[R], di[R], up[R], rhs[R];
-            if constexpr (UNI) assemble<R, FULL>(tp, c, N, mu1, u, g_at, hf_at, lo, di, up, rhs);
-            else assemble_general<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, hfs, lo, di, up, rhs);
+            if constexpr (ROT) {
+#pragma unroll
+                for (int j = 0; j < R; ++j) { lo[j] = hlo[j]; up[j] = hup[j]; }
+                if constexpr (UNI) assemble_tail<R, FULL>(tp, c, N, mu1, u, g_at, huL, huR, hse, lo, di, up, rhs);
+                else assemble_general_tail<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, huL, huR, hse, lo, di, up, rhs);
+            } else {
+                if constexpr (UNI) assemble<R, FULL>(tp, c, N, mu1, u, g_at, hf_at, lo, di, up, rhs);
+                else assemble_general<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, hfs, lo, di, up, rhs);
+            }
             tp.template solve<R>(lo, di, up, rhs);
             double nd = 0.0, nu = 0.0;
 #pragma unroll
@@ -113,7 +140,27 @@ __device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, Wi
                 nd = __builtin_fma(rhs[j], rhs[j], nd);
                 nu = __builtin_fma(u[j], u[j], nu);
             }
-            tp.sum2(nd, nu, nd, nu);
+            if constexpr (ROT && UNI) {
+                // the head in chunks of four elements, a round of the norm reduction in front of each: left to itself the
+                // scheduler emits the whole head and then the reduction in one dependent piece
+                WaveSum2 ws;
+                tp.halo(u[0], u[R - 1], huL, huR);
+                ws.start(nd, nu);
+                auto weave = [&](auto kc) {
+                    constexpr int K = decltype(kc)::value, J0 = 4 * K, J1 = J0 + 4 < R ? J0 + 4 : R;
+                    if constexpr (K < 5) ws.template round<K>();
+                    if constexpr (J0 < R) assemble_p1_rows<R, J0, J1>(c, u, huR, hf_at, hlo, hup, hse);
+                };
+                static_assert(R <= 24, "six chunks");
+                weave(std::integral_constant<int, 0>{}); weave(std::integral_constant<int, 1>{});
+                weave(std::integral_constant<int, 2>{}); weave(std::integral_constant<int, 3>{});
+                weave(std::integral_constant<int, 4>{}); weave(std::integral_constant<int, 5>{});
+                hlo[0] = __builtin_fma(-c.dt6, __builtin_fma(2.0, u[0], huL), c.aoff);
+                ws.finish(nd, nu);
+            } else {
+                head();
+                tp.sum2(nd, nu, nd, nu);
+            }
             if constexpr (TRACE) {
                 if (tp.first()) a.errs[((size_t)s * a.nsteps + step) * a.max_it + k] = sqrt(nd) / sqrt(nu);
             }

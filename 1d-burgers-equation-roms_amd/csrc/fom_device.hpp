@@ -26,6 +26,13 @@
 #define BG_PCR_EARLY_EXIT 1
 #endif
 
+// fom_sample forms the off-diagonals and SUPG terms of the NEXT iterate in front of the stopping test, where one wave per
+// sample has nothing else to issue between the dependent rounds of the norm reduction (see fom_sample; topologies with
+// rotates_picard only); 0: every iteration starts with them, the listing of the loop before the rotation
+#ifndef BG_PICARD_ROTATE
+#define BG_PICARD_ROTATE 1
+#endif
+
 namespace bg {
 
 constexpr double GP_A = 0.78867513459481287;  // (1 + 1/sqrt(3)) / 2
@@ -168,6 +175,40 @@ __device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u
     lo[0] = __builtin_fma(-c.dt6, __builtin_fma(2.0, u[0], uL), c.aoff);
 }
 
+// Elements [J0, J1) of assemble_p1 alone, for a caller that places other work between the chunks (fom_sample weaves the
+// norm reduction in): one group of four of supg_terms (J0 a multiple of four, J1 = J0 + 4 <= R), or the R % 4 elements left
+// over (J1 = R).  The arithmetic of every element is assemble_p1's and supg_terms'; lo[0] stays with the caller.
+template <int R, int J0, int J1, typename HF>
+__device__ __forceinline__ void assemble_p1_rows(const MeshConst& c, const double (&u)[R], double uR, HF&& hf,
+                                                 double (&lo)[R], double (&up)[R], double (&se)[R])
+{
+    constexpr int G = R / 4 * 4;
+    static_assert(J0 % 4 == 0 && J0 < J1 && J1 <= R && (J0 < G ? J1 == J0 + 4 : J1 == R), "one supg group or the remainder");
+    double mx[4], t[4];
+#pragma unroll
+    for (int j = J0; j < J1; ++j) {
+        const double ur = (j == R - 1) ? uR : u[j + 1];
+        const double w = u[j] + ur;
+        const double dif = ur - u[j];
+        up[j] = __builtin_fma(c.dt6, w + u[j], c.aoff);
+        if (j + 1 < R) lo[j + 1] = __builtin_fma(-c.dt6, w + ur, c.aoff);
+        mx[j - J0] = fmax(fabs(w), 2.0e-10);
+        t[j - J0] = __builtin_fma(w, dif, -hf(j));
+    }
+    if constexpr (J0 < G) {
+        const double p01 = mx[0] * mx[1], p23 = mx[2] * mx[3];
+        const double r = BG_RCP(p01 * p23);
+        const double r01 = r * p23, r23 = r * p01;
+        se[J0] = t[0] * (r01 * mx[1]);
+        se[J0 + 1] = t[1] * (r01 * mx[0]);
+        se[J0 + 2] = t[2] * (r23 * mx[3]);
+        se[J0 + 3] = t[3] * (r23 * mx[2]);
+    } else {
+#pragma unroll
+        for (int j = J0; j < J1; ++j) se[j] = t[j - J0] * BG_RCP(mx[j - J0]);
+    }
+}
+
 template <int R, bool FULL, typename GF>
 __device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0, bool first, bool last_lane,
                                             double mu1, const double (&u)[R], double uL, double uR, double seL,
@@ -210,6 +251,29 @@ __device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0,
         r = __builtin_fma(-p, ur, r);
         lo[j] = l; di[j] = d; up[j] = p; rhs[j] = r;
     }
+}
+
+// The two halves as calls of their own.  The head reads u, hf and the mesh constants only: not g, which changes per time
+// step, and nothing of the solve.  So the head of an iterate can be formed as soon as the iterate exists, ahead of the
+// stopping test, and serves whichever comes next: the next iteration, or the first iteration of the next time step, which
+// starts from the same u (BG_PICARD_ROTATE, fom.hip).  The head hands uL, uR, se, lo and up to the tail.
+// assemble below is head followed by tail, but written out: through the two calls the compiler commutes the operands of
+// w = u[j] + ur in the kernels of 2 to 6 rows per lane (same bits, another listing).
+template <int R, class Topo, typename HF>
+__device__ __forceinline__ void assemble_head(Topo& tp, const MeshConst& c, const double (&u)[R], HF&& hf, double& uL,
+                                              double& uR, double (&se)[R], double (&lo)[R], double (&up)[R])
+{
+    tp.halo(u[0], u[R - 1], uL, uR);
+    assemble_p1<R>(c, u, uL, uR, hf, lo, up, se);
+}
+
+template <int R, bool FULL, class Topo, typename GF>
+__device__ __forceinline__ void assemble_tail(Topo& tp, const MeshConst& c, int N, double mu1, const double (&u)[R],
+                                              GF&& g, double uL, double uR, const double (&se)[R], double (&lo)[R],
+                                              double (&di)[R], double (&up)[R], double (&rhs)[R])
+{
+    const double seL = tp.below_se(se[R - 1]);
+    assemble_p2<R, FULL>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 template <int R, bool FULL, class Topo, typename GF, typename HF>
@@ -359,6 +423,26 @@ __device__ __forceinline__ void assemble_general_p2(const ElemGeom<R>& gm, doubl
         r = __builtin_fma(-p, ur, r);
         lo[j] = l; di[j] = d; up[j] = p; rhs[j] = r;
     }
+}
+
+// ... and as head and tail (see assemble_head)
+template <int R, class Topo>
+__device__ __forceinline__ void assemble_general_head(Topo& tp, const ElemGeom<R>& gm, double dt, const double (&u)[R],
+                                                      const double (&hfs)[R], double& uL, double& uR, double (&se)[R],
+                                                      double (&lo)[R], double (&up)[R])
+{
+    tp.halo(u[0], u[R - 1], uL, uR);
+    assemble_general_p1<R>(gm, dt, u, uL, uR, hfs, lo, up, se);
+}
+
+template <int R, class Topo>
+__device__ __forceinline__ void assemble_general_tail(Topo& tp, const ElemGeom<R>& gm, double dt, double kap, int N,
+                                                      double mu1, const double (&u)[R], const double (&g)[R], double uL,
+                                                      double uR, const double (&se)[R], double (&lo)[R],
+                                                      double (&di)[R], double (&up)[R], double (&rhs)[R])
+{
+    const double seL = tp.below_se(se[R - 1]);
+    assemble_general_p2<R>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 template <int R, class Topo>

@@ -137,7 +137,11 @@ __device__ __forceinline__ double wave_max_nan(double v, bool nan)
 //   below_se    v of thread g-1 through WideLds::se: once per Picard iteration, the solve's barriers lie between two uses
 //   below, above, gmax, gmax_nan   the FD stepper's exchanges: alternating buffers, so one barrier each in any sequence.
 //               gmax_nan(v, nan): gmax of v >= 0, NaN when `nan` holds in any of the sample's threads (np.max, not fmax)
+//   rotates_picard   whether fom_sample may form the next iterate's assemble_head ahead of sum2 (BG_PICARD_ROTATE): the wave
+//               form's exchanges are DPP moves and order freely; the workgroup form's halo() and below_se() refill LDS
+//               buffers between barriers, and a halo() in front of sum2's barrier has not been argued
 struct WaveTopo {
+    static constexpr bool rotates_picard = true;
     int g;                                           // = lane
     __device__ __forceinline__ bool first() const { return g == 0; }        // owns global row 0
     __device__ __forceinline__ bool last() const { return g == 63; }        // owns the last row when N = 64 R (FULL)
@@ -161,6 +165,7 @@ struct WaveTopo {
 };
 
 struct WgTopo {
+    static constexpr bool rotates_picard = false;
     WideLds& s;
     int g;                                           // = threadIdx.x
     int par;                                         // alternating exchange buffers: one barrier per exchange

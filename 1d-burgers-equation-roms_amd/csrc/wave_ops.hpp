@@ -104,6 +104,35 @@ __device__ __forceinline__ void wave_sum2(double a, double b, double& sa, double
                           __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// wave_sum2 in its stages, for a caller that has independent work to place between them: each round waits for the one
+// before (a DPP move of the running sum, then the add).  start, round<0> ... round<4>, finish are wave_sum2's operations
+// in wave_sum2's order.
+struct WaveSum2 {
+    double v;
+    __device__ __forceinline__ void start(double a, double b)
+    {
+        auto l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+        auto h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+        v = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+    }
+    template <int I>
+    __device__ __forceinline__ void round()
+    {
+        if constexpr (I == 0) v += dpp_mov<0x111>(v);
+        if constexpr (I == 1) v += dpp_mov<0x112>(v);
+        if constexpr (I == 2) v += dpp_mov<0x114>(v);
+        if constexpr (I == 3) v += dpp_mov<0x118>(v);
+        if constexpr (I == 4) v += dpp_mov<0x142, 0xA>(v);
+    }
+    __device__ __forceinline__ void finish(double& sa, double& sb) const
+    {
+        sa = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 31),
+                              __builtin_amdgcn_readlane(__double2loint(v), 31));
+        sb = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
+                              __builtin_amdgcn_readlane(__double2loint(v), 63));
+    }
+};
+
 __device__ __forceinline__ double sel(bool c, double a, double b) { return c ? a : b; }
 
 // inf or NaN in a WAVE-UNIFORM value (every lane holds the same v): exponent field all ones; zeros and denormals are
