@@ -26,6 +26,16 @@
 #define BG_PCR_EARLY_EXIT 1
 #endif
 
+// pcr64 closes the interface system by Jacobi sweeps after its stride-1 step once every coupling of the wave is small
+// enough for six of them (see pcr64); 0: every wave goes on to the stride-2 step, the listing before the sweeps
+#ifndef BG_PCR_JACOBI_EXIT
+#define BG_PCR_JACOBI_EXIT 1
+#endif
+// fewest rows per lane at which that exit is compiled in (1: everywhere)
+#ifndef BG_PCR_JACOBI_MIN_ROWS
+#define BG_PCR_JACOBI_MIN_ROWS 12
+#endif
+
 // fom_sample forms the off-diagonals and SUPG terms of the NEXT iterate in front of the stopping test, where one wave per
 // sample has nothing else to issue between the dependent rounds of the norm reduction (see fom_sample; topologies with
 // rotates_picard only); 0: every iteration starts with them, the listing of the loop before the rotation
@@ -470,6 +480,15 @@ __device__ __forceinline__ double pcr_step_rhs(double A, double C, double D)
     return __builtin_fma(-Dp, C, __builtin_fma(-Dm, A, D));
 }
 
+// One Jacobi sweep x <- D - A x[j-s] - C x[j+s] on the same equations.  pcr_step_rhs shifts the vector it updates; the
+// sweep shifts the iterate x and keeps D as the base (from x = D the two are the same operation).
+template <int CTRL_DN, int CTRL_UP, int REPS>
+__device__ __forceinline__ double pcr_jacobi_sweep(double A, double C, double D, double x)
+{
+    const double xm = dpp_shift<CTRL_DN, REPS>(x), xp = dpp_shift<CTRL_UP, REPS>(x);
+    return __builtin_fma(-xp, C, __builtin_fma(-xm, A, D));
+}
+
 template <int CTRL_DN, int CTRL_UP, int REPS, bool LAST>
 __device__ __forceinline__ void pcr_step(double& A, double& C, double& D)
 {
@@ -568,10 +587,20 @@ __device__ __forceinline__ void wang_finish(const double (&lo)[R], const double 
 // step then adds r * 0), and D_n * 1.0 is D_n, bit for bit.  So the short exit forms D_n alone: no DPP moves of
 // the couplings, no reciprocal, no multiply, and the chain in front of the back-transpose is two DPP moves and
 // two FMAs long (budget and measurements: DESIGN.md K1).
-__device__ __forceinline__ double pcr64(double A, double C, double D)
+//
+// Jacobi exit (BG_PCR_JACOBI_EXIT): after the stride-1 step the equations read A x[j-2] + x[j] + C x[j+2] = D, that is
+// (I + N) x = D with ||N||_inf <= 2 m for couplings <= m, and where the mesh gives a lane many rows m is already small
+// (9.3e-4 at 16 rows per lane on the flagship workload).  The wave asks once whether EVERY lane has
+// |A| <= tau_J and |C| <= tau_J, tau_J = 2^-9, a NaN or inf coupling failing the test as it does the one against tau.
+// If so it runs K = 6 sweeps x <- D - A x[j-2] - C x[j+2] from x = D and returns x: no update of A and C, no
+// reciprocal, no transpose in either direction and no LDS instruction, two double moves by two lanes and two FMAs a
+// sweep.  x_0 = D is off by N x, a sweep multiplies the error by -N, so with rho = 2 tau_J = 2^-8 the result is off by
+// <= rho^(K+1) max|x| <= 2^-56 max|D| / (1 - 2^-8): below half an ulp of the largest interface unknown, the standard of
+// the exit against tau.  One threshold and one K for every workload.  A wave with one lane over tau_J, or a non-finite
+// one, runs everything after the stride-1 step as before (pcr64_from_stride2), both exits of the tau test included.
+__device__ __forceinline__ double pcr64_from_stride2(double A, double C, double D)
 {
     const int lane = lane_id();
-    pcr_step<0x138, 0x130, 1, false>(A, C, D);
     pcr_step<0x138, 0x130, 2, false>(A, C, D);
     {
         const int src = ((4 * (lane & 15) + (lane >> 4)) << 2);
@@ -602,6 +631,29 @@ __device__ __forceinline__ double pcr64(double A, double C, double D)
     return from_lane_rot(D, (16 * (lane & 3) + (lane >> 2)) << 2);
 }
 
+// ROWS = rows per lane of the caller's partition: a wave that fails the test has paid for the sweeps, so the exit is
+// compiled in where the mesh gives a lane at least BG_PCR_JACOBI_MIN_ROWS rows (DESIGN.md K1 has the measurements).
+template <int ROWS>
+__device__ __forceinline__ double pcr64(double A, double C, double D)
+{
+    pcr_step<0x138, 0x130, 1, false>(A, C, D);
+    if constexpr (BG_PCR_JACOBI_EXIT && ROWS >= BG_PCR_JACOBI_MIN_ROWS) {
+        constexpr double tau_j = 0x1p-9;
+        constexpr int sweeps = 6;
+        const bool coupled = !(__builtin_fabs(A) <= tau_j && __builtin_fabs(C) <= tau_j);
+        const bool eliminate = __builtin_amdgcn_ballot_w64(coupled) != 0;
+        // As with the exit against tau: the sweeps stand ahead of the branch and the elimination is one `if` without
+        // an `else`, out of line, which starts again from A, C, D of the stride-1 step.
+        double X = D;
+#pragma unroll
+        for (int k = 0; k < sweeps; ++k) X = pcr_jacobi_sweep<0x138, 0x130, 2>(A, C, D, X);
+        if (__builtin_expect(eliminate, 0)) X = pcr64_from_stride2(A, C, D);
+        return X;
+    } else {
+        return pcr64_from_stride2(A, C, D);
+    }
+}
+
 // Pivot-free tridiagonal solve across the wave (Wang partition + PCR on the 64
 // interface unknowns).  In: lo/di/up/rhs.  Out: solution in rhs.  lo, di are clobbered.
 template <int R>
@@ -610,7 +662,7 @@ __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], 
 {
     if constexpr (R == 1) {
         const double rb = BG_RCP(di[0]);
-        rhs[0] = pcr64(lo[0] * rb, up[0] * rb, rhs[0] * rb);
+        rhs[0] = pcr64<R>(lo[0] * rb, up[0] * rb, rhs[0] * rb);
     } else {
         double gs[R];
         const double dp = wang_reduce<R>(lo, di, up, rhs, gs);
@@ -619,7 +671,7 @@ __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], 
         const double R0 = from_lane_above(rhs[0] * di[0]);
         double A, C, D;           // normalised interface equation: A x[p-1] + x[p] + C x[p+1] = D
         wang_interface<R>(lo, up, rhs, dp, F0, G0, R0, A, C, D);
-        const double X = pcr64(A, C, D);
+        const double X = pcr64<R>(A, C, D);
         wang_finish<R>(lo, di, rhs, gs, X, from_lane_below(X));
     }
 }

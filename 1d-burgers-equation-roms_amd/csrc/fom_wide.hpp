@@ -92,7 +92,7 @@ __device__ __forceinline__ void wide_tridiag_solve(WideLds& s, int g, double (&l
     s.pcr[1][2][e + WIDE_PAD] = D;
     __syncthreads();
     wide_pcr_step<2>(s.pcr[1], e, A, C, D);
-    s.x[e + WIDE_PAD] = pcr64(A, C, D);                      // stride-4 system e & 3 = this wave, in lane order
+    s.x[e + WIDE_PAD] = pcr64<R>(A, C, D);                   // stride-4 system e & 3 = this wave, in lane order
     __syncthreads();
     wang_finish<R>(lo, di, rhs, gs, s.x[g + WIDE_PAD], s.x[g + WIDE_PAD - 1]);
 }
