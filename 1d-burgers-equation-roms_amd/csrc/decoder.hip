@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void decode_mlp_kernel(const uint16_t* __re
 #pragma unroll
         for (int kb = 0; kb < MAXKB; ++kb) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[kb], bq[kb], acc, 0, 0, 0);
         // acc[v] = feature 32 mt + 8 (v / 4) + 4 (l / 32) + v % 4 of column l % 32: four consecutive features per group of 4.
-        // The activation kind is wave-uniform: one switch per tile, selects inside (no divergent branches around expf).
+        // The activation kind is wave-uniform: one switch per tile, selects inside (no divergent branches around expm1f).
         auto epilogue = [&](auto kind_c) __attribute__((always_inline)) {
             constexpr int KIND = decltype(kind_c)::value;
 #pragma unroll
@@ -282,7 +282,8 @@ __global__ __launch_bounds__(256, 2) void decode_mlp_kernel(const uint16_t* __re
                     const uint16_t bb = (uint16_t)((e < 2 ? b_cur[g].x : b_cur[g].y) >> (16 * (e & 1)));
                     // Linear: float32 accumulate + bias, rounded to bf16; activation in float32 on that value, rounded again
                     float v = bf16_to_f32(f32_to_bf16(acc[4 * g + e] + bf16_to_f32(bb)));
-                    if constexpr (KIND == BG_ACT_ELU) { const float ex = alpha * (expf(fminf(v, 0.0f)) - 1.0f); v = v > 0.0f ? v : ex; }
+                    // ELU as torch has it, expm1 times alpha: expf(v) - 1 cancels below |v| = 2^-6 and is 0 once expf rounds to 1
+                    if constexpr (KIND == BG_ACT_ELU) { const float ex = expm1f(fminf(v, 0.0f)) * alpha; v = v > 0.0f ? v : ex; }
                     else if constexpr (KIND == BG_ACT_RELU) v = fmaxf(v, 0.0f);
                     else if constexpr (KIND == BG_ACT_TANH) v = tanhf(v);
                     const uint32_t h = f32_to_bf16(v);
