@@ -107,6 +107,12 @@ _SIGNATURES = {
     "bg_quad_rom_run_long_phif_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_quad_rom_run_long_h3f_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_quad_rom_run_long": _loop(5, [c_double_p] * 3),
+    "bg_hyper_quad_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 3),
+    "bg_hyper_quad_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
+    "bg_hyper_quad_rom_phif_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_hyper_quad_rom_h3f_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    # N, B, n, m, nodes, nsteps, projection, xn, then node, pos, xi, Phif, H3f, q0, the batch (u0n for u0), ..., qhist for hist
+    "bg_hyper_quad_rom_run": _loop(7, [c_int_p, c_int_p] + [c_double_p] * 4),
     "bg_rom_run_wide_max_r": (ctypes.c_int, []),
     "bg_rom_run_wide_phi_elems": (ctypes.c_longlong, [ctypes.c_int]),
     "bg_rom_run_wide": _loop(5, [c_double_p]),

@@ -905,6 +905,68 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
     return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
 
 
+# ---- row sampling for the hyper-reduced quadratic-manifold PROM (rom.quadratic_run_hyper, bg_hyper_quad_rom_run) ----
+def hyper_quad_rom_limits():
+    """(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run.  Needs no device."""
+    from . import lib as _lib
+    return _lib.limits("bg_hyper_quad_rom_limits", 3)
+
+
+def quad_row_sampling_system(X, Phi, H, runs, dt, projection, E=0.0, stride=10):
+    """(G, pairs): the training matrix of build_quad_row_sampling, (pairs n, N).  ``X``, ``Phi`` (N, n), ``H`` (N, n(n+1)/2):
+    host arrays; ``projection``: "galerkin" or "lspg".  This stepper has no SUPG term (picard_rows with supg=False)."""
+    n = Phi.shape[1]
+    I, J = np.triu_indices(n)
+    idx = np.zeros((n, n), dtype=np.int64)
+    idx[I, J] = idx[J, I] = np.arange(len(I))
+    H3 = H[:, idx] * (np.ones((n, n)) + np.eye(n))                              # (N, n, n): tangent = Phi + H3 . q
+    blocks = []
+    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
+        steps = np.arange(0, Sn.shape[1] - 1, int(stride))
+        Q = Phi.T @ Sn                                                          # (n, nT+1)
+        Un = Phi @ Q[:, steps] + H @ (Q[I][:, steps] * Q[J][:, steps])          # on the manifold
+        U0 = Phi @ Q[:, steps + 1] + H @ (Q[I][:, steps + 1] * Q[J][:, steps + 1])
+        for k, s in enumerate(steps):
+            W = Phi + H3 @ Q[:, s + 1]
+            blocks.append(row_contributions(X, W, U0[:, k], Un[:, k], mu1, mu2, float(dt), projection, float(E), False))
+    return _stack_contributions(blocks, "build_quad_row_sampling")
+
+
+def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, stride=10, min_rows=None, max_rows=None):
+    """build_row_sampling for the quadratic-manifold PROM (rom.quadratic_run_hyper): the same host NNLS (nnls_rows, row 0
+    forced in with weight 1) on training pairs that lie on the manifold.  For every run (hist (N, nT+1), mu1, mu2) and every
+    ``stride``-th step n: q_n = Phi^T s_n, Un = Phi q_n + H sym(q_n), U0 likewise at n + 1, and the contributions
+    c_i = w_i R_i of all mesh rows (picard_rows without the SUPG term, which this stepper does not have) with the tangent
+    W = Phi + H dQ/dq(q_{n+1}): w_i = W[i] for "galerkin", (A W)[i] for "lspg".
+
+    ``tau`` defaults to 1e-5, not the 1e-4 of the other builders: at 1e-4 the LSPG iteration is unusable.  Measured with the
+    numpy restatement of the sampled iteration against the full PROM (N = 2049, dt = 0.0125, n = 40, alpha = 1e-2, nine
+    training runs, every 10th step, rel-L2 over 4 steps at mu = (4.6, 0.021) and (5.3, 0.017)): Galerkin tau = 1e-4: 172 rows,
+    1.6e-3 .. 1.8e-3; LSPG 1e-4: 156 rows, 7.4e-2 .. 9.9e-2 with three iterations more than the full PROM; LSPG 1e-5: 171
+    rows, 1.9e-3 .. 2.1e-3; LSPG 1e-6: 174 rows, 1.6e-3 .. 1.8e-3; at tau <= 1e-5 every iteration count equals the full PROM's.
+    ``min_rows`` defaults to 3 n as the POD builder's does.  The training matrix has a small numerical rank (184 .. 190 of
+    2049 columns there, 107 .. 110 of 1024 at N = 1024 with the same dt), and a sampling with more rows than that rank fits
+    it exactly and then IS the full PROM to rounding: with ``min_rows`` = 250 the loop stayed within 2e-9 of the full PROM
+    over 40 steps at N = 1024 (dt = 0.025) and N = 4096 (dt = 0.00625), every count equal, where the default's 161 .. 179
+    rows drifted to 2e-3 .. 2e-2 and, LSPG at N = 4096, ended in steps that hit the cap.  For long runs ask for
+    ``min_rows`` above the rank.  ``max_rows`` defaults to the kernel's limit (hyper_quad_rom_limits); needing more is a
+    ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    projection = str(projection).lower()
+    if projection not in ("galerkin", "lspg"):
+        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
+    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    Phi, H = _host_matrix(Phi), _host_matrix(H)
+    N = len(X)
+    if Phi.ndim != 2 or H.ndim != 2 or Phi.shape[0] != N or H.shape != (N, Phi.shape[1] * (Phi.shape[1] + 1) // 2):
+        raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2), one row per mesh node")
+    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
+        raise ValueError("build_quad_row_sampling takes at least one run, stride >= 1 and tau > 0")
+    min_rows = min(3 * Phi.shape[1], N) if min_rows is None else int(min_rows)
+    max_rows = hyper_quad_rom_limits()[1] if max_rows is None else int(max_rows)
+    G, pairs = quad_row_sampling_system(X, Phi, H, runs, dt, projection, E, stride)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+
+
 # ---- row sampling for the hyper-reduced POD-RBF PROM (rom.pod_rbf_run_hyper, bg_hyper_rbf_rom_run) ----
 def hyper_rbf_rom_limits():
     """(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run.  Needs no device."""

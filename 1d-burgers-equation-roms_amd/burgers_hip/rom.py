@@ -66,6 +66,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
     _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
+    _Route("bg_hyper_quad_rom_run", 1, "bg_quad_rom_max_n", 3, "bg_fom_max_n", group=4, supg=False),
 )}
 
 
@@ -906,6 +907,117 @@ def quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, Phi_H_or_plan, proj, E=0.0, 
     return res
 
 
+def _quad_decoder(Phid, Hd, rows):
+    """decode(q) for q (rows, n) on the device: u = Phi q + H Q(q) (:1116-1118) as ONE GEMM [q | Q(q)] . [Phi^T; H^T]; the
+    left operand comes from bg_quad_features."""
+    L, device, n = _lib.load(), Phid.device, Phid.shape[1]
+    I, J, _, _ = sym_index_tables(n, device)
+    WT = torch.cat([Phid.t(), Hd.t()], 0).contiguous()       # (n + k, N)
+    I32, J32 = I.to(torch.int32).contiguous(), J.to(torch.int32).contiguous()
+    feat = torch.empty((rows, n + len(I)), dtype=torch.float64, device=device)
+
+    def decode(q):
+        with torch.cuda.device(device):
+            _lib.check(L.bg_quad_features(rows, n, _lib.ptr(q), _lib.ptr(I32), _lib.ptr(J32), _lib.ptr(feat),
+                                          _lib.stream_ptr(device)), "bg_quad_features")
+        return feat @ WT
+    return decode
+
+
+class HyperQuadPlan:
+    """What bg_hyper_quad_rom_run reads besides the batch, built once per manifold, sampling and mesh (include/burgers_hip.h):
+    the table of the sorted distinct stencil nodes of the sampled rows (``nodes``, at most 3 m), their coordinates ``xn``,
+    the table position ``pos`` of every sampled row, the weights ``xi``, and bg_quad_rom_run's operand copies Phif, H3f of
+    Phi and H restricted to the table nodes.  ``sampling``: a pod.RowSampling (pod.build_quad_row_sampling).  Everything the
+    shapes, the sampling and the manifold decide is refused with a ValueError before the device is touched -- also
+    |Phi^T Phi - I|_max > 1e-8 or |Phi^T H|_max > 1e-8: the loop carries q from step to step instead of re-projecting
+    Phi^T u^n, which is exact only for an orthonormal Phi and an H fitted on the residual of the projection."""
+
+    def __init__(self, Phi, H, sampling, X, device):
+        route = _ROUTES["bg_hyper_quad_rom_run"]
+        max_n, max_m, max_nodes = _lib.limits("bg_hyper_quad_rom_limits", 3)
+        Ph, Hh = (np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64) for A in (Phi, H))
+        if Ph.ndim != 2 or Ph.shape[1] < 1 or Hh.shape != (Ph.shape[0], Ph.shape[1] * (Ph.shape[1] + 1) // 2):
+            raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
+        N, n = Ph.shape
+        Xh = check_mesh(X)
+        if N < route.min_n or N > _limit(route.max_n) or len(Xh) != N:
+            raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of Phi and H per mesh node")
+        if n > max_n:
+            raise ValueError(f"{route.entry} covers n <= {max_n} (got {n})")
+        rows, xi = _sampling_rows(route, sampling, N, max_m)
+        if not (np.isfinite(Ph).all() and np.isfinite(Hh).all()) or np.abs(Ph.T @ Ph - np.eye(n)).max() > 1e-8:
+            raise ValueError("Phi must have orthonormal columns (to 1e-8): the loop does not re-project Phi^T u^n")
+        if np.abs(Ph.T @ Hh).max() > 1e-8:
+            raise ValueError("Phi^T H must vanish (to 1e-8): the loop does not re-project Phi^T u^n")
+        nodes = _stencil_nodes(route, rows, N, max_nodes)
+        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        device = _lib.require_device(device)
+        self.N, self.n = N, n
+        self.Phi, self.H = _as_dev(Ph, device), _as_dev(Hh, device)
+        _put_table(self, nodes, rows, xi, sampling, Xh, device)
+        _, self.Phif, self.H3f = _quad_operand_copies(self.Phi[self.nodes].contiguous(), self.H[self.nodes].contiguous())
+        L = _lib.load()
+        assert (self.Phif.numel(), self.H3f.numel()) == (L.bg_hyper_quad_rom_phif_elems(len(nodes)), L.bg_hyper_quad_rom_h3f_elems(len(nodes)))
+
+
+class HyperQuadRomResult:
+    """Result of quadratic_run_hyper: the reduced coordinates ``q`` (B, nT+1, n) (column 0: Phi^T u0), ``iters``, ``flags``,
+    ``info``, the ``plan`` and the ``path``.  ``hist`` (B, nT+1, N) is decoded on demand, U = Phi q + H Q(q) with the decode
+    of the host-driven route and u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
+    (B, N, nT+1) layout."""
+
+    def __init__(self, res, plan, u0d):
+        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
+        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
+
+    @property
+    def hist(self):
+        if self._hist is None:
+            B, cols, n = self.q.shape
+            self._hist = _quad_decoder(self.plan.Phi, self.plan.H, B * cols)(self.q.reshape(B * cols, n)).reshape(B, cols, -1)
+            self._hist[:, 0] = self._u0
+        return self._hist
+
+    def snapshots(self):
+        return FomResult(self.hist, self.iters, self.flags).snapshots()
+
+    @property
+    def newton_steps(self):
+        return int(self.iters.sum().item())
+
+
+def quadratic_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, H, sampling_or_plan, proj, E=0.0, newton_tol=1e-6, newton_itmax=25,
+                        device=None, balance=True):
+    """``pod_quadratic_manifold`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_quad_rom_run): both
+    projections are assembled from the sampled mesh rows of a pod.RowSampling (pod.build_quad_row_sampling) with their
+    weights, on the table of their stencil nodes, so a pass streams a few hundred rows of the tangent tensor whatever the
+    mesh: N up to bg_fom_max_n(), n <= 40, m <= 256, at most 768 table nodes (bg_hyper_quad_rom_limits).  q carries over from
+    step to step (no Phi^T u^n: Phi must be orthonormal and Phi^T H = 0).  ``sampling_or_plan``: the sampling, or a
+    HyperQuadPlan of this manifold, sampling and mesh to reuse across calls (``res.plan``; ``Phi`` and ``H`` are then not
+    looked at).  A plan built for another mesh or device and a sampling trained for the other projection are refused.
+    Nothing is synchronised.  Returns a HyperQuadRomResult."""
+    Xh = check_mesh(X)
+    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperQuadPlan) else HyperQuadPlan(Phi, H, sampling_or_plan, Xh, device)
+    device = _lib.require_device(device)
+    if plan.Phi.device != device:
+        raise ValueError("the plan was built on another device")
+    if not np.array_equal(plan.Xh, Xh):
+        raise ValueError("the plan was built for another mesh")
+    if plan.projection != proj:
+        raise ValueError("the row sampling was trained for the other projection")
+    u0d, _, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
+    q0 = _project_rows(u0d, plan.Phi)
+    u0n = u0d[:, plan.nodes].contiguous()
+    res = _device_loop(_ROUTES["bg_hyper_quad_rom_run"], Xh, u0d, mu1, mu2, nsteps, device, 0, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.n, plan.m, plan.n_nodes, int(nsteps), proj, _lib.ptr(plan.xn), _lib.ptr(plan.node),
+                           _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.Phif), _lib.ptr(plan.H3f), _lib.ptr(q0),
+                           _lib.ptr(u0n), *inputs[1:], float(dt), float(E), float(newton_tol), int(newton_itmax), opts, *outputs),
+                       keep=(plan, q0, u0n), cols=plan.n)
+    return HyperQuadRomResult(res, plan, u0d)
+
+
 def _quad_route(N, n, fused=True, long_mesh=False):
     """Which way quadratic_run takes an (N, n) manifold: a device-side loop's entry point, or "host"."""
     quad, long = _ROUTES["bg_quad_rom_run"], _ROUTES["bg_quad_rom_run_long"]
@@ -917,15 +1029,20 @@ def _quad_route(N, n, fused=True, long_mesh=False):
 
 
 def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0, newton_tol=1e-6,
-                  newton_itmax=25, device=None, fused=True, plan=None, long_mesh=False):
+                  newton_itmax=25, device=None, fused=True, plan=None, long_mesh=False, hyper=None):
     """Batched ``pod_quadratic_manifold`` (no SUPG term in this variant, :1142).  ``fused`` (default): the device-side
     time loop bg_quad_rom_run where it applies (N <= 512, n <= 40); otherwise, or with ``fused=False``, the batched
     iteration (bg_quad_tangent -> bg_rom_reduce_frag -> bg_lu_solve_update -> decode GEMM) driven from the host.
     ``plan``: a QuadFusedPlan of (Phi, H) to reuse across calls.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= bg_quad_rom_run_long_max_n() with n <=
     bg_quad_rom_run_long_max_r() take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration
-    (``plan`` may then be a QuadLongPlan)."""
+    (``plan`` may then be a QuadLongPlan).
+    ``hyper`` (opt-in): a pod.RowSampling (pod.build_quad_row_sampling) or a HyperQuadPlan sends the call through the
+    hyper-reduced loop quadratic_run_hyper, which assembles both projections from the sampled mesh rows only; manifolds and
+    samplings it does not cover are refused, not rerouted."""
     proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
+    if hyper is not None:
+        return check_singular(quadratic_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, H, hyper, proj, E, newton_tol, newton_itmax, device))
     if long_mesh and fused and _quad_route(np.shape(Phi)[0], np.shape(Phi)[1], long_mesh=True) == "bg_quad_rom_run_long":
         what = plan if isinstance(plan, QuadLongPlan) else (Phi, H)
         return check_singular(quadratic_run_long(X, u0, mu1, mu2, dt, nsteps, what, proj, E, newton_tol, newton_itmax, device))
@@ -943,22 +1060,11 @@ def quadratic_run(X, u0, mu1, mu2, dt, nsteps, Phi, H, projection="LSPG", E=0.0,
     kk = n * (n + 1) // 2
     if Hd.shape != (c.N, kk) or Phid.shape[0] != c.N:
         raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
-    I, J, idx, fac = sym_index_tables(n, c.device)
-    PhiT, HT = Phid.t().contiguous(), Hd.t().contiguous()
+    _, _, idx, fac = sym_index_tables(n, c.device)
     # H3[i, a, b] = H[i, pair(a, b)] * (1 + delta_ab):  tangent = Phi + H3 . q   (:1120-1123)
     H3 = (Hd[:, idx] * fac).reshape(c.N * n, n).contiguous()
 
-    # decode u = Phi q + H Q(q) (:1116-1118) as ONE GEMM [q | Q(q)] . [Phi^T; H^T]; the left operand comes from bg_quad_features
-    WT = torch.cat([PhiT, HT], 0).contiguous()               # (n + k, N)
-    I32, J32 = I.to(torch.int32).contiguous(), J.to(torch.int32).contiguous()
-    feat = torch.empty((c.B, n + kk), dtype=torch.float64, device=c.device)
-
-    def decode(q):
-        with torch.cuda.device(c.device):
-            _lib.check(c.L.bg_quad_features(c.B, n, _lib.ptr(q), _lib.ptr(I32), _lib.ptr(J32), _lib.ptr(feat), c.stream()),
-                       "bg_quad_features")
-        return feat @ WT
-
+    decode = _quad_decoder(Phid, Hd, c.B)
     H3t = H3.t().contiguous()
     Phi_flat = Phid.reshape(1, c.N * n)
     per = int(c.L.bg_rom_frag_elems(c.N, n))
@@ -1273,6 +1379,40 @@ def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, 
                             X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
+def _sampling_rows(route, sampling, N, max_m):
+    """(rows int64, xi float64) of a pod.RowSampling on the host, checked against a mesh of N nodes and the loop's ``max_m``:
+    what HyperAnnPlan, HyperRbfPlan and HyperQuadPlan refuse alike, each a ValueError."""
+    rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
+    xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
+    m = len(rows)
+    if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
+        raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
+    if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
+        raise ValueError("the weights must be finite and >= 0")
+    if m > max_m:
+        raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+    return rows, xi
+
+
+def _stencil_nodes(route, rows, N, max_nodes):
+    """The sorted distinct stencil nodes of the sampled rows (ValueError beyond ``max_nodes``)."""
+    nodes = np.unique(np.clip(rows[:, None] + np.arange(-1, 2)[None, :], 0, N - 1))
+    if len(nodes) > max_nodes:
+        raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
+    return nodes
+
+
+def _put_table(plan, nodes, rows, xi, sampling, Xh, device):
+    """The table arguments the hyper-reduced closure and quadratic loops share, on ``device``: ``nodes`` (int64, for
+    gathers), ``node``, ``pos``, ``xi``, ``xn``, with ``m``, ``n_nodes``, ``Xh`` and the ``sampling``."""
+    plan.m, plan.n_nodes, plan.Xh, plan.sampling = len(rows), len(nodes), Xh.copy(), sampling
+    plan.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
+    plan.node = plan.nodes.to(torch.int32)
+    plan.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
+    plan.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+    plan.xn = _as_dev(Xh[nodes], device)
+
+
 class _HyperClosurePlan:
     """What HyperAnnPlan and HyperRbfPlan share: the checks of bases, mesh and sampling on the host, and the table of the
     sorted distinct stencil nodes of the sampled rows on the device (include/burgers_hip.h, bg_hyper_ann_rom_run)."""
@@ -1288,15 +1428,7 @@ class _HyperClosurePlan:
             raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of U_p and U_s per mesh node")
         if n > max_n or nbar > max_nbar:
             raise ValueError(f"{route.entry} covers n <= {max_n} and nbar <= {max_nbar} (got {n}, {nbar})")
-        rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
-        xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
-        m = len(rows)
-        if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
-            raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
-        if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
-            raise ValueError("the weights must be finite and >= 0")
-        if m > max_m:
-            raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+        rows, xi = _sampling_rows(route, sampling, N, max_m)
         return Up, Us, Xh, rows, xi
 
     def _pack_table(self, route, Up, Us, Xh, rows, xi, sampling, max_nodes, device, workgroups_per_cu, ut_shape):
@@ -1307,20 +1439,13 @@ class _HyperClosurePlan:
         U = np.concatenate([Up, Us], axis=1)
         if not np.isfinite(U).all() or np.abs(U.T @ U - np.eye(n + nbar)).max() > 1e-8:
             raise ValueError("[U_p U_s] must have orthonormal columns (to 1e-8): the loop does not re-project U_p^T u^n")
-        nodes = np.unique(np.clip(rows[:, None] + np.arange(-1, 2)[None, :], 0, N - 1))
-        if len(nodes) > max_nodes:
-            raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
+        nodes = _stencil_nodes(route, rows, N, max_nodes)
         self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
         device = _lib.require_device(device)
-        self.N, self.n, self.nbar, self.m, self.n_nodes, self.Xh = N, n, nbar, len(rows), len(nodes), Xh.copy()
-        self.sampling = sampling
+        self.N, self.n, self.nbar = N, n, nbar
         self.wg_per_cu = workgroups_per_cu(len(nodes))
         self.Up, self.Us = _as_dev(Up, device), _as_dev(Us, device)
-        self.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
-        self.node = self.nodes.to(torch.int32)
-        self.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
-        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
-        self.xn = _as_dev(Xh[nodes], device)
+        _put_table(self, nodes, rows, xi, sampling, Xh, device)
         UTn = np.zeros(ut_shape(len(nodes)))
         UTn[:n + nbar, :len(nodes)] = U[nodes].T
         self.UTn = _as_dev(UTn, device)

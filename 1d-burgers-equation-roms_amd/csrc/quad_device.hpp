@@ -1,5 +1,6 @@
 // quad_device.hpp -- the whole quadratic-manifold PROM time loop of FOUR samples on one compute unit: the one source of
-// bg_quad_rom_run (quad_fused.hip, N <= 512) and bg_quad_rom_run_long (quad_long.hip, 513 <= N <= 1024).
+// bg_quad_rom_run (quad_fused.hip, N <= 512), bg_quad_rom_run_long (quad_long.hip, 513 <= N <= 1024) and the hyper-reduced
+// bg_hyper_quad_rom_run (quad_hyper.hip, any N, on the table of a row sampling's stencil nodes).
 //
 // Replaces FEMBurgers.pod_quadratic_manifold (reference FEM/fem_burgers.py:1081-1175) for a batch of samples: decoder
 // u = Phi q + H Q(q) (:1116-1118), tangent T = Phi + H dQ/dq (:1120-1123), A(u), R(u) (:1133-1147), the reduced system
@@ -34,6 +35,20 @@
 //   K::Nodes                     where g = M u^n + dt F and dt F of the wave's sample live between the step start and the
 //                                assembly: put_fdt, and init if dt F is `staged` through the tangent rows (setup), fdt,
 //                                set_g (step start), g (assembly)
+//   K::Args, K::hyper            the argument block, and whether the kernel is the hyper-reduced form below
+//
+// The hyper-reduced form (K::hyper, Args = HyperQuadRunArgs: bg_hyper_quad_rom_run, quad_hyper.hip).  Both projections are
+// sums over mesh rows and row i needs state, tangent and coordinates at nodes i - 1, i, i + 1 only.  The caller packs the
+// sorted distinct stencil nodes of the m sampled rows (node[k], k < nodes <= 3 m) with their coordinates and the rows of
+// Phi and H at them; the stencil nodes of a sampled row are consecutive integers, hence consecutive table entries, so the
+// table is a non-uniform mesh of `nodes` nodes and the body runs on it with a.N = nodes, x = xn, u0 = u0n.  What differs:
+//   - a table node that is only a neighbour assembles as a row outside the mesh and every coefficient is multiplied by the
+//     row's weight xi (Galerkin) or sqrt(xi) (LSPG), 0 there: its row vanishes from both sums.  Whether a sampled row is the
+//     Dirichlet row or the last row is decided by node[k] against the mesh's own node count a.meshN.  Mesh row and factor
+//     of a table node are the same for every sample: scattered once per workgroup into LDS (K::hyper_row, K::hyper_mul);
+//   - q starts from q0 (the caller's Phi^T u0) and carries over from step to step: Phi^T H = 0 for a manifold fitted on the
+//     residual of the projection, so Phi^T (Phi q + H Q(q)) = q and the Phi^T u^n of the step start is compiled out;
+//   - the history is q of every step, [B][nsteps+1][n]; no vector of mesh length is touched.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,6 +92,57 @@ struct QuadRunArgs {
     int N, NPAD, NG, B, n, nsteps, max_it, nonuniform;
 };
 
+// bg_hyper_quad_rom_run: N is the table's node count and x, Phif, H3f, u0 are the table's xn [nodes], Phi and H restricted to
+// the table nodes, u0n [B][nodes]; hist is qhist [B][nsteps+1][n]; PhiT is not read; nonuniform is 1
+struct HyperQuadRunArgs : QuadRunArgs {
+    const int32_t* node;    // [nodes] ascending mesh nodes of the table
+    const int32_t* pos;     // [nrows] table position of every sampled row
+    const double* xi;       // [nrows] weights
+    const double* q0;       // [B][n]
+    int meshN, nrows;       // the mesh's own node count (it decides the Dirichlet row and the last row); sampled rows
+};
+
+// pick_sample that skips: wave w of group grp takes order[4 grp + w]; entries outside [0, B) are skipped.  One exit, and the
+// test last: with an early `return false` the kernel spilled three more scalar registers.
+struct QuadSkippingOrder {
+    static __device__ __forceinline__ bool pick_sample(const QuadRunArgs& a, int grp, int w, bool& valid, int& sb)
+    {
+        int sraw[QG];                                  // the group's four samples, read by every wave: the skip below is workgroup-uniform
+#pragma unroll
+        for (int j = 0; j < QG; ++j) {
+            const int sl = grp * QG + j;
+            sraw[j] = sl < a.B ? (a.order ? a.order[sl] : sl) : -1;
+            if (sraw[j] >= a.B) sraw[j] = -1;
+        }
+        const int mine = w == 0 ? sraw[0] : (w == 1 ? sraw[1] : (w == 2 ? sraw[2] : sraw[3]));
+        valid = mine >= 0;
+        sb = valid ? mine : 0;                         // a padding wave computes on a copy of sample 0, stores nothing
+        return (sraw[0] & sraw[1] & sraw[2] & sraw[3]) >= 0;             // false: no valid entry in this group
+    }
+};
+
+// K::Nodes with both arrays in the owning wave's registers: rows lane + 64 m of its sample, ROWS / 64 doubles each
+template <int ROWS>
+struct QuadRegisterNodes {
+    static constexpr int QM = ROWS / 64;
+    double fdt_[QM], gv[QM];        // dt F and g = M u^n + dt F
+    // dt F is staged in the wave's (still unused) tangent rows, and the kernel hands row lane + 64 m to init(m, .): the
+    // setup loop stays rolled (four exp per row), the register arrays want static indices
+    static constexpr bool staged = true;
+    __device__ __forceinline__ void put_fdt(double* Tw, int, int i, double v) { Tw[i] = v; }
+    __device__ __forceinline__ void init(int m, double v) { fdt_[m] = v; gv[m] = 0.0; }
+    __device__ __forceinline__ double fdt(int, int, int m) const { return fdt_[m]; }
+    __device__ __forceinline__ void set_g(int, int, int m, double v) { gv[m] = v; }
+    // g of row 64 slab + lane: this lane's gv[slab] (zero beyond N), by a chain of selects on the wave-uniform slab number
+    __device__ __forceinline__ double g(int, int, int, int slab) const
+    {
+        double gi = 0.0;
+#pragma unroll
+        for (int m = 0; m < QM; ++m) gi = (slab == m) ? gv[m] : gi;
+        return gi;
+    }
+};
+
 template <bool GAL>
 struct QuadAcc {
     static constexpr int main_pairs = GAL ? QNB * QNB : QNB * (QNB + 1) / 2;
@@ -86,8 +152,9 @@ struct QuadAcc {
 // The kernel itself, not a device function that a kernel of each file calls: at 512 registers the register allocation of the
 // loop did not survive a wrapper (more spills in all four instantiations).
 template <class K, bool GAL>
-__global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
+__global__ __launch_bounds__(256, 1) void quad_rom_kernel(typename K::Args a)
 {
+    constexpr bool HYPER = K::hyper;
     constexpr int NACC = QuadAcc<GAL>::total;
     constexpr int QM = K::rows / 64;              // mesh rows per lane of a per-node sweep: row lane + 64 m
     constexpr int QW = K::window;                 // 16-byte slots of the tangent stream in flight per wave (divides 28)
@@ -102,7 +169,8 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform by construction: tile and row arithmetic on the scalar unit
-    const int N = a.N, n = a.n, NPAD = a.NPAD;
+    const int N = a.N, n = a.n;                                 // HYPER: N is the table's node count
+    [[maybe_unused]] const int NPAD = a.NPAD;
     const double h = (a.x[N - 1] - a.x[0]) / (double)(N - 1);
     const int nslab = (N + QRS - 1) / QRS;
     double* Tw = s_T + w * QTJ;                       // this wave's sample
@@ -111,6 +179,26 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
     const int pk = lane >> 4, pblk = (lane >> 2) & 3, pt = lane & 3;
 
     for (int e = tid; e < QG * QTJ; e += 256) s_T[e] = 0.0;        // ring slots are read before their first write (row -1 of slab 0): keep them finite
+    if constexpr (HYPER) {
+        // mesh row (a.meshN: not sampled, a row outside the mesh) and weight factor of every table node, the same for every
+        // sample: K::hyper_row holds 1 + the sampled row's index on its way there
+        for (int k = tid; k < K::rows; k += 256) K::hyper_row(k) = 0;
+        __syncthreads();
+        for (int j = tid; j < a.nrows; j += 256) {
+            const int p = a.pos[j];
+            if ((unsigned)p < (unsigned)N) K::hyper_row(p) = j + 1;
+        }
+        __syncthreads();
+        for (int k = tid; k < K::rows; k += 256) {
+            int j = K::hyper_row(k);
+            const int ir = j ? a.node[k] : a.meshN;
+            // (a sampled row whose neighbour the table does not hold -- not a table the contract allows -- is left out)
+            if ((unsigned)ir >= (unsigned)a.meshN || (ir > 0 && k == 0) || (ir < a.meshN - 1 && k == N - 1)) j = 0;
+            const double xi = j ? a.xi[j - 1] : 0.0;
+            K::hyper_row(k) = j ? ir : a.meshN;
+            K::hyper_mul(k) = GAL ? xi : sqrt(xi);
+        }
+    }
     const int ngroups = (a.B + QG - 1) / QG;
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         bool valid;                                    // false: a padding wave, computes on a copy of sample sb, stores nothing
@@ -118,7 +206,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
         if (!K::pick_sample(a, grp, w, valid, sb)) continue;
         const int smp = sb;
         const double mu1 = a.mu1[sb], mu2 = a.mu2[sb];
-        double* hist = a.hist + (size_t)sb * (size_t)(a.nsteps + 1) * (size_t)N;
+        double* hist = a.hist + (size_t)sb * (size_t)(a.nsteps + 1) * (size_t)(HYPER ? n : N);      // HYPER: q of every step
         __syncthreads();                               // the previous group is done with LDS
         // ---- per-sample constants (compute_forcing_vector :427-461) and the initial state, wave-local ------------
         typename K::Nodes nodes;                       // g and dt F of this wave's sample
@@ -127,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
             if (i < N) {
                 rom_nodal_forcing(a.x, i, N, mu2, h, a.nonuniform, frPrev, fl, hf);
                 u = a.u0[(size_t)sb * N + i];
-                if (valid) hist[i] = u;
+                if constexpr (!HYPER) { if (valid) hist[i] = u; }
             }
             nodes.put_fdt(Tw, w, i, a.dt * (frPrev + fl));
             s_u[w][i + 2] = u;
@@ -140,6 +228,11 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
             for (int m = 0; m < QM; ++m) nodes.init(m, Tw[lane + 64 * m]);
         }
         int flags = 0, info_out = 0;
+        [[maybe_unused]] double qcarry = 0.0;          // HYPER: q = q0 (the caller's Phi^T u0), then the previous step's
+        if constexpr (HYPER) {
+            qcarry = (lane < n) ? a.q0[(size_t)sb * n + lane] : 0.0;
+            if (valid && lane < n) hist[lane] = qcarry;
+        }
         PhaseClock<kPhaseClock, 8> clk;                // diagnostic builds (tools/time_quad_fused.py)
         // T rows of a row group (4 mesh rows) for the four samples.  H3 of a mesh row is symmetric: only its 55 upper 4 x 4 blocks
         // (a <= b) are stored and streamed -- 3.7 MB instead of 6.5 MB per pass through the CU's vector-memory path, which bounded
@@ -230,12 +323,13 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
         auto ring_row = [](int i) { return 4 * (((i + 4) >> 2) % QRING) + ((i + 4) & 3); };
 
         for (int step = 0; step < a.nsteps; ++step) {
-            // ---- g = M u^n + dt F (`M @ U[:, m] + At*F`, :1144), q = Phi^T u^n (:1129); wave-local ------------------
+            // ---- g = M u^n + dt F (`M @ U[:, m] + At*F`, :1144), q = Phi^T u^n (:1129; HYPER: q carries over); wave-local ----
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             double q = 0.0;                                // lane a < n holds q_a
+            if constexpr (HYPER) q = qcarry;
             {
-                double uu[QM];
+                [[maybe_unused]] double uu[QM];
 #pragma unroll
                 for (int m = 0; m < QM; ++m) {
                     const int i = lane + 64 * m;
@@ -245,6 +339,7 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                     if (i < N) g = rom_mass_rhs_node(a.x, i, N, um, u0, ur, nodes.fdt(w, i, m), h, a.nonuniform);
                     nodes.set_g(w, i, m, g);
                 }
+                if constexpr (!HYPER)
                 for (int c0 = 0; c0 < QN; c0 += 4) {
                     double f[4][QM];
 #pragma unroll
@@ -334,6 +429,16 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
                             const double um = s_u[w][i + 1], u0 = s_u[w][i + 2];
                             const double ur = (lane == QRS - 1) ? s_unext[w] : s_u[w][i + 3];
                             double lo, di, up, R;
+                            if constexpr (HYPER) {
+                                // table node i as mesh row ir (a.meshN where the node is only a neighbour: a row outside the
+                                // mesh, weight 0), the table coordinates as the x[ir - 1], x[ir], x[ir + 1] of the row routine
+                                const int ir = K::hyper_row(i);
+                                const bool in = ir < a.meshN;
+                                rom_assemble_row(ir, a.meshN, um, u0, ur, in ? nodes.g(w, i, N, slab) : 0.0, 0.0, 0.0, mu1, mc, 1,
+                                                 a.x + (in ? i - ir : 0), a.dt, a.E, lo, di, up, R);
+                                const double wm = K::hyper_mul(i);
+                                lo *= wm; di *= wm; up *= wm; R *= wm;
+                            } else
                             rom_assemble_row(i, N, um, u0, (i + 1 < N) ? ur : 0.0, nodes.g(w, i, N, slab), 0.0, 0.0, mu1, mc,
                                              a.nonuniform, a.x, a.dt, a.E, lo, di, up, R);
                             *reinterpret_cast<double2*>(&s_coef[w][lane][0]) = make_double2(lo, di);
@@ -481,10 +586,15 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
             clk.lap(7);
             // ---- U[:, m+1] = u (:1173): one coalesced row per sample ---------------------------------------------------------
             if (valid) {
-                double* hrow = hist + (size_t)(step + 1) * N;
-                for (int i = lane; i < N; i += 64) hrow[i] = s_u[w][i + 2];
+                if constexpr (HYPER) {                     // q of the step; u stays in LDS for the next step's mass row
+                    if (lane < n) hist[(size_t)(step + 1) * n + lane] = q;
+                } else {
+                    double* hrow = hist + (size_t)(step + 1) * N;
+                    for (int i = lane; i < N; i += 64) hrow[i] = s_u[w][i + 2];
+                }
                 if (lane == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
             }
+            if constexpr (HYPER) qcarry = q;
         }
         if (valid && lane == 0) {
             a.flags[smp] = flags;
@@ -494,8 +604,20 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(QuadRunArgs a)
     }
 }
 
-// The launch of quad_rom_kernel<K, projection> once the entry point has checked its arguments: at most one workgroup per
-// compute unit, each taking groups of four samples in turn.
+// quad_rom_kernel<K, projection> on a filled argument block: at most one workgroup per compute unit, each taking groups of
+// four samples in turn.
+template <class K>
+inline int quad_rom_dispatch(const typename K::Args& a, int projection, void* stream)
+{
+    const int grid = persistent_grid((a.B + QG - 1) / QG, 1);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_projection(projection, [&](auto p) {
+        hipLaunchKernelGGL((quad_rom_kernel<K, decltype(p)::galerkin>), dim3(grid), dim3(256), 0, st, a);
+        return check_launch();
+    });
+}
+
+// The launch of quad_rom_kernel<K, projection> once the entry point has checked its arguments.
 template <class K>
 inline int quad_rom_launch(int N, int B, int n, int nsteps, int projection, const double* x, const double* PhiT,
                            const double* Phif, const double* H3f, const double* u0, const double* mu1, const double* mu2, double dt, double E, double tol, int max_it, int options,
@@ -505,12 +627,7 @@ inline int quad_rom_launch(int N, int B, int n, int nsteps, int projection, cons
     a.x = x; a.PhiT = PhiT; a.Phif = Phif; a.H3f = H3f; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters;
     a.flags = flags; a.info = info; a.order = order; a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.NPAD = ((N + 63) / 64) * 64; a.NG = (N + 3) / 4;
     a.B = B; a.n = n; a.nsteps = nsteps; a.max_it = max_it; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
-    const int grid = persistent_grid((B + QG - 1) / QG, 1);
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_projection(projection, [&](auto p) {
-        hipLaunchKernelGGL((quad_rom_kernel<K, decltype(p)::galerkin>), dim3(grid), dim3(256), 0, st, a);
-        return check_launch();
-    });
+    return quad_rom_dispatch<K>(a, projection, stream);
 }
 
 }  // namespace bg

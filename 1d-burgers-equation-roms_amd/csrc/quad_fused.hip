@@ -18,6 +18,8 @@ __shared__ __attribute__((aligned(16))) double s_g[QG][QNMAX];             // M 
 __shared__ __attribute__((aligned(16))) double s_fdt[QG][QNMAX];           // dt F
 
 struct QuadFused {
+    using Args = QuadRunArgs;
+    static constexpr bool hyper = false;
     static constexpr int rows = QNMAX;
     static constexpr int window = BG_QUAD_WINDOW;
 

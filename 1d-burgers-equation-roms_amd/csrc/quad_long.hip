@@ -21,46 +21,12 @@ constexpr int QNMIN = 513;             // below: bg_quad_rom_run
 #define BG_QUAD_LONG_WINDOW 14
 #endif
 
-struct QuadLong {
+struct QuadLong : QuadSkippingOrder {       // pick_sample: order entries outside [0, B) are skipped
+    using Args = QuadRunArgs;
+    static constexpr bool hyper = false;
     static constexpr int rows = QNMAX;
     static constexpr int window = BG_QUAD_LONG_WINDOW;
-
-    // wave w of group grp takes order[4 grp + w]; entries outside [0, B) are skipped.  One exit, and the test last: with
-    // an early `return false` the kernel spilled three more scalar registers.
-    static __device__ __forceinline__ bool pick_sample(const QuadRunArgs& a, int grp, int w, bool& valid, int& sb)
-    {
-        int sraw[QG];                                  // the group's four samples, read by every wave: the skip below is workgroup-uniform
-#pragma unroll
-        for (int j = 0; j < QG; ++j) {
-            const int sl = grp * QG + j;
-            sraw[j] = sl < a.B ? (a.order ? a.order[sl] : sl) : -1;
-            if (sraw[j] >= a.B) sraw[j] = -1;
-        }
-        const int mine = w == 0 ? sraw[0] : (w == 1 ? sraw[1] : (w == 2 ? sraw[2] : sraw[3]));
-        valid = mine >= 0;
-        sb = valid ? mine : 0;                         // a padding wave computes on a copy of sample 0, stores nothing
-        return (sraw[0] & sraw[1] & sraw[2] & sraw[3]) >= 0;             // false: no valid entry in this group
-    }
-
-    struct Nodes {                      // both arrays in the owning wave's registers: rows lane + 64 m of its sample
-        static constexpr int QM = rows / 64;
-        double fdt_[QM], gv[QM];        // dt F and g = M u^n + dt F
-        // dt F is staged in the wave's (still unused) tangent rows, and the kernel hands row lane + 64 m to init(m, .): the
-        // setup loop stays rolled (four exp per row), the register arrays want static indices
-        static constexpr bool staged = true;
-        __device__ __forceinline__ void put_fdt(double* Tw, int, int i, double v) { Tw[i] = v; }
-        __device__ __forceinline__ void init(int m, double v) { fdt_[m] = v; gv[m] = 0.0; }
-        __device__ __forceinline__ double fdt(int, int, int m) const { return fdt_[m]; }
-        __device__ __forceinline__ void set_g(int, int, int m, double v) { gv[m] = v; }
-        // g of row 64 slab + lane: this lane's gv[slab] (zero beyond N), by a chain of selects on the wave-uniform slab number
-        __device__ __forceinline__ double g(int, int, int, int slab) const
-        {
-            double gi = 0.0;
-#pragma unroll
-            for (int m = 0; m < QM; ++m) gi = (slab == m) ? gv[m] : gi;
-            return gi;
-        }
-    };
+    using Nodes = QuadRegisterNodes<rows>;  // both arrays in the owning wave's registers
 };
 
 static_assert(sizeof(double) * (QG * QTJ + QG * (QNMAX + 4) + QG * QRS * 4 + QG * QN + QG) + sizeof(int) * QG <= 160 * 1024, "LDS per workgroup");

@@ -114,14 +114,17 @@ class FEMBurgers:
 
     # ---------------------------------------------------------------- quadratic manifold
     def pod_quadratic_manifold(self, At, nTimeSteps, u0, uxa, E, mu2, Phi, H, projection="LSPG",
-                               newton_tol=1e-6, newton_itmax=25, long_mesh=False):
+                               newton_tol=1e-6, newton_itmax=25, long_mesh=False, hyper=None):
         """Quadratic-manifold PROM (reference :1081-1175); ``uxa`` is the left Dirichlet value.  ``long_mesh``: meshes of
-        513 .. 1024 nodes with n <= 40 take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration."""
+        513 .. 1024 nodes with n <= 40 take the device-side loop bg_quad_rom_run_long instead of the host-driven iteration.
+        ``hyper``: a row sampling (burgers_hip.pod.build_quad_row_sampling) or a rom.HyperQuadPlan sends the call through the
+        hyper-reduced device-side loop bg_hyper_quad_rom_run, which assembles both projections from the sampled mesh rows
+        only (any mesh the FOM takes, n <= 40, at most 256 rows and 768 stencil nodes)."""
         batched = self._batched(uxa, mu2, u0)
         res = _rom.quadratic_run(self.X, np.asarray(u0, dtype=np.float64), uxa, mu2, At, int(nTimeSteps),
                                  np.asarray(Phi, dtype=np.float64), np.asarray(H, dtype=np.float64),
                                  projection=projection, E=E, newton_tol=newton_tol, newton_itmax=newton_itmax,
-                                 long_mesh=long_mesh)
+                                 long_mesh=long_mesh, hyper=hyper)
         if self.verbose and (res.flags != 0).any():
             print("  Warning: Newton did not converge")
         return self._finish(res, batched)

@@ -580,6 +580,49 @@ int bg_quad_rom_run_long(int N, int B, int n, int nsteps, int projection, const 
                          int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * bg_hyper_quad_rom_run -- the quadratic-manifold PROM time loop HYPER-REDUCED: both projections of pod_quadratic_manifold
+ *   are assembled from m sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j
+ *   with the tangent T = Phi + H dQ/dq(q), y_j = (A T)[i_j], R_j = (A u - b)[i_j], w_j = T[i_j] (Galerkin) or y_j (LSPG).
+ *   3 <= N <= bg_fom_max_n(): the kernel never touches a vector of mesh length, and a pass streams the H3 rows of the table
+ *   alone.  reference: FEM/fem_burgers.py:1081-1175 with the sums over mesh rows restricted and weighted and without the
+ *   re-projection q = Phi^T u^n at the start of a step (below).  No SUPG term (:1142).  Opt-in: nothing routes here unless
+ *   asked (burgers_hip/rom.py, quadratic_run_hyper; hyper= of quadratic_run and of the facade).  The caller packs once per
+ *   manifold, sampling and mesh:
+ *   xn, node, pos, xi: the table of the sorted distinct stencil nodes of the sampled rows, as bg_hyper_ann_rom_run takes
+ *          it, the coordinates first (xn [nodes]; node [nodes] int32 ascending, m <= nodes <= 3 m; pos [m] int32, entries
+ *          outside [0, nodes) are skipped; xi [m] finite, >= 0);
+ *   Phif   [NG][10][16], H3f [NG][28][64][2] (16-byte aligned), NG = ceil(nodes / 4): bg_quad_rom_run's operand copies built
+ *          from Phi[node] and H[node], the table in place of the mesh; sizes bg_hyper_quad_rom_phif_elems(nodes),
+ *          bg_hyper_quad_rom_h3f_elems(nodes) doubles (0 outside 1 .. 768).  No PhiT: nothing is re-projected;
+ *   q0     [B][n] = Phi^T u0;   u0n  [B][nodes] u0 at the table nodes;
+ *   qhist  [B][nsteps+1][n] q of every step, row 0 = q0: U = Phi q + H Q(q) is the kernel's own decode;
+ *   iters, flags, info: as bg_quad_rom_run; options: not read (the table is always a non-uniform mesh);
+ *   order: as bg_quad_rom_run_long, entries outside [0, B) are skipped.
+ *   The mass row of the first step reads u0n itself; every pass assembles at the decode of its q.  q carries over from step
+ *   to step: for orthonormal Phi and Phi^T H = 0 (a manifold fitted on the residual of the projection) it equals the
+ *   reference's Phi^T u^n.  Row 0 is the Dirichlet row, row N - 1 has no right element: decided by node[], so a table node
+ *   that is only a neighbour contributes nothing.
+ *   Limits (bg_hyper_quad_rom_limits): n <= 40, m <= 256, nodes <= 768.
+ *   Errors, in this order: N < 3, n, m or nodes < 1, B or nsteps < 0, max_it < 1, dt <= 0: BG_ERR_BAD_ARG; an unknown
+ *   projection: BG_ERR_PROJECTION; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; n, m or nodes beyond the limits:
+ *   BG_ERR_UNSUPPORTED_R; m > N or nodes outside [m, min(3 m, N)]: BG_ERR_BAD_ARG; B = 0: BG_OK with nothing launched
+ *   (pointers may be null); a null operand or output with B > 0, H3f not 16-byte aligned: BG_ERR_BAD_ARG.  Sizes the kernel
+ *   does not cover are refused, never rerouted.
+ *   One 256-thread workgroup owns four samples and runs bg_quad_rom_run's loop on the table (csrc/quad_device.hpp,
+ *   csrc/quad_hyper.hip), instantiated for nodes <= 512 and <= 768; bg_hyper_quad_rom_workgroups_per_cu(nodes) of them
+ *   are resident per CU (0: no such table).
+ * --------------------------------------------------------------------------------- */
+int bg_hyper_quad_rom_limits(int *max_n, int *max_m, int *max_nodes);
+int bg_hyper_quad_rom_workgroups_per_cu(int nodes);
+long long bg_hyper_quad_rom_phif_elems(int nodes);
+long long bg_hyper_quad_rom_h3f_elems(int nodes);
+int bg_hyper_quad_rom_run(int N, int B, int n, int m, int nodes, int nsteps, int projection, const double *xn,
+                          const int32_t *node, const int32_t *pos, const double *xi, const double *Phif, const double *H3f,
+                          const double *q0, const double *u0n, const double *mu1, const double *mu2, double dt, double E,
+                          double tol, int max_it, int options, double *qhist, int32_t *iters, int32_t *flags,
+                          int32_t *info, const int32_t *order, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * bg_ann_rom_run -- batched replacement of FEMBurgers.pod_ann_prom, the WHOLE time loop on the device
  *   reference: FEM/fem_burgers.py:1177-1251 (loop), compute_ann_jacobian :1254-1275, model POD-ANN/pod_ann.py:38-56.
  *   One workgroup owns one sample for all time steps and Gauss-Newton iterations: assembly, fp64-MFMA projection of the
