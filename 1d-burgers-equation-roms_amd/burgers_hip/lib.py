@@ -203,6 +203,12 @@ _SIGNATURES = {
     "bg_local_rom_run_long_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
     "bg_local_rom_run_long_bases_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_local_rom_run_long": _loop(7, _LOCAL_OPERANDS, out=_LOOP_OUT_CLUSTERS),
+    "bg_hyper_local_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 4),
+    "bg_hyper_local_rom_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    # N, B, C, rmax, mg, m, nsteps, projection, rows, xi, xs, PhiS, widths, trans, pick, centres, qg0, pu0, u0s, mu1, mu2, the step,
+    # the outputs with clusters (qhist for hist)
+    "bg_hyper_local_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_int_p] + [c_double_p] * 3 + [c_int_p] + [c_double_p] * 8 +
+                               _LOOP_STEP + _LOOP_OUT_CLUSTERS),
 }
 
 _lib = None

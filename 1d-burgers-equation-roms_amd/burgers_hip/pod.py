@@ -967,6 +967,69 @@ def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, st
     return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
 
 
+# ---- row sampling for the hyper-reduced local POD PROM (rom.local_prom_run_hyper, bg_hyper_local_rom_run) ----
+def hyper_local_rom_limits():
+    """(max_r, max_m, max_mg, max_clusters) of bg_hyper_local_rom_run.  Needs no device."""
+    from . import lib as _lib
+    return _lib.limits("bg_hyper_local_rom_limits", 4)
+
+
+def _host_local_bases(centres, local_bases, U_global, num_global_modes, N, who):
+    """(centres (C, mg), [Phi_0 .. Phi_{C-1}], U_g (N, mg)) as host float64 arrays; ValueError for shapes that cannot be right
+    or a centre without a basis."""
+    centres, mg = _host_matrix(centres), int(num_global_modes)
+    Ug = _host_matrix(U_global)
+    if centres.ndim != 2 or centres.shape[1] != mg or Ug.ndim != 2 or Ug.shape[0] != N or Ug.shape[1] < mg:
+        raise ValueError(f"{who}: centres must be (C, m) and U_global (N, >= m) with m = num_global_modes")
+    missing = [c for c in range(len(centres)) if c not in local_bases]
+    if missing:
+        raise ValueError(f"{who}: centre {missing[0]} has no local basis")
+    bases = [_host_matrix(local_bases[c]) for c in range(len(centres))]
+    if any(b.ndim != 2 or b.shape[0] != N or b.shape[1] < 1 for b in bases):
+        raise ValueError(f"{who}: every local basis must be (N, >= 1), one row per mesh node")
+    return centres, bases, np.ascontiguousarray(Ug[:, :mg])
+
+
+def local_row_sampling_system(X, centres, local_bases, U_global, num_global_modes, runs, dt, projection, E=0.0, supg=True,
+                              stride=10):
+    """(G, pairs): the training matrix of build_local_row_sampling, column i the contributions of mesh row i.  For every run
+    and every ``stride``-th step n the cluster c is the nearest centre to U_g^T s_n (the first index of the smallest squared
+    distance, as local_prom_burgers picks it), the pair is Un = Phi_c Phi_c^T s_n, U0 = Phi_c Phi_c^T s_{n+1}, and the block
+    row_contributions(X, Phi_c, U0, Un, ...) has r_c rows; the full reduced right-hand sides are d = G 1.  ``X``: a host
+    array; ``projection``: "galerkin" or "lspg"."""
+    centres, bases, Ug = _host_local_bases(centres, local_bases, U_global, num_global_modes, len(X), "local_row_sampling_system")
+    blocks = []
+    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
+        for n in range(0, Sn.shape[1] - 1, int(stride)):
+            qg = Ug.T @ Sn[:, n]
+            Phi = bases[int(np.argmin(((centres - qg[None, :]) ** 2).sum(1)))]
+            P = Phi @ (Phi.T @ Sn[:, n:n + 2])
+            blocks.append(row_contributions(X, Phi, P[:, 1], P[:, 0], mu1, mu2, float(dt), projection, float(E), supg))
+    return _stack_contributions(blocks, "build_local_row_sampling")
+
+
+def build_local_row_sampling(X, centres, local_bases, U_global, num_global_modes, runs, dt, projection, E=0.0, supg=True,
+                             tau=1e-4, stride=10, min_rows=None, max_rows=None):
+    """build_row_sampling for the local POD PROM (rom.local_prom_run_hyper): ONE sampling for all clusters, fitted by the same
+    host NNLS (nnls_rows, row 0 forced in with weight 1) on training pairs that each lie in the span of the cluster the
+    reference would hold there (local_row_sampling_system).  ``centres`` (C, m), ``local_bases`` {c: (N, r_c)}, ``U_global``
+    and ``num_global_modes`` are local_prom_burgers's arguments; ``runs`` as in build_row_sampling.
+    ``min_rows`` defaults to min(3 max_c r_c, N), ``max_rows`` to the kernel's limit (hyper_local_rom_limits); needing more
+    is a ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    projection = str(projection).lower()
+    if projection not in ("galerkin", "lspg"):
+        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
+    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    N = len(X)
+    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
+        raise ValueError("build_local_row_sampling takes at least one run, stride >= 1 and tau > 0")
+    _, bases, _ = _host_local_bases(centres, local_bases, U_global, num_global_modes, N, "build_local_row_sampling")
+    min_rows = min(3 * max(b.shape[1] for b in bases), N) if min_rows is None else int(min_rows)
+    max_rows = hyper_local_rom_limits()[1] if max_rows is None else int(max_rows)
+    G, pairs = local_row_sampling_system(X, centres, local_bases, U_global, num_global_modes, runs, dt, projection, E, supg, stride)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+
+
 # ---- row sampling for the hyper-reduced POD-RBF PROM (rom.pod_rbf_run_hyper, bg_hyper_rbf_rom_run) ----
 def hyper_rbf_rom_limits():
     """(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run.  Needs no device."""

@@ -67,6 +67,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
     _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
     _Route("bg_hyper_quad_rom_run", 1, "bg_quad_rom_max_n", 3, "bg_fom_max_n", group=4, supg=False),
+    _Route("bg_hyper_local_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
 )}
 
 
@@ -2006,6 +2007,161 @@ def local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_glo
                               num_global_modes, projection, E, tol, max_it, device, plan, balance, options)
 
 
+class HyperLocalPlan:
+    """What bg_hyper_local_rom_run reads besides the batch, built once per clustering, sampling and mesh on the device
+    (include/burgers_hip.h): the stack PhiS of HyperPodPlan's stencil tables, one per cluster; ``trans`` [C][C][40][40] =
+    Phi_c^T Phi_p and ``pick`` [C][mg][40] = U_g^T Phi_p, zero padded; the widths, centres, rows, weights and stencil
+    coordinates; the zero-padded bases ``stack`` (C, N, rmax) and ``UgT`` for the projections of u0 and the decode.
+    ``sampling``: a pod.RowSampling (pod.build_local_row_sampling), one for all clusters, row 0 among its rows.  Everything the
+    shapes, the sampling and the bases decide is refused with a ValueError before the device is touched -- also a basis with
+    |Phi_c^T Phi_c - I|_max > 1e-8: the loop carries q from step to step and crosses from one basis to the next by
+    Phi_c^T Phi_p q, which is the reference's Phi_c^T u^n only for orthonormal columns."""
+
+    def __init__(self, centres, local_bases, U_global, num_global_modes, sampling, X, device):
+        route = _ROUTES["bg_hyper_local_rom_run"]
+        max_r, max_m, max_mg, max_c = _lib.limits("bg_hyper_local_rom_limits", 4)
+        host = lambda A: np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64)
+        Xh = check_mesh(X)
+        N, mg = len(Xh), int(num_global_modes)
+        cen, Ug = host(centres), host(U_global)
+        if cen.ndim != 2 or cen.shape[0] < 1 or cen.shape[1] != mg or mg < 1:
+            raise ValueError(f"centres must be (C, m) with m = {mg} >= 1")
+        C = cen.shape[0]
+        if Ug.ndim != 2 or Ug.shape[0] != N or Ug.shape[1] < mg:
+            raise ValueError(f"U_global must be (N, >= m) with N = {N}, m = {mg}")
+        if N < route.min_n or N > _limit(route.max_n):
+            raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)}")
+        missing = [c for c in range(C) if c not in local_bases]
+        if missing:
+            raise ValueError(f"centre {missing[0]} has no local basis")
+        bases = [host(local_bases[c]) for c in range(C)]
+        for c, b in enumerate(bases):
+            if b.ndim != 2 or b.shape[0] != N:
+                raise ValueError(f"local basis {c} must have one row per mesh node (N = {N})")
+            if b.shape[1] < 1 or b.shape[1] > max_r:
+                raise ValueError(f"local basis {c} must have 1 .. {max_r} columns (got {b.shape[1]})")
+        if mg > max_mg or C > max_c:
+            raise ValueError(f"beyond bg_hyper_local_rom_limits: m {mg} (<= {max_mg}), {C} centres (<= {max_c})")
+        rows, xi = _sampling_rows(route, sampling, N, max_m)
+        if rows[0] != 0:
+            raise ValueError("row 0 (the Dirichlet row) must be among the sampled rows")
+        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        for c, b in enumerate(bases):
+            if not np.isfinite(b).all() or np.abs(b.T @ b - np.eye(b.shape[1])).max() > 1e-8:
+                raise ValueError(f"local basis {c} must have orthonormal columns (to 1e-8): the loop does not re-project Phi^T u^n")
+        if not (np.isfinite(cen).all() and np.isfinite(Ug[:, :mg]).all()):
+            raise ValueError("centres and U_global must be finite")
+        m = len(rows)
+        elems = _lib.load().bg_hyper_local_rom_table_elems(C, m)
+        if elems == 0:
+            raise ValueError(f"{route.entry} does not cover C = {C}, m = {m}")
+        device = _lib.require_device(device)
+        self.N, self.C, self.mg, self.m, self.Xh, self.sampling = N, C, mg, m, Xh.copy(), sampling
+        self.widths_host = [b.shape[1] for b in bases]
+        self.rmax = max(self.widths_host)
+        R = max_r                                                                # the padded width of trans and pick
+        self.stack = torch.zeros((C, N, self.rmax), dtype=torch.float64, device=device)
+        for c, b in enumerate(bases):
+            self.stack[c, :, :b.shape[1]] = _as_dev(b, device)
+        self.UgT = _as_dev(Ug[:, :mg], device).t().contiguous()
+        self.centres = _as_dev(cen, device).contiguous()
+        self.widths = torch.as_tensor(self.widths_host, dtype=torch.int32, device=device)
+        idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
+        self.inside = (idx >= 0) & (idx < N)
+        self.stencil = idx.clamp(0, N - 1)
+        mpad = (m + 31) // 32 * 32
+        cols = elems // (C * 3 * mpad)
+        self.PhiS = torch.zeros((C, mpad, 3, cols), dtype=torch.float64, device=device)
+        self.PhiS[:, :m, :, :self.rmax] = self.stack[:, self.stencil] * self.inside[None, :, :, None]
+        flat = self.stack.permute(1, 0, 2).reshape(N, C * self.rmax)              # all bases side by side
+        self._proj = torch.cat([self.UgT.t(), flat], dim=1).contiguous()          # U_g | Phi_0 | ... | Phi_{C-1}
+        self._chunk = max(1, min(256, (1 << 25) // self._proj.numel()))           # at most 256 MB per product of project()
+        gram = (flat.t() @ flat).reshape(C, self.rmax, C, self.rmax).permute(0, 2, 1, 3)      # [c][p] = Phi_c^T Phi_p
+        self.trans = torch.zeros((C, C, R, R), dtype=torch.float64, device=device)
+        self.trans[:, :, :self.rmax, :self.rmax] = gram
+        self.pick = torch.zeros((C, mg, R), dtype=torch.float64, device=device)
+        self.pick[:, :, :self.rmax] = torch.matmul(self.UgT[None], self.stack)
+        self.xs = _as_dev(Xh, device)[self.stencil].contiguous()
+        self.rows = torch.as_tensor(rows, dtype=torch.int32, device=device)
+        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+
+
+    def project(self, u0d):
+        """(qg0 (B, mg), pu0 (B, C, rmax)) = U_g^T u0 and Phi_c^T u0 for every cluster, by _project_rows in chunks of a size
+        the plan fixes: a sample's bits do not depend on the batch around it."""
+        out = _project_rows(u0d, self._proj, self._chunk)
+        return out[:, :self.mg].contiguous(), out[:, self.mg:].reshape(u0d.shape[0], self.C, self.rmax).contiguous()
+
+
+class HyperLocalRomResult:
+    """Result of local_prom_run_hyper: the reduced coordinates ``q`` (B, nT+1, rmax) -- entry n + 1 in the basis of
+    ``clusters[:, n]``, entry 0 the projection of u0 on the first cluster's basis -- ``clusters`` (B, nT) int32, ``iters``,
+    ``flags``, ``info``, the ``plan`` and the ``path``.  ``hist`` (B, nT+1, N) is decoded on demand, column n + 1 =
+    Phi_{clusters[:, n]} q[:, n + 1] with u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
+    (B, N, nT+1) layout."""
+
+    def __init__(self, res, plan, u0d, clusters):
+        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
+        self.plan, self.clusters, self._keep, self._u0, self._hist = plan, clusters, res._keep, u0d, None
+
+    @property
+    def hist(self):
+        if self._hist is None:
+            B, cols, _ = self.q.shape
+            self._hist = torch.empty((B, cols, self.plan.N), dtype=torch.float64, device=self.q.device)
+            self._hist[:, 0] = self._u0
+            if cols > 1:
+                cl = self.clusters.long()
+                for c in range(self.plan.C):                                     # one product per cluster over its (sample, step) pairs
+                    b, n = (cl == c).nonzero(as_tuple=True)
+                    if b.numel():
+                        self._hist[b, n + 1] = self.q[b, n + 1] @ self.plan.stack[c].t()
+        return self._hist
+
+    def snapshots(self):
+        return FomResult(self.hist, self.iters, self.flags).snapshots()
+
+    @property
+    def newton_steps(self):
+        return int(self.iters.sum().item())
+
+
+def local_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes, sampling_or_plan, proj,
+                         E=0.0, tol=1e-6, max_it=20, device=None, options=0, balance=True):
+    """``local_prom_burgers`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_local_rom_run): every cluster's
+    reduced system is assembled from the sampled mesh rows of ONE pod.RowSampling (pod.build_local_row_sampling) with their
+    weights, so an iteration costs O(m r^2) whatever the mesh: N up to bg_fom_max_n(), orthonormal bases of at most 40
+    modes, m <= 256, at most 64 centres and global modes (bg_hyper_local_rom_limits).  The cluster pick works from reduced
+    coordinates and a switch crosses to the new basis by Phi_c^T Phi_p q.  The pivoting repair runs inside the call,
+    nothing is synchronised.  ``sampling_or_plan``: the sampling, or a HyperLocalPlan of this clustering, sampling and mesh
+    to reuse across calls (``res.plan``; centres, bases and U_global are then not looked at).  A plan built for another
+    mesh or device and a sampling trained for the other projection are refused; what the loop does not cover is a
+    ValueError, never rerouted.  Returns a HyperLocalRomResult."""
+    Xh = check_mesh(X)
+    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperLocalPlan) else \
+        HyperLocalPlan(centers, local_bases, U_global, num_global_modes, sampling_or_plan, Xh, device)
+    device = _lib.require_device(device)
+    if plan.stack.device != device:
+        raise ValueError("the plan was built on another device")
+    if not np.array_equal(plan.Xh, Xh):
+        raise ValueError("the plan was built for another mesh")
+    if plan.projection != proj:
+        raise ValueError("the row sampling was trained for the other projection")
+    u0d, _, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
+    B = u0d.shape[0]
+    qg0, pu0 = plan.project(u0d)
+    u0s = (u0d[:, plan.stencil] * plan.inside).contiguous()
+    clusters = torch.zeros((B, int(nsteps)), dtype=torch.int32, device=device)
+    res = _device_loop(_ROUTES["bg_hyper_local_rom_run"], Xh, u0d, mu1, mu2, nsteps, device, options, balance,
+                       lambda f, N, B, x, inputs, opts, outputs: f(
+                           N, B, plan.C, plan.rmax, plan.mg, plan.m, int(nsteps), proj, _lib.ptr(plan.rows), _lib.ptr(plan.xi),
+                           _lib.ptr(plan.xs), _lib.ptr(plan.PhiS), _lib.ptr(plan.widths), _lib.ptr(plan.trans), _lib.ptr(plan.pick),
+                           _lib.ptr(plan.centres), _lib.ptr(qg0), _lib.ptr(pu0), _lib.ptr(u0s), *inputs[1:], float(dt), float(E),
+                           float(tol), int(max_it), opts, *outputs[:4], _lib.ptr(clusters), *outputs[4:]),
+                       keep=(plan, qg0, pu0, u0s, clusters), cols=plan.rmax)
+    return HyperLocalRomResult(res, plan, u0d, clusters)
+
+
 def _local_route(N, fused=False, long_mesh=False):
     """The device loops local_prom_run tries for a mesh of N nodes, in this order; each is taken if the LocalPodPlan of the
     clustering for it is ``ok`` (inside its limits, a basis for every centre), and "host" is what is left."""
@@ -2015,7 +2171,7 @@ def _local_route(N, fused=False, long_mesh=False):
 
 
 def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
-                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, fused=False, long_mesh=False):
+                   projection="Galerkin", E=0.0, tol=1e-6, max_it=20, device=None, fused=False, long_mesh=False, hyper=None):
     """Batched ``local_prom_burgers`` (FEM/fem_burgers.py:979-1079): each sample picks, once per time
     step, the local basis of the cluster whose centre is nearest to ``U_global[:, :m]^T u^n``
     (= ``kmeans.predict``), then iterates like ``pod_prom_burgers`` in that basis.  The bases are
@@ -2026,8 +2182,14 @@ def local_prom_run(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, 
     (N <= 512, widths <= 40, m and C <= 64, a basis for every centre); otherwise, and by default, the host-driven
     iteration.
     ``long_mesh`` (opt-in, with ``fused``): meshes of 512 < N <= 1024 whose clustering is inside
-    bg_local_rom_run_long_limits take the device-side loop bg_local_rom_run_long instead of the host-driven iteration."""
+    bg_local_rom_run_long_limits take the device-side loop bg_local_rom_run_long instead of the host-driven iteration.
+    ``hyper`` (opt-in): a pod.RowSampling (pod.build_local_row_sampling) or a HyperLocalPlan sends the call through the
+    hyper-reduced loop local_prom_run_hyper, which assembles every cluster's reduced system from the sampled mesh rows only;
+    what it does not cover is refused, not rerouted."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    if hyper is not None:
+        return check_singular(local_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes,
+                                                   hyper, proj, E, tol, max_it, device))
     tries = _local_route(np.shape(X)[0], fused, long_mesh)
     if "bg_local_rom_run_long" in tries:
         dev = _lib.require_device(device)

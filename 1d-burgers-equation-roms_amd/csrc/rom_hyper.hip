@@ -27,6 +27,12 @@
 // mass row and assembly rom_device.hpp's rom_mass_rhs_node and rom_assemble_row, reading the stencil coordinates xs as a
 // mesh x.  This file's own: the contiguous slab DMA, the weights, the start from u0s, the frame of the loop, and the
 // per-sample forcing loads (hyper_row_forcing, which says why).
+//
+// Local POD (bg_hyper_local_rom_run) is the same body with LOCAL = true: one table per cluster, the nearest-centre pick at the
+// top of every time step from reduced coordinates, and the change of basis q <- Phi_c^T Phi_p q when the cluster changes
+// (the additions sit under `if constexpr (LOCAL)`, described at HyperLocalRunArgs).  Its kernel and entry point are compiled
+// in a translation unit of their own, rom_hyper_local.hip, which includes this file with BG_ROM_HYPER_LOCAL_TU defined, as
+// rom_local_fused.hip does with rom_fused.hip: the four kernels here are meant to stay exactly what they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,9 +66,32 @@ struct HyperRunArgs {
     int N, B, r, m, nsteps, max_it, supg, nonuniform, force_pivoted;
 };
 
+// Local POD (LOCAL; reference FEMBurgers.local_prom_burgers, FEM/fem_burgers.py:979-1079, with the sums over mesh rows
+// restricted and weighted by ONE sampling for all clusters).  The state of a sample is (p, q): the cluster held and the
+// coordinates in its basis, u = Phi_p q.  PhiS is the stack [C][MPAD][3][LPS] of the clusters' stencil tables (`table` doubles
+// each), q0 the projections [B][C][r] of u0 on every basis.  At the top of step n >= 1: q_g = pick[p] q (= U_g^T u^n), the
+// nearest centre c (local_nearest_centre, the pick of the full local loops), and if c != p
+//   one lift-only sweep over the OLD table leaves u^n at the stencil nodes of every sampled row in LDS (H.g, H.u0, H.ur), which
+//   the first iteration of the step reads where the first iteration of a run reads u0s -- the reference assembles g, A and R
+//   at U0 = u^n, which is not in the new span, while Y and W are the new basis's;
+//   q <- trans[c][p] q, the base of the update: the reference's q = Phi_c^T U0 + dq.
+// From the second iteration on, and in steps without a switch, the step is the POD loop's with the width widths[c]: the solve
+// gives the unknowns at and beyond it a unit diagonal and a zero correction (LongLayout::solve_add).  Step 0 picks from qg0.
+struct HyperLocalRunArgs : HyperRunArgs {
+    const int32_t* widths;  // [C], 1 .. r (clamped to r)
+    const double* trans;    // [C][C][LR][LR]: trans[c][p] = Phi_c^T Phi_p, zero rows and columns beyond the widths
+    const double* pick;     // [C][mg][LR]: pick[p] = U_g^T Phi_p, zero columns beyond the width
+    const double* centres;  // [C][mg]
+    const double* qg0;      // [B][mg] = U_g^T u0
+    int32_t* clusters;      // [B][nsteps] or null
+    long long table;        // doubles of one cluster's table in PhiS
+    int C, mg;
+};
+
 struct HyperLds {
     double* g; double* fdt; double* hl; double* hr; double* w;      // [HMMAX] per sampled row: M u^n + dt F, dt F, h_f left / right, weight factor
     int* row;                                                        // [HMMAX] mesh row (N beyond m: an identity row with weight 0)
+    double* u0; double* ur; double* qg;                              // LOCAL: [HMMAX] u^n at nodes i, i + 1 after a switch (i - 1 in g); [64] q_g
 };
 
 // Loads of the forcing term at a sampled row with the stencil coordinates xm, x0, xp: dt F_i, and h_e (f(gp1) + f(gp2)) of
@@ -97,8 +126,8 @@ __device__ __forceinline__ void hyper_row_forcing(double xm, double x0, double x
 // The body for wave W of the workgroup (a template parameter of the whole body, as in rom_stream_body: every wave keeps
 // its own quarter of the block pairs in accumulators that never change registers).  The description K is LongLayout as it
 // stands: the items, matrix steps, parking and solve of the r <= 40 streaming loops.
-template <bool GAL, bool PIV, int W>
-__device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLds& L, const HyperLds& H)
+template <bool GAL, bool PIV, int W, bool LOCAL = false, class A = HyperRunArgs>
+__device__ __forceinline__ void hyper_body(const A& a, const StreamLds& L, const HyperLds& H)
 {
     using K = LongLayout;
     constexpr int NB = LNB, R = LR, PS = LPS;
@@ -132,14 +161,37 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
         double* qhist = a.qhist + (size_t)smp * (size_t)(a.nsteps + 1) * (size_t)a.r;
         const double* u0s = a.u0s + (size_t)smp * (size_t)m * 3;
         __syncthreads();
+        // LOCAL: the cluster held with its table and width (workgroup-uniform: every wave computes the same pick); otherwise the
+        // arguments are read where they are used, as before there was a pick
+        int cl = 0, r_local = 0;
+        const double* PhiL = nullptr;
+        auto step_table = [&]() -> const double* { if constexpr (LOCAL) return PhiL; else return a.PhiS; };
+        auto step_width = [&]() -> int { if constexpr (LOCAL) return r_local; else return a.r; };
+        auto q0_row = [&]() -> const double* {
+            if constexpr (LOCAL) return a.q0 + ((size_t)smp * a.C + cl) * a.r; else return a.q0 + (size_t)smp * a.r;
+        };
+        auto hold_cluster = [&](int c) {
+            if constexpr (LOCAL) {
+                cl = c;
+                PhiL = a.PhiS + (size_t)c * (size_t)a.table;
+                r_local = a.widths[c] < a.r ? a.widths[c] : a.r;      // (clamped: the tables are LR wide, a.r <= LR)
+            }
+        };
+        if constexpr (LOCAL) {
+            if (tid < a.mg) H.qg[tid] = a.qg0[(size_t)smp * a.mg + tid];
+        }
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial coordinates -------
         for (int j = tid; j < nslab * HS; j += 256) {
             double fdt = 0.0, hl = 0.0, hr = 0.0;
             if (j < m) hyper_row_forcing(a.xs[3 * j], a.xs[3 * j + 1], a.xs[3 * j + 2], H.row[j], N, mu2, h, a.nonuniform, a.dt, fdt, hl, hr);
             H.fdt[j] = fdt; H.hl[j] = hl; H.hr[j] = hr;
         }
+        if constexpr (LOCAL) {                                    // the cluster of u0 (:1011-1012) and its projection of u0
+            __syncthreads();
+            hold_cluster(local_nearest_centre(H.qg, a.centres, a.C, a.mg, tid & 63));
+        }
         if (tid < R) {
-            const double q = (tid < a.r) ? a.q0[(size_t)smp * a.r + tid] : 0.0;
+            const double q = (tid < a.r) ? q0_row()[tid] : 0.0;
             s_q[tid] = q;
             if (tid < a.r) qhist[tid] = q;
         }
@@ -150,7 +202,7 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
         // LDS DMA of slab `slab` (rows 3 HS slab .. of the table, contiguous) into buffer `buf`: wave w moves the 1-KB pieces
         // w, w + 4, ...; lanes beyond the slab's end write nothing (the next buffer starts there)
         auto slab_dma = [&](int slab, int buf) {
-            const char* src = reinterpret_cast<const char*>(a.PhiS + (size_t)slab * HSLAB);
+            const char* src = reinterpret_cast<const char*>(step_table() + (size_t)slab * HSLAB);
             const int ln = tid & 63;
             for (int j = w; j < HCHUNKS; j += 4) {
                 const int o = 1024 * j + 16 * ln;
@@ -160,13 +212,63 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
         };
 
         for (int step = 0; step < a.nsteps && info_out == 0 && !aborted; ++step) {
+            bool switched = false;
+            if constexpr (LOCAL) {
+                if (step > 0) {
+                    // ---- q_g = pick[p] q (U_g^T u^n, :1011) by four lanes per global mode, then kmeans.predict (:1012) ------------
+                    {
+                        const int j = tid >> 2, pt = tid & 3;
+                        double s = 0.0;
+                        if (j < a.mg) {
+                            const double* pr = a.pick + ((size_t)cl * a.mg + j) * R + NB * pt;
+#pragma unroll
+                            for (int c = 0; c < NB; ++c) s = __builtin_fma(pr[c], s_q[NB * pt + c], s);
+                        }
+                        s += dpp_mov<0xB1>(s); s += dpp_mov<0x4E>(s);
+                        if (pt == 0 && j < a.mg) H.qg[j] = s;
+                    }
+                    __syncthreads();
+                    const int c = local_nearest_centre(H.qg, a.centres, a.C, a.mg, tid & 63);
+                    if (c != cl) {                                 // workgroup-uniform
+                        // ---- u^n = Phi_p q at the stencil nodes: one lift-only sweep over the old table (no DMA is in flight) ----
+                        const int q4 = tid >> 2, pt = tid & 3;
+                        slab_dma(0, 0);
+                        for (int slab = 0; slab < nslab; ++slab) {
+                            const int cur = slab & 1;
+                            const double* s_P = s_slab + cur * HSLAB;
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's DMA pieces of the slab have landed
+                            __syncthreads();                                          // ... and everybody's; the other buffer is no longer read
+                            if (slab + 1 < nslab) slab_dma(slab + 1, cur ^ 1);
+                            if (q4 < HS) {                                            // (wave-uniform: the first HS / 16 waves)
+                                double um, u0, ur;
+                                stream_lift_rows<NB, PS>(s_P + 3 * q4 * PS + NB * pt, s_q + NB * pt, um, u0, ur);
+                                if (pt == 0) { const int j = slab * HS + q4; H.g[j] = um; H.u0[j] = u0; H.ur[j] = ur; }
+                            }
+                        }
+                        // ---- q <- Phi_c^T Phi_p q by four lanes per row of trans[c][p] (zero rows beyond the new width) ------------
+                        double t = 0.0;
+                        if (q4 < R) {
+                            const double* tr = a.trans + (((size_t)c * a.C + cl) * R + q4) * R + NB * pt;
+#pragma unroll
+                            for (int e = 0; e < NB; ++e) t = __builtin_fma(tr[e], s_q[NB * pt + e], t);
+                        }
+                        t += dpp_mov<0xB1>(t); t += dpp_mov<0x4E>(t);
+                        __syncthreads();                           // the sweep is over: the slabs and the old q are no longer read
+                        if (pt == 0 && q4 < R) s_q[q4] = t;        // (read again behind the barriers of the first iteration)
+                        hold_cluster(c);
+                        switched = true;
+                    }
+                }
+                if (tid == 0 && a.clusters) a.clusters[(size_t)smp * a.nsteps + step] = cl;
+            }
             int k = 0;
             while (true) {
                 // per-lane indices from an opaque copy of the thread index (see rom_stream_body)
                 int tid_i = tid;
                 asm volatile("" : "+v"(tid_i));
                 const int lane = tid_i & 63, pk = lane >> 4, pblk = (lane >> 2) & 3, pt = lane & 3;
-                const bool lift = step > 0 || k > 0;     // the first iteration of a run assembles at u0 itself (:725)
+                // the first iteration of a run assembles at u0 itself (:725); LOCAL: the first after a switch at the old basis's u^n
+                const bool lift = LOCAL ? ((step > 0 && !switched) || k > 0) : (step > 0 || k > 0);
                 double acc[NACC];
 #pragma unroll
                 for (int p = 0; p < NACC; ++p) acc[p] = 0.0;
@@ -186,7 +288,10 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
                             stream_lift_rows<NB, PS>(s_P + 3 * q4 * PS + NB * pt, s_q + NB * pt, um, u0, ur);
                         } else {
                             um = u0 = ur = 0.0;
-                            if (pt == 0 && j < m) { um = u0s[3 * j]; u0 = u0s[3 * j + 1]; ur = u0s[3 * j + 2]; }
+                            if (pt == 0 && j < m) {
+                                if (LOCAL && step > 0) { um = H.g[j]; u0 = H.u0[j]; ur = H.ur[j]; }      // (H.g[j] becomes g below)
+                                else { um = u0s[3 * j]; u0 = u0s[3 * j + 1]; ur = u0s[3 * j + 2]; }
+                            }
                         }
                         if (pt == 0) {
                             const int i = H.row[j];
@@ -230,8 +335,8 @@ __device__ __forceinline__ void hyper_body(const HyperRunArgs& a, const StreamLd
                 __syncthreads();
                 // ---- solve(Ar, -br) (:767), q <- q + dq, err = |dq| / |q|  (:770-776) -------------------------------------------
                 double nd, nq;
-                const double qk = (lane < a.r) ? s_q[lane] : 0.0;                 // read before the solve's first barrier
-                K::template solve_add<PIV, W>(L, a.r, lane, qk, aborted, info_out, nd, nq);
+                const double qk = (lane < step_width()) ? s_q[lane] : 0.0;        // read before the solve's first barrier
+                K::template solve_add<PIV, W>(L, step_width(), lane, qk, aborted, info_out, nd, nq);
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;
@@ -270,7 +375,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : HWG_PER_CU) void rom_hyper_kernel(Hy
     double* const s_diag = s_m + 512;
     static_assert(LR * LSW + 512 + 3 * 64 <= 2 * HSLAB, "the solve's arrays fit over the slabs");
     const StreamLds L{s_slab, nullptr, nullptr, nullptr, nullptr, s_cf, s_q, s_m, s_diag, s_diag + 64, s_diag + 128, s_bad, nullptr};
-    const HyperLds H{s_g, s_fdt, s_hl, s_hr, s_w, s_row};
+    const HyperLds H{s_g, s_fdt, s_hl, s_hr, s_w, s_row, nullptr, nullptr, nullptr};
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {       // wave-uniform by construction
         case 0: hyper_body<GAL, PIV, 0>(a, L, H); break;
         case 1: hyper_body<GAL, PIV, 1>(a, L, H); break;
@@ -281,6 +386,7 @@ __global__ __launch_bounds__(256, PIV ? 1 : HWG_PER_CU) void rom_hyper_kernel(Hy
 
 }  // namespace
 
+#ifndef BG_ROM_HYPER_LOCAL_TU
 extern "C" {
 
 int bg_hyper_rom_limits(int* max_r, int* max_m)
@@ -326,3 +432,4 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
 }
 
 }  // extern "C"
+#endif  // BG_ROM_HYPER_LOCAL_TU

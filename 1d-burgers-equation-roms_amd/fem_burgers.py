@@ -163,14 +163,19 @@ class FEMBurgers:
 
     # ------------------------------------------------------------------------- local POD
     def local_prom_burgers(self, At, nTimeSteps, u0, mu1, E, mu2, kmeans, local_bases, U_global,
-                           num_global_modes, projection="Galerkin", fused=False, long_mesh=False):
+                           num_global_modes, projection="Galerkin", fused=False, long_mesh=False, hyper=None):
         """Local (clustered) POD PROM (reference :979-1079).  ``kmeans`` is the fitted
         scikit-learn KMeans of the reference (only ``cluster_centers_`` is used: ``predict`` is the
         nearest centre), ``local_bases`` a dict cluster id -> (N, r_c) basis.  ``fused``: the whole time loop
         on the device (bg_local_rom_run) where it covers the clustering; the default is the host-driven iteration.
-        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_local_rom_run_long."""
+        ``long_mesh`` (with ``fused``): meshes of 513 .. 1024 nodes take the device-side loop bg_local_rom_run_long.
+        ``hyper``: a row sampling (burgers_hip.pod.build_local_row_sampling) or a rom.HyperLocalPlan sends the call through
+        the hyper-reduced device-side loop bg_hyper_local_rom_run, which assembles every cluster's reduced system from the
+        same sampled mesh rows (any mesh the FOM takes, orthonormal bases of at most 40 modes, at most 64 centres and global
+        modes and 256 rows)."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.local_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                   np.asarray(kmeans.cluster_centers_, dtype=np.float64), local_bases, U_global,
-                                  int(num_global_modes), projection=projection, E=E, fused=fused, long_mesh=long_mesh)
+                                  int(num_global_modes), projection=projection, E=E, fused=fused, long_mesh=long_mesh,
+                                  hyper=hyper)
         return self._finish(res, batched)

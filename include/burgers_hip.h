@@ -790,6 +790,48 @@ int bg_local_rom_run_long(int N, int B, int C, int rmax, int m, int nsteps, int 
                           int max_it, int options, double *hist, int32_t *iters, int32_t *flags, int32_t *info,
                           int32_t *clusters, const int32_t *order, void *stream);
 
+/* bg_hyper_local_rom_run -- the local POD PROM time loop HYPER-REDUCED: bg_hyper_rom_run with one basis per time step, the
+ *   reduced system of every cluster assembled from the SAME m sampled mesh rows and weights (one sampling for all clusters).
+ *   3 <= N <= bg_fom_max_n(): the kernel never touches a vector of mesh length, so the pick and the change of basis work on
+ *   reduced coordinates.  widths <= 40, m <= 256, mg <= 64, C <= 64 (bg_hyper_local_rom_limits).
+ *   reference: FEM/fem_burgers.py:979-1079 with the sums over mesh rows restricted and weighted; with all rows, unit weights
+ *   and orthonormal bases the loop is the reference's.  Opt-in: nothing routes here unless asked (burgers_hip/rom.py,
+ *   local_prom_run_hyper; the facade's hyper=).
+ *   The state of a sample is (p, q): the cluster held and the coordinates in its basis, u = Phi_p q.
+ *   rows, xi, xs, u0s, mu1, mu2, iters, flags, info, order, options: as bg_hyper_rom_run;
+ *   PhiS     [C][MPAD][3][42] (bg_hyper_local_rom_table_elems(C, m) doubles, 16-byte aligned; 0 for a C or m the kernel does
+ *            not cover): block c is bg_hyper_rom_run's table of cluster c's basis, zero columns beyond widths[c];
+ *   widths   [C] int32, 1 .. rmax (clamped to rmax);
+ *   trans    [C][C][40][40]: trans[c][p] = Phi_c^T Phi_p, zero rows beyond widths[c] and zero columns beyond widths[p];
+ *   pick     [C][mg][40]: pick[p] = U_g^T Phi_p with U_g the first mg global modes, zero columns beyond widths[p];
+ *   centres  [C][mg] (the KMeans cluster_centers_);
+ *   qg0      [B][mg] = U_g^T u0;   pu0  [B][C][rmax] = Phi_c^T u0 for every cluster, zero beyond widths[c];
+ *   qhist    [B][nsteps+1][rmax]: entry n + 1 holds the coordinates in the basis of clusters[b][n], zero beyond its width;
+ *            entry 0 is pu0 of the first cluster; the caller decodes U = Phi_c q;
+ *   clusters [B][nsteps] int32 or NULL: the cluster of every sample and step.
+ *   Step n >= 1 starts with q_g = pick[p] q and c = argmin_c |q_g - centres[c]|^2 (the distance summed in j order, the first
+ *   index of the minimum, a NaN distance counting as the smallest: the pick of bg_local_rom_run); step 0 picks from qg0 and
+ *   starts from pu0 and u0s.  If c != p, one lift-only sweep over table p leaves u^n = Phi_p q at the stencil nodes, which
+ *   the first iteration of the step assembles at (g = M u^n + dt F, A and R, as the reference does with U0 = u^n outside the
+ *   new span) while Y and W come from table c; the base of the update is q <- trans[c][p] q, the reference's
+ *   q = Phi_c^T U0 + dq.  From the second iteration on, and in steps without a switch, the step is bg_hyper_rom_run's with
+ *   the width widths[c]: unknowns at and beyond it get a unit diagonal and a zero correction.  A step without a switch
+ *   costs no sweep more than bg_hyper_rom_run's.  The repair kernel redoes a marked sample from u0 and recomputes its picks.
+ *   Errors: N < 3, C, rmax, mg, m, max_it < 1, B or nsteps < 0, dt <= 0, m > N, a null operand or output with B > 0
+ *   (clusters may be null), PhiS not 16-byte aligned: BG_ERR_BAD_ARG; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; rmax > 40,
+ *   m > 256, mg > 64 or C > 64: BG_ERR_UNSUPPORTED_R; an unknown projection: BG_ERR_PROJECTION; B = 0: BG_OK with nothing
+ *   launched.  Sizes the kernel does not cover are refused, never rerouted.
+ *   csrc/rom_hyper_local.hip: the LOCAL instantiations of csrc/rom_hyper.hip's loop; workgroup k of G = min(B, 2 CUs) takes
+ *   the slots k, k + G, ... */
+int bg_hyper_local_rom_limits(int *max_r, int *max_m, int *max_mg, int *max_clusters);
+long long bg_hyper_local_rom_table_elems(int C, int m);
+int bg_hyper_local_rom_run(int N, int B, int C, int rmax, int mg, int m, int nsteps, int projection, const int32_t *rows,
+                           const double *xi, const double *xs, const double *PhiS, const int32_t *widths,
+                           const double *trans, const double *pick, const double *centres, const double *qg0,
+                           const double *pu0, const double *u0s, const double *mu1, const double *mu2, double dt, double E,
+                           double tol, int max_it, int options, double *qhist, int32_t *iters, int32_t *flags, int32_t *info,
+                           int32_t *clusters, const int32_t *order, void *stream);
+
 /* bg_decode_modes_bf16 -- the contraction of the non-intrusive POD-ANN decoder (bf16 tier of BASELINE config 5)
  *   reference: `Uhat = U_modes @ Qhat.T`, Non-Instrusive/predict_pod_ann.py:73-80, for a batch of (mu1, mu2) samples
  *   out[b][i][t] = sum_k Um[i][k] * Q[b * Nt + t][k]: bf16 operands, float32 accumulate, each result written once as
