@@ -240,7 +240,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void fom_fused_kernel(FomArgs
 {
     const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
     if (s >= a.B) return;                                   // wave-uniform
-    WaveTopo tp{lane_id()};
+    WaveTopoT<UNI> tp{lane_id()};                           // uniform mesh: the one-sided closing of pcr64
     fom_sample<R, FULL, UNI, TRACE, false>(a, tp, s, nullptr);
 }
 
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 1) void tridiag_solve_kernel(Sol
 {
     const int s = blockIdx.x * WAVES_PER_WG + (int)(threadIdx.x >> 6);
     if (s >= a.B) return;
-    WaveTopo tp{lane_id()};
+    WaveTopoT<true> tp{lane_id()};
     solve_sample<R>(a, tp, s);
 }
 

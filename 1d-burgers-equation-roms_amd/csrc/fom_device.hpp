@@ -36,6 +36,12 @@
 #define BG_PCR_JACOBI_MIN_ROWS 12
 #endif
 
+// where the caller asks for it (pcr64<ROWS, true>), pcr64 closes an interface system that couples upwards only by six
+// one-sided sweeps and one fold of the lower coupling (see pcr64_onesided); 0: the listing before that route
+#ifndef BG_PCR_ONESIDED_EXIT
+#define BG_PCR_ONESIDED_EXIT 1
+#endif
+
 // fom_sample forms the off-diagonals and SUPG terms of the NEXT iterate in front of the stopping test, where one wave per
 // sample has nothing else to issue between the dependent rounds of the norm reduction (see fom_sample; topologies with
 // rotates_picard only); 0: every iteration starts with them, the listing of the loop before the rotation
@@ -631,32 +637,79 @@ __device__ __forceinline__ double pcr64_from_stride2(double A, double C, double 
     return from_lane_rot(D, (16 * (lane & 3) + (lane >> 2)) << 2);
 }
 
+// Everything after the stride-1 step where the Jacobi exit is compiled in: the ballot against tau_J, the six two-sided
+// sweeps, otherwise pcr64_from_stride2.
+__device__ __forceinline__ double pcr64_jacobi(double A, double C, double D)
+{
+    constexpr double tau_j = 0x1p-9;
+    constexpr int sweeps = 6;
+    const bool coupled = !(__builtin_fabs(A) <= tau_j && __builtin_fabs(C) <= tau_j);
+    const bool eliminate = __builtin_amdgcn_ballot_w64(coupled) != 0;
+    // As with the exit against tau: the sweeps stand ahead of the branch and the elimination is one `if` without
+    // an `else`, out of line, which starts again from A, C, D of the stride-1 step.
+    double X = D;
+#pragma unroll
+    for (int k = 0; k < sweeps; ++k) X = pcr_jacobi_sweep<0x138, 0x130, 2>(A, C, D, X);
+    if (__builtin_expect(eliminate, 0)) X = pcr64_from_stride2(A, C, D);
+    return X;
+}
+
+// One-sided exit (BG_PCR_ONESIDED_EXIT, callers that pass ONESIDED): a convection-dominated matrix couples an interface
+// to one side only.  Inside a lane the flagship's left spike decays by 0.49 per row and its right one by 0.80, so after
+// the stride-1 step |A| <= 3.9e-10 where |C| reaches 9.3e-4.  An A that small moves x by 1e-10 relative:
+// it has to be applied once, to a modestly accurate x, and not in every sweep.  The wave asks once whether EVERY lane has
+// |A| <= tau_A = 2^-28 and |C| <= tau_J = 2^-9 (negated form: a NaN or inf coupling fails).  If so it runs, from y = D,
+//   two sweeps  y <- D - C y[j+2],   then side by side the fold  D' = D - A y[j-2]  and a third sweep  y <- D - C y[j+2],
+//   then three sweeps  y <- D' - C y[j+2]  from the current y
+// and returns y: seven moves of one double by two lanes and seven FMAs, against twelve and twelve of the six two-sided
+// sweeps, in a chain six sweeps long.  The fold reads the second iterate and not the third, so that it does not stand in
+// that chain: a sweep is one dependent move by two lanes and one FMA, with one wave per SIMD nothing else fills the wait
+// between them, and with the fold behind the third sweep the route measured no faster than the six two-sided sweeps, whose
+// two moves fill each other's waits.
+// Bound, with c = max|C| <= 2^-9, a = max|A| <= 2^-28, U = (I + C S+)^-1 and the exact x = U (D - A S- x): a sweep
+// contracts towards U D by c and y_0 = D is c |D| / (1 - c) off it, so y_2 is within c^3 |D| / (1 - c) of U D and, x - U D
+// being a |x|, within (c^3 + a) |D| (1 + o(1)) of x.  The fold therefore misses D - A S- x by <= a (c^3 + a) |D| =
+// 1.5 * 2^-55 |D|.  y_3 is within c^4 |D| of U D and so within (c^4 + a) |D| of the fixed point U D' of the last three
+// sweeps, which leave c^3 of that, 2^-55 |D|.  Together 2.5 * 2^-55 (1 + o(1)) |D| and, with |D| <= (1 + c + a) max|x|,
+// < 2^-53 max|x|: below half an ulp of the largest interface unknown, the standard of both exits above.  A wave with one
+// lane over either threshold (a leftward flow with |C| <= tau_A included: the mirrored route is not built) restarts from
+// A, C, D of the stride-1 step and runs pcr64_jacobi, in one `if` without an `else`, out of line, with the route
+// standing ahead of that branch as the sweeps do there.
+__device__ __forceinline__ double pcr64_onesided(double A, double C, double D)
+{
+    constexpr double tau_a = 0x1p-28, tau_j = 0x1p-9;
+    const bool twosided = !(__builtin_fabs(A) <= tau_a && __builtin_fabs(C) <= tau_j);
+    const bool fallback = __builtin_amdgcn_ballot_w64(twosided) != 0;
+    double y = D;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) y = __builtin_fma(-dpp_shift<0x130, 2>(y), C, D);
+    const double Df = __builtin_fma(-dpp_shift<0x138, 2>(y), A, D);
+    y = __builtin_fma(-dpp_shift<0x130, 2>(y), C, D);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) y = __builtin_fma(-dpp_shift<0x130, 2>(y), C, Df);
+    if (__builtin_expect(fallback, 0)) y = pcr64_jacobi(A, C, D);
+    return y;
+}
+
 // ROWS = rows per lane of the caller's partition: a wave that fails the test has paid for the sweeps, so the exit is
 // compiled in where the mesh gives a lane at least BG_PCR_JACOBI_MIN_ROWS rows (DESIGN.md K1 has the measurements).
-template <int ROWS>
+// ONESIDED = the caller's systems are expected to pass the one-sided ballot (a wave that fails it has paid for that
+// route before it takes the other): the kernels that have it are listed in DESIGN.md K1.
+template <int ROWS, bool ONESIDED = false>
 __device__ __forceinline__ double pcr64(double A, double C, double D)
 {
     pcr_step<0x138, 0x130, 1, false>(A, C, D);
     if constexpr (BG_PCR_JACOBI_EXIT && ROWS >= BG_PCR_JACOBI_MIN_ROWS) {
-        constexpr double tau_j = 0x1p-9;
-        constexpr int sweeps = 6;
-        const bool coupled = !(__builtin_fabs(A) <= tau_j && __builtin_fabs(C) <= tau_j);
-        const bool eliminate = __builtin_amdgcn_ballot_w64(coupled) != 0;
-        // As with the exit against tau: the sweeps stand ahead of the branch and the elimination is one `if` without
-        // an `else`, out of line, which starts again from A, C, D of the stride-1 step.
-        double X = D;
-#pragma unroll
-        for (int k = 0; k < sweeps; ++k) X = pcr_jacobi_sweep<0x138, 0x130, 2>(A, C, D, X);
-        if (__builtin_expect(eliminate, 0)) X = pcr64_from_stride2(A, C, D);
-        return X;
+        if constexpr (BG_PCR_ONESIDED_EXIT && ONESIDED) return pcr64_onesided(A, C, D);
+        else return pcr64_jacobi(A, C, D);
     } else {
         return pcr64_from_stride2(A, C, D);
     }
 }
 
 // Pivot-free tridiagonal solve across the wave (Wang partition + PCR on the 64
-// interface unknowns).  In: lo/di/up/rhs.  Out: solution in rhs.  lo, di are clobbered.
-template <int R>
+// interface unknowns).  In: lo/di/up/rhs.  Out: solution in rhs.  lo, di are clobbered.  ONESIDED: see pcr64.
+template <int R, bool ONESIDED = false>
 __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], const double (&up)[R],
                                               double (&rhs)[R])
 {
@@ -671,7 +724,7 @@ __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], 
         const double R0 = from_lane_above(rhs[0] * di[0]);
         double A, C, D;           // normalised interface equation: A x[p-1] + x[p] + C x[p+1] = D
         wang_interface<R>(lo, up, rhs, dp, F0, G0, R0, A, C, D);
-        const double X = pcr64<R>(A, C, D);
+        const double X = pcr64<R, ONESIDED>(A, C, D);
         wang_finish<R>(lo, di, rhs, gs, X, from_lane_below(X));
     }
 }

@@ -140,7 +140,10 @@ __device__ __forceinline__ double wave_max_nan(double v, bool nan)
 //   rotates_picard   whether fom_sample may form the next iterate's assemble_head ahead of sum2 (BG_PICARD_ROTATE): the wave
 //               form's exchanges are DPP moves and order freely; the workgroup form's halo() and below_se() refill LDS
 //               buffers between barriers, and a halo() in front of sum2's barrier has not been argued
-struct WaveTopo {
+//   ONESIDED    (one wavefront per sample) the solve closes its interface system by the one-sided route of pcr64 where a
+//               lane owns enough rows; for kernels whose systems couple upwards only
+template <bool ONESIDED>
+struct WaveTopoT {
     static constexpr bool rotates_picard = true;
     int g;                                           // = lane
     __device__ __forceinline__ bool first() const { return g == 0; }        // owns global row 0
@@ -160,9 +163,10 @@ struct WaveTopo {
     template <int R>
     __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
     {
-        tridiag_solve<R>(lo, di, up, rhs);
+        tridiag_solve<R, ONESIDED>(lo, di, up, rhs);
     }
 };
+using WaveTopo = WaveTopoT<false>;
 
 struct WgTopo {
     static constexpr bool rotates_picard = false;
