@@ -129,6 +129,9 @@ _SIGNATURES = {
     "bg_hyper_rom_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     # N, B, r, m, nsteps, projection, rows, xi, xs, PhiS, q0, u0s, mu1, mu2, the step, the outputs (qhist for hist)
     "bg_hyper_rom_run": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),
+    "bg_hyper_rom_wide_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
+    "bg_hyper_rom_wide_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "bg_hyper_rom_run_wide": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),      # as bg_hyper_rom_run
     "bg_hyper_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 6),
     "bg_hyper_ann_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
     # N, B, n, nbar, m, nodes, nsteps, projection, node, xn, pos, xi, UTn, q0, u0n, mu1, mu2, the MLP, the step, qhist, qshist, ...

@@ -776,6 +776,12 @@ def hyper_rom_limits():
     return _lib.limits("bg_hyper_rom_limits", 2)
 
 
+def hyper_wide_rom_limits():
+    """(max_r, max_m) of bg_hyper_rom_run_wide.  Needs no device."""
+    from . import lib as _lib
+    return _lib.limits("bg_hyper_rom_wide_limits", 2)
+
+
 def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None):
     """The sampled mesh rows and weights of the hyper-reduced POD PROM (ECSW-style: energy-conserving sampling and
     weighting), fitted on the host by non-negative least squares.
@@ -786,7 +792,12 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     Row 0 (the Dirichlet row) is forced in with weight 1 and moved to the right-hand side; the other weights are
     nnls_rows(G[:, 1:], d - G[:, 0]): stopped at |G xi - d| <= tau |d|, then filled by the same greedy rule up to
     ``min_rows`` rows (default 3 r: fewer rows have diverged at r = 40 even where the training residual was met).
-    ``max_rows`` defaults to the kernel's limit (hyper_rom_limits); needing more is a ValueError.  Returns a RowSampling."""
+    ``max_rows`` defaults to the limit of the loop that takes r: hyper_rom_limits' (256) up to its r = 40, hyper_wide_rom_limits'
+    (512) above; needing more is a ValueError.  Returns a RowSampling.
+    Two facts about wide bases, from a study at N = 600, r = 96 (3 r = 288 rows): the fill up to 3 r needs enough training
+    pairs -- with three runs and stride 20 the greedy rule has no column left to add at 269, and ``min_rows`` must be given
+    (200 rows stayed within 4e-11 of the full PROM there); and the NNLS is host work, about a minute at r = 96 with nine runs
+    and stride 10 on eight threads."""
     projection = str(projection).lower()
     if projection not in ("galerkin", "lspg"):
         raise ValueError("projection must be 'Galerkin' or 'LSPG'")
@@ -799,9 +810,11 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
         raise ValueError("build_row_sampling takes at least one run, stride >= 1 and tau > 0")
     min_rows = min(3 * r, N) if min_rows is None else int(min_rows)
-    max_rows = hyper_rom_limits()[1] if max_rows is None else int(max_rows)
+    if max_rows is None:
+        narrow_r, narrow_m = hyper_rom_limits()
+        max_rows = narrow_m if r <= narrow_r else hyper_wide_rom_limits()[1]
     G, pairs = row_sampling_system(X, Phi, runs, dt, projection, E, supg, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, int(max_rows))
 
 
 def _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows):

@@ -64,6 +64,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_local_rom_run_long", "bg_rom_run_long_workgroups_per_cu"),
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
+    _Route("bg_hyper_rom_run_wide", 1, min_n=3, max_n="bg_fom_max_n", redo=True),
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
     _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
     _Route("bg_hyper_quad_rom_run", 1, "bg_quad_rom_max_n", 3, "bg_fom_max_n", group=4, supg=False),
@@ -544,14 +545,15 @@ class HyperPodPlan:
     index of the stencil nodes (``stencil``, clipped to the mesh, with ``inside`` marking the slots that exist).
     ``sampling``: a pod.RowSampling.  What the shapes and the sampling alone decide is refused before the device is
     touched; every refusal is a ValueError."""
+    entry, limits, table_elems, slab_rows = "bg_hyper_rom_run", "bg_hyper_rom_limits", "bg_hyper_rom_table_elems", 32
 
     def __init__(self, Phi, sampling, X, device):
         shape = tuple(np.shape(Phi))
         if len(shape) != 2:
             raise ValueError("Phi must be (N, r)")
         N, r = shape
-        route = _ROUTES["bg_hyper_rom_run"]
-        max_r, max_m = _lib.limits("bg_hyper_rom_limits", 2)
+        route = _ROUTES[self.entry]
+        max_r, max_m = _lib.limits(self.limits, 2)
         Xh = check_mesh(X)
         if r < 1 or r > max_r:
             raise ValueError(f"Phi must be (N, r) with 1 <= r <= {max_r}")
@@ -564,7 +566,7 @@ class HyperPodPlan:
             raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
         if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
             raise ValueError("the weights must be finite and >= 0")
-        elems = _lib.load().bg_hyper_rom_table_elems(m, r)
+        elems = getattr(_lib.load(), self.table_elems)(m, r)
         if m > max_m or elems == 0:
             raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
         device = _lib.require_device(device)
@@ -575,7 +577,7 @@ class HyperPodPlan:
         idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
         self.inside = (idx >= 0) & (idx < N)
         self.stencil = idx.clamp(0, N - 1)
-        cols = elems // (3 * ((m + 31) // 32 * 32))
+        cols = elems // (3 * ((m + self.slab_rows - 1) // self.slab_rows * self.slab_rows))
         table = torch.zeros((elems // (3 * cols), 3, cols), dtype=torch.float64, device=device)
         table[:m, :, :r] = self.Phi[self.stencil] * self.inside[:, :, None]
         self.PhiS = table
@@ -584,10 +586,18 @@ class HyperPodPlan:
         self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
 
 
+class HyperWidePodPlan(HyperPodPlan):
+    """What bg_hyper_rom_run_wide reads besides the batch: a HyperPodPlan against the wide loop's limits (r <= 96, m <= 512,
+    bg_hyper_rom_wide_limits) with the table PhiS in its layout, 98 doubles per row and m rounded up to 16.  The basis, the
+    rows and the weights it keeps also serve the redo of marked samples (_pod_prom_run_hyper_library)."""
+    entry, limits, table_elems, slab_rows = "bg_hyper_rom_run_wide", "bg_hyper_rom_wide_limits", "bg_hyper_rom_wide_table_elems", 16
+
+
 class HyperRomResult:
     """Result of pod_prom_run_hyper: the reduced coordinates ``q`` (B, nT+1, r), ``iters``, ``flags``, ``info`` and the
-    ``plan``.  ``hist`` (B, nT+1, N) is decoded on demand, U = Phi q as one batched product with u0 itself in column 0 as in
-    every other loop, and kept; ``snapshots()`` is its (B, N, nT+1) layout."""
+    ``plan``; from the wide loop also ``redone``, the number of samples redone on the host side.  ``hist`` (B, nT+1, N) is
+    decoded on demand, U = Phi q as one batched product with u0 itself in column 0 as in every other loop, and kept;
+    ``snapshots()`` is its (B, N, nT+1) layout."""
 
     def __init__(self, res, plan, u0d):
         self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
@@ -608,17 +618,15 @@ class HyperRomResult:
         return int(self.iters.sum().item())
 
 
-def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
-                       options=0, balance=True):
-    """``pod_prom_burgers`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_rom_run): the reduced system
-    is assembled from the sampled mesh rows of a pod.RowSampling (pod.build_row_sampling) with their weights, so an
-    iteration costs O(m r^2) whatever the mesh: N up to bg_fom_max_n(), r <= 40, m <= 256 (bg_hyper_rom_limits).  The
-    pivoting repair runs inside the call, nothing is synchronised.  ``sampling_or_plan``: the sampling, or a HyperPodPlan
-    of this basis, sampling and mesh to reuse across calls (``res.plan``; ``Phi`` is then not looked at).  A sampling trained
-    for the other projection is refused.  Returns a HyperRomResult."""
+def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options, balance):
+    """pod_prom_run_hyper's narrow loop and pod_prom_run_hyper_wide: the plan (or the sampling to build one from) against the
+    call, q0 and u0 at the stencil, the launch, and for a route with ``redo`` the marked samples again on the host side."""
+    route = _ROUTES[plan_type.entry]
     device = _lib.require_device(device)
     Xh = check_mesh(X)
-    plan = sampling_or_plan if isinstance(sampling_or_plan, HyperPodPlan) else HyperPodPlan(Phi, sampling_or_plan, Xh, device)
+    if isinstance(sampling_or_plan, HyperPodPlan) and type(sampling_or_plan) is not plan_type:
+        raise ValueError(f"{route.entry} takes a {plan_type.__name__}")
+    plan = sampling_or_plan if isinstance(sampling_or_plan, plan_type) else plan_type(Phi, sampling_or_plan, Xh, device)
     _check_plan(plan, Xh, device)
     if not np.array_equal(plan.Xh, Xh):
         raise ValueError("the plan was built for another mesh")
@@ -627,12 +635,58 @@ def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj,
     u0d, _, mu2d = _batch_inputs(u0, mu1, mu2, plan.N, device)
     q0 = (u0d @ plan.Phi).contiguous()
     u0s = (u0d[:, plan.stencil] * plan.inside).contiguous()
-    res = _device_loop(_ROUTES["bg_hyper_rom_run"], Xh, u0d, mu1, mu2, nsteps, device, options, balance,
+    res = _device_loop(route, Xh, u0d, mu1, mu2, nsteps, device, options, balance,
                        lambda f, N, B, x, inputs, opts, outputs: f(
                            N, B, plan.r, plan.m, int(nsteps), proj, _lib.ptr(plan.rows), _lib.ptr(plan.xi), _lib.ptr(plan.xs),
                            _lib.ptr(plan.PhiS), _lib.ptr(q0), _lib.ptr(u0s), *inputs[1:], float(dt), float(E), float(tol),
                            int(max_it), opts, *outputs), keep=(plan, q0, u0s), cols=plan.r)
-    return HyperRomResult(res, plan, u0d)
+    out = HyperRomResult(res, plan, u0d)
+    if route.redo:
+        _redo_marked_hyper(out, plan, dt, nsteps, proj, E, tol, max_it)
+    return out
+
+
+def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                       options=0, balance=True):
+    """``pod_prom_burgers`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_rom_run): the reduced system
+    is assembled from the sampled mesh rows of a pod.RowSampling (pod.build_row_sampling) with their weights, so an
+    iteration costs O(m r^2) whatever the mesh: N up to bg_fom_max_n(), r <= 40, m <= 256 (bg_hyper_rom_limits).  The
+    pivoting repair runs inside the call, nothing is synchronised.  ``sampling_or_plan``: the sampling, or a HyperPodPlan
+    of this basis, sampling and mesh to reuse across calls (``res.plan``; ``Phi`` is then not looked at).  A sampling trained
+    for the other projection is refused.  Returns a HyperRomResult.
+    A HyperWidePodPlan, or a sampling with a basis of more than bg_hyper_rom_limits' r modes, goes to the wide loop
+    (pod_prom_run_hyper_wide: r <= 96, m <= 512, which does synchronise)."""
+    if isinstance(sampling_or_plan, HyperWidePodPlan) or (
+            not isinstance(sampling_or_plan, HyperPodPlan) and len(np.shape(Phi)) == 2
+            and np.shape(Phi)[1] > _lib.limits(HyperPodPlan.limits, 2)[0]):
+        return pod_prom_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options,
+                                       balance)
+    return _run_hyper_pod(HyperPodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options,
+                          balance)
+
+
+def pod_prom_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                            options=0, balance=True):
+    """pod_prom_run_hyper for bases of up to 96 modes on up to 512 sampled rows (bg_hyper_rom_run_wide,
+    bg_hyper_rom_wide_limits; meant for r > 40): the same loop with pod_prom_run_wide's 96 x 96 solve.  There is no repair
+    kernel: samples whose elimination would have needed a row exchange come back marked and are redone by the weighted-row
+    library iteration (_pod_prom_run_hyper_library) -- the full PROM's library path answers another question -- so unlike
+    pod_prom_run_hyper this wrapper reads ``info`` back and synchronises the host.  ``sampling_or_plan``: the sampling, or a
+    HyperWidePodPlan to reuse across calls.  Returns a HyperRomResult with ``redone``."""
+    return _run_hyper_pod(HyperWidePodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device,
+                          options, balance)
+
+
+def _redo_marked_hyper(out, plan, dt, nsteps, proj, E, tol, max_it):
+    """_redo_marked for a HyperRomResult: the samples marked BG_INFO_NEEDS_PIVOTING again through the weighted-row library
+    iteration (LU with partial pivoting).  Reads ``info`` back, so it synchronises the host."""
+    _, u0d, mu1d, mu2d = out._keep[:4]
+    redo = (out.info == _lib.BG_INFO_NEEDS_PIVOTING).nonzero().squeeze(1)
+    if redo.numel():
+        rr = _pod_prom_run_hyper_library(plan, u0d[redo], mu1d[redo], mu2d[redo], dt, nsteps, proj, E, tol, max_it)
+        out.q[redo], out.iters[redo], out.flags[redo] = rr.q, rr.iters, rr.flags
+        out.info[redo] = 0
+    out.redone = int(redo.numel())
 
 
 def check_singular(res):
@@ -673,9 +727,9 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
     take the device-side loop bg_rom_run_long instead of the library path.
     ``long_wide`` (opt-in, with ``fused``): meshes of 512 < N <= bg_rom_run_long_wide_max_n() with bg_rom_run_long_max_r() < r
     <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path.
-    ``hyper`` (opt-in): a pod.RowSampling or a HyperPodPlan sends the call through the hyper-reduced loop
-    pod_prom_run_hyper, which assembles the reduced system from the sampled mesh rows only; sizes it does not cover are
-    refused, not rerouted."""
+    ``hyper`` (opt-in): a pod.RowSampling, a HyperPodPlan or a HyperWidePodPlan sends the call through the hyper-reduced loop
+    pod_prom_run_hyper, which assembles the reduced system from the sampled mesh rows only (r <= 40: bg_hyper_rom_run;
+    41 <= r <= 96: bg_hyper_rom_run_wide); sizes it does not cover are refused, not rerouted."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
     if hyper is not None:
         return check_singular(pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device))
@@ -779,6 +833,52 @@ def _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it
 
 
 # ------------------------------------------------------------ quadratic manifold
+def _pod_prom_run_hyper_library(plan, u0, mu1, mu2, dt, nsteps, proj, E, tol, max_it):
+    """_pod_prom_run_library with the two projections restricted to the rows of ``plan`` (a HyperPodPlan or HyperWidePodPlan)
+    and weighted by its xi -- bg_hyper_rom_run's iteration as library calls: bg_fom_assemble on the full state, the sampled
+    rows gathered, the rows of Y = A Phi from the stencil, rocSOLVER LU, q <- q + dq, the first assembly at u0 itself.  It
+    redoes the samples bg_hyper_rom_run_wide hands back and is the baseline of tools/time_hyper_wide_rom.py.  Returns a
+    namespace with ``q`` (B, nT+1, r), ``iters``, ``flags`` and ``path``."""
+    from . import fom as _fom
+    c = _setup(plan.Xh, u0, mu1, mu2, dt, E, plan.Phi.device, max_n=_lib.load().bg_fom_max_n())
+    rows = plan.rows.long()
+    P3 = plan.Phi[plan.stencil] * plan.inside[:, :, None]            # (m, 3, r): Phi[i-1], Phi[i], Phi[i+1] of every sampled row
+    gal = proj == _lib.BG_PROJ_GALERKIN
+    w = plan.xi if gal else plan.xi.sqrt()                            # the weight goes into lo, di, up and R, as in the kernel
+    PhiT = plan.Phi.t().contiguous()
+    qhist = torch.empty((c.B, nsteps + 1, plan.r), dtype=torch.float64, device=c.device)
+    iters = torch.zeros((c.B, nsteps), dtype=torch.int32, device=c.device)
+    flags = torch.zeros((c.B,), dtype=torch.int32, device=c.device)
+    q = c.u0 @ plan.Phi
+    qhist[:, 0] = q
+    U0 = c.u0.clone()
+    for n in range(nsteps):
+        Un = U0.clone()
+        active = torch.ones((c.B,), dtype=torch.bool, device=c.device)
+        k = torch.zeros((c.B,), dtype=torch.int32, device=c.device)
+        while True:
+            lo, di, up, rhs = _fom.fom_assemble(plan.Xh, U0, Un, c.mu1, c.mu2, c.dt, E=c.E, supg=True, device=c.device)
+            lo, di, up, rhs = (v[:, rows] * w for v in (lo, di, up, rhs))
+            Y = lo.unsqueeze(2) * P3[:, 0] + di.unsqueeze(2) * P3[:, 1] + up.unsqueeze(2) * P3[:, 2]      # (B, m, r), weighted
+            W = P3[:, 1].expand(c.B, -1, -1) if gal else Y
+            Ar = torch.matmul(W.transpose(1, 2), Y)                         # sum_j xi_j w_j^T y_j
+            br = -torch.matmul(W.transpose(1, 2), rhs.unsqueeze(2)).squeeze(2)      # sum_j xi_j w_j R_j, R = -rhs
+            dq = _batched_solve(Ar, -br, active)
+            qn = q + dq
+            err = torch.linalg.vector_norm(dq, dim=1) / torch.linalg.vector_norm(qn, dim=1)
+            q = torch.where(active[:, None], qn, q)
+            U0 = torch.where(active[:, None], q @ PhiT, U0)
+            k += active.to(torch.int32)
+            flags |= (active & ~torch.isfinite(err)).to(torch.int32) * _lib.BG_FLAG_NONFINITE
+            active = active & (err > tol) & (k < max_it)
+            if not bool(active.any()):
+                break
+        flags |= (k >= max_it).to(torch.int32) * _lib.BG_FLAG_HIT_CAP
+        iters[:, n] = k
+        qhist[:, n + 1] = q
+    return SimpleNamespace(q=qhist, iters=iters, flags=flags, path="library")
+
+
 def sym_index_tables(n, device):
     """Row-major upper-triangle pair order of get_sym (:263-273) and the (n, n) lookup of
     the pair index, with the factor (1 + delta_ab) of get_dQ_dq (:292-312)."""

@@ -33,6 +33,10 @@
 // (the additions sit under `if constexpr (LOCAL)`, described at HyperLocalRunArgs).  Its kernel and entry point are compiled
 // in a translation unit of their own, rom_hyper_local.hip, which includes this file with BG_ROM_HYPER_LOCAL_TU defined, as
 // rom_local_fused.hip does with rom_fused.hip: the four kernels here are meant to stay exactly what they were.
+//
+// The larger bases (bg_hyper_rom_run_wide, 40 < r <= 96, m <= 512) are the same body with another description K in the place of
+// LongLayout (HyperDims says what the body asks of one): rom_hyper_wide.hip, which includes this file with
+// BG_ROM_HYPER_WIDE_TU defined for the same reason.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,10 +46,21 @@ namespace {
 
 using namespace bg;
 
-constexpr int HS = 32;                 // sampled rows per slab
-constexpr int HMMAX = 256;             // sampled rows held
-constexpr int HSLAB = 3 * HS * LPS;    // doubles of one slab buffer: three stencil rows per sampled row
-constexpr int HCHUNKS = (HSLAB * 8 + 1023) / 1024;
+// What the body needs of a description K besides rom_stream_device.hpp's list: the sampled rows per slab and how many
+// values of q a lane carries through the solve (1: K::solve_add(L, r, lane, base, ...) as LongLayout's;
+// 2: rows lane and 64 + lane, K::solve_add<GAL, W>(L, r, lane, base0, base1, force, aborted, nd, nq), no repair).
+template <class K>
+struct HyperDims;
+template <>
+struct HyperDims<LongLayout> {
+    static constexpr int HS = 32, per_lane = 1;
+};
+template <class K>
+constexpr int hyper_slab = 3 * HyperDims<K>::HS * K::PS;      // doubles of one slab buffer: three stencil rows per sampled row
+
+constexpr int HS = HyperDims<LongLayout>::HS;                  // sampled rows per slab
+constexpr int HMMAX = 256;                                     // sampled rows held
+constexpr int HSLAB = hyper_slab<LongLayout>;
 constexpr int HWG_PER_CU = 2;
 
 struct HyperRunArgs {
@@ -124,13 +139,14 @@ __device__ __forceinline__ void hyper_row_forcing(double xm, double x0, double x
 }
 
 // The body for wave W of the workgroup (a template parameter of the whole body, as in rom_stream_body: every wave keeps
-// its own quarter of the block pairs in accumulators that never change registers).  The description K is LongLayout as it
-// stands: the items, matrix steps, parking and solve of the r <= 40 streaming loops.
-template <bool GAL, bool PIV, int W, bool LOCAL = false, class A = HyperRunArgs>
+// its own quarter of the block pairs in accumulators that never change registers).  The description K: LongLayout as it
+// stands (the items, matrix steps, parking and solve of the r <= 40 streaming loops), or rom_hyper_wide.hip's for r <= 96.
+template <bool GAL, bool PIV, int W, bool LOCAL = false, class A = HyperRunArgs, class K = LongLayout>
 __device__ __forceinline__ void hyper_body(const A& a, const StreamLds& L, const HyperLds& H)
 {
-    using K = LongLayout;
-    constexpr int NB = LNB, R = LR, PS = LPS;
+    static_assert(!LOCAL || HyperDims<K>::per_lane == 1, "the local additions are written for one value of q per lane");
+    constexpr int NB = K::NB, R = 4 * NB, PS = K::PS;
+    constexpr int HS = HyperDims<K>::HS, HSLAB = hyper_slab<K>, HCHUNKS = (HSLAB * 8 + 1023) / 1024;
     constexpr int NACC = StreamItems<K, GAL>::per_wave;
     constexpr int w = W;
     double* const s_slab = L.slab;
@@ -335,8 +351,13 @@ __device__ __forceinline__ void hyper_body(const A& a, const StreamLds& L, const
                 __syncthreads();
                 // ---- solve(Ar, -br) (:767), q <- q + dq, err = |dq| / |q|  (:770-776) -------------------------------------------
                 double nd, nq;
-                const double qk = (lane < step_width()) ? s_q[lane] : 0.0;        // read before the solve's first barrier
-                K::template solve_add<PIV, W>(L, step_width(), lane, qk, aborted, info_out, nd, nq);
+                if constexpr (HyperDims<K>::per_lane == 1) {
+                    const double qk = (lane < step_width()) ? s_q[lane] : 0.0;    // read before the solve's first barrier
+                    K::template solve_add<PIV, W>(L, step_width(), lane, qk, aborted, info_out, nd, nq);
+                } else {
+                    const double qk0 = (lane < step_width()) ? s_q[lane] : 0.0, qk1 = (64 + lane < step_width()) ? s_q[64 + lane] : 0.0;
+                    K::template solve_add<GAL, W>(L, step_width(), lane, qk0, qk1, a.force_pivoted != 0, aborted, nd, nq);
+                }
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;
                 ++k;
@@ -384,9 +405,32 @@ __global__ __launch_bounds__(256, PIV ? 1 : HWG_PER_CU) void rom_hyper_kernel(Hy
     }
 }
 
+// The argument checks of bg_hyper_rom_run and bg_hyper_rom_run_wide (bases of up to r_max modes on up to m_max sampled rows) and
+// the kernel's arguments, as stream_run_args for the streaming loops.  BG_OK with B == 0 means there is nothing to launch.
+inline int hyper_run_args(HyperRunArgs& a, int r_max, int m_max, int N, int B, int r, int m, int nsteps, int projection,
+                          const int32_t* rows, const double* xi, const double* xs, const double* PhiS, const double* q0, const double* u0s,
+                          const double* mu1, const double* mu2, double dt, double E, double tol, int max_it, int options, double* qhist,
+                          int32_t* iters, int32_t* flags, int32_t* info, const int32_t* order)
+{
+    if (N < 3 || B < 0 || r < 1 || m < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
+    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
+    if (N > bg_fom_max_n()) return BG_ERR_UNSUPPORTED_N;
+    if (r > r_max || m > m_max) return BG_ERR_UNSUPPORTED_R;
+    if (m > N) return BG_ERR_BAD_ARG;
+    if (B == 0) return BG_OK;
+    if (!rows || !xi || !xs || !PhiS || !q0 || !u0s || !mu1 || !mu2 || !qhist || !flags || !info || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
+    if ((uintptr_t)PhiS & 15) return BG_ERR_BAD_ARG;
+    a.rows = rows; a.xi = xi; a.xs = xs; a.PhiS = PhiS; a.q0 = q0; a.u0s = u0s; a.mu1 = mu1; a.mu2 = mu2; a.qhist = qhist;
+    a.iters = iters; a.flags = flags; a.info = info; a.order = order;
+    a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.r = r; a.m = m; a.nsteps = nsteps; a.max_it = max_it;
+    a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
+    a.force_pivoted = (options & BG_OPT_FORCE_PIVOTED) ? 1 : 0;
+    return BG_OK;
+}
+
 }  // namespace
 
-#ifndef BG_ROM_HYPER_LOCAL_TU
+#if !defined(BG_ROM_HYPER_LOCAL_TU) && !defined(BG_ROM_HYPER_WIDE_TU)
 extern "C" {
 
 int bg_hyper_rom_limits(int* max_r, int* max_m)
@@ -409,20 +453,10 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
                      double tol, int max_it, int options, double* qhist, int32_t* iters, int32_t* flags, int32_t* info,
                      const int32_t* order, void* stream)
 {
-    if (N < 3 || B < 0 || r < 1 || m < 1 || nsteps < 0 || max_it < 1 || !(dt > 0.0)) return BG_ERR_BAD_ARG;
-    if (projection != BG_PROJ_GALERKIN && projection != BG_PROJ_LSPG) return BG_ERR_PROJECTION;
-    if (N > bg_fom_max_n()) return BG_ERR_UNSUPPORTED_N;
-    if (r > LR || m > HMMAX) return BG_ERR_UNSUPPORTED_R;
-    if (m > N) return BG_ERR_BAD_ARG;
-    if (B == 0) return BG_OK;
-    if (!rows || !xi || !xs || !PhiS || !q0 || !u0s || !mu1 || !mu2 || !qhist || !flags || !info || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
-    if ((uintptr_t)PhiS & 15) return BG_ERR_BAD_ARG;
     HyperRunArgs a;
-    a.rows = rows; a.xi = xi; a.xs = xs; a.PhiS = PhiS; a.q0 = q0; a.u0s = u0s; a.mu1 = mu1; a.mu2 = mu2; a.qhist = qhist;
-    a.iters = iters; a.flags = flags; a.info = info; a.order = order;
-    a.dt = dt; a.E = E; a.tol = tol; a.N = N; a.B = B; a.r = r; a.m = m; a.nsteps = nsteps; a.max_it = max_it;
-    a.supg = options & BG_OPT_SUPG; a.nonuniform = (options & BG_OPT_NONUNIFORM) ? 1 : 0;
-    a.force_pivoted = (options & BG_OPT_FORCE_PIVOTED) ? 1 : 0;
+    const int rc = hyper_run_args(a, LR, HMMAX, N, B, r, m, nsteps, projection, rows, xi, xs, PhiS, q0, u0s, mu1, mu2, dt, E, tol, max_it,
+                                  options, qhist, iters, flags, info, order);
+    if (rc != BG_OK || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     return dispatch_projection(projection, [&](auto p) {
         return launch_fast_then_repair(B, HWG_PER_CU, a.force_pivoted != 0, [&](auto piv, int grid) {
@@ -432,4 +466,4 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
 }
 
 }  // extern "C"
-#endif  // BG_ROM_HYPER_LOCAL_TU
+#endif  // neither BG_ROM_HYPER_LOCAL_TU nor BG_ROM_HYPER_WIDE_TU

@@ -105,7 +105,8 @@ class FEMBurgers:
         instead of the library path.  ``long_wide``: meshes of 513 .. 1024 nodes with 41 .. 96 modes take the device-side
         loop bg_rom_run_long_wide instead of the library path.  ``hyper``: a row sampling (burgers_hip.pod.build_row_sampling)
         or a rom.HyperPodPlan sends the call through the hyper-reduced device-side loop bg_hyper_rom_run, which assembles the
-        reduced system from the sampled mesh rows only (any mesh the FOM takes, at most 40 modes and 256 rows)."""
+        reduced system from the sampled mesh rows only (any mesh the FOM takes, at most 40 modes and 256 rows); with a basis
+        of 41 .. 96 modes (or a rom.HyperWidePodPlan) through bg_hyper_rom_run_wide, at most 512 rows."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                 np.asarray(Phi, dtype=np.float64), projection=projection, E=E, blocked=blocked,

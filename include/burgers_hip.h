@@ -363,6 +363,28 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
                      const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
                      int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_hyper_rom_run_wide -- bg_hyper_rom_run for the larger bases: r <= 96 (meant for r > 40, where bg_hyper_rom_run ends),
+ *   m <= 512 (bg_hyper_rom_wide_limits), 3 <= N <= bg_fom_max_n().  reference: FEM/fem_burgers.py:709-785 with the sums
+ *   over mesh rows restricted and weighted.  Opt-in: burgers_hip/rom.py, pod_prom_run_hyper_wide; pod_prom_run_hyper and the
+ *   facade's hyper= send bases of 41 .. 96 modes here.
+ *   Arguments, semantics and return codes are bg_hyper_rom_run's, with these differences:
+ *   PhiS   [MPAD][3][98], MPAD = m rounded up to 16 (bg_hyper_rom_wide_table_elems(m, r) doubles, 16-byte aligned; 0 for an m
+ *          or r the kernel does not cover), otherwise laid out like bg_hyper_rom_run's table;
+ *   info   the solve is bg_rom_run_wide's guarded pivot-free 96 x 96 elimination and there is no repair kernel: a sample whose
+ *          elimination meets a multiplier above 1 or a zero pivot is marked BG_INFO_NEEDS_PIVOTING, its qhist and iters are
+ *          then undefined, and the caller redoes it (rom.py: the weighted-row library iteration).  BG_OPT_FORCE_PIVOTED
+ *          (tests) marks every sample after its first solve;
+ *   Errors: r > 96 or m > 512: BG_ERR_UNSUPPORTED_R; m > N or PhiS not 16-byte aligned: BG_ERR_BAD_ARG; the rest as
+ *          bg_hyper_rom_run.
+ *   The table streams through LDS 16 sampled rows at a time (two buffers of 37 632 B, over which the 96 x 98 system is parked);
+ *   one workgroup per compute unit (csrc/rom_hyper_wide.hip); workgroup k of G = min(B, CUs) takes the slots k, k + G, ... */
+int bg_hyper_rom_wide_limits(int *max_r, int *max_m);
+long long bg_hyper_rom_wide_table_elems(int m, int r);
+int bg_hyper_rom_run_wide(int N, int B, int r, int m, int nsteps, int projection, const int32_t *rows, const double *xi,
+                          const double *xs, const double *PhiS, const double *q0, const double *u0s, const double *mu1,
+                          const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
+                          int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
 /* bg_hyper_ann_rom_run -- the POD-ANN PROM time loop HYPER-REDUCED: both projections of pod_ann_prom are assembled from m
  *   sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j with the tangent
  *   W = U_p + U_s dN(q_p), y_j = (A W)[i_j], R_j = (A u - b)[i_j], w_j = W[i_j] (Galerkin) or y_j (LSPG).
