@@ -230,6 +230,12 @@ def _check_solver(solver):
 
 
 _host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy())                          # a tensor as the array np.save gets
+_host_matrix = lambda A: np.ascontiguousarray(_host64(A))
+
+
+def _host64(A):
+    """A tensor or an array as a float64 host array, its layout kept."""
+    return np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64)
 _npy = lambda directory, name: np.load(os.path.join(directory, name), allow_pickle=False)  # .npy / .npz, never a pickle
 
 
@@ -310,7 +316,7 @@ class KMeansResult:
         if isinstance(q, torch.Tensor) and q.is_cuda:
             t = q.to(torch.float64).reshape(-1, self.centres.shape[1]).contiguous()
             return _assign(t, self.centres.to(t.device))[0]
-        t = torch.as_tensor(np.atleast_2d(np.asarray(q.detach().cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float64)))
+        t = torch.as_tensor(np.atleast_2d(_host64(q)))
         return _assign(t, torch.as_tensor(self.cluster_centers_))[0].numpy()
 
 
@@ -770,16 +776,34 @@ def nnls_rows(G, d, tau, min_cols, max_cols):
     raise ValueError("row sampling: the active-set iteration did not end")
 
 
-def hyper_rom_limits():
-    """(max_r, max_m) of bg_hyper_rom_run.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_rom_limits", 2)
+def _limits_accessor(symbol, count, doc):
+    def limits():
+        from . import lib as _lib
+        return _lib.limits(symbol, count)
+    limits.__doc__ = f"{doc}.  Needs no device."
+    return limits
 
 
-def hyper_wide_rom_limits():
-    """(max_r, max_m) of bg_hyper_rom_run_wide.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_rom_wide_limits", 2)
+for _name, _symbol, _count, _doc in (
+        ("hyper_rom_limits", "bg_hyper_rom_limits", 2, "(max_r, max_m) of bg_hyper_rom_run"),
+        ("hyper_wide_rom_limits", "bg_hyper_rom_wide_limits", 2, "(max_r, max_m) of bg_hyper_rom_run_wide"),
+        ("hyper_ann_rom_limits", "bg_hyper_ann_rom_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run"),
+        ("hyper_quad_rom_limits", "bg_hyper_quad_rom_limits", 3, "(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run"),
+        ("hyper_local_rom_limits", "bg_hyper_local_rom_limits", 4, "(max_r, max_m, max_mg, max_clusters) of bg_hyper_local_rom_run"),
+        ("hyper_rbf_rom_limits", "bg_hyper_rbf_rom_limits", 5, "(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run")):
+    globals()[_name] = _limits_accessor(_symbol, _count, _doc)
+    globals()[_name].__name__ = globals()[_name].__qualname__ = _name
+
+
+def _sampling_prelude(who, X, projection, runs, tau, stride):
+    """What the five build_*_row_sampling functions open with: the projection in lower case (ValueError unless Galerkin or
+    LSPG), the mesh as a host array, and the refusal of no runs, stride < 1 or tau <= 0 in the name of ``who``."""
+    projection = str(projection).lower()
+    if projection not in ("galerkin", "lspg"):
+        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
+    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
+        raise ValueError(f"{who} takes at least one run, stride >= 1 and tau > 0")
+    return projection, _host64(X)
 
 
 def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None):
@@ -798,17 +822,12 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     pairs -- with three runs and stride 20 the greedy rule has no column left to add at 269, and ``min_rows`` must be given
     (200 rows stayed within 4e-11 of the full PROM there); and the NNLS is host work, about a minute at r = 96 with nine runs
     and stride 10 on eight threads."""
-    projection = str(projection).lower()
-    if projection not in ("galerkin", "lspg"):
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
-    Phi = np.ascontiguousarray(Phi.detach().cpu().numpy() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64)
+    projection, X = _sampling_prelude("build_row_sampling", X, projection, runs, tau, stride)
+    Phi = _host_matrix(Phi)
     N = len(X)
     if Phi.ndim != 2 or Phi.shape[0] != N:
         raise ValueError("Phi must have one row per mesh node")
     r = Phi.shape[1]
-    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
-        raise ValueError("build_row_sampling takes at least one run, stride >= 1 and tau > 0")
     min_rows = min(3 * r, N) if min_rows is None else int(min_rows)
     if max_rows is None:
         narrow_r, narrow_m = hyper_rom_limits()
@@ -842,7 +861,7 @@ def row_sampling_system(X, Phi, runs, dt, projection, E=0.0, supg=True, stride=1
 def _host_runs(runs, N):
     """The runs (hist (N, nT+1), mu1, mu2) of a row-sampling builder as host float64 arrays and floats."""
     for hist, mu1, mu2 in runs:
-        Sn = np.asarray(hist.detach().cpu() if isinstance(hist, torch.Tensor) else hist, dtype=np.float64)
+        Sn = _host64(hist)
         if Sn.ndim != 2 or Sn.shape[0] != N or Sn.shape[1] < 2:
             raise ValueError("every run is (hist (N, nT+1), mu1, mu2)")
         yield Sn, float(mu1), float(mu2)
@@ -855,36 +874,33 @@ def _stack_contributions(blocks, who):
     return G, len(blocks)
 
 
+def _manifold_row_sampling_system(who, X, P, S, lift, tangents, runs, dt, projection, E, supg, stride):
+    """(G, pairs) for a PROM on the manifold u = P q + S lift(q): what ann_, rbf_ and quad_row_sampling_system share.  For
+    every run and every ``stride``-th step n: Q = P^T hist, the pair Un, U0 lifted from q_n, q_{n+1}, and the contributions of
+    all mesh rows with the tangent W = P + dW.  ``lift(q)``: (pairs, n) -> (pairs, k), the coordinates on S;
+    ``tangents(q)``: (pairs, n) -> the (N, n) increments dW, one per pair.  Each model keeps its own arithmetic in the two."""
+    blocks = []
+    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
+        steps = np.arange(0, Sn.shape[1] - 1, int(stride))
+        Q = P.T @ Sn                                                            # (n, nT+1)
+        q_n, q_1 = Q[:, steps].T, Q[:, steps + 1].T
+        Un = P @ q_n.T + S @ lift(q_n).T                                        # on the manifold
+        U0 = P @ q_1.T + S @ lift(q_1).T
+        for dW, u0, un in zip(tangents(q_1), U0.T, Un.T):
+            blocks.append(row_contributions(X, P + dW, u0, un, mu1, mu2, float(dt), projection, float(E), supg))
+    return _stack_contributions(blocks, who)
+
+
 # ---- row sampling for the hyper-reduced POD-ANN PROM (rom.pod_ann_run_hyper, bg_hyper_ann_rom_run) ----
-def hyper_ann_rom_limits():
-    """(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_ann_rom_limits", 6)
-
-
-def _host_matrix(A):
-    return np.ascontiguousarray(A.detach().cpu().numpy() if isinstance(A, torch.Tensor) else A, dtype=np.float64)
-
-
 def ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg=True, stride=10):
     """(G, pairs): the training matrix of build_ann_row_sampling, (pairs n, N).  ``X``, ``U_p``, ``U_s``: host arrays;
     ``model``: the closure, evaluated on the host in float32 (value and Jacobian, as the PROM evaluates them)."""
     import copy
     from . import rom as _rom
-    n = U_p.shape[1]
-    ann = _rom.AnnEvaluator(copy.deepcopy(model).to(device="cpu", dtype=torch.float32).eval(), n, torch.float32)
-    blocks = []
-    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
-        steps = np.arange(0, Sn.shape[1] - 1, int(stride))
-        Qp = U_p.T @ Sn                                                        # (n, nT+1)
-        q_n, q_1 = torch.as_tensor(Qp[:, steps].T.copy()), torch.as_tensor(Qp[:, steps + 1].T.copy())
-        Un = U_p @ Qp[:, steps] + U_s @ ann.forward(q_n).numpy().T              # on the closure manifold
-        U0 = U_p @ Qp[:, steps + 1] + U_s @ ann.forward(q_1).numpy().T
-        dN = ann.jacobian(q_1).numpy()                                          # (pairs, nbar, n)
-        for k in range(len(steps)):
-            W = U_p + U_s @ dN[k]
-            blocks.append(row_contributions(X, W, U0[:, k], Un[:, k], mu1, mu2, float(dt), projection, float(E), supg))
-    return _stack_contributions(blocks, "build_ann_row_sampling")
+    ann = _rom.AnnEvaluator(copy.deepcopy(model).to(device="cpu", dtype=torch.float32).eval(), U_p.shape[1], torch.float32)
+    return _manifold_row_sampling_system(
+        "build_ann_row_sampling", X, U_p, U_s, lambda q: ann.forward(torch.as_tensor(q.copy())).numpy(),
+        lambda q: (U_s @ J for J in ann.jacobian(torch.as_tensor(q.copy())).numpy()), runs, dt, projection, E, supg, stride)
 
 
 def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None,
@@ -902,16 +918,11 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
     and iteration totals within 1 of the full PROM's; the default was therefore left at 3 n.  A closure whose fit is met by few rows may need more: at N = 2049 a random closure ran with
     ``min_rows`` = 120.  ``max_rows`` defaults to the kernel's limit (hyper_ann_rom_limits); needing more is a ValueError.
     Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
-    projection = str(projection).lower()
-    if projection not in ("galerkin", "lspg"):
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    projection, X = _sampling_prelude("build_ann_row_sampling", X, projection, runs, tau, stride)
     U_p, U_s = _host_matrix(U_p), _host_matrix(U_s)
     N = len(X)
     if U_p.ndim != 2 or U_s.ndim != 2 or U_p.shape[0] != N or U_s.shape[0] != N:
         raise ValueError("U_p and U_s must have one row per mesh node")
-    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
-        raise ValueError("build_ann_row_sampling takes at least one run, stride >= 1 and tau > 0")
     min_rows = min(3 * U_p.shape[1], N) if min_rows is None else int(min_rows)
     max_rows = hyper_ann_rom_limits()[4] if max_rows is None else int(max_rows)
     G, pairs = ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E, supg, stride)
@@ -919,12 +930,6 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
 
 
 # ---- row sampling for the hyper-reduced quadratic-manifold PROM (rom.quadratic_run_hyper, bg_hyper_quad_rom_run) ----
-def hyper_quad_rom_limits():
-    """(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_quad_rom_limits", 3)
-
-
 def quad_row_sampling_system(X, Phi, H, runs, dt, projection, E=0.0, stride=10):
     """(G, pairs): the training matrix of build_quad_row_sampling, (pairs n, N).  ``X``, ``Phi`` (N, n), ``H`` (N, n(n+1)/2):
     host arrays; ``projection``: "galerkin" or "lspg".  This stepper has no SUPG term (picard_rows with supg=False)."""
@@ -933,16 +938,9 @@ def quad_row_sampling_system(X, Phi, H, runs, dt, projection, E=0.0, stride=10):
     idx = np.zeros((n, n), dtype=np.int64)
     idx[I, J] = idx[J, I] = np.arange(len(I))
     H3 = H[:, idx] * (np.ones((n, n)) + np.eye(n))                              # (N, n, n): tangent = Phi + H3 . q
-    blocks = []
-    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
-        steps = np.arange(0, Sn.shape[1] - 1, int(stride))
-        Q = Phi.T @ Sn                                                          # (n, nT+1)
-        Un = Phi @ Q[:, steps] + H @ (Q[I][:, steps] * Q[J][:, steps])          # on the manifold
-        U0 = Phi @ Q[:, steps + 1] + H @ (Q[I][:, steps + 1] * Q[J][:, steps + 1])
-        for k, s in enumerate(steps):
-            W = Phi + H3 @ Q[:, s + 1]
-            blocks.append(row_contributions(X, W, U0[:, k], Un[:, k], mu1, mu2, float(dt), projection, float(E), False))
-    return _stack_contributions(blocks, "build_quad_row_sampling")
+    return _manifold_row_sampling_system(
+        "build_quad_row_sampling", X, Phi, H, lambda q: (q.T[I] * q.T[J]).T, lambda q: (H3 @ qk for qk in q), runs, dt, projection,
+        E, False, stride)
 
 
 def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, stride=10, min_rows=None, max_rows=None):
@@ -964,16 +962,11 @@ def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, st
     rows drifted to 2e-3 .. 2e-2 and, LSPG at N = 4096, ended in steps that hit the cap.  For long runs ask for
     ``min_rows`` above the rank.  ``max_rows`` defaults to the kernel's limit (hyper_quad_rom_limits); needing more is a
     ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
-    projection = str(projection).lower()
-    if projection not in ("galerkin", "lspg"):
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    projection, X = _sampling_prelude("build_quad_row_sampling", X, projection, runs, tau, stride)
     Phi, H = _host_matrix(Phi), _host_matrix(H)
     N = len(X)
     if Phi.ndim != 2 or H.ndim != 2 or Phi.shape[0] != N or H.shape != (N, Phi.shape[1] * (Phi.shape[1] + 1) // 2):
         raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2), one row per mesh node")
-    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
-        raise ValueError("build_quad_row_sampling takes at least one run, stride >= 1 and tau > 0")
     min_rows = min(3 * Phi.shape[1], N) if min_rows is None else int(min_rows)
     max_rows = hyper_quad_rom_limits()[1] if max_rows is None else int(max_rows)
     G, pairs = quad_row_sampling_system(X, Phi, H, runs, dt, projection, E, stride)
@@ -981,12 +974,6 @@ def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, st
 
 
 # ---- row sampling for the hyper-reduced local POD PROM (rom.local_prom_run_hyper, bg_hyper_local_rom_run) ----
-def hyper_local_rom_limits():
-    """(max_r, max_m, max_mg, max_clusters) of bg_hyper_local_rom_run.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_local_rom_limits", 4)
-
-
 def _host_local_bases(centres, local_bases, U_global, num_global_modes, N, who):
     """(centres (C, mg), [Phi_0 .. Phi_{C-1}], U_g (N, mg)) as host float64 arrays; ValueError for shapes that cannot be right
     or a centre without a basis."""
@@ -1029,13 +1016,8 @@ def build_local_row_sampling(X, centres, local_bases, U_global, num_global_modes
     and ``num_global_modes`` are local_prom_burgers's arguments; ``runs`` as in build_row_sampling.
     ``min_rows`` defaults to min(3 max_c r_c, N), ``max_rows`` to the kernel's limit (hyper_local_rom_limits); needing more
     is a ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
-    projection = str(projection).lower()
-    if projection not in ("galerkin", "lspg"):
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    projection, X = _sampling_prelude("build_local_row_sampling", X, projection, runs, tau, stride)
     N = len(X)
-    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
-        raise ValueError("build_local_row_sampling takes at least one run, stride >= 1 and tau > 0")
     _, bases, _ = _host_local_bases(centres, local_bases, U_global, num_global_modes, N, "build_local_row_sampling")
     min_rows = min(3 * max(b.shape[1] for b in bases), N) if min_rows is None else int(min_rows)
     max_rows = hyper_local_rom_limits()[1] if max_rows is None else int(max_rows)
@@ -1044,19 +1026,13 @@ def build_local_row_sampling(X, centres, local_bases, U_global, num_global_modes
 
 
 # ---- row sampling for the hyper-reduced POD-RBF PROM (rom.pod_rbf_run_hyper, bg_hyper_rbf_rom_run) ----
-def hyper_rbf_rom_limits():
-    """(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run.  Needs no device."""
-    from . import lib as _lib
-    return _lib.limits("bg_hyper_rbf_rom_limits", 5)
-
-
 def _rbf_host_closure(X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel):
     """(value, jacobian) of the scaled RBF closure on the host in fp64 numpy, for a batch q (P, n): value (P, nbar) and
     jacobian (P, nbar, n).  The closure of rom.RbfClosure (scaling with the dx / dy floors of _rbf_range); training
     arithmetic for build_rbf_row_sampling, not a stepper."""
     kind = _rbf_kind(kernel)
     Xt, Wm = _host_matrix(X_train), _host_matrix(W)
-    vec = lambda v: np.array(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1)
+    vec = lambda v: _host64(v).reshape(-1)
     x_min, y_min = vec(x_min), vec(y_min)
     dx, dy = _rbf_range(x_min, vec(x_max)), _rbf_range(y_min, vec(y_max))
     if Xt.ndim != 2 or Wm.ndim != 2 or Wm.shape != (Xt.shape[0], len(dy)) or Xt.shape[1] != len(dx):
@@ -1095,18 +1071,9 @@ def rbf_row_sampling_system(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_mi
     value, jacobian = _rbf_host_closure(X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel)
     if U_p.shape[1] != np.shape(X_train)[1] or U_s.shape[1] != np.shape(W)[1]:
         raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
-    blocks = []
-    for Sn, mu1, mu2 in _host_runs(runs, len(X)):
-        steps = np.arange(0, Sn.shape[1] - 1, int(stride))
-        Qp = U_p.T @ Sn                                                        # (n, nT+1)
-        q_n, q_1 = Qp[:, steps].T, Qp[:, steps + 1].T
-        Un = U_p @ q_n.T + U_s @ value(q_n).T                                   # on the closure manifold
-        U0 = U_p @ q_1.T + U_s @ value(q_1).T
-        J = jacobian(q_1)                                                       # (pairs, nbar, n)
-        for k in range(len(steps)):
-            Wt = U_p + U_s @ J[k]
-            blocks.append(row_contributions(X, Wt, U0[:, k], Un[:, k], mu1, mu2, float(dt), projection, float(E), supg))
-    return _stack_contributions(blocks, "build_rbf_row_sampling")
+    return _manifold_row_sampling_system(
+        "build_rbf_row_sampling", X, U_p, U_s, value, lambda q: (U_s @ J for J in jacobian(q)), runs, dt, projection, E, supg,
+        stride)
 
 
 def build_rbf_row_sampling(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, runs, dt, projection,
@@ -1128,16 +1095,11 @@ def build_rbf_row_sampling(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min
     (241 nodes, residual 1e-13) LSPG stays within 2e-11.  ``max_rows`` defaults to the kernel's limit
     (hyper_rbf_rom_limits); needing more is a ValueError.
     Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
-    projection = str(projection).lower()
-    if projection not in ("galerkin", "lspg"):
-        raise ValueError("projection must be 'Galerkin' or 'LSPG'")
-    X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+    projection, X = _sampling_prelude("build_rbf_row_sampling", X, projection, runs, tau, stride)
     U_p, U_s = _host_matrix(U_p), _host_matrix(U_s)
     N = len(X)
     if U_p.ndim != 2 or U_s.ndim != 2 or U_p.shape[0] != N or U_s.shape[0] != N:
         raise ValueError("U_p and U_s must have one row per mesh node")
-    if int(stride) < 1 or not (tau > 0.0) or len(runs) < 1:
-        raise ValueError("build_rbf_row_sampling takes at least one run, stride >= 1 and tau > 0")
     max_rows = hyper_rbf_rom_limits()[3] if max_rows is None else int(max_rows)
     min_rows = min(200, N, max_rows) if min_rows is None else int(min_rows)
     G, pairs = rbf_row_sampling_system(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, runs, dt,

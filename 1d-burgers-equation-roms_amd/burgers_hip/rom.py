@@ -538,13 +538,110 @@ def pod_prom_run_long_wide(X, u0, mu1, mu2, dt, nsteps, Phi_or_plan, proj, E=0.0
                           E, tol, max_it, device, options, balance)
 
 
+# ------------------------------------------------ the frame of the hyper-reduced loops
+# A plan holds what its loop reads besides the batch, built once per operands, sampling and mesh: N, m, Xh, the sampling, its
+# projection code, the weights xi, and one of two tables of the sampled rows -- the three-point stencil of every row
+# (_put_stencil: the POD and local loops) or the sorted distinct stencil nodes (_put_table: the closure and quadratic loops).
+_SAMPLING_PROJECTION = "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')"
+_host64 = _pod._host64
+
+
+def _sampling_rows(route, sampling, N, max_m):
+    """(rows int64, xi float64) of a pod.RowSampling on the host, checked against a mesh of N nodes and the loop's ``max_m``:
+    what every hyper plan refuses alike, each a ValueError."""
+    rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
+    xi = _host64(sampling.xi).reshape(-1)
+    m = len(rows)
+    if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
+        raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
+    if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
+        raise ValueError("the weights must be finite and >= 0")
+    if m > max_m:
+        raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+    return rows, xi
+
+
+def _stencil_nodes(route, rows, N, max_nodes):
+    """The sorted distinct stencil nodes of the sampled rows (ValueError beyond ``max_nodes``)."""
+    nodes = np.unique(np.clip(rows[:, None] + np.arange(-1, 2)[None, :], 0, N - 1))
+    if len(nodes) > max_nodes:
+        raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
+    return nodes
+
+
+def _put_table(plan, nodes, rows, xi, sampling, Xh, device):
+    """The table arguments the hyper-reduced closure and quadratic loops share, on ``device``: ``nodes`` (int64, for
+    gathers), ``node``, ``pos``, ``xi``, ``xn``, with ``m``, ``n_nodes``, ``Xh`` and the ``sampling``."""
+    plan.m, plan.n_nodes, plan.Xh, plan.sampling = len(rows), len(nodes), Xh.copy(), sampling
+    plan.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
+    plan.node = plan.nodes.to(torch.int32)
+    plan.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
+    plan.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+    plan.xn = _as_dev(Xh[nodes], device)
+
+
+def _put_stencil(plan, rows, xi, sampling, Xh, device):
+    """The stencil arguments the hyper-reduced POD and local loops share, on ``device``: the gather index ``stencil`` (m, 3)
+    of the nodes i-1, i, i+1 of every sampled row, clipped to the mesh, with ``inside`` marking the slots that exist, their
+    coordinates ``xs``, ``rows`` (int32) and ``xi``, with ``m``, ``Xh`` and the ``sampling``."""
+    plan.m, plan.Xh, plan.sampling = len(rows), Xh.copy(), sampling
+    idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
+    plan.inside = (idx >= 0) & (idx < len(Xh))
+    plan.stencil = idx.clamp(0, len(Xh) - 1)
+    plan.xs = _as_dev(Xh, device)[plan.stencil].contiguous()
+    plan.rows = torch.as_tensor(rows, dtype=torch.int32, device=device)
+    plan.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
+
+
+def _require_orthonormal(U, what, carried):
+    """ValueError unless the host matrix ``U`` is finite with |U^T U - I|_max <= 1e-8: the hyper loops carry their reduced
+    coordinates from step to step instead of re-projecting ``carried``, which is exact only for orthonormal columns."""
+    if not np.isfinite(U).all() or np.abs(U.T @ U - np.eye(U.shape[1])).max() > 1e-8:
+        raise ValueError(f"{what} must have orthonormal columns (to 1e-8): the loop does not re-project {carried}")
+
+
+def _check_hyper_call(plan, Xh, device, proj):
+    """A hyper plan against the call it serves: its device, mesh and projection, each a ValueError.  Returns the device."""
+    device = _lib.require_device(device)
+    if plan.xi.device != device:
+        raise ValueError("the plan was built on another device")
+    if not np.array_equal(plan.Xh, Xh):
+        raise ValueError("the plan was built for another mesh")
+    if plan.projection != proj:
+        raise ValueError("the row sampling was trained for the other projection")
+    return device
+
+
+class _HyperResult:
+    """What the results of the hyper-reduced loops share: the reduced coordinates ``q`` (B, nT+1, r), ``iters``, ``flags``,
+    ``info``, the ``path`` and the ``plan``.  ``hist`` (B, nT+1, N) is decoded on demand by the subclass's ``_decode`` with u0
+    itself in column 0 as in every other loop, and kept; ``snapshots()`` is its (B, N, nT+1) layout."""
+
+    def __init__(self, res, plan, u0d):
+        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
+        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
+
+    @property
+    def hist(self):
+        if self._hist is None:
+            self._hist = self._decode()
+            self._hist[:, 0] = self._u0
+        return self._hist
+
+    def snapshots(self):
+        return FomResult(self.hist, self.iters, self.flags).snapshots()
+
+    @property
+    def newton_steps(self):
+        return int(self.iters.sum().item())
+
+
 class HyperPodPlan:
     """What bg_hyper_rom_run reads besides the batch, built once per basis, sampling and mesh on the device
     (include/burgers_hip.h): the packed stencil table PhiS (rows Phi[i-1], Phi[i], Phi[i+1] of every sampled row, 42 doubles
-    each, zero outside the mesh and beyond r), the stencil coordinates xs (m, 3), the rows and weights, and the gather
-    index of the stencil nodes (``stencil``, clipped to the mesh, with ``inside`` marking the slots that exist).
-    ``sampling``: a pod.RowSampling.  What the shapes and the sampling alone decide is refused before the device is
-    touched; every refusal is a ValueError."""
+    each, zero outside the mesh and beyond r) and _put_stencil's arguments: the stencil coordinates xs (m, 3), the rows and
+    weights, and the gather index of the stencil nodes.  ``sampling``: a pod.RowSampling.  What the shapes and the sampling
+    alone decide is refused before the device is touched; every refusal is a ValueError."""
     entry, limits, table_elems, slab_rows = "bg_hyper_rom_run", "bg_hyper_rom_limits", "bg_hyper_rom_table_elems", 32
 
     def __init__(self, Phi, sampling, X, device):
@@ -559,31 +656,20 @@ class HyperPodPlan:
             raise ValueError(f"Phi must be (N, r) with 1 <= r <= {max_r}")
         if N < route.min_n or N > _limit(route.max_n) or len(Xh) != N:
             raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)} with one row of Phi per mesh node")
-        rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
-        xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
+        rows, xi = _sampling_rows(route, sampling, N, max_m)
         m = len(rows)
-        if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
-            raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
-        if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
-            raise ValueError("the weights must be finite and >= 0")
         elems = getattr(_lib.load(), self.table_elems)(m, r)
-        if m > max_m or elems == 0:
+        if elems == 0:
             raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
+        self.projection = _projection(str(sampling.projection), _SAMPLING_PROJECTION)
         device = _lib.require_device(device)
         self.Phi = _as_dev(Phi, device)
-        self.N, self.r, self.m, self.Xh = N, r, m, Xh.copy()
-        self.projection = PROJ[str(sampling.projection).lower()]
-        self.sampling = sampling
-        idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
-        self.inside = (idx >= 0) & (idx < N)
-        self.stencil = idx.clamp(0, N - 1)
+        self.N, self.r = N, r
+        _put_stencil(self, rows, xi, sampling, Xh, device)
         cols = elems // (3 * ((m + self.slab_rows - 1) // self.slab_rows * self.slab_rows))
         table = torch.zeros((elems // (3 * cols), 3, cols), dtype=torch.float64, device=device)
         table[:m, :, :r] = self.Phi[self.stencil] * self.inside[:, :, None]
         self.PhiS = table
-        self.xs = _as_dev(Xh, device)[self.stencil].contiguous()
-        self.rows = torch.as_tensor(rows, dtype=torch.int32, device=device)
-        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
 
 
 class HyperWidePodPlan(HyperPodPlan):
@@ -593,45 +679,23 @@ class HyperWidePodPlan(HyperPodPlan):
     entry, limits, table_elems, slab_rows = "bg_hyper_rom_run_wide", "bg_hyper_rom_wide_limits", "bg_hyper_rom_wide_table_elems", 16
 
 
-class HyperRomResult:
-    """Result of pod_prom_run_hyper: the reduced coordinates ``q`` (B, nT+1, r), ``iters``, ``flags``, ``info`` and the
-    ``plan``; from the wide loop also ``redone``, the number of samples redone on the host side.  ``hist`` (B, nT+1, N) is
-    decoded on demand, U = Phi q as one batched product with u0 itself in column 0 as in every other loop, and kept;
-    ``snapshots()`` is its (B, N, nT+1) layout."""
+class HyperRomResult(_HyperResult):
+    """Result of pod_prom_run_hyper (_HyperResult); from the wide loop also ``redone``, the number of samples redone on the
+    host side.  The decode is U = Phi q as one batched product."""
 
-    def __init__(self, res, plan, u0d):
-        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
-        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
-
-    @property
-    def hist(self):
-        if self._hist is None:
-            self._hist = torch.matmul(self.q, self.plan.Phi.t())
-            self._hist[:, 0] = self._u0
-        return self._hist
-
-    def snapshots(self):
-        return FomResult(self.hist, self.iters, self.flags).snapshots()
-
-    @property
-    def newton_steps(self):
-        return int(self.iters.sum().item())
+    def _decode(self):
+        return torch.matmul(self.q, self.plan.Phi.t())
 
 
 def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options, balance):
     """pod_prom_run_hyper's narrow loop and pod_prom_run_hyper_wide: the plan (or the sampling to build one from) against the
     call, q0 and u0 at the stencil, the launch, and for a route with ``redo`` the marked samples again on the host side."""
     route = _ROUTES[plan_type.entry]
-    device = _lib.require_device(device)
     Xh = check_mesh(X)
     if isinstance(sampling_or_plan, HyperPodPlan) and type(sampling_or_plan) is not plan_type:
         raise ValueError(f"{route.entry} takes a {plan_type.__name__}")
     plan = sampling_or_plan if isinstance(sampling_or_plan, plan_type) else plan_type(Phi, sampling_or_plan, Xh, device)
-    _check_plan(plan, Xh, device)
-    if not np.array_equal(plan.Xh, Xh):
-        raise ValueError("the plan was built for another mesh")
-    if plan.projection != proj:
-        raise ValueError("the row sampling was trained for the other projection")
+    device = _check_hyper_call(plan, Xh, device, proj)
     u0d, _, mu2d = _batch_inputs(u0, mu1, mu2, plan.N, device)
     q0 = (u0d @ plan.Phi).contiguous()
     u0s = (u0d[:, plan.stencil] * plan.inside).contiguous()
@@ -1037,7 +1101,7 @@ class HyperQuadPlan:
     def __init__(self, Phi, H, sampling, X, device):
         route = _ROUTES["bg_hyper_quad_rom_run"]
         max_n, max_m, max_nodes = _lib.limits("bg_hyper_quad_rom_limits", 3)
-        Ph, Hh = (np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64) for A in (Phi, H))
+        Ph, Hh = _host64(Phi), _host64(H)
         if Ph.ndim != 2 or Ph.shape[1] < 1 or Hh.shape != (Ph.shape[0], Ph.shape[1] * (Ph.shape[1] + 1) // 2):
             raise ValueError("Phi must be (N, n) and H (N, n(n+1)/2)")
         N, n = Ph.shape
@@ -1047,12 +1111,11 @@ class HyperQuadPlan:
         if n > max_n:
             raise ValueError(f"{route.entry} covers n <= {max_n} (got {n})")
         rows, xi = _sampling_rows(route, sampling, N, max_m)
-        if not (np.isfinite(Ph).all() and np.isfinite(Hh).all()) or np.abs(Ph.T @ Ph - np.eye(n)).max() > 1e-8:
-            raise ValueError("Phi must have orthonormal columns (to 1e-8): the loop does not re-project Phi^T u^n")
-        if np.abs(Ph.T @ Hh).max() > 1e-8:
+        _require_orthonormal(Ph, "Phi", "Phi^T u^n")
+        if not np.isfinite(Hh).all() or np.abs(Ph.T @ Hh).max() > 1e-8:
             raise ValueError("Phi^T H must vanish (to 1e-8): the loop does not re-project Phi^T u^n")
         nodes = _stencil_nodes(route, rows, N, max_nodes)
-        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        self.projection = _projection(str(sampling.projection), _SAMPLING_PROJECTION)
         device = _lib.require_device(device)
         self.N, self.n = N, n
         self.Phi, self.H = _as_dev(Ph, device), _as_dev(Hh, device)
@@ -1062,30 +1125,13 @@ class HyperQuadPlan:
         assert (self.Phif.numel(), self.H3f.numel()) == (L.bg_hyper_quad_rom_phif_elems(len(nodes)), L.bg_hyper_quad_rom_h3f_elems(len(nodes)))
 
 
-class HyperQuadRomResult:
-    """Result of quadratic_run_hyper: the reduced coordinates ``q`` (B, nT+1, n) (column 0: Phi^T u0), ``iters``, ``flags``,
-    ``info``, the ``plan`` and the ``path``.  ``hist`` (B, nT+1, N) is decoded on demand, U = Phi q + H Q(q) with the decode
-    of the host-driven route and u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
-    (B, N, nT+1) layout."""
+class HyperQuadRomResult(_HyperResult):
+    """Result of quadratic_run_hyper (_HyperResult; column 0 of ``q``: Phi^T u0).  The decode is U = Phi q + H Q(q), that of
+    the host-driven route."""
 
-    def __init__(self, res, plan, u0d):
-        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
-        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
-
-    @property
-    def hist(self):
-        if self._hist is None:
-            B, cols, n = self.q.shape
-            self._hist = _quad_decoder(self.plan.Phi, self.plan.H, B * cols)(self.q.reshape(B * cols, n)).reshape(B, cols, -1)
-            self._hist[:, 0] = self._u0
-        return self._hist
-
-    def snapshots(self):
-        return FomResult(self.hist, self.iters, self.flags).snapshots()
-
-    @property
-    def newton_steps(self):
-        return int(self.iters.sum().item())
+    def _decode(self):
+        B, cols, n = self.q.shape
+        return _quad_decoder(self.plan.Phi, self.plan.H, B * cols)(self.q.reshape(B * cols, n)).reshape(B, cols, -1)
 
 
 def quadratic_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, H, sampling_or_plan, proj, E=0.0, newton_tol=1e-6, newton_itmax=25,
@@ -1100,13 +1146,7 @@ def quadratic_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, H, sampling_or_plan, p
     Nothing is synchronised.  Returns a HyperQuadRomResult."""
     Xh = check_mesh(X)
     plan = sampling_or_plan if isinstance(sampling_or_plan, HyperQuadPlan) else HyperQuadPlan(Phi, H, sampling_or_plan, Xh, device)
-    device = _lib.require_device(device)
-    if plan.Phi.device != device:
-        raise ValueError("the plan was built on another device")
-    if not np.array_equal(plan.Xh, Xh):
-        raise ValueError("the plan was built for another mesh")
-    if plan.projection != proj:
-        raise ValueError("the row sampling was trained for the other projection")
+    device = _check_hyper_call(plan, Xh, device, proj)
     u0d, _, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
     q0 = _project_rows(u0d, plan.Phi)
     u0n = u0d[:, plan.nodes].contiguous()
@@ -1480,47 +1520,13 @@ def pod_ann_run_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E=0.0, 
                             X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, proj, E, tol, max_it, device, options, plan, balance)
 
 
-def _sampling_rows(route, sampling, N, max_m):
-    """(rows int64, xi float64) of a pod.RowSampling on the host, checked against a mesh of N nodes and the loop's ``max_m``:
-    what HyperAnnPlan, HyperRbfPlan and HyperQuadPlan refuse alike, each a ValueError."""
-    rows = np.asarray(sampling.rows.cpu() if isinstance(sampling.rows, torch.Tensor) else sampling.rows).astype(np.int64).reshape(-1)
-    xi = np.asarray(sampling.xi.cpu() if isinstance(sampling.xi, torch.Tensor) else sampling.xi, dtype=np.float64).reshape(-1)
-    m = len(rows)
-    if m < 1 or m > N or len(xi) != m or rows[0] < 0 or rows[-1] >= N or not np.all(np.diff(rows) > 0):
-        raise ValueError("the sampled rows must be ascending, distinct and in [0, N), one weight each")
-    if not (np.isfinite(xi).all() and (xi >= 0.0).all()):
-        raise ValueError("the weights must be finite and >= 0")
-    if m > max_m:
-        raise ValueError(f"{route.entry} covers at most {max_m} sampled rows (got {m})")
-    return rows, xi
-
-
-def _stencil_nodes(route, rows, N, max_nodes):
-    """The sorted distinct stencil nodes of the sampled rows (ValueError beyond ``max_nodes``)."""
-    nodes = np.unique(np.clip(rows[:, None] + np.arange(-1, 2)[None, :], 0, N - 1))
-    if len(nodes) > max_nodes:
-        raise ValueError(f"{route.entry} covers at most {max_nodes} stencil nodes (got {len(nodes)})")
-    return nodes
-
-
-def _put_table(plan, nodes, rows, xi, sampling, Xh, device):
-    """The table arguments the hyper-reduced closure and quadratic loops share, on ``device``: ``nodes`` (int64, for
-    gathers), ``node``, ``pos``, ``xi``, ``xn``, with ``m``, ``n_nodes``, ``Xh`` and the ``sampling``."""
-    plan.m, plan.n_nodes, plan.Xh, plan.sampling = len(rows), len(nodes), Xh.copy(), sampling
-    plan.nodes = torch.as_tensor(nodes, dtype=torch.int64, device=device)
-    plan.node = plan.nodes.to(torch.int32)
-    plan.pos = torch.as_tensor(np.searchsorted(nodes, rows), dtype=torch.int32, device=device)
-    plan.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
-    plan.xn = _as_dev(Xh[nodes], device)
-
-
 class _HyperClosurePlan:
     """What HyperAnnPlan and HyperRbfPlan share: the checks of bases, mesh and sampling on the host, and the table of the
     sorted distinct stencil nodes of the sampled rows on the device (include/burgers_hip.h, bg_hyper_ann_rom_run)."""
 
     def _check_sizes(self, route, U_p, U_s, sampling, X, max_n, max_nbar, max_m):
         """Bases, mesh and sampling against each other and the limits; returns the host copies (Up, Us, Xh, rows, xi)."""
-        Up, Us = (np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64) for A in (U_p, U_s))
+        Up, Us = _host64(U_p), _host64(U_s)
         if Up.ndim != 2 or Us.ndim != 2 or Up.shape[0] != Us.shape[0] or Up.shape[1] < 1 or Us.shape[1] < 1:
             raise ValueError("U_p and U_s must be (N, n) and (N, nbar)")
         N, n, nbar = Up.shape[0], Up.shape[1], Us.shape[1]
@@ -1538,10 +1544,9 @@ class _HyperClosurePlan:
         [n + nbar][nodes].  Returns the device."""
         N, n, nbar = Up.shape[0], Up.shape[1], Us.shape[1]
         U = np.concatenate([Up, Us], axis=1)
-        if not np.isfinite(U).all() or np.abs(U.T @ U - np.eye(n + nbar)).max() > 1e-8:
-            raise ValueError("[U_p U_s] must have orthonormal columns (to 1e-8): the loop does not re-project U_p^T u^n")
+        _require_orthonormal(U, "[U_p U_s]", "U_p^T u^n")
         nodes = _stencil_nodes(route, rows, N, max_nodes)
-        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        self.projection = _projection(str(sampling.projection), _SAMPLING_PROJECTION)
         device = _lib.require_device(device)
         self.N, self.n, self.nbar = N, n, nbar
         self.wg_per_cu = workgroups_per_cu(len(nodes))
@@ -1579,31 +1584,18 @@ class HyperAnnPlan(_HyperClosurePlan):
         self.model = _ann_model_pack(layers, device)
 
 
-class HyperClosureRomResult:
-    """Result of pod_ann_run_hyper and pod_rbf_run_hyper: the primary coordinates ``q`` (B, nT+1, n) and the closure values
-    ``q_s`` (B, nT+1, nbar) of every step's decode (column 0: U_p^T u0, and zeros: no closure value belongs to u0),
-    ``iters``, ``flags``, ``info`` and the ``plan``.  ``hist``
-    (B, nT+1, N) is decoded on demand, U = U_p q + U_s q_s as one batched product -- the kernel's own decode, not a second
-    evaluation of the closure -- with u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
-    (B, N, nT+1) layout."""
+class HyperClosureRomResult(_HyperResult):
+    """Result of pod_ann_run_hyper and pod_rbf_run_hyper (_HyperResult): ``q`` holds the primary coordinates (column 0:
+    U_p^T u0) and ``q_s`` (B, nT+1, nbar) the closure values of every step's decode (column 0: zeros, no closure value belongs
+    to u0).  The decode is U = U_p q + U_s q_s as one batched product -- the kernel's own decode, not a second evaluation of
+    the closure."""
 
     def __init__(self, res, plan, u0d, q_s):
-        self.q, self.q_s, self.iters, self.flags, self.info, self.path = res.hist, q_s, res.iters, res.flags, res.info, res.path
-        self.plan, self._keep, self._u0, self._hist = plan, res._keep, u0d, None
+        super().__init__(res, plan, u0d)
+        self.q_s = q_s
 
-    @property
-    def hist(self):
-        if self._hist is None:
-            self._hist = torch.matmul(torch.cat([self.q, self.q_s], dim=2), torch.cat([self.plan.Up, self.plan.Us], dim=1).t())
-            self._hist[:, 0] = self._u0
-        return self._hist
-
-    def snapshots(self):
-        return FomResult(self.hist, self.iters, self.flags).snapshots()
-
-    @property
-    def newton_steps(self):
-        return int(self.iters.sum().item())
+    def _decode(self):
+        return torch.matmul(torch.cat([self.q, self.q_s], dim=2), torch.cat([self.plan.Up, self.plan.Us], dim=1).t())
 
 
 HyperAnnRomResult = HyperClosureRomResult        # the name pod_ann_run_hyper's result has had
@@ -1645,13 +1637,7 @@ def _hyper_closure_run(route, plan, Xh, u0, mu1, mu2, nsteps, proj, device, opti
     """What pod_ann_run_hyper and pod_rbf_run_hyper share: the plan against the call (device, mesh, projection), q0 and u0
     at the table nodes, the launch through _device_loop and the result.  ``head(N, B, nsteps, proj, q0, u0n, inputs)``: the
     entry point's argument list up to max_it; options, qhist, qshist and the other outputs follow it."""
-    device = _lib.require_device(device)
-    if plan.Up.device != device:
-        raise ValueError("the plan was built on another device")
-    if not np.array_equal(plan.Xh, Xh):
-        raise ValueError("the plan was built for another mesh")
-    if plan.projection != proj:
-        raise ValueError("the row sampling was trained for the other projection")
+    device = _check_hyper_call(plan, Xh, device, proj)
     u0d, mu1d, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
     q0 = _project_rows(u0d, plan.Up)
     u0n = u0d[:, plan.nodes].contiguous()
@@ -1885,13 +1871,12 @@ class HyperRbfPlan(_HyperClosurePlan):
         max_n, max_nbar, max_ns, max_m, max_nodes = _lib.limits("bg_hyper_rbf_rom_limits", 5)
         Up, Us, Xh, rows, xi = self._check_sizes(route, U_p, U_s, sampling, X, max_n, max_nbar, max_m)
         n, nbar = Up.shape[1], Us.shape[1]
-        host = lambda a: np.array(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
-        Xt, Wm = host(X_train), host(W)
+        Xt, Wm = _host64(X_train), _host64(W)
         if Xt.ndim != 2 or Wm.ndim != 2 or Xt.shape[1] != n or Wm.shape != (Xt.shape[0], nbar) or Xt.shape[0] < 1:
             raise ValueError("X_train must be (Ns, n) and W (Ns, nbar) for the n, nbar of U_p, U_s")
         scal = {}
         for name, v, k in (("x_min", x_min, n), ("x_max", x_max, n), ("y_min", y_min, nbar), ("y_max", y_max, nbar)):
-            scal[name] = host(v)
+            scal[name] = _host64(v)
             if scal[name].shape != (k,):
                 raise ValueError(f"{name} must have {k} entries")
         if Xt.shape[0] > max_ns:
@@ -2110,8 +2095,8 @@ def local_prom_run_long(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_glo
 class HyperLocalPlan:
     """What bg_hyper_local_rom_run reads besides the batch, built once per clustering, sampling and mesh on the device
     (include/burgers_hip.h): the stack PhiS of HyperPodPlan's stencil tables, one per cluster; ``trans`` [C][C][40][40] =
-    Phi_c^T Phi_p and ``pick`` [C][mg][40] = U_g^T Phi_p, zero padded; the widths, centres, rows, weights and stencil
-    coordinates; the zero-padded bases ``stack`` (C, N, rmax) and ``UgT`` for the projections of u0 and the decode.
+    Phi_c^T Phi_p and ``pick`` [C][mg][40] = U_g^T Phi_p, zero padded; the widths and centres, and _put_stencil's
+    arguments; the zero-padded bases ``stack`` (C, N, rmax) and ``UgT`` for the projections of u0 and the decode.
     ``sampling``: a pod.RowSampling (pod.build_local_row_sampling), one for all clusters, row 0 among its rows.  Everything the
     shapes, the sampling and the bases decide is refused with a ValueError before the device is touched -- also a basis with
     |Phi_c^T Phi_c - I|_max > 1e-8: the loop carries q from step to step and crosses from one basis to the next by
@@ -2120,55 +2105,43 @@ class HyperLocalPlan:
     def __init__(self, centres, local_bases, U_global, num_global_modes, sampling, X, device):
         route = _ROUTES["bg_hyper_local_rom_run"]
         max_r, max_m, max_mg, max_c = _lib.limits("bg_hyper_local_rom_limits", 4)
-        host = lambda A: np.asarray(A.detach().cpu() if isinstance(A, torch.Tensor) else A, dtype=np.float64)
         Xh = check_mesh(X)
         N, mg = len(Xh), int(num_global_modes)
-        cen, Ug = host(centres), host(U_global)
-        if cen.ndim != 2 or cen.shape[0] < 1 or cen.shape[1] != mg or mg < 1:
-            raise ValueError(f"centres must be (C, m) with m = {mg} >= 1")
-        C = cen.shape[0]
-        if Ug.ndim != 2 or Ug.shape[0] != N or Ug.shape[1] < mg:
-            raise ValueError(f"U_global must be (N, >= m) with N = {N}, m = {mg}")
+        cen, bases, Ug = _pod._host_local_bases(centres, local_bases, U_global, mg, N, route.entry)
+        C = len(cen)
+        if C < 1 or mg < 1:
+            raise ValueError(f"centres must be (C, m) with C >= 1 and m = {mg} >= 1")
         if N < route.min_n or N > _limit(route.max_n):
             raise ValueError(f"{route.entry} covers {route.min_n} <= N <= {_limit(route.max_n)}")
-        missing = [c for c in range(C) if c not in local_bases]
-        if missing:
-            raise ValueError(f"centre {missing[0]} has no local basis")
-        bases = [host(local_bases[c]) for c in range(C)]
         for c, b in enumerate(bases):
-            if b.ndim != 2 or b.shape[0] != N:
-                raise ValueError(f"local basis {c} must have one row per mesh node (N = {N})")
-            if b.shape[1] < 1 or b.shape[1] > max_r:
-                raise ValueError(f"local basis {c} must have 1 .. {max_r} columns (got {b.shape[1]})")
+            if b.shape[1] > max_r:
+                raise ValueError(f"local basis {c} must have at most {max_r} columns (got {b.shape[1]})")
         if mg > max_mg or C > max_c:
             raise ValueError(f"beyond bg_hyper_local_rom_limits: m {mg} (<= {max_mg}), {C} centres (<= {max_c})")
         rows, xi = _sampling_rows(route, sampling, N, max_m)
         if rows[0] != 0:
             raise ValueError("row 0 (the Dirichlet row) must be among the sampled rows")
-        self.projection = _projection(str(sampling.projection), "the row sampling's projection must be 'galerkin' or 'lspg' (got '{}')")
+        self.projection = _projection(str(sampling.projection), _SAMPLING_PROJECTION)
         for c, b in enumerate(bases):
-            if not np.isfinite(b).all() or np.abs(b.T @ b - np.eye(b.shape[1])).max() > 1e-8:
-                raise ValueError(f"local basis {c} must have orthonormal columns (to 1e-8): the loop does not re-project Phi^T u^n")
-        if not (np.isfinite(cen).all() and np.isfinite(Ug[:, :mg]).all()):
+            _require_orthonormal(b, f"local basis {c}", "Phi^T u^n")
+        if not (np.isfinite(cen).all() and np.isfinite(Ug).all()):
             raise ValueError("centres and U_global must be finite")
         m = len(rows)
         elems = _lib.load().bg_hyper_local_rom_table_elems(C, m)
         if elems == 0:
             raise ValueError(f"{route.entry} does not cover C = {C}, m = {m}")
         device = _lib.require_device(device)
-        self.N, self.C, self.mg, self.m, self.Xh, self.sampling = N, C, mg, m, Xh.copy(), sampling
+        self.N, self.C, self.mg = N, C, mg
+        _put_stencil(self, rows, xi, sampling, Xh, device)
         self.widths_host = [b.shape[1] for b in bases]
         self.rmax = max(self.widths_host)
         R = max_r                                                                # the padded width of trans and pick
         self.stack = torch.zeros((C, N, self.rmax), dtype=torch.float64, device=device)
         for c, b in enumerate(bases):
             self.stack[c, :, :b.shape[1]] = _as_dev(b, device)
-        self.UgT = _as_dev(Ug[:, :mg], device).t().contiguous()
+        self.UgT = _as_dev(Ug, device).t().contiguous()
         self.centres = _as_dev(cen, device).contiguous()
         self.widths = torch.as_tensor(self.widths_host, dtype=torch.int32, device=device)
-        idx = torch.as_tensor(rows, device=device)[:, None] + torch.arange(-1, 2, device=device)[None, :]      # (m, 3)
-        self.inside = (idx >= 0) & (idx < N)
-        self.stencil = idx.clamp(0, N - 1)
         mpad = (m + 31) // 32 * 32
         cols = elems // (C * 3 * mpad)
         self.PhiS = torch.zeros((C, mpad, 3, cols), dtype=torch.float64, device=device)
@@ -2181,10 +2154,6 @@ class HyperLocalPlan:
         self.trans[:, :, :self.rmax, :self.rmax] = gram
         self.pick = torch.zeros((C, mg, R), dtype=torch.float64, device=device)
         self.pick[:, :, :self.rmax] = torch.matmul(self.UgT[None], self.stack)
-        self.xs = _as_dev(Xh, device)[self.stencil].contiguous()
-        self.rows = torch.as_tensor(rows, dtype=torch.int32, device=device)
-        self.xi = torch.as_tensor(xi, dtype=torch.float64, device=device)
-
 
     def project(self, u0d):
         """(qg0 (B, mg), pu0 (B, C, rmax)) = U_g^T u0 and Phi_c^T u0 for every cluster, by _project_rows in chunks of a size
@@ -2193,37 +2162,25 @@ class HyperLocalPlan:
         return out[:, :self.mg].contiguous(), out[:, self.mg:].reshape(u0d.shape[0], self.C, self.rmax).contiguous()
 
 
-class HyperLocalRomResult:
-    """Result of local_prom_run_hyper: the reduced coordinates ``q`` (B, nT+1, rmax) -- entry n + 1 in the basis of
-    ``clusters[:, n]``, entry 0 the projection of u0 on the first cluster's basis -- ``clusters`` (B, nT) int32, ``iters``,
-    ``flags``, ``info``, the ``plan`` and the ``path``.  ``hist`` (B, nT+1, N) is decoded on demand, column n + 1 =
-    Phi_{clusters[:, n]} q[:, n + 1] with u0 itself in column 0 as in every other loop, and kept; ``snapshots()`` is its
-    (B, N, nT+1) layout."""
+class HyperLocalRomResult(_HyperResult):
+    """Result of local_prom_run_hyper (_HyperResult): entry n + 1 of ``q`` (B, nT+1, rmax) is in the basis of
+    ``clusters[:, n]`` (B, nT) int32, entry 0 the projection of u0 on the first cluster's basis.  The decode is column n + 1 =
+    Phi_{clusters[:, n]} q[:, n + 1]."""
 
     def __init__(self, res, plan, u0d, clusters):
-        self.q, self.iters, self.flags, self.info, self.path = res.hist, res.iters, res.flags, res.info, res.path
-        self.plan, self.clusters, self._keep, self._u0, self._hist = plan, clusters, res._keep, u0d, None
+        super().__init__(res, plan, u0d)
+        self.clusters = clusters
 
-    @property
-    def hist(self):
-        if self._hist is None:
-            B, cols, _ = self.q.shape
-            self._hist = torch.empty((B, cols, self.plan.N), dtype=torch.float64, device=self.q.device)
-            self._hist[:, 0] = self._u0
-            if cols > 1:
-                cl = self.clusters.long()
-                for c in range(self.plan.C):                                     # one product per cluster over its (sample, step) pairs
-                    b, n = (cl == c).nonzero(as_tuple=True)
-                    if b.numel():
-                        self._hist[b, n + 1] = self.q[b, n + 1] @ self.plan.stack[c].t()
-        return self._hist
-
-    def snapshots(self):
-        return FomResult(self.hist, self.iters, self.flags).snapshots()
-
-    @property
-    def newton_steps(self):
-        return int(self.iters.sum().item())
+    def _decode(self):
+        B, cols, _ = self.q.shape
+        hist = torch.empty((B, cols, self.plan.N), dtype=torch.float64, device=self.q.device)
+        if cols > 1:
+            cl = self.clusters.long()
+            for c in range(self.plan.C):                                         # one product per cluster over its (sample, step) pairs
+                b, n = (cl == c).nonzero(as_tuple=True)
+                if b.numel():
+                    hist[b, n + 1] = self.q[b, n + 1] @ self.plan.stack[c].t()
+        return hist
 
 
 def local_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_global, num_global_modes, sampling_or_plan, proj,
@@ -2240,13 +2197,7 @@ def local_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, centers, local_bases, U_gl
     Xh = check_mesh(X)
     plan = sampling_or_plan if isinstance(sampling_or_plan, HyperLocalPlan) else \
         HyperLocalPlan(centers, local_bases, U_global, num_global_modes, sampling_or_plan, Xh, device)
-    device = _lib.require_device(device)
-    if plan.stack.device != device:
-        raise ValueError("the plan was built on another device")
-    if not np.array_equal(plan.Xh, Xh):
-        raise ValueError("the plan was built for another mesh")
-    if plan.projection != proj:
-        raise ValueError("the row sampling was trained for the other projection")
+    device = _check_hyper_call(plan, Xh, device, proj)
     u0d, _, _ = _batch_inputs(u0, mu1, mu2, plan.N, device)
     B = u0d.shape[0]
     qg0, pu0 = plan.project(u0d)

@@ -259,6 +259,8 @@ def test_plan_reuse_refusals_and_the_empty_batch(hip, monkeypatch):
         with pytest.raises(ValueError):
             rom.HyperPodPlan(Phi, bad, X, dev)
     with pytest.raises(ValueError):
+        rom.HyperPodPlan(Phi, pod.RowSampling(np.arange(N, dtype=np.int32), np.ones(N), "petrov", 0.0, 0, 0.0), X, dev)      # an unknown projection
+    with pytest.raises(ValueError):
         rom.HyperPodPlan(np.concatenate([Phi] * 3, axis=1)[:, :41], all_rows(N, "Galerkin"), X, dev)        # one column too many
     X3, _ = mesh(300)
     with pytest.raises(ValueError):

@@ -251,6 +251,8 @@ def test_plan_reuse_refusals_and_the_empty_batch(hip, monkeypatch):
         with pytest.raises(ValueError):
             rom.HyperWidePodPlan(Phi, bad, X, dev)
     with pytest.raises(ValueError):
+        rom.HyperWidePodPlan(Phi, pod.RowSampling(np.arange(N, dtype=np.int32), np.ones(N), "petrov", 0.0, 0, 0.0), X, dev)      # an unknown projection
+    with pytest.raises(ValueError):
         rom.HyperWidePodPlan(np.zeros((N, 97)), unit_rows(np.arange(N), "Galerkin"), X, dev)                      # one column too many
     X5, _ = mesh(513)
     with pytest.raises(ValueError):

@@ -1,6 +1,7 @@
 """What at least three of the tools/time_*.py scripts share: the import path, the 3 x 3 training grid and its snapshots
-built on the device, the bench's parameter draw, the warm-up plus event-timed repetitions, the tail of the report
-line, and the decoder of the phase-clock record.  What a script measures, its options and its FLOP count stay in the script."""
+built on the device with the list of training runs split from them, the bench's parameter draw, the warm-up plus
+event-timed repetitions of one route or of several alternately, the tail of the report line, and the decoder of the
+phase-clock record.  What a script measures, its options and its FLOP count stay in the script."""
 import collections
 import os
 import sys
@@ -11,14 +12,22 @@ sys.path[:0] = [REPO, os.path.join(REPO, "1d-burgers-equation-roms_amd")]
 import numpy as np, torch
 
 PEAK = 78.6e12                                             # fp64 matrix peak of one MI355X, FLOP/s
+TRAIN_MU1, TRAIN_MU2 = np.repeat(np.linspace(4.25, 5.5, 3), 3), np.tile(np.linspace(0.015, 0.03, 3), 3)      # the 3 x 3 training grid
 
 
 def training_snapshots(N, dt, steps=200):
     """(X, S): the uniform mesh and the snapshot matrix of the FOM runs of the 3 x 3 training grid, on the device."""
     from burgers_hip import fom, pod
     X = np.linspace(0, 100, N)
-    mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-    return X, pod.snapshot_matrix(fom.fom_run(X, np.ones(N), mu1t, mu2t, dt, steps).hist).contiguous()
+    return X, pod.snapshot_matrix(fom.fom_run(X, np.ones(N), TRAIN_MU1, TRAIN_MU2, dt, steps).hist).contiguous()
+
+
+def training_list(S, host=False):
+    """The ``runs`` of the pod.build_*_row_sampling functions, (hist (N, nT+1), mu1, mu2) per training point, split from the
+    snapshot matrix ``S`` of training_snapshots; ``host``: every hist as a host copy."""
+    T1 = S.shape[1] // 9
+    hists = [S[:, k * T1:(k + 1) * T1] for k in range(9)]
+    return [(h.cpu() if host else h, TRAIN_MU1[k], TRAIN_MU2[k]) for k, h in enumerate(hists)]
 
 
 def draw(B, seed=20251121):
@@ -36,6 +45,22 @@ def time_runs(run, reps=1):
         e0.record(); res = run(); e1.record(); torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
     return ms, res
+
+
+def time_alternately(runs, reps):
+    """The routes ``runs`` {name: callable} timed alternately in one process: one warm-up of each (code objects, library
+    handles, allocator), then ``reps`` rounds with every call between HIP events.  Returns (rates, last): the
+    sample-Newton-steps/s of every repetition and the last result, by name."""
+    rates, last = {k: [] for k in runs}, {}
+    for f in runs.values():
+        f(); torch.cuda.synchronize()
+    for _ in range(reps):
+        for k, f in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
+            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    return rates, last
 
 
 def rates_of(ms, res):

@@ -12,7 +12,7 @@ full route's fastest, and the worst per-sample rel-L2 of the hyper-reduced run a
 usage: python tools/time_hyper_ann_rom.py [--host] [--n 1024] [--batch 2048] [--steps 12] [--dt DT] [--tau 1e-4] [--min-rows M] [--reps 3]"""
 import argparse, json, os
 import numpy as np, torch
-from _timing import GOLDEN, draw, training_snapshots
+from _timing import GOLDEN, draw, time_alternately, training_list, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--host", action="store_true"); ap.add_argument("--n", type=int, default=1024)
 ap.add_argument("--batch", type=int, default=2048); ap.add_argument("--steps", type=int, default=12)
@@ -44,9 +44,7 @@ for i in range(6):
                 lin.weight.mul_(3.0); lin.bias.mul_(3.0)
     layers += [lin] + ([nn.ELU()] if i < 5 else [])
 model = nn.Sequential(*layers).eval()
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-T1 = S.shape[1] // 9
-train = [(S[:, k * T1:(k + 1) * T1].cpu(), mu1t[k], mu2t[k]) for k in range(9)]
+train = training_list(S, host=True)
 mu1, mu2 = draw(a.batch)
 min_rows = a.min_rows if a.min_rows is not None else (None if N == 512 else 120)
 worst = lambda x, y: float(((x.flatten(1) - y.flatten(1)).norm(dim=1) / y.flatten(1).norm(dim=1)).max())
@@ -61,15 +59,7 @@ for proj in ("Galerkin", "LSPG"):
     runs["decoded"] = decoded
     runs["full"] = lambda: rom.pod_ann_run(X, np.ones(N), mu1, mu2, dt, a.steps, Up, Us, model, projection=proj,
                                            fused=not a.host and N <= 512)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     hy, full = last["hyper"], last["full"]
     fmt = lambda vs: [float(f"{v:.4g}") for v in vs]
     print(json.dumps({

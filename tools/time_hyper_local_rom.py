@@ -13,8 +13,8 @@ full loop's fastest, the worst per-sample rel-L2 against the full local PROM ove
 of samples whose cluster path differs.
 usage: python tools/time_hyper_local_rom.py [--batch 1024] [--steps 40] [--n 1024] [--dt 0.025] [--tau 1e-4] [--reps 3] [--host]"""
 import argparse, json
-import numpy as np, torch
-from _timing import draw, training_snapshots
+import numpy as np
+from _timing import draw, time_alternately, training_list, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--n", type=int, default=1024); ap.add_argument("--dt", type=float, default=0.025)
@@ -33,9 +33,7 @@ bases = {}
 for c, w in enumerate(WIDTHS):
     members = S[:, d2[c] <= 1.5 ** 2 * d2.min(0).values].contiguous()
     bases[c] = pod.thin_svd(members)[0][:, :w].contiguous()
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-T1 = S.shape[1] // 9
-train = [(S[:, k * T1:(k + 1) * T1].cpu(), mu1t[k], mu2t[k]) for k in range(9)]
+train = training_list(S, host=True)
 mu1, mu2 = draw(a.batch)
 full_plan = rom.LocalPodPlan(centres, bases, Ug, MG, N, Ug.device, long_mesh=True) if long_ok else None
 assert full_plan is None or full_plan.ok, full_plan.reason
@@ -56,15 +54,7 @@ for proj in ("Galerkin", "LSPG"):
                                                        plan=full_plan)
     if a.host:
         runs["host"] = lambda: rom.local_prom_run(X, np.ones(N), mu1, mu2, a.dt, a.steps, centres, bases, Ug, MG, projection=proj)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     hy = last["hyper"]
     fmt = lambda v: [float(f"{x:.4g}") for x in v]
     out = {"projection": proj, "N": N, "batch": a.batch, "steps": a.steps, "dt": a.dt, "tau": a.tau, "rows": s.m,

@@ -11,8 +11,8 @@ repetitions; the hyper loop also with its on-demand decode included), whether th
 full route's fastest, and the worst per-sample rel-L2 of the hyper-reduced run against the full PROM.
 usage: python tools/time_hyper_quad_rom.py [--host] [--n 1024] [--r 40] [--batch 1024] [--steps 40] [--dt DT] [--tau 1e-5] [--min-rows M] [--reps 3]"""
 import argparse, json
-import numpy as np, torch
-from _timing import draw, training_snapshots
+import numpy as np
+from _timing import draw, time_alternately, training_list, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--host", action="store_true"); ap.add_argument("--n", type=int, default=1024)
 ap.add_argument("--r", type=int, default=40); ap.add_argument("--batch", type=int, default=1024)
@@ -27,9 +27,7 @@ X, S = training_snapshots(N, dt)
 S = S.cpu()
 Phi, H, _ = pod.build_quadratic_manifold(S, a.r, alpha=1e-2)
 Phi, H = Phi.contiguous(), H.contiguous()
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-T1 = S.shape[1] // 9
-train = [(S[:, k * T1:(k + 1) * T1], mu1t[k], mu2t[k]) for k in range(9)]
+train = training_list(S)
 mu1, mu2 = draw(a.batch)
 long_mesh = not a.host and 512 < N <= 1024
 full_plan = rom.QuadLongPlan(Phi, H, "cuda") if long_mesh else None           # built once per (Phi, H), outside the timing
@@ -45,15 +43,7 @@ for proj in ("Galerkin", "LSPG"):
     runs["decoded"] = decoded
     runs["full"] = lambda: rom.quadratic_run(X, np.ones(N), mu1, mu2, dt, a.steps, Phi, H, projection=proj,
                                              fused=not a.host, long_mesh=long_mesh, plan=full_plan)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     hy, full = last["hyper"], last["full"]
     fmt = lambda vs: [float(f"{v:.4g}") for v in vs]
     print(json.dumps({

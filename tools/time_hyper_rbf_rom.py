@@ -14,7 +14,7 @@ hyper-reduced run against the full PROM.
 usage: python tools/time_hyper_rbf_rom.py [--host] [--n 1024] [--batch 1024] [--steps 12] [--dt DT] [--tau 1e-4] [--min-rows M] [--reps 3]"""
 import argparse, json
 import numpy as np, torch
-from _timing import draw, training_snapshots
+from _timing import draw, time_alternately, training_list, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--host", action="store_true"); ap.add_argument("--n", type=int, default=1024)
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=12)
@@ -35,9 +35,7 @@ Xt, Ys = scale(Qp, x_min, x_max), scale(Qs, y_min, y_max)
 K = 1.0 / np.sqrt(1.0 + eps ** 2 * ((Xt[:, None, :] - Xt[None]) ** 2).sum(-1))
 W = np.linalg.solve(K + 1e-8 * np.eye(len(K)), Ys)
 cl = (Up, Us, Xt, W, eps, x_min, x_max, y_min, y_max)
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-T1 = Sh.shape[1] // 9
-train = [(Sh[:, k * T1:(k + 1) * T1], mu1t[k], mu2t[k]) for k in range(9)]
+train = training_list(Sh)
 mu1, mu2 = draw(a.batch)
 dev = torch.device("cuda", 0)
 full_plan = rom.RbfFusedPlan(*cl, kernel, dev, long_mesh=N > 512) if N <= 1024 and not a.host else None
@@ -56,15 +54,7 @@ for proj in ("Galerkin", "LSPG"):
     else:
         fused = rom.pod_rbf_run_long if N > 512 else rom.pod_rbf_run_fused
         runs["full"] = lambda: fused(X, np.ones(N), mu1, mu2, dt, a.steps, *cl, projection=proj, kernel=kernel, plan=full_plan)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     hy, full = last["hyper"], last["full"]
     fmt = lambda vs: [float(f"{v:.4g}") for v in vs]
     med = {k: float(np.median(v)) for k, v in rates.items()}

@@ -10,7 +10,7 @@ against the FOM.
 usage: python tools/time_hyper_rom.py [--batch 1024] [--steps 40] [--n 1024] [--r 40] [--dt 0.025] [--tau 1e-4] [--reps 3] [--no-full]"""
 import argparse, json
 import numpy as np, torch
-from _timing import draw, training_snapshots
+from _timing import draw, time_alternately, training_list, training_snapshots
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--n", type=int, default=1024); ap.add_argument("--r", type=int, default=40)
@@ -21,9 +21,7 @@ from burgers_hip import fom, pod, rom
 N = a.n
 X, S = training_snapshots(N, a.dt)
 Phi = pod.pod_basis(S, n_modes=a.r)[0].contiguous()
-mu1t = np.repeat(np.linspace(4.25, 5.5, 3), 3); mu2t = np.tile(np.linspace(0.015, 0.03, 3), 3)
-T1 = S.shape[1] // 9
-train = [(S[:, k * T1:(k + 1) * T1].cpu(), mu1t[k], mu2t[k]) for k in range(9)]
+train = training_list(S, host=True)
 mu1, mu2 = draw(a.batch)
 worst = lambda x, y: float(((x.flatten(1) - y.flatten(1)).norm(dim=1) / y.flatten(1).norm(dim=1)).max())
 truth = fom.fom_run(X, np.ones(N), mu1, mu2, a.dt, a.steps).hist
@@ -38,15 +36,7 @@ for proj in ("Galerkin", "LSPG"):
     runs["decoded"] = decoded
     if not a.no_full:
         runs["full"] = lambda: rom.pod_prom_run(X, np.ones(N), mu1, mu2, a.dt, a.steps, Phi, projection=proj, long_mesh=True)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     hy = last["hyper"]
     out = {"projection": proj, "N": N, "r": a.r, "batch": a.batch, "steps": a.steps, "dt": a.dt, "tau": a.tau, "rows": s.m,
            "training_residual": float(f"{s.residual:.3g}"), "path": hy.path, "newton_steps": int(hy.iters.sum().item()),

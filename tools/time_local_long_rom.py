@@ -6,7 +6,7 @@ LSPG r = 40 POD run at mu = (4.9, 0.022), steps 0, 4, ..., 40, bases Phi[:, :w] 
 Prints one JSON line per projection: sample-Picard-steps/s of each route (median of --reps), their ratio, the switches.
 usage: python tools/time_local_long_rom.py [--batch 1024] [--steps 40] [--n 1024] [--dt 0.025] [--reps 3] [--host]"""
 import argparse, json
-from _timing import draw, training_snapshots
+from _timing import draw, time_alternately, training_snapshots
 import numpy as np, torch
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--steps", type=int, default=40)
@@ -28,15 +28,7 @@ for proj in ("Galerkin", "LSPG"):
                                                       projection=proj, plan=plan)}
     if a.host:
         runs["host"] = lambda: rom.local_prom_run(X, np.ones(N), mu1, mu2, a.dt, a.steps, centres, bases, Phi, 12, projection=proj)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     cl = last["device"].clusters
     out = {"projection": proj, "N": N, "batch": a.batch, "steps": a.steps, "dt": a.dt, "path": last["device"].path,
            "switches": int((cl[:, 1:] != cl[:, :-1]).sum().item()), "capped_samples": int((last["device"].flags & 1).ne(0).sum().item()),

@@ -7,7 +7,7 @@ Prints one JSON line per projection: sample-Newton-steps/s of each route (all re
 total, the capped samples, and with --host the ratio, whether counts and flags are identical and the worst per-sample rel-L2.
 usage: python tools/time_rbf_long_rom.py [--batch 1024] [--steps 12] [--n 1024] [--dt 0.025] [--reps 3] [--kernel gaussian] [--host]"""
 import argparse, json, os, sys
-from _timing import REPO
+from _timing import REPO, time_alternately
 import numpy as np, torch
 sys.path.insert(0, os.path.join(REPO, "tests"))
 ap = argparse.ArgumentParser()
@@ -29,15 +29,7 @@ for proj in ("Galerkin", "LSPG"):
                                                    kernel=a.kernel, plan=plan)}
     if a.host:
         runs["host"] = lambda: rom.pod_rbf_run(X, np.ones(N), mu1, mu2, a.dt, a.steps, *cl, projection=proj, kernel=a.kernel)
-    rates, last = {k: [] for k in runs}, {}
-    for f in runs.values():                                     # warm-up: code objects, library handles, allocator
-        f(); torch.cuda.synchronize()
-    for _ in range(a.reps):
-        for k, f in runs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(); last[k] = f(); e1.record(); torch.cuda.synchronize()
-            rates[k].append(int(last[k].iters.sum().item()) / e0.elapsed_time(e1) * 1e3)
+    rates, last = time_alternately(runs, a.reps)
     dev = last["device"]
     out = {"projection": proj, "kernel": a.kernel, "N": N, "batch": a.batch, "steps": a.steps, "dt": a.dt, "path": dev.path,
            "newton_steps": int(dev.iters.sum().item()), "capped_samples": int((dev.flags & 1).ne(0).sum().item()),
