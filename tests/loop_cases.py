@@ -1,6 +1,6 @@
 """What more than one device-loop test needs: the training snapshots and their singular vectors, the parameter draw, the
-comparisons of two results and of a POD loop with the oracle, the raw-ABI ``order`` and plan-reuse checks of the streaming
-POD loops, the dense local clustering's widths, and the library handle and argument-validation check of the ABI tests.
+non-constant initial states, the comparisons of two results and of a POD loop with the oracle, the raw-ABI ``order`` and
+plan-reuse checks of the streaming POD loops, the dense local clustering's widths, and the library handle and argument-validation check of the ABI tests.
 The shapes each loop is tested at, and why, stay in that loop's test file.  torch and the oracle are imported where they are
 used, so that the CPU-side ABI tests need neither."""
 import ctypes
@@ -40,6 +40,20 @@ def pod_basis(N, dt, r, E=0.0, seed=None):
 def draw(B, seed=20251121):
     rng = np.random.default_rng(seed)
     return rng.uniform(4.25, 5.5, B), rng.uniform(0.015, 0.03, B)
+
+
+RUN = [2, 6, 3, 7, 0, 8]
+STEP = [20, 45, 70, 95, 120, 145]
+
+
+def initial_states(N, dt, E, seed, B, steps=STEP):
+    """(B, N) non-constant starts, one per sample, outside the span of a POD basis of training_snapshots(N, dt, E, seed): sample b
+    is the stored FOM state of training run RUN[b] at step ``steps[b]`` (a moving front, at other parameters than draw(B) gives the
+    sample) times 1 + 1e-3 sin((5 + 3 b) pi x / 100).  A new array: the caller may change it."""
+    X, S, _ = training_snapshots(N, dt, E, seed)
+    cols = [201 * RUN[b] + steps[b] for b in range(B)]
+    wave = 1.0 + 1e-3 * np.sin((5 + 3 * np.arange(B))[:, None] * np.pi * X[None, :] / 100.0)
+    return np.ascontiguousarray(S[:, cols].T * wave)
 
 
 def to_np(t):
@@ -89,13 +103,14 @@ def max_multiplier(X, dt, nT, mu1, mu2, Phi, proj, E):
     return worst
 
 
-def check_pod_vs_oracle(res, X, dt, nT, mu1, mu2, Phi, proj, E=0.0, samples=None, tol=TOL):
+def check_pod_vs_oracle(res, X, dt, nT, mu1, mu2, Phi, proj, E=0.0, samples=None, tol=TOL, u0=None):
     """Every listed sample (default: all) of a POD loop's result: rel-L2 of the history below ``tol``, every iteration count
-    equal to the oracle's; no flag raised and no sample left marked."""
+    equal to the oracle's; no flag raised and no sample left marked.  ``u0``: the (B, N) starts of the run (None: ones)."""
     from oracle import burgers_ref as br
     hist, iters = to_np(res.hist), to_np(res.iters)
     for s in (range(len(mu1)) if samples is None else samples):
-        U, ito = br.pod_prom_burgers(X, dt, nT, np.ones(len(X)), mu1[s], E, mu2[s], Phi, projection=proj, return_iters=True)
+        start = np.ones_like(X, dtype=np.float64) if u0 is None else u0[s]
+        U, ito = br.pod_prom_burgers(X, dt, nT, start, mu1[s], E, mu2[s], Phi, projection=proj, return_iters=True)
         err = rel_l2(hist[s].T, U)
         print(f"N={len(X)} r={Phi.shape[1]} {proj} sample {s}: rel-L2 {err:.2e}, iterations {iters[s].tolist()} / {ito.tolist()}")
         assert err < tol, (proj, s, err)
