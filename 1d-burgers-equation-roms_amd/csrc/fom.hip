@@ -115,30 +115,69 @@ __device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, Wi
     };
     head();
 
+    // Lean iterations (BG_PICARD_LEAN).  Far from convergence an iteration solves A v = b for the new iterate itself: the
+    // three FMAs per row of A u in the right-hand side are not issued (assemble_p2, ITER), and du = v - u serves the stopping
+    // norm only.  Such a solve is as accurate as the pivot-free solver, 1e-15 |u| to 1e-14 |u|, and unlike the solve for the
+    // increment not corrected below that by the iteration after it, so a time step should not END on one.  A step
+    // therefore runs in two loops, each a straight body: lean iterations while the stopping test is missed by more than
+    // BG_PICARD_LEAN_FACTOR in the error (its square in the norms), then iterations for the increment until the test is met
+    // or the cap reached; the history keeps the accuracy of the increment form.  Every step starts lean, whatever the step
+    // before it did: a step is a function of its initial state alone, so a run restarted from a stored time level repeats
+    // the original bit for bit.  A lean iteration ends a step only where the error falls by more than the factor in one
+    // iteration (a step's first included: a step that converges at once), or at the cap; the step's result is then the
+    // solver's, off by 1e-15 relative, and counted and flagged like any other.  Every branch derives from the sums all
+    // threads of the sample hold, so it is uniform.
+    // The second loop body costs registers.  It is left out where the kernel has none to give: the parked form, and a
+    // graded mesh at 24 or more rows per thread, which spills as it is (profiles/iterate_form_resources.tsv).
+    constexpr bool LEANS = BG_PICARD_LEAN && !PARK && (UNI || R < 24);
+    constexpr double lean2 = BG_PICARD_LEAN_FACTOR * BG_PICARD_LEAN_FACTOR;
     int flags = 0;
     for (int step = 0; step < a.nsteps; ++step) {
         if constexpr (UNI) mass_rhs<R, FULL>(tp, c, N, u, fdt, g_put);
         else mass_rhs_general<R>(tp, gm, N, u, fdt, g);
         int k = 0;
-        bool more;
-        do {
+        bool more = true, far = LEANS;
+        auto iteration = [&](auto lean_c) __attribute__((always_inline)) {
+            constexpr bool LEAN = decltype(lean_c)::value;
             double lo[R], di[R], up[R], rhs[R];
             if constexpr (ROT) {
 #pragma unroll
                 for (int j = 0; j < R; ++j) { lo[j] = hlo[j]; up[j] = hup[j]; }
-                if constexpr (UNI) assemble_tail<R, FULL>(tp, c, N, mu1, u, g_at, huL, huR, hse, lo, di, up, rhs);
-                else assemble_general_tail<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, huL, huR, hse, lo, di, up, rhs);
+                if constexpr (UNI) assemble_tail<R, FULL, LEAN>(tp, c, N, mu1, u, g_at, huL, huR, hse, lo, di, up, rhs);
+                else assemble_general_tail<R, LEAN>(tp, gm, a.dt, c.kap, N, mu1, u, g, huL, huR, hse, lo, di, up, rhs);
             } else {
-                if constexpr (UNI) assemble<R, FULL>(tp, c, N, mu1, u, g_at, hf_at, lo, di, up, rhs);
-                else assemble_general<R>(tp, gm, a.dt, c.kap, N, mu1, u, g, hfs, lo, di, up, rhs);
+                if constexpr (UNI) assemble<R, FULL, LEAN>(tp, c, N, mu1, u, g_at, hf_at, lo, di, up, rhs);
+                else assemble_general<R, LEAN>(tp, gm, a.dt, c.kap, N, mu1, u, g, hfs, lo, di, up, rhs);
             }
-            tp.template solve<R>(lo, di, up, rhs);
+            // The solve leaves the last multiply of its rows j < R-1 open, x_j = rhs[j] * di[j] (wang_finish).  LEAN: x is the
+            // new iterate, du_j = x_j - u_j is one FMA of the two factors, formed while u_j is still the old iterate, and
+            // x_j then takes u_j's registers with no move.  Otherwise x is the increment.
+            // Contraction is off here: the next assembly adds to the product x_j (LEAN) or to the sum u_j + x_j, and left to
+            // itself the compiler fuses those, so that the assembly reads an unrounded iterate where the history holds the
+            // rounded one; which sums it fuses differs between the instantiations, and traced and untraced runs, which
+            // must agree bit for bit, then differ in the last place.
+            // A kernel without the lean loop keeps the whole solve and the update as they were: its listing is unchanged.
+            tp.template solve<R, !LEANS>(lo, di, up, rhs);
             double nd = 0.0, nu = 0.0;
 #pragma unroll
             for (int j = 0; j < R; ++j) {
-                u[j] += rhs[j];
-                nd = __builtin_fma(rhs[j], rhs[j], nd);
-                nu = __builtin_fma(u[j], u[j], nu);
+                if constexpr (!LEANS) {
+                    u[j] += rhs[j];
+                    nd = __builtin_fma(rhs[j], rhs[j], nd);
+                    nu = __builtin_fma(u[j], u[j], nu);
+                } else {
+#pragma clang fp contract(off)
+                    double d;
+                    if constexpr (LEAN) {
+                        d = (j < R - 1) ? __builtin_fma(rhs[j], di[j], -u[j]) : rhs[j] - u[j];
+                        u[j] = (j < R - 1) ? rhs[j] * di[j] : rhs[j];
+                    } else {
+                        d = (j < R - 1) ? rhs[j] * di[j] : rhs[j];
+                        u[j] += d;
+                    }
+                    nd = __builtin_fma(d, d, nd);
+                    nu = __builtin_fma(u[j], u[j], nu);
+                }
             }
             if constexpr (ROT && UNI) {
                 // the head in chunks of four elements, a round of the norm reduction in front of each: left to itself the
@@ -168,8 +207,15 @@ __device__ __forceinline__ void fom_sample(const FomArgs& a, Topo& tp, int s, Wi
             // reference: error = ||dU|| / ||U1||; continue while error > tol and k < cap.
             // NaN compares false and ends the loop, as in the reference.
             more = (nd > a.tol2 * nu) && (k < a.max_it);
+            far = LEANS && nd > lean2 * (a.tol2 * nu);                    // a NaN norm compares false: not far
             flags |= uniform_nonfinite(nd, nu) ? BG_FLAG_NONFINITE : 0;   // scalar: nd, nu are readlane results
-        } while (more);
+        };
+        if constexpr (LEANS) {
+            while (far && more) iteration(std::true_type{});
+            while (more) iteration(std::false_type{});
+        } else {
+            do iteration(std::false_type{}); while (more);      // the one loop, as it was
+        }
         if (k >= a.max_it) flags |= BG_FLAG_HIT_CAP;
         store_rows<R>(hist + (size_t)(step + 1) * N, N, row0, FULL, u);
         if (tp.first()) a.iters[(size_t)s * a.nsteps + step] = k;
@@ -200,13 +246,13 @@ __device__ __forceinline__ void assemble_sample(const AsmArgs& a, Topo& tp, int 
         auto g_at = [&](int j) { return g[j]; };
         auto hf_at = [&](int j) { return hfs[j]; };
         mass_rhs<R, FULL>(tp, c, N, un, fdt, g_put);
-        assemble<R, FULL>(tp, c, N, a.mu1[s], u, g_at, hf_at, lo, di, up, rhs);
+        assemble<R, FULL, false>(tp, c, N, a.mu1[s], u, g_at, hf_at, lo, di, up, rhs);
     } else {
         ElemGeom<R> gm;
         geom_setup<R>(a.x, N, row0, a.dt, a.E, gm);
         forcing_setup_general<R>(a.x, N, row0, a.mu2[s], a.dt, hfs, fdt);
         mass_rhs_general<R>(tp, gm, N, un, fdt, g);
-        assemble_general<R>(tp, gm, a.dt, c.kap, N, a.mu1[s], u, g, hfs, lo, di, up, rhs);
+        assemble_general<R, false>(tp, gm, a.dt, c.kap, N, a.mu1[s], u, g, hfs, lo, di, up, rhs);
     }
     store_rows<R>(a.lo + (size_t)s * N, N, row0, FULL, lo);
     store_rows<R>(a.di + (size_t)s * N, N, row0, FULL, di);

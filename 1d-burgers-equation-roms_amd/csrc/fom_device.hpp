@@ -49,6 +49,16 @@
 #define BG_PICARD_ROTATE 1
 #endif
 
+// fom_sample starts every time step with lean iterations, which solve for the new iterate itself, A v = b, and not for the
+// increment, A du = b - A u, and stays with them while the stopping test is missed by more than a factor of
+// BG_PICARD_LEAN_FACTOR (see assemble_p2 and fom_sample); 0: every iteration solves for the increment
+#ifndef BG_PICARD_LEAN
+#define BG_PICARD_LEAN 1
+#endif
+#ifndef BG_PICARD_LEAN_FACTOR
+#define BG_PICARD_LEAN_FACTOR 16.0
+#endif
+
 namespace bg {
 
 constexpr double GP_A = 0.78867513459481287;  // (1 + 1/sqrt(3)) / 2
@@ -168,10 +178,25 @@ __device__ __forceinline__ void supg_terms(const double (&mx)[R], const double (
     for (int j = G; j < R; ++j) se[j] = t[j] * BG_RCP(mx[j]);
 }
 
-// One assembly: diagonals lo/di/up of A(u) and rhs = b - A u  (= -R of the reference), in two halves around the
-// exchange of se.  p1: off-diagonals and the SUPG element terms se[];  p2: diagonal, right-hand side, special rows.
+// One assembly: diagonals lo/di/up of A(u) and the right-hand side, in two halves around the exchange of se.
+// p1: off-diagonals and the SUPG element terms se[];  p2: diagonal, right-hand side, special rows.
 // `first` / `last_lane` mark the threads that own global row 0 / (FULL only) the last row.
-// hf(j), g(j): hfs and g of local row j (a register array, or an LDS read when a kernel parks them there)
+// ITER chooses the right-hand side at compile time.  The matrix is the same, bit for bit, so every exit of pcr64, whose
+// ballots read the couplings only, goes the way it went.
+//   false  rhs = b - A u (= -R of the reference): the solve gives the increment.  The diagnostic assembly (bg_fom_assemble)
+//          and the iterations of fom_sample near convergence.
+//   true   rhs = b: the solve gives the new iterate itself, A v = b, and the three FMAs per row of A u are not issued.  b is
+//          mu1 on the Dirichlet row, has no right element on the last row and is 0 on a padded row, whose solution is then
+//          0, as u is there.  The lean iterations of fom_sample, far from convergence (fom.hip).
+// What a lean solve costs: the solve's errors are relative to what it solves for.  The exits of pcr64 truncate by half an
+// ulp of the largest interface unknown, the Wang sweeps round at the size of their unknowns and rcp1 is 2.1e-15 off: that
+// is 1e-15 |u| to 1e-14 |u| per solve for the iterate, where for the increment it is the same fraction of |du|, which
+// shrinks with the iteration.  A lean iteration is therefore as accurate as the pivot-free solve and not corrected below
+// that by the next one, and the du = v - u of its stopping test carries the same absolute error, to be compared with the
+// tol |u| = 1e-6 |u| it is tested against.  A time step that ENDED on a lean iteration would carry 1e-15 to 1e-14 into the
+// history, where the increment form leaves 1e-16: over the 500 steps of tests/test_fom_gpu.py's committed N = 512 run that
+// moved the wave and the workgroup form 3e-12 max|u| apart, against the 1e-12 the suite allows them.  So
+// fom_sample goes lean only far from convergence, and a step's last iterations solve for the increment.
 template <int R, typename HF>
 __device__ __forceinline__ void assemble_p1(const MeshConst& c, const double (&u)[R], double uL, double uR,
                                             HF&& hf, double (&lo)[R], double (&up)[R], double (&se)[R])
@@ -225,7 +250,7 @@ __device__ __forceinline__ void assemble_p1_rows(const MeshConst& c, const doubl
     }
 }
 
-template <int R, bool FULL, typename GF>
+template <int R, bool FULL, bool ITER, typename GF>
 __device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0, bool first, bool last_lane,
                                             double mu1, const double (&u)[R], double uL, double uR, double seL,
                                             GF&& g, const double (&se)[R], double (&lo)[R],
@@ -254,7 +279,7 @@ __device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0,
             d = pad ? 1.0 : d;
             p = pad ? 0.0 : p;
             l = pad ? 0.0 : l;
-            bb = pad ? 0.0 : bb;   // u is 0 on padded rows, so rhs becomes 0
+            bb = pad ? 0.0 : bb;   // u is 0 on padded rows, so rhs becomes 0 (ITER: so the solution is 0)
         }
         if (j == 0) {           // Dirichlet row (global row 0)
             d = first ? 1.0 : d;
@@ -262,9 +287,12 @@ __device__ __forceinline__ void assemble_p2(const MeshConst& c, int N, int row0,
             l = first ? 0.0 : l;
             bb = first ? mu1 : bb;
         }
-        double r = __builtin_fma(-l, um, bb);
-        r = __builtin_fma(-d, u[j], r);
-        r = __builtin_fma(-p, ur, r);
+        double r = bb;
+        if constexpr (!ITER) {
+            r = __builtin_fma(-l, um, r);
+            r = __builtin_fma(-d, u[j], r);
+            r = __builtin_fma(-p, ur, r);
+        }
         lo[j] = l; di[j] = d; up[j] = p; rhs[j] = r;
     }
 }
@@ -283,16 +311,16 @@ __device__ __forceinline__ void assemble_head(Topo& tp, const MeshConst& c, cons
     assemble_p1<R>(c, u, uL, uR, hf, lo, up, se);
 }
 
-template <int R, bool FULL, class Topo, typename GF>
+template <int R, bool FULL, bool ITER, class Topo, typename GF>
 __device__ __forceinline__ void assemble_tail(Topo& tp, const MeshConst& c, int N, double mu1, const double (&u)[R],
                                               GF&& g, double uL, double uR, const double (&se)[R], double (&lo)[R],
                                               double (&di)[R], double (&up)[R], double (&rhs)[R])
 {
     const double seL = tp.below_se(se[R - 1]);
-    assemble_p2<R, FULL>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    assemble_p2<R, FULL, ITER>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
-template <int R, bool FULL, class Topo, typename GF, typename HF>
+template <int R, bool FULL, bool ITER, class Topo, typename GF, typename HF>
 __device__ __forceinline__ void assemble(Topo& tp, const MeshConst& c, int N, double mu1, const double (&u)[R], GF&& g,
                                          HF&& hf, double (&lo)[R], double (&di)[R], double (&up)[R], double (&rhs)[R])
 {
@@ -300,7 +328,7 @@ __device__ __forceinline__ void assemble(Topo& tp, const MeshConst& c, int N, do
     tp.halo(u[0], u[R - 1], uL, uR);
     assemble_p1<R>(c, u, uL, uR, hf, lo, up, se);
     const double seL = tp.below_se(se[R - 1]);
-    assemble_p2<R, FULL>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    assemble_p2<R, FULL, ITER>(c, N, tp.g * R, tp.first(), tp.last(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 // ------------------------------------------------------------------------------------
@@ -375,7 +403,7 @@ __device__ __forceinline__ void mass_rhs_general(Topo& tp, const ElemGeom<R>& gm
 }
 
 // assemble_general in the same two halves.  p1: off-diagonals and the SUPG element terms se[];
-// p2: diagonal, right-hand side, special rows.  `first` marks the thread that owns global row 0.
+// p2: diagonal, right-hand side (ITER as in assemble_p2), special rows.  `first` marks the thread that owns global row 0.
 template <int R>
 __device__ __forceinline__ void assemble_general_p1(const ElemGeom<R>& gm, double dt, const double (&u)[R], double uL,
                                                     double uR, const double (&hfs)[R], double (&lo)[R],
@@ -398,7 +426,7 @@ __device__ __forceinline__ void assemble_general_p1(const ElemGeom<R>& gm, doubl
     lo[0] = __builtin_fma(-dt6, __builtin_fma(2.0, u[0], uL), gm.h6[0] - gm.eh[0]);
 }
 
-template <int R>
+template <int R, bool ITER>
 __device__ __forceinline__ void assemble_general_p2(const ElemGeom<R>& gm, double dt, double kap, int N, int row0,
                                                     bool first, double mu1, const double (&u)[R], double uL,
                                                     double uR, double seL, const double (&g)[R],
@@ -434,9 +462,12 @@ __device__ __forceinline__ void assemble_general_p2(const ElemGeom<R>& gm, doubl
             l = first ? 0.0 : l;
             bb = first ? mu1 : bb;
         }
-        double r = __builtin_fma(-l, um, bb);
-        r = __builtin_fma(-d, u[j], r);
-        r = __builtin_fma(-p, ur, r);
+        double r = bb;
+        if constexpr (!ITER) {
+            r = __builtin_fma(-l, um, r);
+            r = __builtin_fma(-d, u[j], r);
+            r = __builtin_fma(-p, ur, r);
+        }
         lo[j] = l; di[j] = d; up[j] = p; rhs[j] = r;
     }
 }
@@ -451,17 +482,17 @@ __device__ __forceinline__ void assemble_general_head(Topo& tp, const ElemGeom<R
     assemble_general_p1<R>(gm, dt, u, uL, uR, hfs, lo, up, se);
 }
 
-template <int R, class Topo>
+template <int R, bool ITER, class Topo>
 __device__ __forceinline__ void assemble_general_tail(Topo& tp, const ElemGeom<R>& gm, double dt, double kap, int N,
                                                       double mu1, const double (&u)[R], const double (&g)[R], double uL,
                                                       double uR, const double (&se)[R], double (&lo)[R],
                                                       double (&di)[R], double (&up)[R], double (&rhs)[R])
 {
     const double seL = tp.below_se(se[R - 1]);
-    assemble_general_p2<R>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    assemble_general_p2<R, ITER>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
-template <int R, class Topo>
+template <int R, bool ITER, class Topo>
 __device__ __forceinline__ void assemble_general(Topo& tp, const ElemGeom<R>& gm, double dt, double kap, int N,
                                                  double mu1, const double (&u)[R], const double (&g)[R],
                                                  const double (&hfs)[R], double (&lo)[R], double (&di)[R],
@@ -471,7 +502,7 @@ __device__ __forceinline__ void assemble_general(Topo& tp, const ElemGeom<R>& gm
     tp.halo(u[0], u[R - 1], uL, uR);
     assemble_general_p1<R>(gm, dt, u, uL, uR, hfs, lo, up, se);
     const double seL = tp.below_se(se[R - 1]);
-    assemble_general_p2<R>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
+    assemble_general_p2<R, ITER>(gm, dt, kap, N, tp.g * R, tp.first(), mu1, u, uL, uR, seL, g, se, lo, di, up, rhs);
 }
 
 // One PCR step on normalised equations A x[j-s] + x[j] + C x[j+s] = D; neighbours come from
@@ -556,7 +587,9 @@ __device__ __forceinline__ void wang_interface(const double (&lo)[R], const doub
 }
 
 // Back-substitution: X = this lane's last unknown, XL = the previous lane's.  Solution lands in rhs[].
-template <int R>
+// SCALE = false leaves the last multiply of the rows j < R-1 to the caller: x_j = rhs[j] * di[j], and rhs[R-1] = X as
+// always.  fom_sample forms x_j - u_j from the two factors in one FMA and writes x_j over u_j after it (fom.hip).
+template <int R, bool SCALE = true>
 __device__ __forceinline__ void wang_finish(const double (&lo)[R], const double (&di)[R], double (&rhs)[R],
                                             const double (&gs)[R], double X, double XL)
 {
@@ -564,7 +597,7 @@ __device__ __forceinline__ void wang_finish(const double (&lo)[R], const double 
     for (int j = 0; j < R - 1; ++j) {
         double v = __builtin_fma(-lo[j], XL, rhs[j]);
         v = __builtin_fma(-gs[j], X, v);
-        rhs[j] = v * di[j];
+        rhs[j] = SCALE ? v * di[j] : v;
     }
     rhs[R - 1] = X;
 }
@@ -604,6 +637,10 @@ __device__ __forceinline__ void wang_finish(const double (&lo)[R], const double 
 // <= rho^(K+1) max|x| <= 2^-56 max|D| / (1 - 2^-8): below half an ulp of the largest interface unknown, the standard of
 // the exit against tau.  One threshold and one K for every workload.  A wave with one lane over tau_J, or a non-finite
 // one, runs everything after the stride-1 step as before (pcr64_from_stride2), both exits of the tau test included.
+//
+// What "half an ulp of the largest interface unknown" is in absolute terms depends on the caller's unknown, for all three
+// exits (tau, Jacobi, one-sided): 1e-16 |du| where the Picard loop solves for the increment, 1e-16 |u| in its lean
+// iterations, which solve for the iterate (assemble_p2, ITER).  The thresholds read the couplings only and stay as they are.
 __device__ __forceinline__ double pcr64_from_stride2(double A, double C, double D)
 {
     const int lane = lane_id();
@@ -709,7 +746,8 @@ __device__ __forceinline__ double pcr64(double A, double C, double D)
 
 // Pivot-free tridiagonal solve across the wave (Wang partition + PCR on the 64
 // interface unknowns).  In: lo/di/up/rhs.  Out: solution in rhs.  lo, di are clobbered.  ONESIDED: see pcr64.
-template <int R, bool ONESIDED = false>
+// SCALE = false: the solution is rhs[j] * di[j] for j < R-1 and rhs[R-1] (see wang_finish; R = 1 has no such rows).
+template <int R, bool ONESIDED = false, bool SCALE = true>
 __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], const double (&up)[R],
                                               double (&rhs)[R])
 {
@@ -725,7 +763,7 @@ __device__ __forceinline__ void tridiag_solve(double (&lo)[R], double (&di)[R], 
         double A, C, D;           // normalised interface equation: A x[p-1] + x[p] + C x[p+1] = D
         wang_interface<R>(lo, up, rhs, dp, F0, G0, R0, A, C, D);
         const double X = pcr64<R, ONESIDED>(A, C, D);
-        wang_finish<R>(lo, di, rhs, gs, X, from_lane_below(X));
+        wang_finish<R, SCALE>(lo, di, rhs, gs, X, from_lane_below(X));
     }
 }
 

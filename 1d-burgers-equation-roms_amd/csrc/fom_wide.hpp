@@ -66,8 +66,8 @@ __device__ __forceinline__ void wide_pcr_step(const double (&buf)[3][WIDE_LEN], 
     C = -(Cp * C) * rb;
 }
 
-// Pivot-free tridiagonal solve across the workgroup.  In: lo/di/up/rhs.  Out: solution in rhs.
-template <int R>
+// Pivot-free tridiagonal solve across the workgroup.  In: lo/di/up/rhs.  Out: solution in rhs (SCALE: see wang_finish).
+template <int R, bool SCALE = true>
 __device__ __forceinline__ void wide_tridiag_solve(WideLds& s, int g, double (&lo)[R], double (&di)[R],
                                                    const double (&up)[R], double (&rhs)[R])
 {
@@ -94,7 +94,7 @@ __device__ __forceinline__ void wide_tridiag_solve(WideLds& s, int g, double (&l
     wide_pcr_step<2>(s.pcr[1], e, A, C, D);
     s.x[e + WIDE_PAD] = pcr64<R>(A, C, D);                   // stride-4 system e & 3 = this wave, in lane order
     __syncthreads();
-    wang_finish<R>(lo, di, rhs, gs, s.x[g + WIDE_PAD], s.x[g + WIDE_PAD - 1]);
+    wang_finish<R, SCALE>(lo, di, rhs, gs, s.x[g + WIDE_PAD], s.x[g + WIDE_PAD - 1]);
 }
 
 // sums over the whole workgroup, the same value in every thread (fixed summation order)
@@ -160,10 +160,10 @@ struct WaveTopoT {
     __device__ __forceinline__ double gmax(double v) { return wave_max(v); }
     __device__ __forceinline__ double gmax_nan(double v, bool nan) { return wave_max_nan(v, nan); }
     __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wave_sum2(a, b, sa, sb); }
-    template <int R>
+    template <int R, bool SCALE = true>
     __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
     {
-        tridiag_solve<R, ONESIDED>(lo, di, up, rhs);
+        tridiag_solve<R, ONESIDED, SCALE>(lo, di, up, rhs);
     }
 };
 using WaveTopo = WaveTopoT<false>;
@@ -221,10 +221,10 @@ struct WgTopo {
         return ((b0 != b0) | (b1 != b1) | (b2 != b2) | (b3 != b3)) ? __builtin_nan("") : m;
     }
     __device__ __forceinline__ void sum2(double a, double b, double& sa, double& sb) { wide_sum2(s, g, a, b, sa, sb); }
-    template <int R>
+    template <int R, bool SCALE = true>
     __device__ __forceinline__ void solve(double (&lo)[R], double (&di)[R], const double (&up)[R], double (&rhs)[R])
     {
-        wide_tridiag_solve<R>(s, g, lo, di, up, rhs);
+        wide_tridiag_solve<R, SCALE>(s, g, lo, di, up, rhs);
     }
 };
 

@@ -95,6 +95,13 @@ int bg_fom_max_n(void);
  *   tol, max_it              the reference hard-codes 1e-6 and 20 (:663)
  *   supg                     option bits: BG_OPT_SUPG (fom_burgers has it) | BG_OPT_NONUNIFORM
  *
+ *   The iteration: a time step starts with iterations that solve A(u) v = b for the new iterate v itself (du = v - u
+ *   serves the stopping norm ||du|| / ||v|| only) and stays with them while the stopping test is missed by more than a
+ *   factor of 16; from there on an iteration solves A(u) du = b - A(u) u for the increment, as the reference does, so
+ *   that the state a step ends on is corrected below the accuracy of the pivot-free solve.  Counts are the reference's k.
+ *   Where a thread's registers do not hold both loop bodies (N > 6144; a non-uniform mesh of 1024 < N <= 1536 or
+ *   N > 4096) every iteration solves for the increment.
+ *
  *   Range of the state: the SUPG quotients t_e / max(|u_e + u_{e+1}|, 2e-10) of four neighbouring elements share
  *   one reciprocal of the product of their denominators, which must stay below 1.8e308: every |u| <~ 5e76 is safe
  *   (the product cannot underflow).  Beyond that the reciprocal is 0 and its Newton step NaN: the sample turns
