@@ -397,7 +397,8 @@ int fom_args(FomArgs& a, bool traced, int N, int B, int nsteps, const double* x,
     if (B == 0) return BG_OK;
     if (!x || !u0 || !mu1 || !mu2 || !hist || !flags || (traced && !errs) || (nsteps > 0 && !iters)) return BG_ERR_BAD_ARG;
     a.x = x; a.u0 = u0; a.mu1 = mu1; a.mu2 = mu2; a.hist = hist; a.iters = iters; a.flags = flags; a.errs = errs;
-    a.dt = dt; a.E = E; a.tol2 = tol * tol;
+    // the kernels test nd > tol2 nu for the reference's error > tol; a negative tol never stops a step, which its square would
+    a.dt = dt; a.E = E; a.tol2 = tol < 0.0 ? -1.0 : tol * tol;
     a.N = N; a.B = B; a.nsteps = nsteps; a.max_it = max_it; a.supg = supg & BG_OPT_SUPG;
     return BG_OK;
 }

@@ -92,7 +92,9 @@ int bg_fom_max_n(void);
  *   hist   [B][nsteps+1][N]  hist[b][0] = u0[b]; hist[b][t+1] = state after step t
  *   iters  [B][nsteps]       Picard iterations taken per step (the reference's k)
  *   flags  [B]               BG_FLAG_* bits
- *   tol, max_it              the reference hard-codes 1e-6 and 20 (:663)
+ *   tol, max_it              the reference hard-codes 1e-6 and 20 (:663).  A step iterates while error > tol and k < max_it,
+ *                            after a first iteration that always runs: tol = 0 and tol < 0 run every step to max_it, tol = inf
+ *                            and tol = NaN (no comparison holds) give one iteration per step, flagged only where max_it = 1.
  *   supg                     option bits: BG_OPT_SUPG (fom_burgers has it) | BG_OPT_NONUNIFORM
  *
  *   The iteration: a time step starts with iterations that solve A(u) v = b for the new iterate v itself (du = v - u

@@ -39,9 +39,31 @@ def test_lu_solve_vs_numpy(hip, n):
     assert info.cpu().numpy()[0] != 0 and info.cpu().numpy()[1] == 0
 
 
-@pytest.mark.parametrize("N,r,shared", [(512, 40, True), (512, 21, False), (512, 5, False), (256, 16, True),
-                                        (300, 33, True), (96, 7, False), (512, 47, True), (128, 40, False)])
-def test_rom_reduce_vs_oracle(hip, N, r, shared):
+def signed_states(kind, X, B, rng):
+    """States of the other sign for rom_assemble_row: "negative" -(1 + 4 rand), "signed" 3 sin(7 pi x / 100) + 0.2 randn
+    (tests/test_fom_controls_gpu.py, section 5a).  Ar and br are sums over the rows, so no element sum comes near the
+    clamp of the SUPG quotient: left to right, a node whose element sum is below 0.05 is moved until the sum is +-0.075."""
+    N = len(X)
+    if kind == "negative":
+        return -(1.0 + 4.0 * rng.random((B, N)))
+    U = 3.0 * np.sin(7 * np.pi * X / 100)[None, :] + 0.2 * rng.standard_normal((B, N))
+    for e in range(N - 1):
+        w = U[:, e] + U[:, e + 1]
+        U[:, e + 1] = np.where(np.abs(w) < 0.05, np.where(w >= 0, 0.075, -0.075) - U[:, e], U[:, e + 1])
+    w = U[:, :-1] + U[:, 1:]
+    assert np.abs(w).min() >= 0.05 and (w > 0).any() and (w < 0).any()
+    return U
+
+
+REDUCE_SHAPES = [(512, 40, True), (512, 21, False), (512, 5, False), (256, 16, True), (300, 33, True), (96, 7, False),
+                 (512, 47, True), (128, 40, False)]
+REDUCE_CASES = [(*s, "positive") for s in REDUCE_SHAPES] + \
+               [(*s, kind) for kind in ("negative", "signed") for s in ((512, 21, False), (300, 33, True), (96, 7, False))]
+
+
+@pytest.mark.parametrize("N,r,shared,state", REDUCE_CASES,
+                         ids=[f"{N}-{r}-{shared}" + ("" if state == "positive" else f"-{state}") for N, r, shared, state in REDUCE_CASES])
+def test_rom_reduce_vs_oracle(hip, N, r, shared, state):
     from burgers_hip import rom
     rng = np.random.default_rng(N * 100 + r)
     X, _ = mesh(N)
@@ -49,6 +71,8 @@ def test_rom_reduce_vs_oracle(hip, N, r, shared):
     mu1 = rng.uniform(4.25, 5.5, B); mu2 = rng.uniform(0.015, 0.03, B)
     dt, E = 0.05, 0.01
     U = 1.0 + 4.0 * rng.random((B, N)); Un = 1.0 + 4.0 * rng.random((B, N))
+    if state != "positive":                     # drawn after the positive ones, which keeps their stream as it was
+        U, Un = signed_states(state, X, B, rng), signed_states(state, X, B, rng)
     W = rng.standard_normal((N, r)) if shared else rng.standard_normal((B, N, r))
     c = rom._setup(X, Un, mu1, mu2, dt, E, None)
     G = torch.empty((B, N), dtype=torch.float64, device="cuda")
