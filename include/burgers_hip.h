@@ -241,6 +241,18 @@ int bg_lu_solve_update(int n, int B, const double *A, const double *rhs, int mod
  *   Phi    [N][r] row-major (the reference's U_modes .npy layout), shared by all samples; N <= 512, r <= 40
  *          (bg_rom_run_max_r) -- beyond that use bg_rom_reduce + bg_lu_solve_update (BG_ERR_UNSUPPORTED_R / _N)
  *   u0, mu1, mu2, hist, iters, flags: as bg_fom_run (hist[b][0] = u0[b]; flags BG_FLAG_*)
+ *   tol, max_it   the stopping controls of EVERY device-side time loop of this header (bg_rom_run*, bg_hyper_*rom_run*,
+ *          bg_quad_rom_run*, bg_ann_rom_run*, bg_rbf_rom_run*, bg_local_rom_run*); max_it >= 1.  As in bg_fom_run the first
+ *          iteration of a step always runs, and there are two rules, those of bg_lu_solve_update:
+ *            Picard and closure loops (modes 1 and 3): go on while err > tol and k < max_it; BG_FLAG_HIT_CAP whenever a
+ *              step ends with k >= max_it, a step that converged in exactly max_it iterations included;
+ *            quadratic-manifold loops (mode 2): stop once err < tol or k >= max_it; BG_FLAG_HIT_CAP only where the step
+ *              at the cap did not converge ("Newton did not converge", :1171).
+ *          tol = 0 and tol < 0: no step converges, every count is max_it and every sample is flagged, under both rules.
+ *          tol = inf: one iteration per step; no flag unless max_it = 1 (quadratic: never).  The references' ``while``
+ *          loops run no iteration at tol = inf; one iteration per step is what they give at max_it = 1.  The flag is
+ *          sticky over the steps of a sample and is that sample's alone: a persistent workgroup starts every sample it
+ *          takes with flags, info and the iteration counter cleared.  (tests/test_rom_controls_gpu.py)
  *   info   [B] (required): 0, or k+1 when the reduced matrix of a sample is exactly singular at elimination step k
  *          (np.linalg.solve raises LinAlgError there); that sample stops and its remaining history is undefined
  *   options BG_OPT_SUPG (pod_prom_burgers has it) | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED

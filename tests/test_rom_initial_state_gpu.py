@@ -18,7 +18,8 @@ Conditions on the references, asserted in ``reference`` on the reference's own o
   2. every step converges below the cap.  Most iterations: POD 8 (20), quadratic 10 (25), POD-ANN 11 (50), POD-RBF 27 in
      step 1 and 12 afterwards (30), local 7 (20).
   3. the counts at tol * 1.001 and tol / 1.001 are those at tol: no stopping decision sits on the edge.  Where a sample
-     missed 2 or 3 at loop_cases.STEP its step is moved (``moved``, next to the case).
+     missed 2 or 3 at loop_cases.STEP its step is moved (``moved``, next to the case); four more are moved for the
+     conditions of tests/test_rom_controls_gpu.py, which runs these cases off the default tol and cap.
   4. the local loops start in a cluster other than 0, not the same for all samples, with a tie margin >= 1e-8.  First
      clusters 2, 5, 6, 4, 5, 9 on 96 nodes and 2, 5, 6, 4, 4, 9 on 513; smallest margin of any pick 1.1e-3.
   5. steps 1 .. nT of the reference move by at least 10 gates when u0 is shifted by one node, replaced by the next
@@ -80,10 +81,30 @@ def _p(proj):
     return rom.PROJ[proj.lower()]
 
 
+def controls(tol, max_it, f=1.0, names=("tol", "max_it")):
+    """The stopping controls as keyword arguments under the spelling ``names`` of a reference or runner: the tolerance in
+    force (None: 1e-6) times ``f``, and the cap only where one is given (None: the callee's own default)."""
+    kw = {names[0]: (1e-6 if tol is None else tol) * f}
+    if max_it is not None:
+        kw[names[1]] = max_it
+    return kw
+
+
+NEWTON = ("newton_tol", "newton_itmax")         # the quadratic manifold's spelling of tol and max_it
+RBF = ("tol_newton", "max_newton")              # POD-RBF's
+
+
+def _mu(mu):
+    return (MU1, MU2) if mu is None else mu
+
+
 # ---- the cases: what the reference and the loop of one route are run on ------------------------------------------------------------
 # A case is a SimpleNamespace: entry, family, X, u0 (B, N), nT, cap, gate, rows (None: all, the oracle), span (the bases of
-# condition 1), ref(proj, b, start, f, backwards) -> (U (N, nT+1), iters, extra), projected(proj, b, start), launch(proj, u0) -> res,
-# q0(start) -> what q[:, 0] must be (hyper routes).
+# condition 1), ref(proj, b, start, f, backwards, tol, max_it) -> (U (N, nT+1), iters, extra), projected(proj, b, start),
+# launch(proj, u0, tol, max_it, mu, balance) -> res, facade(proj, u0, tol, max_it) -> res of the family's routing front end,
+# q0(start) -> what q[:, 0] must be (hyper routes).  tol and max_it (None: 1e-6 and the family's default cap) go to the
+# reference and to the runner under its own spelling (``controls``); mu = (mu1, mu2) replaces the draw in a launch and
+# ``balance`` is the runner's (tests/test_rom_controls_gpu.py).
 def pod_case(entry, shape, r, run, left_out=None, Phi=None, steps=STEP):
     from oracle import burgers_ref as br
     N, dt, E, seed = shape
@@ -92,23 +113,30 @@ def pod_case(entry, shape, r, run, left_out=None, Phi=None, steps=STEP):
         P = Phi
     rows = None if left_out is None else np.setdiff1d(np.arange(N), left_out)
 
-    def ref(proj, b, start, f=1.0, backwards=False):
+    def ref(proj, b, start, f=1.0, backwards=False, tol=None, max_it=None):
+        kw = controls(tol, max_it, f)
         if rows is None:
-            U, it = br.pod_prom_burgers(X, dt, NT, start, MU1[b], E, MU2[b], P, projection=proj, tol=1e-6 * f, return_iters=True)
+            U, it = br.pod_prom_burgers(X, dt, NT, start, MU1[b], E, MU2[b], P, projection=proj, return_iters=True, **kw)
             return U, it, {}
-        Q, it = hyper_prom(X, dt, NT, start, MU1[b], E, MU2[b], P, proj, rows, np.ones(len(rows)), tol=1e-6 * f, backwards=backwards)
+        Q, it = hyper_prom(X, dt, NT, start, MU1[b], E, MU2[b], P, proj, rows, np.ones(len(rows)), backwards=backwards, **kw)
         U = P @ Q
         U[:, 0] = start
         return U, it, {"Q": Q}
 
-    def launch(proj, u0):
+    def launch(proj, u0, tol=None, max_it=None, mu=None, balance=True):
         from burgers_hip import rom
+        kw = controls(tol, max_it)
         if rows is None:
-            return getattr(rom, run)(X, u0, MU1, MU2, dt, NT, P, _p(proj), E=E)
-        return rom.pod_prom_run_hyper(X, u0, MU1, MU2, dt, NT, P, unit_sampling(rows, proj), _p(proj), E=E)
+            return getattr(rom, run)(X, u0, *_mu(mu), dt, NT, P, _p(proj), E=E, balance=balance, **kw)
+        return rom.pod_prom_run_hyper(X, u0, *_mu(mu), dt, NT, P, unit_sampling(rows, proj), _p(proj), E=E, balance=balance, **kw)
+
+    def facade(proj, u0, tol=None, max_it=None):
+        from burgers_hip import rom
+        return rom.pod_prom_run(X, u0, MU1, MU2, dt, NT, P, projection=proj, E=E, fused=True, **controls(tol, max_it))
 
     return SimpleNamespace(entry=entry, family="POD", X=X, dt=dt, E=E, Phi=P, u0=initial_states(N, dt, E, seed, B, steps), nT=NT, cap=20, gate=TOL,
-                           rows=rows, span=[P], ref=ref, projected=lambda proj, b, u: P @ (P.T @ u), launch=launch, q0=lambda u: P.T @ u)
+                           rows=rows, span=[P], ref=ref, projected=lambda proj, b, u: P @ (P.T @ u), launch=launch, facade=facade,
+                           q0=lambda u: P.T @ u)
 
 
 def quad_case(entry, case, run, left_out=None, steps=STEP):
@@ -117,30 +145,35 @@ def quad_case(entry, case, run, left_out=None, steps=STEP):
     X, Phi, H = hq.case_data(case)
     rows = None if left_out is None else np.setdiff1d(np.arange(N), left_out)
 
-    def ref(proj, b, start, f=1.0, backwards=False):
+    def ref(proj, b, start, f=1.0, backwards=False, tol=None, max_it=None):
         if rows is None:
-            U, it = br.pod_quadratic_manifold(X, dt, NT, start, MU1[b], E, MU2[b], Phi, H, projection=proj, newton_tol=1e-6 * f,
-                                              return_iters=True)
+            U, it = br.pod_quadratic_manifold(X, dt, NT, start, MU1[b], E, MU2[b], Phi, H, projection=proj, return_iters=True,
+                                              **controls(tol, max_it, f, NEWTON))
             return U, it, {}
-        Q, it = hq.hyper_quad_prom(X, dt, NT, start, MU1[b], E, MU2[b], Phi, H, proj, rows, np.ones(len(rows)), tol=1e-6 * f,
-                                   backwards=backwards)
+        Q, it = hq.hyper_quad_prom(X, dt, NT, start, MU1[b], E, MU2[b], Phi, H, proj, rows, np.ones(len(rows)), backwards=backwards,
+                                   **controls(tol, max_it, f))
         return hq.decode(Phi, H, Q, start), it, {"Q": Q}
 
     def projected(proj, b, u):
         q = Phi.T @ u
         return Phi @ q + H @ br.get_sym(q)
 
-    def launch(proj, u0):
+    def launch(proj, u0, tol=None, max_it=None, mu=None, balance=True):
         from burgers_hip import rom
+        kw = controls(tol, max_it, names=NEWTON)
         if run == "fused":
             plan = rom.QuadFusedPlan(Phi, H, torch.device("cuda", torch.cuda.current_device()))
-            return rom.quadratic_run_fused(X, u0, MU1, MU2, dt, NT, plan, _p(proj), E=E)
+            return rom.quadratic_run_fused(X, u0, *_mu(mu), dt, NT, plan, _p(proj), E=E, balance=balance, **kw)
         if run == "long":
-            return rom.quadratic_run_long(X, u0, MU1, MU2, dt, NT, (Phi, H), _p(proj), E=E)
-        return rom.quadratic_run_hyper(X, u0, MU1, MU2, dt, NT, Phi, H, unit_sampling(rows, proj), _p(proj), E=E)
+            return rom.quadratic_run_long(X, u0, *_mu(mu), dt, NT, (Phi, H), _p(proj), E=E, balance=balance, **kw)
+        return rom.quadratic_run_hyper(X, u0, *_mu(mu), dt, NT, Phi, H, unit_sampling(rows, proj), _p(proj), E=E, balance=balance, **kw)
+
+    def facade(proj, u0, tol=None, max_it=None):
+        from burgers_hip import rom
+        return rom.quadratic_run(X, u0, MU1, MU2, dt, NT, Phi, H, projection=proj, E=E, long_mesh=True, **controls(tol, max_it, names=NEWTON))
 
     return SimpleNamespace(entry=entry, family="quadratic", X=X, u0=initial_states(N, dt, E, seed, B, steps), nT=NT, cap=hq.CAP, gate=TOL,
-                           rows=rows, span=[Phi], ref=ref, projected=projected, launch=launch, q0=lambda u: Phi.T @ u)
+                           rows=rows, span=[Phi], ref=ref, projected=projected, launch=launch, facade=facade, q0=lambda u: Phi.T @ u)
 
 
 ANN_WIDE = (96, 0.05, 12, 40, (64,), 112, 3.0, 0.01, 7)         # perturbed-96 with 12 primary modes: beyond bg_ann_rom_run's 8
@@ -153,26 +186,32 @@ def ann_case(entry, case, run, left_out=None, steps=STEP):
     Ws, bs = aw.weights(model)
     rows = None if left_out is None else np.setdiff1d(np.arange(N), left_out)
 
-    def ref(proj, b, start, f=1.0, backwards=False):
+    def ref(proj, b, start, f=1.0, backwards=False, tol=None, max_it=None):
+        kw = controls(tol, max_it, f)
         if rows is None:
-            U, it = br.pod_ann_prom(X, dt, NT, start, MU1[b], E, MU2[b], Up, Us, Ws, bs, projection=proj, tol=1e-6 * f, return_iters=True)
+            U, it = br.pod_ann_prom(X, dt, NT, start, MU1[b], E, MU2[b], Up, Us, Ws, bs, projection=proj, return_iters=True, **kw)
             return U, it, {}
         Q, Qs, it = har.hyper_ann_prom(X, dt, NT, start, MU1[b], E, MU2[b], Up, Us, Ws, bs, proj, rows, np.ones(len(rows)),
-                                       tol=1e-6 * f, backwards=backwards)
+                                       backwards=backwards, **kw)
         return har.decode(Up, Us, Q, Qs, start), it, {"Q": Q}
 
     def projected(proj, b, u):
         q = Up.T @ u
         return Up @ q + Us @ br.mlp_forward(Ws, bs, q.astype(np.float32)).astype(np.float64)
 
-    def launch(proj, u0):
+    def launch(proj, u0, tol=None, max_it=None, mu=None, balance=True):
         from burgers_hip import rom
+        kw = controls(tol, max_it)
         if rows is None:
-            return getattr(rom, run)(X, u0, MU1, MU2, dt, NT, Up, Us, model, _p(proj), E=E)
-        return rom.pod_ann_run_hyper(X, u0, MU1, MU2, dt, NT, Up, Us, model, unit_sampling(rows, proj), _p(proj), E=E)
+            return getattr(rom, run)(X, u0, *_mu(mu), dt, NT, Up, Us, model, _p(proj), E=E, balance=balance, **kw)
+        return rom.pod_ann_run_hyper(X, u0, *_mu(mu), dt, NT, Up, Us, model, unit_sampling(rows, proj), _p(proj), E=E, balance=balance, **kw)
+
+    def facade(proj, u0, tol=None, max_it=None):
+        from burgers_hip import rom
+        return rom.pod_ann_run(X, u0, MU1, MU2, dt, NT, Up, Us, model, projection=proj, E=E, wide=True, **controls(tol, max_it))
 
     return SimpleNamespace(entry=entry, family="POD-ANN", X=X, u0=initial_states(N, dt, E, seed, B, steps), nT=NT, cap=50, gate=aw.TOL32,
-                           rows=rows, span=[Up], ref=ref, projected=projected, launch=launch, q0=lambda u: Up.T @ u)
+                           rows=rows, span=[Up], ref=ref, projected=projected, launch=launch, facade=facade, q0=lambda u: Up.T @ u)
 
 
 @functools.lru_cache(maxsize=None)
@@ -202,27 +241,33 @@ def rbf_case(entry, shape, kernel, run, left_out=None, steps=STEP, fitted=False)
     Up, Us = cl[0], cl[1]
     rows = None if left_out is None else np.setdiff1d(np.arange(N), left_out)
 
-    def ref(proj, b, start, f=1.0, backwards=False):
+    def ref(proj, b, start, f=1.0, backwards=False, tol=None, max_it=None):
         if rows is None:
-            U, it = br.pod_rbf_prom(X, dt, NT, start, MU1[b], E, MU2[b], *cl, projection=proj, kernel=kernel, tol_newton=1e-6 * f,
-                                    return_iters=True)
+            U, it = br.pod_rbf_prom(X, dt, NT, start, MU1[b], E, MU2[b], *cl, projection=proj, kernel=kernel, return_iters=True,
+                                    **controls(tol, max_it, f, RBF))
             return U, it, {}
-        Q, Qs, it = hrr.hyper_rbf_prom(X, dt, NT, start, MU1[b], E, MU2[b], *cl, proj, kernel, rows, np.ones(len(rows)), tol=1e-6 * f,
-                                       backwards=backwards)
+        Q, Qs, it = hrr.hyper_rbf_prom(X, dt, NT, start, MU1[b], E, MU2[b], *cl, proj, kernel, rows, np.ones(len(rows)),
+                                       backwards=backwards, **controls(tol, max_it, f))
         return hrr.decode(Up, Us, Q, Qs, start), it, {"Q": Q}
 
     def projected(proj, b, u):
         q = Up.T @ u
         return Up @ q + Us @ br.rbf_value(q, cl[2], cl[3], cl[4], kernel, *cl[5:])
 
-    def launch(proj, u0):
+    def launch(proj, u0, tol=None, max_it=None, mu=None, balance=True):
         from burgers_hip import rom
+        kw = controls(tol, max_it, names=RBF)
         if rows is None:
-            return getattr(rom, run)(X, u0, MU1, MU2, dt, NT, *cl, projection=proj, kernel=kernel, E=E)
-        return rom.pod_rbf_run_hyper(X, u0, MU1, MU2, dt, NT, *cl, unit_sampling(rows, proj), _p(proj), kernel=kernel, E=E)
+            return getattr(rom, run)(X, u0, *_mu(mu), dt, NT, *cl, projection=proj, kernel=kernel, E=E, balance=balance, **kw)
+        return rom.pod_rbf_run_hyper(X, u0, *_mu(mu), dt, NT, *cl, unit_sampling(rows, proj), _p(proj), kernel=kernel, E=E, balance=balance, **kw)
+
+    def facade(proj, u0, tol=None, max_it=None):
+        from burgers_hip import rom
+        return rom.pod_rbf_run(X, u0, MU1, MU2, dt, NT, *cl, projection=proj, kernel=kernel, E=E, fused=True, long_mesh=True,
+                               **controls(tol, max_it, names=RBF))
 
     return SimpleNamespace(entry=entry, family="POD-RBF", X=X, u0=initial_states(N, dt, E, seed, B, steps), nT=NT, cap=30, gate=TOL,
-                           rows=rows, span=[Up], ref=ref, projected=projected, launch=launch, q0=lambda u: Up.T @ u)
+                           rows=rows, span=[Up], ref=ref, projected=projected, launch=launch, facade=facade, q0=lambda u: Up.T @ u)
 
 
 def local_case(entry, shape, run, left_out=None, steps=LOCAL_STEPS):
@@ -237,27 +282,36 @@ def local_case(entry, shape, run, left_out=None, steps=LOCAL_STEPS):
         two = np.sort(d2)[:2]
         return int(np.argmin(d2)), float((two[1] - two[0]) / two[1])
 
-    def ref(proj, b, start, f=1.0, backwards=False):
+    def ref(proj, b, start, f=1.0, backwards=False, tol=None, max_it=None):
+        kw = controls(tol, max_it, f)
         if rows is None:
             U, it, cl = br.local_prom_burgers(X, dt, NT_LOCAL, start, MU1[b], E, MU2[b], centres, bases, Ug, hl.MG, projection=proj,
-                                              tol=1e-6 * f, return_iters=True)
+                                              return_iters=True, **kw)
             return U, it, {"clusters": cl, "margin": first_pick(start)[1]}
         U, Q, it, cl, margin = hl.hyper_local_prom(X, dt, NT_LOCAL, start, MU1[b], E, MU2[b], centres, bases, Ug, hl.MG, proj, rows,
-                                                   np.ones(len(rows)), tol=1e-6 * f, backwards=backwards)
+                                                   np.ones(len(rows)), backwards=backwards, **kw)
         return U, it, {"Q": Q, "clusters": cl, "margin": margin}
 
     def projected(proj, b, u):
         P = bases[first_pick(u)[0]]
         return P @ (P.T @ u)
 
-    def launch(proj, u0):
+    def launch(proj, u0, tol=None, max_it=None, mu=None, balance=True):
         from burgers_hip import rom
+        kw = controls(tol, max_it)
         if rows is None:
-            return getattr(rom, run)(X, u0, MU1, MU2, dt, NT_LOCAL, centres, bases, Ug, hl.MG, projection=proj, E=E)
-        return rom.local_prom_run_hyper(X, u0, MU1, MU2, dt, NT_LOCAL, centres, bases, Ug, hl.MG, unit_sampling(rows, proj), _p(proj), E=E)
+            return getattr(rom, run)(X, u0, *_mu(mu), dt, NT_LOCAL, centres, bases, Ug, hl.MG, projection=proj, E=E, balance=balance, **kw)
+        return rom.local_prom_run_hyper(X, u0, *_mu(mu), dt, NT_LOCAL, centres, bases, Ug, hl.MG, unit_sampling(rows, proj), _p(proj), E=E,
+                                        balance=balance, **kw)
+
+    def facade(proj, u0, tol=None, max_it=None):
+        from burgers_hip import rom
+        return rom.local_prom_run(X, u0, MU1, MU2, dt, NT_LOCAL, centres, bases, Ug, hl.MG, projection=proj, E=E, fused=True, long_mesh=True,
+                                  **controls(tol, max_it))
 
     return SimpleNamespace(entry=entry, family="local", X=X, u0=initial_states(N, dt, E, seed, B, steps), nT=NT_LOCAL, cap=20,
-                           gate=TOL, rows=rows, span=list(bases.values()), ref=ref, projected=projected, launch=launch, bases=bases, q0=None)
+                           gate=TOL, rows=rows, span=list(bases.values()), ref=ref, projected=projected, launch=launch, facade=facade,
+                           bases=bases, q0=None)
 
 
 def moved(steps):
@@ -280,21 +334,28 @@ CASES = {
     "bg_rom_run_long_wide-77": lambda: pod_case("bg_rom_run_long_wide", (513, 0.05, 0.0, None), 77, "pod_prom_run_long_wide"),
     "bg_hyper_rom_run": lambda: pod_case("bg_hyper_rom_run", PERTURBED, 17, None, left_out=LEFT_OUT),
     "bg_hyper_rom_run_wide-41": lambda: pod_case("bg_hyper_rom_run_wide", PERTURBED_WIDE, 41, None, left_out=LEFT_OUT + [158]),
-    "bg_hyper_rom_run_wide-64": lambda: pod_case("bg_hyper_rom_run_wide", (200, 0.08, 0.0, None), 64, None, left_out=LEFT_OUT + [198]),
+    # sample 2 at step 70: at tol = 1e-9 a Galerkin count sits within 1.001 of the edge (test_rom_controls_gpu.py, condition 2)
+    "bg_hyper_rom_run_wide-64": lambda: pod_case("bg_hyper_rom_run_wide", (200, 0.08, 0.0, None), 64, None, left_out=LEFT_OUT + [198],
+                                                 steps=moved({2: 72})),
     # the quadratic manifold: pod_quadratic_manifold, and tests/hyper_quad_ref.py
     "bg_quad_rom_run": lambda: quad_case("bg_quad_rom_run", "perturbed-96", "fused"),
     "bg_quad_rom_run_long": lambda: quad_case("bg_quad_rom_run_long", (513, 0.05, 21, 0.0, None), "long"),
     "bg_hyper_quad_rom_run": lambda: quad_case("bg_hyper_quad_rom_run", "perturbed-96", "hyper", left_out=LEFT_OUT, steps=moved({3: 98})),
     # POD-ANN: pod_ann_prom, and tests/hyper_ann_ref.py
-    "bg_ann_rom_run": lambda: ann_case("bg_ann_rom_run", "perturbed-96", "pod_ann_run_fused"),
+    # sample 5 at step 145 (both loops on perturbed-96): the LSPG run capped at two iterations amplifies a 1e-6 perturbation of
+    # u0 by 130 (bg_hyper_ann_rom_run: 3200), the others by less than 1 (test_rom_controls_gpu.py, condition 3)
+    "bg_ann_rom_run": lambda: ann_case("bg_ann_rom_run", "perturbed-96", "pod_ann_run_fused", steps=moved({5: 150})),
     "bg_ann_rom_run_wide": lambda: ann_case("bg_ann_rom_run_wide", ANN_WIDE, "pod_ann_run_wide", steps=moved({3: 98})),
-    "bg_hyper_ann_rom_run": lambda: ann_case("bg_hyper_ann_rom_run", "perturbed-96", None, left_out=LEFT_OUT, steps=moved({0: 25, 4: 125})),
+    "bg_hyper_ann_rom_run": lambda: ann_case("bg_hyper_ann_rom_run", "perturbed-96", None, left_out=LEFT_OUT,
+                                                 steps=moved({0: 25, 4: 125, 5: 150})),
     # POD-RBF, both kernels: pod_rbf_prom, and tests/hyper_rbf_ref.py
     "bg_rbf_rom_run-gaussian": lambda: rbf_case("bg_rbf_rom_run", RBF_96, "gaussian", "pod_rbf_run_fused", steps=moved({3: 90})),
     "bg_rbf_rom_run-imq": lambda: rbf_case("bg_rbf_rom_run", RBF_96, "imq", "pod_rbf_run_fused"),
     "bg_rbf_rom_run_long-gaussian": lambda: rbf_case("bg_rbf_rom_run_long", (513, 0.05, 0.0, None), "gaussian", "pod_rbf_run_long", fitted=True),
+    # sample 1: 52, not the 50 that cleared this file's conditions: at 50 an LSPG count at tol = 1e-9 sits on the edge
+    # (test_rom_controls_gpu.py, condition 2)
     "bg_rbf_rom_run_long-imq": lambda: rbf_case("bg_rbf_rom_run_long", (513, 0.05, 0.0, None), "imq", "pod_rbf_run_long", fitted=True,
-                                                steps=moved({1: 50})),
+                                                steps=moved({1: 52})),
     "bg_hyper_rbf_rom_run-gaussian": lambda: rbf_case("bg_hyper_rbf_rom_run", RBF_96, "gaussian", None, left_out=LEFT_OUT,
                                                       steps=moved({3: 90, 5: 150})),
     "bg_hyper_rbf_rom_run-imq": lambda: rbf_case("bg_hyper_rbf_rom_run", RBF_96, "imq", None, left_out=LEFT_OUT),
