@@ -137,6 +137,11 @@ _SIGNATURES = {
     # N, B, n, nbar, m, nodes, nsteps, projection, node, xn, pos, xi, UTn, q0, u0n, mu1, mu2, the MLP, the step, qhist, qshist, ...
     "bg_hyper_ann_rom_run": (ctypes.c_int, [ctypes.c_int] * 8 + [c_int_p, c_double_p, c_int_p] + [c_double_p] * 6 + _ANN_MLP +
                              _LOOP_STEP + [c_double_p] + _LOOP_OUT),
+    "bg_hyper_ann_rom_wide_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 6),
+    "bg_hyper_ann_rom_wide_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
+    "bg_hyper_ann_rom_wide_ut_ld": (ctypes.c_int, [ctypes.c_int]),
+    "bg_hyper_ann_rom_run_wide": (ctypes.c_int, [ctypes.c_int] * 8 + [c_int_p, c_double_p, c_int_p] + [c_double_p] * 6 + _ANN_MLP +
+                                  _LOOP_STEP + [c_double_p] + _LOOP_OUT),      # as bg_hyper_ann_rom_run
     "bg_hyper_rbf_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 5),
     "bg_hyper_rbf_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
     "bg_hyper_rbf_rom_ut_ld": (ctypes.c_int, [ctypes.c_int]),

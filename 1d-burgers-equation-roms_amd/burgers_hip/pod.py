@@ -788,6 +788,7 @@ for _name, _symbol, _count, _doc in (
         ("hyper_rom_limits", "bg_hyper_rom_limits", 2, "(max_r, max_m) of bg_hyper_rom_run"),
         ("hyper_wide_rom_limits", "bg_hyper_rom_wide_limits", 2, "(max_r, max_m) of bg_hyper_rom_run_wide"),
         ("hyper_ann_rom_limits", "bg_hyper_ann_rom_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run"),
+        ("hyper_ann_wide_rom_limits", "bg_hyper_ann_rom_wide_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run_wide"),
         ("hyper_quad_rom_limits", "bg_hyper_quad_rom_limits", 3, "(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run"),
         ("hyper_local_rom_limits", "bg_hyper_local_rom_limits", 4, "(max_r, max_m, max_mg, max_clusters) of bg_hyper_local_rom_run"),
         ("hyper_rbf_rom_limits", "bg_hyper_rbf_rom_limits", 5, "(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run")):
@@ -891,7 +892,7 @@ def _manifold_row_sampling_system(who, X, P, S, lift, tangents, runs, dt, projec
     return _stack_contributions(blocks, who)
 
 
-# ---- row sampling for the hyper-reduced POD-ANN PROM (rom.pod_ann_run_hyper, bg_hyper_ann_rom_run) ----
+# ---- row sampling for the hyper-reduced POD-ANN PROM (rom.pod_ann_run_hyper, bg_hyper_ann_rom_run and _run_wide) ----
 def ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg=True, stride=10):
     """(G, pairs): the training matrix of build_ann_row_sampling, (pairs n, N).  ``X``, ``U_p``, ``U_s``: host arrays;
     ``model``: the closure, evaluated on the host in float32 (value and Jacobian, as the PROM evaluates them)."""
@@ -905,7 +906,8 @@ def ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E=0.0, sup
 
 def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None,
                            max_rows=None):
-    """build_row_sampling for the POD-ANN PROM (rom.pod_ann_run_hyper): the same host NNLS (nnls_rows, row 0 forced in with
+    """build_row_sampling for the POD-ANN PROM (rom.pod_ann_run_hyper: bg_hyper_ann_rom_run for n <= 8 primary modes, and
+    rom.pod_ann_run_hyper_wide: bg_hyper_ann_rom_run_wide for n <= 20): the same host NNLS (nnls_rows, row 0 forced in with
     weight 1) on training pairs that lie on the closure manifold.  For every run (hist (N, nT+1), mu1, mu2) and every
     ``stride``-th step n: q_n = U_p^T s_n, Un = U_p q_n + U_s N(q_n), U0 likewise at n + 1, and the contributions
     c_i = w_i R_i of all mesh rows (picard_rows) with the tangent W = U_p + U_s dN(q_{n+1}): w_i = W[i] for "galerkin",
@@ -916,7 +918,8 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
     the sampled iteration stayed within 6.4e-4 / 2.6e-3 (rel-L2, 40 steps) of the full PROM at mu = (4.6, 0.021) and
     (5.3, 0.017), with no divergence, no capped step that the full PROM does not have (the first LSPG step caps in both)
     and iteration totals within 1 of the full PROM's; the default was therefore left at 3 n.  A closure whose fit is met by few rows may need more: at N = 2049 a random closure ran with
-    ``min_rows`` = 120.  ``max_rows`` defaults to the kernel's limit (hyper_ann_rom_limits); needing more is a ValueError.
+    ``min_rows`` = 120.  ``max_rows`` defaults to the limit of the loop that takes n (hyper_ann_rom_limits, or
+    hyper_ann_wide_rom_limits beyond its n); needing more is a ValueError.
     Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
     projection, X = _sampling_prelude("build_ann_row_sampling", X, projection, runs, tau, stride)
     U_p, U_s = _host_matrix(U_p), _host_matrix(U_s)
@@ -924,7 +927,9 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
     if U_p.ndim != 2 or U_s.ndim != 2 or U_p.shape[0] != N or U_s.shape[0] != N:
         raise ValueError("U_p and U_s must have one row per mesh node")
     min_rows = min(3 * U_p.shape[1], N) if min_rows is None else int(min_rows)
-    max_rows = hyper_ann_rom_limits()[4] if max_rows is None else int(max_rows)
+    if max_rows is None:         # the limit of the loop that takes this n
+        max_rows = (hyper_ann_rom_limits() if U_p.shape[1] <= hyper_ann_rom_limits()[0] else hyper_ann_wide_rom_limits())[4]
+    max_rows = int(max_rows)
     G, pairs = ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E, supg, stride)
     return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
 

@@ -66,6 +66,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
     _Route("bg_hyper_rom_run_wide", 1, min_n=3, max_n="bg_fom_max_n", redo=True),
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
+    _Route("bg_hyper_ann_rom_run_wide", 2, min_n=3, max_n="bg_fom_max_n"), # likewise (HyperAnnWidePlan.wg_per_cu)
     _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
     _Route("bg_hyper_quad_rom_run", 1, "bg_quad_rom_max_n", 3, "bg_fom_max_n", group=4, supg=False),
     _Route("bg_hyper_local_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
@@ -1557,6 +1558,23 @@ class _HyperClosurePlan:
         self.UTn = _as_dev(UTn, device)
         return device
 
+    def _build_ann(self, entry, limits, U_p, U_s, model, sampling, X, device, workgroups_per_cu, ut_shape):
+        """HyperAnnPlan and HyperAnnWidePlan: the checks against the six ``limits`` of ``entry``, the model, the table and the
+        packed closure.  ``workgroups_per_cu(L, nodes)``, ``ut_shape(L, n + nbar, nodes)``: the entry point's own."""
+        route = _ROUTES[entry]
+        max_n, max_nbar, max_w, max_l, max_m, max_nodes = _lib.limits(limits, 6)
+        Up, Us, Xh, rows, xi = self._check_sizes(route, U_p, U_s, sampling, X, max_n, max_nbar, max_m)
+        n, nbar = Up.shape[1], Us.shape[1]
+        if not isinstance(model, nn.Module) or any(p.dtype != torch.float32 for p in model.parameters()):
+            raise ValueError("the closure must be a plain float32 MLP (torch.nn.Module)")
+        layers = _ann_model_layers(model, n, nbar, limits, 6)
+        if layers is None:
+            raise ValueError(f"the closure must be a plain float32 MLP ({n}) -> ({nbar}) of Linear / ELU / ReLU / Tanh layers with "
+                             f"widths <= {max_w} and at most {max_l} layers")
+        device = self._pack_table(route, Up, Us, Xh, rows, xi, sampling, max_nodes, device,
+                                  lambda k: workgroups_per_cu(_lib.load(), k), lambda k: ut_shape(_lib.load(), n + nbar, k))
+        self.model = _ann_model_pack(layers, device)
+
 
 class HyperAnnPlan(_HyperClosurePlan):
     """What bg_hyper_ann_rom_run reads besides the batch, built once per bases, closure, sampling and mesh
@@ -1568,20 +1586,21 @@ class HyperAnnPlan(_HyperClosurePlan):
     from step to step instead of re-projecting U_p^T u^n, which is exact only for orthonormal bases."""
 
     def __init__(self, U_p, U_s, model, sampling, X, device):
-        route = _ROUTES["bg_hyper_ann_rom_run"]
-        max_n, max_nbar, max_w, max_l, max_m, max_nodes = _lib.limits("bg_hyper_ann_rom_limits", 6)
-        Up, Us, Xh, rows, xi = self._check_sizes(route, U_p, U_s, sampling, X, max_n, max_nbar, max_m)
-        n, nbar = Up.shape[1], Us.shape[1]
-        if not isinstance(model, nn.Module) or any(p.dtype != torch.float32 for p in model.parameters()):
-            raise ValueError("the closure must be a plain float32 MLP (torch.nn.Module)")
-        layers = _ann_model_layers(model, n, nbar, "bg_hyper_ann_rom_limits", 6)
-        if layers is None:
-            raise ValueError(f"the closure must be a plain float32 MLP ({n}) -> ({nbar}) of Linear / ELU / ReLU / Tanh layers with "
-                             f"widths <= {max_w} and at most {max_l} layers")
-        device = self._pack_table(route, Up, Us, Xh, rows, xi, sampling, max_nodes, device,
-                                  lambda k: _lib.load().bg_hyper_ann_rom_workgroups_per_cu(k),
-                                  lambda k: (-(-(n + nbar) // 8) * 8, k))
-        self.model = _ann_model_pack(layers, device)
+        self._build_ann("bg_hyper_ann_rom_run", "bg_hyper_ann_rom_limits", U_p, U_s, model, sampling, X, device,
+                        lambda L, k: L.bg_hyper_ann_rom_workgroups_per_cu(k),
+                        lambda L, rows, k: (-(-rows // 8) * 8, k))
+
+
+class HyperAnnWidePlan(_HyperClosurePlan):
+    """What bg_hyper_ann_rom_run_wide reads besides the batch: a HyperAnnPlan against the wide loop's limits (n <= 20,
+    bg_hyper_ann_rom_wide_limits) with UTn in its layout, [n + nbar] rows of the stride bg_hyper_ann_rom_wide_ut_ld gives, zero
+    from ``nodes``.  Takes any model inside those limits, the n <= 8 ones included.  The refusals are HyperAnnPlan's, each a
+    ValueError before the device is touched."""
+
+    def __init__(self, U_p, U_s, model, sampling, X, device):
+        self._build_ann("bg_hyper_ann_rom_run_wide", "bg_hyper_ann_rom_wide_limits", U_p, U_s, model, sampling, X, device,
+                        lambda L, k: L.bg_hyper_ann_rom_wide_workgroups_per_cu(k),
+                        lambda L, rows, k: (rows, L.bg_hyper_ann_rom_wide_ut_ld(k)))
 
 
 class HyperClosureRomResult(_HyperResult):
@@ -1623,10 +1642,35 @@ def pod_ann_run_hyper(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_
     (bg_hyper_ann_rom_limits).  q_p carries over from step to step (no U_p^T u^n: the bases must be orthonormal).
     ``sampling_or_plan``: the sampling, or a HyperAnnPlan of these bases, closure, sampling and mesh to reuse across calls
     (``res.plan``; ``U_p``, ``U_s`` and ``model`` are then not looked at).  A sampling trained for the other projection is
-    refused.  Nothing is synchronised.  Returns a HyperAnnRomResult."""
+    refused.  Nothing is synchronised.  Returns a HyperAnnRomResult.
+    A HyperAnnWidePlan, or a sampling with a model of more than bg_hyper_ann_rom_limits' n primary modes inside
+    bg_hyper_ann_rom_wide_limits (n <= 20), goes to the wide loop (pod_ann_run_hyper_wide)."""
+    if isinstance(sampling_or_plan, HyperAnnWidePlan) or (
+            not isinstance(sampling_or_plan, HyperAnnPlan) and len(np.shape(U_p)) == 2
+            and _lib.limits("bg_hyper_ann_rom_limits", 6)[0] < np.shape(U_p)[1] <= _lib.limits("bg_hyper_ann_rom_wide_limits", 6)[0]):
+        return pod_ann_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_plan, proj, E, tol, max_it, device,
+                                      options, balance)
     Xh = check_mesh(X)
     plan = sampling_or_plan if isinstance(sampling_or_plan, HyperAnnPlan) else HyperAnnPlan(U_p, U_s, model, sampling_or_plan, Xh, device)
     return _hyper_closure_run(_ROUTES["bg_hyper_ann_rom_run"], plan, Xh, u0, mu1, mu2, nsteps, proj, device, options, balance,
+                              lambda N, B, nsteps, proj, q0, u0n, inputs: (
+                                  N, B, plan.n, plan.nbar, plan.m, plan.n_nodes, nsteps, proj, _lib.ptr(plan.node), _lib.ptr(plan.xn),
+                                  _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn), q0, u0n, *inputs[1:], *plan.model.args,
+                                  float(dt), float(E), float(tol), int(max_it)))
+
+
+def pod_ann_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=50,
+                           device=None, options=0, balance=True):
+    """pod_ann_run_hyper for models of up to 20 primary modes (bg_hyper_ann_rom_run_wide, bg_hyper_ann_rom_wide_limits): the
+    loop of bg_ann_rom_run_wide on the table of the sampled rows' stencil nodes.  Runs any model inside those limits, the
+    n <= 8 ones included; what it does not cover is a ValueError.  ``sampling_or_plan``: the sampling, or a HyperAnnWidePlan to
+    reuse across calls (``res.plan``).  Nothing is synchronised.  Returns a HyperClosureRomResult."""
+    Xh = check_mesh(X)
+    if isinstance(sampling_or_plan, HyperAnnPlan):
+        raise ValueError("bg_hyper_ann_rom_run_wide takes a HyperAnnWidePlan")
+    plan = (sampling_or_plan if isinstance(sampling_or_plan, HyperAnnWidePlan)
+            else HyperAnnWidePlan(U_p, U_s, model, sampling_or_plan, Xh, device))
+    return _hyper_closure_run(_ROUTES["bg_hyper_ann_rom_run_wide"], plan, Xh, u0, mu1, mu2, nsteps, proj, device, options, balance,
                               lambda N, B, nsteps, proj, q0, u0n, inputs: (
                                   N, B, plan.n, plan.nbar, plan.m, plan.n_nodes, nsteps, proj, _lib.ptr(plan.node), _lib.ptr(plan.xn),
                                   _lib.ptr(plan.pos), _lib.ptr(plan.xi), _lib.ptr(plan.UTn), q0, u0n, *inputs[1:], *plan.model.args,
@@ -1666,9 +1710,10 @@ def pod_ann_run(X, u0, mu1, mu2, dt, nsteps, U_p, U_s, model, projection="LSPG",
     ``wide`` (opt-in, with ``fused`` and float32): a model with more primary modes than bg_ann_rom_limits allows that is
     inside bg_ann_rom_run_wide_limits (n <= 20) takes the device-side loop bg_ann_rom_run_wide instead of the host-driven
     iteration; every other model routes as without the flag.
-    ``hyper`` (opt-in): a pod.RowSampling (pod.build_ann_row_sampling) or a HyperAnnPlan sends the call through the
-    hyper-reduced loop pod_ann_run_hyper, which assembles both projections from the sampled mesh rows only; models, bases
-    and sizes it does not cover are refused, not rerouted."""
+    ``hyper`` (opt-in): a pod.RowSampling (pod.build_ann_row_sampling), a HyperAnnPlan or a HyperAnnWidePlan sends the call
+    through the hyper-reduced loop pod_ann_run_hyper, which assembles both projections from the sampled mesh rows only
+    (bg_hyper_ann_rom_run; a sampling with 9 <= n <= 20 primary modes and a HyperAnnWidePlan: bg_hyper_ann_rom_run_wide); models,
+    bases and sizes it does not cover are refused, not rerouted."""
     proj = _projection(projection, "projection must be 'Galerkin' or 'LSPG'")
     if hyper is not None:
         if ann_dtype != torch.float32:

@@ -1,7 +1,7 @@
 // rom_ann_device.hpp -- the closure MLP of the POD-ANN time loops: its limits, its part of the kernel arguments, the host-side
 // check that fills it, and the float32 forward-mode layer loop.
-// Used by rom_ann_fused.hip (bg_ann_rom_run, 8 outputs per thread) and rom_ann_wide.hip (bg_ann_rom_run_wide, 4 outputs per
-// thread).  The kernels keep the input set-up, the tables they build from the outputs, the LDS overlays, the opaque
+// Used by rom_ann_fused.hip (bg_ann_rom_run, 8 outputs per thread) and rom_ann_wide_loop_device.hpp (bg_ann_rom_run_wide and
+// bg_hyper_ann_rom_run_wide, 4 outputs per thread).  The kernels keep the input set-up, the tables they build from the outputs, the LDS overlays, the opaque
 // re-derivation of the thread indices, the issue priorities and the loops.
 #pragma once
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // rom_closure_device.hpp -- the mesh side of the closure ROM time loops (one workgroup per sample): what a reduced
 // coordinate q_p and the nbar x 4 NB closure table s_J in LDS drive, whatever closure filled them.
-// Used by rom_rbf_loop_device.hpp (POD-RBF: bg_rbf_rom_run, bg_rbf_rom_run_long, bg_hyper_rbf_rom_run) and rom_ann_wide.hip
-// (POD-ANN: bg_ann_rom_run_wide).
+// Used by rom_rbf_loop_device.hpp (POD-RBF: bg_rbf_rom_run, bg_rbf_rom_run_long, bg_hyper_rbf_rom_run) and
+// rom_ann_wide_loop_device.hpp (POD-ANN: bg_ann_rom_run_wide, bg_hyper_ann_rom_run_wide).
 // The pieces take LDS arrays and scalars, not a kernel-args struct.  NT: threads of the workgroup, NW = NT / 64 its waves,
 // NIT: rows per thread of the strided loops, UT_LD: row stride of UT ([n + nbar][UT_LD]: U_p^T, then U_s^T, zero from N).
 // The per-row loops are kept rolled (#pragma unroll 1): unrolled they take registers from the projection.

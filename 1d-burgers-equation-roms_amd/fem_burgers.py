@@ -137,7 +137,9 @@ class FEMBurgers:
         9 .. 20 primary modes takes the device-side loop bg_ann_rom_run_wide instead of the host-driven iteration.
         ``hyper``: a row sampling (burgers_hip.pod.build_ann_row_sampling) or a rom.HyperAnnPlan sends the call through the
         hyper-reduced device-side loop bg_hyper_ann_rom_run, which assembles both projections from the sampled mesh rows
-        only (any mesh the FOM takes, a plain float32 MLP with at most 8 primary modes, at most 256 rows)."""
+        only (any mesh the FOM takes, a plain float32 MLP with at most 8 primary modes, at most 256 rows); a sampling with a
+        model of 9 .. 20 primary modes, or a rom.HyperAnnWidePlan, goes through bg_hyper_ann_rom_run_wide, the same loop for
+        up to 20 primary modes."""
         import copy
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_ann_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),

@@ -448,6 +448,39 @@ int bg_hyper_ann_rom_run(int N, int B, int n, int nbar, int m, int nodes, int ns
                          double E, double tol, int max_it, int options, double *qhist, double *qshist, int32_t *iters,
                          int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_hyper_ann_rom_run_wide -- bg_hyper_ann_rom_run for up to 20 primary modes (the reference's second POD-ANN model:
+ *   n = 17, nbar = 79), 3 <= N <= bg_fom_max_n().  reference: FEM/fem_burgers.py:1177-1251, 1254-1275 with the sums over
+ *   mesh rows restricted and weighted and without the re-projection q_p = U_p^T u^n at the start of a step.  Opt-in:
+ *   nothing routes here unless asked (burgers_hip/rom.py, pod_ann_run_hyper_wide; hyper= of pod_ann_run and of the facade
+ *   send a sampling of a model with more than 8 primary modes here).
+ *   Arguments, order, types, semantics and return codes are bg_hyper_ann_rom_run's, with these differences:
+ *   UTn    [n + nbar][ut_ld], ut_ld = bg_hyper_ann_rom_wide_ut_ld(nodes) (512 up to 512 nodes, 768 beyond), 16-byte
+ *          aligned: the rows of bg_ann_rom_run_wide's UT = [U_p^T; U_s^T] restricted to the table nodes, zero columns
+ *          from nodes (the layout of bg_hyper_rbf_rom_run, not the row-padded one of bg_hyper_ann_rom_run);
+ *   options BG_OPT_NO_TANGENT_REUSE is accepted and changes nothing: as in bg_ann_rom_run_wide the tangent is evaluated
+ *          at the first pass of every step, at the q_p carried over;
+ *   a sampled row whose neighbour the table does not hold is left out.
+ *   The stopping rule is bg_ann_rom_run_wide's, |dq| / (|q_p| + 1e-14).
+ *   Limits (bg_hyper_ann_rom_wide_limits): n <= 20, nbar <= 128, widths <= 256, layers <= 8, m <= 256, nodes <= 768.
+ *   Checked in this order: N < 3, n, nbar, m, nodes or n_layers < 1, B or nsteps < 0, max_it < 1, dt <= 0:
+ *   BG_ERR_BAD_ARG; an unknown projection: BG_ERR_PROJECTION; N > bg_fom_max_n(): BG_ERR_UNSUPPORTED_N; m or nodes beyond
+ *   the limits: BG_ERR_UNSUPPORTED_R; m > N or nodes outside [m, min(3 m, N)]: BG_ERR_BAD_ARG; the model beyond the limits:
+ *   BG_ERR_UNSUPPORTED_R, or not fitting its widths: BG_ERR_BAD_ARG; B = 0: BG_OK with nothing launched; a null operand or
+ *   output, UTn not 16-byte aligned: BG_ERR_BAD_ARG.  Sizes the kernel does not cover are refused, never rerouted.
+ *   One 256-thread workgroup per sample runs bg_ann_rom_run_wide's loop on the table (csrc/rom_ann_wide_loop_device.hpp,
+ *   csrc/rom_hyper_ann_wide.hip), instantiated for nodes <= 256, <= 512 and <= 768;
+ *   bg_hyper_ann_rom_wide_workgroups_per_cu(nodes) of them are resident per CU (2, 2, 1; 0: no such table). */
+int bg_hyper_ann_rom_wide_limits(int *max_n, int *max_nbar, int *max_width, int *max_layers, int *max_m, int *max_nodes);
+int bg_hyper_ann_rom_wide_workgroups_per_cu(int nodes);
+int bg_hyper_ann_rom_wide_ut_ld(int nodes);
+int bg_hyper_ann_rom_run_wide(int N, int B, int n, int nbar, int m, int nodes, int nsteps, int projection,
+                              const int32_t *node, const double *xn, const int32_t *pos, const double *xi, const double *UTn,
+                              const double *q0, const double *u0n, const double *mu1, const double *mu2, int n_layers,
+                              const int *widths, const float *const *wt, const float *const *bias, const int *acts,
+                              const float *alphas, double dt, double E, double tol, int max_it, int options, double *qhist,
+                              double *qshist, int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order,
+                              void *stream);
+
 /* bg_hyper_rbf_rom_run -- the POD-RBF PROM time loop HYPER-REDUCED: both projections of pod_rbf_prom are assembled from m
  *   sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j with the tangent
  *   W = U_p + U_s J(q_p), y_j = (A W)[i_j], R_j = (A u - b)[i_j], w_j = W[i_j] (Galerkin) or y_j (LSPG).
