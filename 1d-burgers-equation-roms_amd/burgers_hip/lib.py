@@ -28,7 +28,7 @@ BG_ERR_WORKSPACE = -7
 BG_PROJ_GALERKIN, BG_PROJ_LSPG = 0, 1
 BG_FLAG_HIT_CAP, BG_FLAG_NONFINITE = 1, 2
 BG_OPT_SUPG, BG_OPT_NONUNIFORM, BG_OPT_W_COLMAJOR, BG_OPT_MFMA_16X16, BG_OPT_FORCE_PIVOTED, BG_OPT_NO_TANGENT_REUSE = 1, 2, 4, 8, 16, 32
-BG_OPT_FOM_WIDE, BG_OPT_FOM_WAVE = 64, 128
+BG_OPT_FOM_WIDE, BG_OPT_FOM_WAVE, BG_OPT_PIVOT_ON_DEVICE = 64, 128, 256
 BG_ACT_NONE, BG_ACT_ELU, BG_ACT_RELU, BG_ACT_TANH = 0, 1, 2, 3
 BG_COUNTER_SLOTS, BG_COUNTER_STRIDE = 16, 32
 BG_RBF_GAUSSIAN, BG_RBF_IMQ = 0, 1
@@ -132,6 +132,8 @@ _SIGNATURES = {
     "bg_hyper_rom_wide_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
     "bg_hyper_rom_wide_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_hyper_rom_run_wide": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),      # as bg_hyper_rom_run
+    # B, n, A, b, x, piv (int32 or null), info (int32), stream
+    "bg_wide_solve_pivoted": (ctypes.c_int, [ctypes.c_int] * 2 + [c_double_p] * 3 + [c_int_p] * 2 + [ctypes.c_void_p]),
     "bg_hyper_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 6),
     "bg_hyper_ann_rom_workgroups_per_cu": (ctypes.c_int, [ctypes.c_int]),
     # N, B, n, nbar, m, nodes, nsteps, projection, node, xn, pos, xi, UTn, q0, u0n, mu1, mu2, the MLP, the step, qhist, qshist, ...

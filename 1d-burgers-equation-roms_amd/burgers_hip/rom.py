@@ -688,10 +688,22 @@ class HyperRomResult(_HyperResult):
         return torch.matmul(self.q, self.plan.Phi.t())
 
 
-def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options, balance):
+def _pivot_on_device(pivot):
+    """The ``pivot`` keyword of the hyper-reduced POD loops: True for "device", False for "host", anything else a ValueError."""
+    if pivot not in ("host", "device"):
+        raise ValueError(f'pivot must be "host" or "device" (got {pivot!r})')
+    return pivot == "device"
+
+
+def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options, balance,
+                   pivot="host"):
     """pod_prom_run_hyper's narrow loop and pod_prom_run_hyper_wide: the plan (or the sampling to build one from) against the
-    call, q0 and u0 at the stencil, the launch, and for a route with ``redo`` the marked samples again on the host side."""
+    call, q0 and u0 at the stencil, the launch, and for a route with ``redo`` the marked samples again on the host side, or
+    with ``pivot="device"`` by the entry point's own repair kernel (BG_OPT_PIVOT_ON_DEVICE; the narrow loop always has one)."""
     route = _ROUTES[plan_type.entry]
+    on_device = _pivot_on_device(pivot) and route.redo
+    if on_device:
+        options |= _lib.BG_OPT_PIVOT_ON_DEVICE
     Xh = check_mesh(X)
     if isinstance(sampling_or_plan, HyperPodPlan) and type(sampling_or_plan) is not plan_type:
         raise ValueError(f"{route.entry} takes a {plan_type.__name__}")
@@ -706,13 +718,15 @@ def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan
                            _lib.ptr(plan.PhiS), _lib.ptr(q0), _lib.ptr(u0s), *inputs[1:], float(dt), float(E), float(tol),
                            int(max_it), opts, *outputs), keep=(plan, q0, u0s), cols=plan.r)
     out = HyperRomResult(res, plan, u0d)
-    if route.redo:
+    if on_device:
+        out.redone = 0                          # nothing comes back marked: info is not read, nothing is synchronised
+    elif route.redo:
         _redo_marked_hyper(out, plan, dt, nsteps, proj, E, tol, max_it)
     return out
 
 
 def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
-                       options=0, balance=True):
+                       options=0, balance=True, pivot="host"):
     """``pod_prom_burgers`` HYPER-REDUCED, with the whole time loop on the device (bg_hyper_rom_run): the reduced system
     is assembled from the sampled mesh rows of a pod.RowSampling (pod.build_row_sampling) with their weights, so an
     iteration costs O(m r^2) whatever the mesh: N up to bg_fom_max_n(), r <= 40, m <= 256 (bg_hyper_rom_limits).  The
@@ -720,26 +734,31 @@ def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj,
     of this basis, sampling and mesh to reuse across calls (``res.plan``; ``Phi`` is then not looked at).  A sampling trained
     for the other projection is refused.  Returns a HyperRomResult.
     A HyperWidePodPlan, or a sampling with a basis of more than bg_hyper_rom_limits' r modes, goes to the wide loop
-    (pod_prom_run_hyper_wide: r <= 96, m <= 512, which does synchronise)."""
+    (pod_prom_run_hyper_wide: r <= 96, m <= 512, which does synchronise unless ``pivot="device"``; with a narrow plan the
+    keyword is accepted and changes nothing)."""
+    _pivot_on_device(pivot)
     if isinstance(sampling_or_plan, HyperWidePodPlan) or (
             not isinstance(sampling_or_plan, HyperPodPlan) and len(np.shape(Phi)) == 2
             and np.shape(Phi)[1] > _lib.limits(HyperPodPlan.limits, 2)[0]):
         return pod_prom_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options,
-                                       balance)
+                                       balance, pivot)
     return _run_hyper_pod(HyperPodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options,
-                          balance)
+                          balance, pivot)
 
 
 def pod_prom_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
-                            options=0, balance=True):
+                            options=0, balance=True, pivot="host"):
     """pod_prom_run_hyper for bases of up to 96 modes on up to 512 sampled rows (bg_hyper_rom_run_wide,
     bg_hyper_rom_wide_limits; meant for r > 40): the same loop with pod_prom_run_wide's 96 x 96 solve.  There is no repair
     kernel: samples whose elimination would have needed a row exchange come back marked and are redone by the weighted-row
     library iteration (_pod_prom_run_hyper_library) -- the full PROM's library path answers another question -- so unlike
     pod_prom_run_hyper this wrapper reads ``info`` back and synchronises the host.  ``sampling_or_plan``: the sampling, or a
-    HyperWidePodPlan to reuse across calls.  Returns a HyperRomResult with ``redone``."""
+    HyperWidePodPlan to reuse across calls.  Returns a HyperRomResult with ``redone``.
+    ``pivot="device"`` (BG_OPT_PIVOT_ON_DEVICE): the entry point's repair kernel redoes those samples with a pivoted 96 x 96
+    solve on the device instead; ``redone`` is 0, ``info`` is not read back and nothing is synchronised, and an exactly
+    singular reduced system is left in ``info`` for check_singular, as by the narrow loop.  Any other value is a ValueError."""
     return _run_hyper_pod(HyperWidePodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device,
-                          options, balance)
+                          options, balance, pivot)
 
 
 def _redo_marked_hyper(out, plan, dt, nsteps, proj, E, tol, max_it):
@@ -782,7 +801,7 @@ def _pod_route(N, r, fused=True, blocked=False, long_mesh=False, long_wide=False
 
 
 def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0, tol=1e-6, max_it=20,
-                 device=None, fused=True, blocked=False, long_mesh=False, long_wide=False, hyper=None):
+                 device=None, fused=True, blocked=False, long_mesh=False, long_wide=False, hyper=None, pivot="host"):
     """Batched ``pod_prom_burgers``; ``projection`` is case-sensitive like the reference (:754-764).
     ``fused`` (default): the device-side time loop bg_rom_run where it applies (N <= 512, r <= 40); otherwise, or
     with ``fused=False``, the batched iteration bg_rom_reduce -> bg_lu_solve_update driven from the host.
@@ -794,10 +813,13 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
     <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path.
     ``hyper`` (opt-in): a pod.RowSampling, a HyperPodPlan or a HyperWidePodPlan sends the call through the hyper-reduced loop
     pod_prom_run_hyper, which assembles the reduced system from the sampled mesh rows only (r <= 40: bg_hyper_rom_run;
-    41 <= r <= 96: bg_hyper_rom_run_wide); sizes it does not cover are refused, not rerouted."""
+    41 <= r <= 96: bg_hyper_rom_run_wide); sizes it does not cover are refused, not rerouted.
+    ``pivot`` (with ``hyper``): "device" has bg_hyper_rom_run_wide redo the samples that need row exchanges in its own repair
+    kernel, where "host" (default) redoes them through the library; the narrow loop always repairs on the device."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
+    _pivot_on_device(pivot)
     if hyper is not None:
-        return check_singular(pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device))
+        return check_singular(pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device, pivot=pivot))
     route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh, long_wide)
     if route == "library":
         return _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it, device)

@@ -48,7 +48,8 @@ using namespace bg;
 
 // What the body needs of a description K besides rom_stream_device.hpp's list: the sampled rows per slab and how many
 // values of q a lane carries through the solve (1: K::solve_add(L, r, lane, base, ...) as LongLayout's;
-// 2: rows lane and 64 + lane, K::solve_add<GAL, W>(L, r, lane, base0, base1, force, aborted, nd, nq), no repair).
+// 2: rows lane and 64 + lane, K::solve_add<GAL, W>(L, r, lane, base0, base1, force, aborted, nd, nq), and under PIV
+// K::solve_add_pivoted<GAL, W>(L, r, lane, base0, base1, info_out, nd, nq)).
 template <class K>
 struct HyperDims;
 template <>
@@ -356,7 +357,8 @@ __device__ __forceinline__ void hyper_body(const A& a, const StreamLds& L, const
                     K::template solve_add<PIV, W>(L, step_width(), lane, qk, aborted, info_out, nd, nq);
                 } else {
                     const double qk0 = (lane < step_width()) ? s_q[lane] : 0.0, qk1 = (64 + lane < step_width()) ? s_q[64 + lane] : 0.0;
-                    K::template solve_add<GAL, W>(L, step_width(), lane, qk0, qk1, a.force_pivoted != 0, aborted, nd, nq);
+                    if constexpr (PIV) K::template solve_add_pivoted<GAL, W>(L, step_width(), lane, qk0, qk1, info_out, nd, nq);
+                    else K::template solve_add<GAL, W>(L, step_width(), lane, qk0, qk1, a.force_pivoted != 0, aborted, nd, nq);
                 }
                 nd = sqrt(nd); nq = sqrt(nq);
                 const double err = nd / nq;

@@ -6,8 +6,10 @@
 // kernels of bg_hyper_rom_run and bg_hyper_local_rom_run stay exactly what they were) with the description HyperWidePod in the
 // place of LongLayout: rom_wide_device.hpp's WidePod -- 24 four-column blocks, 98-double LDS rows, the upper block pairs only for
 // LSPG, the guarded pivot-free 96 x 96 Gauss-Jordan by all four waves (wide_solve) -- with a solve_add that adds dq to q itself.
-// There is no repair kernel: a sample whose elimination meets a multiplier above 1 or a zero pivot (or every sample under
-// BG_OPT_FORCE_PIVOTED) is marked BG_INFO_NEEDS_PIVOTING and handed back to the caller, as in bg_rom_run_wide.
+// By default there is no repair: a sample whose elimination meets a multiplier above 1 or a zero pivot (or every sample under
+// BG_OPT_FORCE_PIVOTED) is marked BG_INFO_NEEDS_PIVOTING and handed back to the caller, as in bg_rom_run_wide.  With
+// BG_OPT_PIVOT_ON_DEVICE the repair kernel (PIV) follows the fast one, as in bg_hyper_rom_run, and redoes those samples with
+// rom_wide_device.hpp's wide_solve_pivoted; its pivot rows, info and permutation are 448 B of LDS in the guards' place.
 // Nothing here touches a vector of mesh length: 3 <= N <= bg_fom_max_n().
 //
 // The table is PhiS [MPAD][3][98], MPAD = m rounded up to 16: a slab of 16 sampled rows is one contiguous piece of 37 632 B.
@@ -35,6 +37,26 @@ struct HyperWidePod : WidePod {
         wide_solve<GAL>((lds_double_t*)L.slab, (lds_double_t*)L.m, (lds_double_t*)L.diag, (lds_double_t*)L.y, (lds_int_t*)L.bad, W, lane, r);
         const bool tripped = ((L.bad[0] | L.bad[1] | L.bad[2] | L.bad[3]) != 0) || force;      // workgroup-uniform
         if (tripped) aborted = true;
+        add_dq<W>(L, r, lane, base0, base1, nd, nq);
+    }
+
+    // The repair kernel's (PIV): wide_solve_pivoted, whose L.bad holds WPIV_INTS ints.  Nothing is handed back; an exactly
+    // singular system leaves LAPACK's info in info_out and the sample stops.  (A routine of its own and not a parameter of
+    // solve_add: with info_out passed through the fast kernels' call, their register allocation changed.)
+    template <bool GAL, int W>
+    static __device__ __forceinline__ void solve_add_pivoted(const StreamLds& L, int r, int lane, double base0, double base1, int& info_out,
+                                                             double& nd, double& nq)
+    {
+        wide_solve_pivoted<GAL>((lds_double_t*)L.slab, (lds_double_t*)L.m, (lds_double_t*)L.diag, (lds_double_t*)L.y, (lds_int_t*)L.bad, W, lane, r);
+        const int singular = L.bad[WPIV_INFO];                                                 // workgroup-uniform
+        if (singular != 0 && info_out == 0) info_out = singular;
+        add_dq<W>(L, r, lane, base0, base1, nd, nq);
+    }
+
+    // x_k = y_k / d_k of either solve, q = base + dq, the two norms
+    template <int W>
+    static __device__ __forceinline__ void add_dq(const StreamLds& L, int r, int lane, double base0, double base1, double& nd, double& nq)
+    {
         const double dq0 = (lane < r) ? L.y[lane] * rcp(L.diag[lane]) : 0.0;
         const double dq1 = (64 + lane < r) ? L.y[64 + lane] * rcp(L.diag[64 + lane]) : 0.0;
         const double q0 = base0 + dq0, q1 = base1 + dq1;
@@ -53,7 +75,9 @@ struct HyperDims<HyperWidePod> {
 
 constexpr int HWSLAB = hyper_slab<HyperWidePod>;
 
-template <bool GAL>
+// PIV: the repair kernel behind BG_OPT_PIVOT_ON_DEVICE, which redoes the marked samples (every sample under
+// BG_OPT_FORCE_PIVOTED) from u0 with wide_solve_pivoted in every iteration.
+template <bool GAL, bool PIV>
 __global__ __launch_bounds__(256, 1) void rom_hyper_wide_kernel(HyperRunArgs a)
 {
     __shared__ __attribute__((aligned(16))) double s_slab[2 * HWSLAB];            // two slab buffers; later the system
@@ -63,18 +87,19 @@ __global__ __launch_bounds__(256, 1) void rom_hyper_wide_kernel(HyperRunArgs a)
     __shared__ __attribute__((aligned(16))) double s_q[WR];
     __shared__ double s_m[8][WR];                                                 // multipliers of the current and the next panel
     __shared__ double s_diag[WR], s_y[WR];
-    __shared__ int s_bad[4];
-    static_assert(sizeof(double) * (2 * HWSLAB + 5 * HWMMAX + 4 * HWS + WR + 8 * WR + 2 * WR) + 4 * HWMMAX + 16 <= 160 * 1024, "LDS per workgroup");
+    __shared__ int s_bad[PIV ? WPIV_INTS : 4];                                    // the guards; PIV: pivot rows, info, permutation
+    static_assert(sizeof(double) * (2 * HWSLAB + 5 * HWMMAX + 4 * HWS + WR + 8 * WR + 2 * WR) + 4 * HWMMAX + 4 * WPIV_INTS <= 160 * 1024,
+                  "LDS per workgroup");
     static_assert(HWMMAX % HWS == 0 && HWS % 16 == 0 && HWS <= 64, "whole slabs of whole 16-row steps, at most one row per quad");
     static_assert(WR * WPS <= 2 * HWSLAB, "the parked system fits over the slabs");
     static_assert((HWSLAB * 8) % 16 == 0, "a slab is whole 16-byte DMA lanes");
     const StreamLds L{s_slab, nullptr, nullptr, nullptr, nullptr, s_cf, s_q, &s_m[0][0], s_diag, s_y, nullptr, s_bad, nullptr};
     const HyperLds H{s_g, s_fdt, s_hl, s_hr, s_w, s_row, nullptr, nullptr, nullptr};
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {       // wave-uniform by construction
-        case 0: hyper_body<GAL, false, 0, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
-        case 1: hyper_body<GAL, false, 1, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
-        case 2: hyper_body<GAL, false, 2, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
-        default: hyper_body<GAL, false, 3, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
+        case 0: hyper_body<GAL, PIV, 0, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
+        case 1: hyper_body<GAL, PIV, 1, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
+        case 2: hyper_body<GAL, PIV, 2, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
+        default: hyper_body<GAL, PIV, 3, false, HyperRunArgs, HyperWidePod>(a, L, H); break;
     }
 }
 
@@ -108,7 +133,11 @@ int bg_hyper_rom_run_wide(int N, int B, int r, int m, int nsteps, int projection
     if (rc != BG_OK || B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     return dispatch_projection(projection, [&](auto p) {
-        hipLaunchKernelGGL((rom_hyper_wide_kernel<decltype(p)::galerkin>), dim3(persistent_grid(B, 1)), dim3(256), 0, st, a);
+        if (options & BG_OPT_PIVOT_ON_DEVICE)
+            return launch_fast_then_repair(B, 1, a.force_pivoted != 0, [&](auto piv, int grid) {
+                hipLaunchKernelGGL((rom_hyper_wide_kernel<decltype(p)::galerkin, decltype(piv)::value>), dim3(grid), dim3(256), 0, st, a);
+            });
+        hipLaunchKernelGGL((rom_hyper_wide_kernel<decltype(p)::galerkin, false>), dim3(persistent_grid(B, 1)), dim3(256), 0, st, a);
         return check_launch();
     });
 }

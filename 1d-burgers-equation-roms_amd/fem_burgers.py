@@ -97,7 +97,7 @@ class FEMBurgers:
 
     # --------------------------------------------------------------- POD-Galerkin / LSPG
     def pod_prom_burgers(self, At, nTimeSteps, u0, mu1, E, mu2, Phi, projection="Galerkin", blocked=False, long_mesh=False,
-                         long_wide=False, hyper=None):
+                         long_wide=False, hyper=None, pivot="host"):
         """POD projection ROM (reference :709-785).  ``projection`` is "Galerkin" or "LSPG",
         case-sensitive as in the reference; anything else raises ValueError.  ``blocked``: bases of
         97 .. 256 modes take the device-side loop bg_rom_run_blocked instead of the library path.
@@ -106,11 +106,13 @@ class FEMBurgers:
         loop bg_rom_run_long_wide instead of the library path.  ``hyper``: a row sampling (burgers_hip.pod.build_row_sampling)
         or a rom.HyperPodPlan sends the call through the hyper-reduced device-side loop bg_hyper_rom_run, which assembles the
         reduced system from the sampled mesh rows only (any mesh the FOM takes, at most 40 modes and 256 rows); with a basis
-        of 41 .. 96 modes (or a rom.HyperWidePodPlan) through bg_hyper_rom_run_wide, at most 512 rows."""
+        of 41 .. 96 modes (or a rom.HyperWidePodPlan) through bg_hyper_rom_run_wide, at most 512 rows.  ``pivot`` (with
+        ``hyper``): "device" has that loop redo the samples that need row exchanges in its own repair kernel, where "host"
+        (default) redoes them through the library; anything else raises ValueError."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                 np.asarray(Phi, dtype=np.float64), projection=projection, E=E, blocked=blocked,
-                                long_mesh=long_mesh, long_wide=long_wide, hyper=hyper)
+                                long_mesh=long_mesh, long_wide=long_wide, hyper=hyper, pivot=pivot)
         return self._finish(res, batched)
 
     # ---------------------------------------------------------------- quadratic manifold

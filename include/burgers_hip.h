@@ -50,7 +50,8 @@ enum { BG_OPT_SUPG = 1,        /* include the SUPG vector (fom_burgers, pod_prom
        BG_OPT_FORCE_PIVOTED = 16, /* bg_rom_run: take the partial-pivoting branch of the reduced solve every time (tests) */
        BG_OPT_NO_TANGENT_REUSE = 32, /* bg_ann_rom_run: evaluate the closure at every step start even when its float32 input is unchanged (tests) */
        BG_OPT_FOM_WIDE = 64,   /* bg_fom_run: one WORKGROUP per sample also for 64 < N <= 1536 (uniform mesh); measured slower than the default there */
-       BG_OPT_FOM_WAVE = 128   /* bg_fom_run: one WAVEFRONT per sample (the default for N <= 1536; overrides BG_OPT_FOM_WIDE) */ };
+       BG_OPT_FOM_WAVE = 128,  /* bg_fom_run: one WAVEFRONT per sample (the default for N <= 1536; overrides BG_OPT_FOM_WIDE) */
+       BG_OPT_PIVOT_ON_DEVICE = 256 /* bg_hyper_rom_run_wide: a repair kernel redoes the samples that need row exchanges, nothing is handed back */ };
 
 /* bg_rom_run: transient value of info[b] between its two kernels (never seen by the caller);
  * bg_rom_run_wide: info[b] of a sample the caller must redo with a pivoting solve */
@@ -395,6 +396,12 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
  *          elimination meets a multiplier above 1 or a zero pivot is marked BG_INFO_NEEDS_PIVOTING, its qhist and iters are
  *          then undefined, and the caller redoes it (rom.py: the weighted-row library iteration).  BG_OPT_FORCE_PIVOTED
  *          (tests) marks every sample after its first solve;
+ *          with BG_OPT_PIVOT_ON_DEVICE in `options` a second kernel follows the first on the same stream, as in bg_hyper_rom_run:
+ *          it redoes every marked sample from u0 with a 96 x 96 solve with partial pivoting in every iteration (the largest
+ *          entry among the rows not yet used, the lowest row on ties: LAPACK's pivots; the same routine as
+ *          bg_wide_solve_pivoted) and leaves info = 0, or k + 1 where column k of a reduced system had no non-zero
+ *          candidate (exactly singular; the sample stops there, its later qhist and iters are undefined).  No sample comes
+ *          back marked.  BG_OPT_FORCE_PIVOTED then sends every sample through the second kernel alone;
  *   Errors: r > 96 or m > 512: BG_ERR_UNSUPPORTED_R; m > N or PhiS not 16-byte aligned: BG_ERR_BAD_ARG; the rest as
  *          bg_hyper_rom_run.
  *   The table streams through LDS 16 sampled rows at a time (two buffers of 37 632 B, over which the 96 x 98 system is parked);
@@ -405,6 +412,18 @@ int bg_hyper_rom_run_wide(int N, int B, int r, int m, int nsteps, int projection
                           const double *xs, const double *PhiS, const double *q0, const double *u0s, const double *mu1,
                           const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
                           int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
+
+/* bg_wide_solve_pivoted -- x[b] = solve(A[b], b[b]) for a batch of dense systems of 1 <= n <= 96 unknowns by Gauss-Jordan
+ *   elimination with partial pivoting, one workgroup of four waves per system on a persistent grid (one per compute unit;
+ *   csrc/wide_solve.hip).  The routine is the repair solve of bg_hyper_rom_run_wide (rom_wide_device.hpp, wide_solve_pivoted).
+ *   A    [B][n][n] row-major;  b, x [B][n];
+ *   piv  [B][n] or null: piv[b][k] is the row of A[b] used as the pivot of column k -- the largest |entry| of that column
+ *        among the rows not used before, the lowest such row on ties (the rows LAPACK's getrf exchanges into place k);
+ *   info [B]: 0, or k + 1 when column k had no non-zero candidate (exactly singular: x[b] and piv[b] are then undefined;
+ *        the other systems of the batch are not affected).
+ *   Returns BG_ERR_UNSUPPORTED_R for n outside 1 .. 96, BG_ERR_BAD_ARG for B < 0 or a null A, b, x or info, BG_OK without a
+ *   launch for B = 0.  x may not overlap A or b. */
+int bg_wide_solve_pivoted(int B, int n, const double *A, const double *b, double *x, int32_t *piv, int32_t *info, void *stream);
 
 /* bg_hyper_ann_rom_run -- the POD-ANN PROM time loop HYPER-REDUCED: both projections of pod_ann_prom are assembled from m
  *   sampled mesh rows with weights xi >= 0, Ar = sum_j xi_j w_j^T y_j and br = sum_j xi_j w_j^T R_j with the tangent
