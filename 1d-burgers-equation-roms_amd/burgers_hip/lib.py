@@ -33,6 +33,10 @@ BG_ACT_NONE, BG_ACT_ELU, BG_ACT_RELU, BG_ACT_TANH = 0, 1, 2, 3
 BG_COUNTER_SLOTS, BG_COUNTER_STRIDE = 16, 32
 BG_RBF_GAUSSIAN, BG_RBF_IMQ = 0, 1
 BG_INFO_NEEDS_PIVOTING = -1
+BG_NNLS_GO, BG_NNLS_DONE, BG_NNLS_NO_COLUMN, BG_NNLS_FULL, BG_NNLS_FAULT = 0, 1, 2, 3, 4
+# bg_nnls_status (include/burgers_hip.h): 64 bytes
+NNLS_STATUS = np.dtype([(k, np.int32) for k in ("stop", "pick", "fit_done", "dependent", "accepted", "p0", "count", "pick_active")] +
+                       [(k, np.float64) for k in ("w", "resnorm", "rel", "ratio")])
 
 # Fragments of the argument list the device-side time loops share (include/burgers_hip.h), in the order _loop puts them
 _LOOP_BATCH = [c_double_p] * 3                                              # u0, mu1, mu2
@@ -190,6 +194,21 @@ _SIGNATURES = {
     "bg_chol_factor": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, ctypes.c_void_p]),
     # n, nrhs, L, lda, B (in/out), ldb, stream
     "bg_chol_solve": (ctypes.c_int, [ctypes.c_int] * 2 + [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]),
+    "bg_nnls_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
+    "bg_nnls_work_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    # rows, n, ld, At, res, active, tabu (int32), dnorm, tau, min_cols, max_cols, w, status, stream
+    "bg_nnls_pick": (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p] * 2 + [c_int_p] * 2 + [ctypes.c_double] * 2 +
+                     [ctypes.c_int] * 2 + [c_double_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # rows, ld, k, rebuild, At, b, Q, R, ldr, z, x, order, active, tabu (int32), work, status, stream
+    "bg_nnls_append": (ctypes.c_int, [ctypes.c_int] * 4 + [c_double_p] * 4 + [ctypes.c_int] + [c_double_p] * 2 + [c_int_p] * 3 +
+                       [c_double_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # k, R, ldr, z, x, order, active (int32), status, stream
+    "bg_nnls_solve": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_int] + [c_double_p] * 2 + [c_int_p] * 2 +
+                      [ctypes.c_void_p, ctypes.c_void_p]),
+    # rows, ld, k, At, b, x, order (int32), res, stream
+    "bg_nnls_residual": (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p] * 3 + [c_int_p, c_double_p, ctypes.c_void_p]),
+    # n, tabu (int32), j, value, stream
+    "bg_nnls_mark": (ctypes.c_int, [ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "bg_mlp_act_jvp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
     "bg_decode_modes_bf16": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,

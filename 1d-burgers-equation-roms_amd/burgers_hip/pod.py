@@ -728,6 +728,19 @@ def row_contributions(X, Phi, U0, Un, mu1, mu2, dt, projection, E=0.0, supg=True
     return (W * R[:, None]).T
 
 
+def _no_column_left(count, rel, tau, min_cols, dependent=0):
+    """``dependent``: the candidates nnls_rows_device found numerically dependent on the active columns, named when there are any."""
+    why = "" if not dependent else (f"; {dependent} candidates were numerically dependent on the active columns: ``min_rows`` is "
+                                    f"beyond the numerical rank of the training matrix, ask for fewer rows or use solver='host'")
+    return ValueError(f"row sampling: no column left to add at {count} columns, residual {rel:.2e} "
+                      f"(asked: {tau:.1e}, at least {min_cols} columns){why}")
+
+
+def _too_many_rows(rel, tau, min_cols, max_cols):
+    return ValueError(f"row sampling: more than max_rows = {max_cols + 1} rows needed (residual {rel:.2e} at that "
+                      f"point, asked: {tau:.1e} with at least {min_cols + 1} rows)")
+
+
 def nnls_rows(G, d, tau, min_cols, max_cols):
     """Active-set NNLS (Lawson-Hanson) for min |G x - d|, x >= 0, stopped as soon as |G x - d| <= tau |d|; after that the
     same greedy rule (the column with the largest gradient G^T (d - G x)) goes on adding columns until ``min_cols`` are
@@ -747,11 +760,9 @@ def nnls_rows(G, d, tau, min_cols, max_cols):
         w[active | tabu] = -np.inf
         j = int(np.argmax(w))
         if not np.isfinite(w[j]) or (not fit_done and w[j] <= 0.0):
-            raise ValueError(f"row sampling: no column left to add at {int(active.sum())} columns, residual {rel:.2e} "
-                             f"(asked: {tau:.1e}, at least {min_cols} columns)")
+            raise _no_column_left(int(active.sum()), rel, tau, min_cols)
         if int(active.sum()) + 1 > max_cols:
-            raise ValueError(f"row sampling: more than max_rows = {max_cols + 1} rows needed (residual {rel:.2e} at that "
-                             f"point, asked: {tau:.1e} with at least {min_cols + 1} rows)")
+            raise _too_many_rows(rel, tau, min_cols, max_cols)
         active[j] = True
         while True:
             idx = np.flatnonzero(active)
@@ -776,6 +787,151 @@ def nnls_rows(G, d, tau, min_cols, max_cols):
     raise ValueError("row sampling: the active-set iteration did not end")
 
 
+class NnlsWorkspace:
+    """The device-resident state of nnls_rows_device and the entry points of csrc/nnls.hip on it (layouts:
+    include/burgers_hip.h, bg_nnls_pick): ``At`` (n, ld) the columns of G, ``b``, ``res``, the thin QR ``Q`` (kmax, ld),
+    ``R`` (kmax, kmax) stored by columns, ``z``, the weights ``x`` and the columns ``order`` in insertion order, the masks
+    ``active`` and ``tabu`` and the 64-byte ``status``.  ``G`` (rows, n): a host array (uploaded once and transposed on the
+    device) or a device tensor; ``kmax``: the most columns that may become active.  Every method queues its kernels on the
+    current stream of the device; read() alone waits, and brings back the status record as a numpy record."""
+
+    def __init__(self, G, d, kmax, device=None):
+        from . import lib as _lib
+        self._lib, self.L = _lib, _lib.load()
+        self.device = G.device if isinstance(G, torch.Tensor) and G.is_cuda else _lib.require_device(device)
+        dev, f64, i32 = self.device, torch.float64, torch.int32
+        self.rows, self.n = int(G.shape[0]), int(G.shape[1])
+        self.kmax = int(kmax)
+        self.ld = ld = max(8, (self.rows + 7) // 8 * 8)
+        self.At = torch.zeros((max(self.n, 1), ld), dtype=f64, device=dev)
+        if self.n:
+            self.At[:self.n, :self.rows] = torch.as_tensor(G).to(device=dev, dtype=f64).t()
+        self.b = torch.zeros((ld,), dtype=f64, device=dev)
+        self.b[:self.rows] = torch.as_tensor(d).to(device=dev, dtype=f64)
+        self.res = self.b.clone()
+        self.Q = torch.zeros((self.kmax, ld), dtype=f64, device=dev)
+        self.R = torch.zeros((self.kmax, self.kmax), dtype=f64, device=dev)
+        self.z = torch.zeros((self.kmax,), dtype=f64, device=dev)
+        self.x = torch.zeros((self.kmax,), dtype=f64, device=dev)
+        self.order = torch.zeros((self.kmax,), dtype=i32, device=dev)
+        self.active = torch.zeros((max(self.n, 1),), dtype=i32, device=dev)
+        self.tabu = torch.zeros((max(self.n, 1),), dtype=i32, device=dev)
+        self.w = torch.zeros((max(self.n, 1),), dtype=f64, device=dev)
+        self.work = torch.zeros((int(self.L.bg_nnls_work_elems(ld)),), dtype=f64, device=dev)
+        self.status = torch.zeros((_lib.NNLS_STATUS.itemsize,), dtype=torch.uint8, device=dev)
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            self._lib.check(getattr(self.L, name)(*args, self._lib.stream_ptr(self.device)), name)
+
+    def residual(self, k):
+        p = self._lib.ptr
+        self._call("bg_nnls_residual", self.rows, self.ld, int(k), p(self.At), p(self.b), p(self.x), p(self.order), p(self.res))
+
+    def pick(self, dnorm, tau, min_cols, max_cols):
+        p = self._lib.ptr
+        self._call("bg_nnls_pick", self.rows, self.n, self.ld, p(self.At), p(self.res), p(self.active), p(self.tabu), float(dnorm),
+                   float(tau), int(min_cols), int(max_cols), p(self.w), p(self.status))
+
+    def append(self, k, rebuild=False):
+        p = self._lib.ptr
+        self._call("bg_nnls_append", self.rows, self.ld, int(k), int(bool(rebuild)), p(self.At), p(self.b), p(self.Q), p(self.R),
+                   self.kmax, p(self.z), p(self.x), p(self.order), p(self.active), p(self.tabu), p(self.work), p(self.status))
+
+    def solve(self, k):
+        p = self._lib.ptr
+        self._call("bg_nnls_solve", int(k), p(self.R), self.kmax, p(self.z), p(self.x), p(self.order), p(self.active), p(self.status))
+
+    def mark(self, j, value):
+        self._call("bg_nnls_mark", self.n, self._lib.ptr(self.tabu), int(j), int(value))
+
+    def read(self):
+        return np.frombuffer(self.status.cpu().numpy().tobytes(), dtype=self._lib.NNLS_STATUS)[0]
+
+
+def nnls_rows_device(G, d, tau, min_cols, max_cols, device=None, info=None):
+    """nnls_rows on the device (csrc/nnls.hip): the same active-set iteration, decision for decision, with the least-squares
+    fit of the active columns kept as a thin QR on the device -- appended to by two passes of classical Gram-Schmidt, rebuilt
+    from the first dropped position when columns leave -- where nnls_rows factors the whole active block anew at every step.
+    ``G`` (rows, n): a host array (uploaded once) or a device tensor; ``d`` (rows,).  Per outer step the gradient pass reads G
+    once and the append reads Q four times; one 64-byte status record comes back per least-squares solve and nothing else
+    until the weights at the end.  A picked column whose remainder after the two passes is at most
+    BG_NNLS_DEPENDENT_MULTIPLE machine epsilons of its norm is numerically dependent on the active ones: it is not appended
+    and is tabu, which stands for the case in which nnls_rows' fit throws the new column out again.
+    The same two ValueErrors as nnls_rows; ``max_cols`` or n beyond nnls_limits is a ValueError before anything is launched.
+    WHERE IT PARTS FROM nnls_rows: the two pick the same columns as long as the data decide the picks (all test fixtures; N = 1024,
+    r = 40 and the fit phase at N = 4096, r = 96: DESIGN K28).  Once the active columns fit d to rounding, the other columns of such
+    a G are within the dependence cut of their span.  nnls_rows' lstsq (minimum norm) still adds them and shares the weight;
+    this routine does not, so a ``min_cols`` beyond the numerical rank of G ends in "no column left to add" here, the message naming
+    the dependent candidates, where nnls_rows returns (N = 4096, r = 96 at the default 3 r = 288 rows: refused at 202 / 198
+    columns), and a fill that rounding orders (``min_cols`` near that rank) may return other columns than nnls_rows does.
+    ``info``: a dict that receives adds, drops, dependent, solves and min_ratio (the smallest |v| / |G[:, j]| appended).
+    Returns (x, relative residual), x a host float64 array of length n.  Two calls on the same input give the same bits."""
+    from . import lib as _lib
+    rows, n = int(G.shape[0]), int(G.shape[1])
+    tau, min_cols, max_cols = float(tau), int(min_cols), int(max_cols)
+    max_active, limit_cols = nnls_limits()
+    if max_cols > max_active or n > limit_cols:
+        raise ValueError(f"nnls_rows_device: beyond bg_nnls_limits: max_cols {max_cols} (<= {max_active}), {n} columns (<= {limit_cols})")
+    ws = NnlsWorkspace(G, d, max(1, min(max_cols, n)), device)
+    dn = float(np.linalg.norm(_host64(d)))
+    counts = {} if info is None else info                     # kept up to date, so that a refusal leaves them too
+    counts.update({"adds": 0, "drops": 0, "dependent": 0, "solves": 0, "min_ratio": float("inf")})
+    count = 0
+
+    def result(rel):
+        x = np.zeros(n)
+        x[ws.order[:count].cpu().numpy()] = ws.x[:count].cpu().numpy()
+        return x, rel
+
+    if n == 0:
+        rel = 1.0 if dn > 0.0 else 0.0
+        if rel <= tau and min_cols <= 0:
+            return result(rel)
+        raise _no_column_left(0, rel, tau, min_cols)
+    for _ in range(3 * n + 10):
+        ws.residual(count)
+        ws.pick(dn, tau, min_cols, max_cols)                 # the loop head below, taken on the device as well: it gates
+        if count < ws.kmax:                                  # the append and the solve queued behind it
+            ws.append(count)
+            ws.solve(count + 1)
+        st = ws.read()
+        rel = float(st["rel"])
+        fit_done = rel <= tau
+        if fit_done and count >= min_cols:
+            return result(rel)
+        j, wj = int(st["pick"]), float(st["w"])
+        if j < 0 or not np.isfinite(wj) or (not fit_done and wj <= 0.0):
+            raise _no_column_left(count, rel, tau, min_cols, counts["dependent"])
+        if count + 1 > max_cols:
+            raise _too_many_rows(rel, tau, min_cols, max_cols)
+        if int(st["stop"]) != _lib.BG_NNLS_GO:
+            raise RuntimeError(f"nnls_rows_device: the device stopped with {int(st['stop'])} where the host goes on")
+        if st["dependent"]:
+            counts["dependent"] += 1                         # tabu on the device already
+            continue
+        counts["adds"] += 1
+        counts["solves"] += 1
+        counts["min_ratio"] = min(counts["min_ratio"], float(st["ratio"]))
+        held = count + 1
+        while not st["accepted"] and int(st["count"]) > 0:
+            counts["drops"] += held - int(st["count"])
+            held = int(st["count"])
+            for k in range(int(st["p0"]), int(st["count"])):
+                ws.append(k, rebuild=True)
+            ws.solve(int(st["count"]))
+            st = ws.read()
+            counts["solves"] += 1
+            if int(st["stop"]) != _lib.BG_NNLS_GO:
+                raise RuntimeError("nnls_rows_device: the repair of the QR after a drop met a dependent column")
+        count = int(st["count"])
+        if st["pick_active"] and not fit_done:
+            ws.mark(-1, 0)
+        elif not st["pick_active"]:
+            ws.mark(j, 1)                                    # the fit threw the new column out again: not this one next time
+    raise ValueError("row sampling: the active-set iteration did not end")
+
+
 def _limits_accessor(symbol, count, doc):
     def limits():
         from . import lib as _lib
@@ -791,7 +947,8 @@ for _name, _symbol, _count, _doc in (
         ("hyper_ann_wide_rom_limits", "bg_hyper_ann_rom_wide_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run_wide"),
         ("hyper_quad_rom_limits", "bg_hyper_quad_rom_limits", 3, "(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run"),
         ("hyper_local_rom_limits", "bg_hyper_local_rom_limits", 4, "(max_r, max_m, max_mg, max_clusters) of bg_hyper_local_rom_run"),
-        ("hyper_rbf_rom_limits", "bg_hyper_rbf_rom_limits", 5, "(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run")):
+        ("hyper_rbf_rom_limits", "bg_hyper_rbf_rom_limits", 5, "(max_n, max_nbar, max_ns, max_m, max_nodes) of bg_hyper_rbf_rom_run"),
+        ("nnls_limits", "bg_nnls_limits", 2, "(max_active, max_cols) of the bg_nnls_* steps behind nnls_rows_device")):
     globals()[_name] = _limits_accessor(_symbol, _count, _doc)
     globals()[_name].__name__ = globals()[_name].__qualname__ = _name
 
@@ -807,7 +964,8 @@ def _sampling_prelude(who, X, projection, runs, tau, stride):
     return projection, _host64(X)
 
 
-def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None):
+def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None,
+                       solver="host"):
     """The sampled mesh rows and weights of the hyper-reduced POD PROM (ECSW-style: energy-conserving sampling and
     weighting), fitted on the host by non-negative least squares.
 
@@ -822,8 +980,14 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     Two facts about wide bases, from a study at N = 600, r = 96 (3 r = 288 rows): the fill up to 3 r needs enough training
     pairs -- with three runs and stride 20 the greedy rule has no column left to add at 269, and ``min_rows`` must be given
     (200 rows stayed within 4e-11 of the full PROM there); and the NNLS is host work, about a minute at r = 96 with nine runs
-    and stride 10 on eight threads."""
+    and stride 10 on eight threads (113 / 127 s per projection on 16 CPU
+    threads, where ``solver="device"`` fits the first 176 / 172 rows, the host's, in 0.05 / 0.06 s against 3.0 / 2.9 s and refuses
+    the fill to 288 as beyond the rank of G; at N = 1024, r = 40: the host's 123 / 120 rows in 0.06 / 0.04 s against 1.8 / 1.4 s).
+    ``solver``: "host" (the default: nnls_rows, as ever) or "device" (nnls_rows_device, csrc/nnls.hip: the same iteration
+    on a QR kept on the device, DESIGN K28; it refuses a ``min_rows`` beyond the numerical rank of G, see its docstring); anything
+    else is a ValueError."""
     projection, X = _sampling_prelude("build_row_sampling", X, projection, runs, tau, stride)
+    fit = _solver_argument(solver)
     Phi = _host_matrix(Phi)
     N = len(X)
     if Phi.ndim != 2 or Phi.shape[0] != N:
@@ -834,13 +998,24 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
         narrow_r, narrow_m = hyper_rom_limits()
         max_rows = narrow_m if r <= narrow_r else hyper_wide_rom_limits()[1]
     G, pairs = row_sampling_system(X, Phi, runs, dt, projection, E, supg, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, int(max_rows))
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, int(max_rows), **fit)
 
 
-def _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows):
-    """The RowSampling of a training matrix G (pairs r, N): row 0 forced in with weight 1, the rest by nnls_rows."""
+def _solver_argument(solver):
+    """What a build_*_row_sampling passes on to _fit_row_sampling for its ``solver``: nothing for "host", so that the default
+    route calls it as it always has; ValueError for anything but "host" or "device"."""
+    if solver not in ("host", "device"):
+        raise ValueError("solver must be 'host' or 'device'")
+    return {} if solver == "host" else {"solver": solver}
+
+
+def _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows, solver="host"):
+    """The RowSampling of a training matrix G (pairs r, N): row 0 forced in with weight 1, the rest by nnls_rows
+    (``solver`` "host") or nnls_rows_device ("device")."""
+    _solver_argument(solver)
     d = G.sum(axis=1)
-    x, _ = nnls_rows(G[:, 1:], d - G[:, 0], float(tau) * float(np.linalg.norm(d)) / max(float(np.linalg.norm(d - G[:, 0])), 1e-300),
+    fit = nnls_rows if solver == "host" else nnls_rows_device
+    x, _ = fit(G[:, 1:], d - G[:, 0], float(tau) * float(np.linalg.norm(d)) / max(float(np.linalg.norm(d - G[:, 0])), 1e-300),
                      max(min_rows - 1, 0), max_rows - 1)
     xi_full = np.concatenate([[1.0], x])
     rows = np.flatnonzero(xi_full > 0.0)
@@ -905,7 +1080,7 @@ def ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E=0.0, sup
 
 
 def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None,
-                           max_rows=None):
+                           max_rows=None, solver="host"):
     """build_row_sampling for the POD-ANN PROM (rom.pod_ann_run_hyper: bg_hyper_ann_rom_run for n <= 8 primary modes, and
     rom.pod_ann_run_hyper_wide: bg_hyper_ann_rom_run_wide for n <= 20): the same host NNLS (nnls_rows, row 0 forced in with
     weight 1) on training pairs that lie on the closure manifold.  For every run (hist (N, nT+1), mu1, mu2) and every
@@ -920,8 +1095,10 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
     and iteration totals within 1 of the full PROM's; the default was therefore left at 3 n.  A closure whose fit is met by few rows may need more: at N = 2049 a random closure ran with
     ``min_rows`` = 120.  ``max_rows`` defaults to the limit of the loop that takes n (hyper_ann_rom_limits, or
     hyper_ann_wide_rom_limits beyond its n); needing more is a ValueError.
-    Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    Returns a RowSampling; save_row_sampling / load_row_sampling store it.
+    ``solver``: "host" or "device", as in build_row_sampling."""
     projection, X = _sampling_prelude("build_ann_row_sampling", X, projection, runs, tau, stride)
+    fit = _solver_argument(solver)
     U_p, U_s = _host_matrix(U_p), _host_matrix(U_s)
     N = len(X)
     if U_p.ndim != 2 or U_s.ndim != 2 or U_p.shape[0] != N or U_s.shape[0] != N:
@@ -931,7 +1108,7 @@ def build_ann_row_sampling(X, U_p, U_s, model, runs, dt, projection, E=0.0, supg
         max_rows = (hyper_ann_rom_limits() if U_p.shape[1] <= hyper_ann_rom_limits()[0] else hyper_ann_wide_rom_limits())[4]
     max_rows = int(max_rows)
     G, pairs = ann_row_sampling_system(X, U_p, U_s, model, runs, dt, projection, E, supg, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows, **fit)
 
 
 # ---- row sampling for the hyper-reduced quadratic-manifold PROM (rom.quadratic_run_hyper, bg_hyper_quad_rom_run) ----
@@ -948,7 +1125,8 @@ def quad_row_sampling_system(X, Phi, H, runs, dt, projection, E=0.0, stride=10):
         E, False, stride)
 
 
-def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, stride=10, min_rows=None, max_rows=None):
+def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, stride=10, min_rows=None, max_rows=None,
+                            solver="host"):
     """build_row_sampling for the quadratic-manifold PROM (rom.quadratic_run_hyper): the same host NNLS (nnls_rows, row 0
     forced in with weight 1) on training pairs that lie on the manifold.  For every run (hist (N, nT+1), mu1, mu2) and every
     ``stride``-th step n: q_n = Phi^T s_n, Un = Phi q_n + H sym(q_n), U0 likewise at n + 1, and the contributions
@@ -966,8 +1144,10 @@ def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, st
     over 40 steps at N = 1024 (dt = 0.025) and N = 4096 (dt = 0.00625), every count equal, where the default's 161 .. 179
     rows drifted to 2e-3 .. 2e-2 and, LSPG at N = 4096, ended in steps that hit the cap.  For long runs ask for
     ``min_rows`` above the rank.  ``max_rows`` defaults to the kernel's limit (hyper_quad_rom_limits); needing more is a
-    ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it.
+    ``solver``: "host" or "device", as in build_row_sampling."""
     projection, X = _sampling_prelude("build_quad_row_sampling", X, projection, runs, tau, stride)
+    fit = _solver_argument(solver)
     Phi, H = _host_matrix(Phi), _host_matrix(H)
     N = len(X)
     if Phi.ndim != 2 or H.ndim != 2 or Phi.shape[0] != N or H.shape != (N, Phi.shape[1] * (Phi.shape[1] + 1) // 2):
@@ -975,7 +1155,7 @@ def build_quad_row_sampling(X, Phi, H, runs, dt, projection, E=0.0, tau=1e-5, st
     min_rows = min(3 * Phi.shape[1], N) if min_rows is None else int(min_rows)
     max_rows = hyper_quad_rom_limits()[1] if max_rows is None else int(max_rows)
     G, pairs = quad_row_sampling_system(X, Phi, H, runs, dt, projection, E, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows, **fit)
 
 
 # ---- row sampling for the hyper-reduced local POD PROM (rom.local_prom_run_hyper, bg_hyper_local_rom_run) ----
@@ -1014,20 +1194,22 @@ def local_row_sampling_system(X, centres, local_bases, U_global, num_global_mode
 
 
 def build_local_row_sampling(X, centres, local_bases, U_global, num_global_modes, runs, dt, projection, E=0.0, supg=True,
-                             tau=1e-4, stride=10, min_rows=None, max_rows=None):
+                             tau=1e-4, stride=10, min_rows=None, max_rows=None, solver="host"):
     """build_row_sampling for the local POD PROM (rom.local_prom_run_hyper): ONE sampling for all clusters, fitted by the same
     host NNLS (nnls_rows, row 0 forced in with weight 1) on training pairs that each lie in the span of the cluster the
     reference would hold there (local_row_sampling_system).  ``centres`` (C, m), ``local_bases`` {c: (N, r_c)}, ``U_global``
     and ``num_global_modes`` are local_prom_burgers's arguments; ``runs`` as in build_row_sampling.
     ``min_rows`` defaults to min(3 max_c r_c, N), ``max_rows`` to the kernel's limit (hyper_local_rom_limits); needing more
-    is a ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    is a ValueError.  Returns a RowSampling; save_row_sampling / load_row_sampling store it.
+    ``solver``: "host" or "device", as in build_row_sampling."""
     projection, X = _sampling_prelude("build_local_row_sampling", X, projection, runs, tau, stride)
+    fit = _solver_argument(solver)
     N = len(X)
     _, bases, _ = _host_local_bases(centres, local_bases, U_global, num_global_modes, N, "build_local_row_sampling")
     min_rows = min(3 * max(b.shape[1] for b in bases), N) if min_rows is None else int(min_rows)
     max_rows = hyper_local_rom_limits()[1] if max_rows is None else int(max_rows)
     G, pairs = local_row_sampling_system(X, centres, local_bases, U_global, num_global_modes, runs, dt, projection, E, supg, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows, **fit)
 
 
 # ---- row sampling for the hyper-reduced POD-RBF PROM (rom.pod_rbf_run_hyper, bg_hyper_rbf_rom_run) ----
@@ -1082,7 +1264,7 @@ def rbf_row_sampling_system(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_mi
 
 
 def build_rbf_row_sampling(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, runs, dt, projection,
-                           kernel="gaussian", E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None):
+                           kernel="gaussian", E=0.0, supg=True, tau=1e-4, stride=10, min_rows=None, max_rows=None, solver="host"):
     """build_row_sampling for the POD-RBF PROM (rom.pod_rbf_run_hyper): the same host NNLS (nnls_rows, row 0 forced in with
     weight 1) on training pairs that lie on the closure manifold.  For every run (hist (N, nT+1), mu1, mu2) and every
     ``stride``-th step n: q_n = U_p^T s_n, Un = U_p q_n + U_s f(q_n), U0 likewise at n + 1, and the contributions
@@ -1099,8 +1281,10 @@ def build_rbf_row_sampling(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min
     residual of 1e-4 and left the full PROM by O(1) with capped steps, Galerkin 163 rows and 1e-3 ... 1e-2; with 200 rows
     (241 nodes, residual 1e-13) LSPG stays within 2e-11.  ``max_rows`` defaults to the kernel's limit
     (hyper_rbf_rom_limits); needing more is a ValueError.
-    Returns a RowSampling; save_row_sampling / load_row_sampling store it."""
+    Returns a RowSampling; save_row_sampling / load_row_sampling store it.
+    ``solver``: "host" or "device", as in build_row_sampling."""
     projection, X = _sampling_prelude("build_rbf_row_sampling", X, projection, runs, tau, stride)
+    fit = _solver_argument(solver)
     U_p, U_s = _host_matrix(U_p), _host_matrix(U_s)
     N = len(X)
     if U_p.ndim != 2 or U_s.ndim != 2 or U_p.shape[0] != N or U_s.shape[0] != N:
@@ -1109,7 +1293,7 @@ def build_rbf_row_sampling(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min
     min_rows = min(200, N, max_rows) if min_rows is None else int(min_rows)
     G, pairs = rbf_row_sampling_system(X, U_p, U_s, X_train, W, epsilon, x_min, x_max, y_min, y_max, kernel, runs, dt,
                                        projection, E, supg, stride)
-    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows)
+    return _fit_row_sampling(G, pairs, projection, tau, min_rows, max_rows, **fit)
 
 
 def save_row_sampling(directory, sampling):

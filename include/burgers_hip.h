@@ -1040,6 +1040,68 @@ int bg_rbf_gram(int Ns, int n, int kind, double eps, double ridge, const double 
 int bg_chol_factor(int n, double *A, int lda, int *info, void *stream);
 int bg_chol_solve(int n, int nrhs, const double *L, int lda, double *Bm, int ldb, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * bg_nnls_pick / bg_nnls_append / bg_nnls_solve / bg_nnls_residual / bg_nnls_mark -- the steps of the active-set NNLS
+ *   (Lawson-Hanson) behind the hyper-reduction row samplings: min |G x - b|, x >= 0, over the columns of G, with a thin QR
+ *   of the active columns kept on the device (burgers_hip/pod.py nnls_rows_device follows pod.nnls_rows; csrc/nnls.hip).
+ *   The host queues residual, pick, append and solve and reads one bg_nnls_status (64 bytes) per solve; the append and the
+ *   solve look at the status the pick left and do nothing unless it says BG_NNLS_GO.
+ *   At      [n][ld] the candidate columns of G, each contiguous over its `rows` entries; ld >= rows, ld even, 16-byte aligned
+ *   b, res  [rows] right-hand side and current residual (res 16-byte aligned)
+ *   Q       [kmax][ld] orthonormal columns in insertion order, 16-byte aligned
+ *   R       [kmax][ldr] upper triangular, stored by columns: R[c * ldr + i] is row i of column c, i <= c
+ *   z       [kmax] Q^T b;  x [kmax] the weights in insertion order;  order [kmax] int32 the active columns in that order
+ *   active, tabu  [n] int32 masks (0 / 1);  w [n] scratch for the gradient;  work [bg_nnls_work_elems(ld)], 16-byte aligned
+ *   status  [1] bg_nnls_status on the device, zeroed by the caller before the first pick
+ *   Limits (bg_nnls_limits, needs no device): at most max_active = 512 active columns (kmax; the 511 free rows of
+ *   bg_hyper_rom_run_wide and one more) out of at most max_cols = 65536 candidates; BG_ERR_UNSUPPORTED_R beyond them.
+ *   No floating-point atomics, plain vector stores: every sum runs in an order the shapes fix, so two calls give the same bits.
+ * bg_nnls_pick: w[j] = At[j] . res for every column neither active nor tabu (one wave per column, fixed tree), then into
+ *   status: pick = the index of the largest w (the lowest index on ties, -1 when every column is masked; At and res must be
+ *   finite: a NaN entry of w is not singled out as np.argmax would single it out), w, resnorm = |res|,
+ *   rel = resnorm / dnorm (0 for dnorm = 0), fit_done = rel <= tau, and stop = the head of nnls_rows' loop: BG_NNLS_DONE for
+ *   fit_done with count >= min_cols, else BG_NNLS_NO_COLUMN for no pick, a non-finite w or (not fit_done and w <= 0), else
+ *   BG_NNLS_FULL for count + 1 > max_cols, else BG_NNLS_GO; dependent, accepted and pick_active are cleared, p0 = count.
+ *   rows, n, min_cols or max_cols < 0, ld < rows, an odd ld, a negative or NaN dnorm or tau, a null or misaligned operand
+ *   with n > 0: BG_ERR_BAD_ARG.  n == 0: BG_OK with nothing launched.  n > max_cols or max_cols > max_active: _UNSUPPORTED_R.
+ * bg_nnls_append: v = At[j] with j = status.pick (rebuild = 0) or j = order[k] (rebuild = 1: the repair after a drop);
+ *   h = Q[:k] v, v -= Q[:k]^T h, twice (classical Gram-Schmidt, the sums over the columns in insertion order).  Then
+ *   R[:k, k] = h1 + h2, R[k, k] = |v|, Q[k] = v / |v|, z[k] = Q[k] . b, active[j] = 1, status.count = k + 1, and for
+ *   rebuild = 0 order[k] = j, x[k] = 0.  status.ratio = |v| / |At[j]|.  If |v| <= BG_NNLS_DEPENDENT_MULTIPLE * 2^-52 * |At[j]|
+ *   the column is numerically dependent on the active ones: nothing is appended, tabu[j] = 1 and status.dependent = 1
+ *   (with rebuild = 1 that cannot be: status.stop = BG_NNLS_FAULT).
+ *   rows, k or ldr < 0, ld < rows, ldr <= k, an odd ld, a null or misaligned operand with rows > 0: BG_ERR_BAD_ARG.
+ *   rows == 0: BG_OK with nothing launched.  k >= max_active: BG_ERR_UNSUPPORTED_R.
+ * bg_nnls_solve: one workgroup back-substitutes R[:k, :k] s = z[:k].  Every s > 0: x = s, status.accepted = 1.  Otherwise
+ *   nnls_rows' step: ratio = x / (x - s) over the entries with s <= 0 (0 for x = 0, also where s = 0 makes that 0 / 0), alpha its minimum, x = max(x + alpha (s - x), 0) with
+ *   the entries at ratio <= alpha set to 0 (rounded as the host rounds them: no fused multiply-add); every entry now <= 0
+ *   leaves: active cleared, order and x compacted, status.accepted = 0, p0 = the first position that left, count = what
+ *   stays.  Q, R and z are valid up to p0; the caller appends order[p0 .. count) again with rebuild = 1 and solves again.
+ *   status.pick_active says whether the pick is among the columns that stay.  A k that is not status.count: BG_NNLS_FAULT.
+ *   k < 0, ldr < k or a null operand with k > 0: BG_ERR_BAD_ARG.  k == 0: BG_OK with nothing launched.
+ * bg_nnls_residual: res = b - sum_c x[c] At[order[c]] over c < k in insertion order (the columns themselves, not b - Q z).
+ *   rows or k < 0, ld < rows, a null operand with work to do: BG_ERR_BAD_ARG.  rows == 0: BG_OK with nothing launched.
+ * bg_nnls_mark: tabu[j] = value (0 / 1), or every entry for j < 0.  n < 0, j >= n, a null tabu with n > 0: BG_ERR_BAD_ARG.
+ * --------------------------------------------------------------------------------- */
+#define BG_NNLS_DEPENDENT_MULTIPLE 1048576.0   /* 2^20: |v| / |At[j]| <= 2.3e-10 counts as dependent */
+enum { BG_NNLS_GO = 0, BG_NNLS_DONE = 1, BG_NNLS_NO_COLUMN = 2, BG_NNLS_FULL = 3, BG_NNLS_FAULT = 4 };
+typedef struct bg_nnls_status {
+    int32_t stop, pick, fit_done, dependent, accepted, p0, count, pick_active;
+    double w, resnorm, rel, ratio;
+} bg_nnls_status;
+int bg_nnls_limits(int *max_active, int *max_cols);
+long long bg_nnls_work_elems(int ld);
+int bg_nnls_pick(int rows, int n, int ld, const double *At, const double *res, const int32_t *active, const int32_t *tabu,
+                 double dnorm, double tau, int min_cols, int max_cols, double *w, bg_nnls_status *status, void *stream);
+int bg_nnls_append(int rows, int ld, int k, int rebuild, const double *At, const double *b, double *Q, double *R, int ldr,
+                   double *z, double *x, int32_t *order, int32_t *active, int32_t *tabu, double *work,
+                   bg_nnls_status *status, void *stream);
+int bg_nnls_solve(int k, const double *R, int ldr, const double *z, double *x, int32_t *order, int32_t *active,
+                  bg_nnls_status *status, void *stream);
+int bg_nnls_residual(int rows, int ld, int k, const double *At, const double *b, const double *x, const int32_t *order,
+                     double *res, void *stream);
+int bg_nnls_mark(int n, int32_t *tabu, int j, int value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
