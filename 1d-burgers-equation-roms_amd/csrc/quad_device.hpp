@@ -37,18 +37,13 @@
 //                                set_g (step start), g (assembly)
 //   K::Args, K::hyper            the argument block, and whether the kernel is the hyper-reduced form below
 //
-// The hyper-reduced form (K::hyper, Args = HyperQuadRunArgs: bg_hyper_quad_rom_run, quad_hyper.hip).  Both projections are
-// sums over mesh rows and row i needs state, tangent and coordinates at nodes i - 1, i, i + 1 only.  The caller packs the
-// sorted distinct stencil nodes of the m sampled rows (node[k], k < nodes <= 3 m) with their coordinates and the rows of
-// Phi and H at them; the stencil nodes of a sampled row are consecutive integers, hence consecutive table entries, so the
-// table is a non-uniform mesh of `nodes` nodes and the body runs on it with a.N = nodes, x = xn, u0 = u0n.  What differs:
-//   - a table node that is only a neighbour assembles as a row outside the mesh and every coefficient is multiplied by the
-//     row's weight xi (Galerkin) or sqrt(xi) (LSPG), 0 there: its row vanishes from both sums.  Whether a sampled row is the
-//     Dirichlet row or the last row is decided by node[k] against the mesh's own node count a.meshN.  Mesh row and factor
-//     of a table node are the same for every sample: scattered once per workgroup into LDS (K::hyper_row, K::hyper_mul);
+// The hyper-reduced form (K::hyper, Args = HyperQuadRunArgs: bg_hyper_quad_rom_run, quad_hyper.hip) is described in
+// rom_hyper_table_device.hpp, which holds its table side.  Here the table's rows of Phi and H stand for the basis, the body
+// runs with a.N = nodes, x = xn, u0 = u0n and the mesh's own node count is a.meshN, and:
+//   - mesh row and factor of a table node are in LDS (K::hyper_row, K::hyper_mul);
 //   - q starts from q0 (the caller's Phi^T u0) and carries over from step to step: Phi^T H = 0 for a manifold fitted on the
 //     residual of the projection, so Phi^T (Phi q + H Q(q)) = q and the Phi^T u^n of the step start is compiled out;
-//   - the history is q of every step, [B][nsteps+1][n]; no vector of mesh length is touched.
+//   - the history is q of every step, [B][nsteps+1][n]: there is no closure value.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,6 +51,7 @@
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
 #include "rom_device.hpp"
+#include "rom_hyper_table_device.hpp"
 
 namespace bg {
 
@@ -94,11 +90,7 @@ struct QuadRunArgs {
 
 // bg_hyper_quad_rom_run: N is the table's node count and x, Phif, H3f, u0 are the table's xn [nodes], Phi and H restricted to
 // the table nodes, u0n [B][nodes]; hist is qhist [B][nsteps+1][n]; PhiT is not read; nonuniform is 1
-struct HyperQuadRunArgs : QuadRunArgs {
-    const int32_t* node;    // [nodes] ascending mesh nodes of the table
-    const int32_t* pos;     // [nrows] table position of every sampled row
-    const double* xi;       // [nrows] weights
-    const double* q0;       // [B][n]
+struct HyperQuadRunArgs : QuadRunArgs, HyperTableArgs {
     int meshN, nrows;       // the mesh's own node count (it decides the Dirichlet row and the last row); sampled rows
 };
 
@@ -182,22 +174,9 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(typename K::Args a)
     if constexpr (HYPER) {
         // mesh row (a.meshN: not sampled, a row outside the mesh) and weight factor of every table node, the same for every
         // sample: K::hyper_row holds 1 + the sampled row's index on its way there
-        for (int k = tid; k < K::rows; k += 256) K::hyper_row(k) = 0;
-        __syncthreads();
-        for (int j = tid; j < a.nrows; j += 256) {
-            const int p = a.pos[j];
-            if ((unsigned)p < (unsigned)N) K::hyper_row(p) = j + 1;
-        }
-        __syncthreads();
-        for (int k = tid; k < K::rows; k += 256) {
-            int j = K::hyper_row(k);
-            const int ir = j ? a.node[k] : a.meshN;
-            // (a sampled row whose neighbour the table does not hold -- not a table the contract allows -- is left out)
-            if ((unsigned)ir >= (unsigned)a.meshN || (ir > 0 && k == 0) || (ir < a.meshN - 1 && k == N - 1)) j = 0;
-            const double xi = j ? a.xi[j - 1] : 0.0;
-            K::hyper_row(k) = j ? ir : a.meshN;
-            K::hyper_mul(k) = GAL ? xi : sqrt(xi);
-        }
+        hyper_scatter_rows<256>(&K::hyper_row(0), K::rows, a.pos, a.nrows, N, tid);
+        for (int k = tid; k < K::rows; k += 256)
+            hyper_table_node<GAL>(K::hyper_row(k), k, a.node, a.xi, a.meshN, N, K::hyper_row(k), K::hyper_mul(k));
     }
     const int ngroups = (a.B + QG - 1) / QG;
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
@@ -430,14 +409,10 @@ __global__ __launch_bounds__(256, 1) void quad_rom_kernel(typename K::Args a)
                             const double ur = (lane == QRS - 1) ? s_unext[w] : s_u[w][i + 3];
                             double lo, di, up, R;
                             if constexpr (HYPER) {
-                                // table node i as mesh row ir (a.meshN where the node is only a neighbour: a row outside the
-                                // mesh, weight 0), the table coordinates as the x[ir - 1], x[ir], x[ir + 1] of the row routine
-                                const int ir = K::hyper_row(i);
-                                const bool in = ir < a.meshN;
-                                rom_assemble_row(ir, a.meshN, um, u0, ur, in ? nodes.g(w, i, N, slab) : 0.0, 0.0, 0.0, mu1, mc, 1,
-                                                 a.x + (in ? i - ir : 0), a.dt, a.E, lo, di, up, R);
-                                const double wm = K::hyper_mul(i);
-                                lo *= wm; di *= wm; up *= wm; R *= wm;
+                                const int ir = K::hyper_row(i);       // a.meshN where the node is only a neighbour
+                                hyper_assemble_row(i, ir, a.meshN, K::hyper_mul(i), um, u0, ur,
+                                                   ir < a.meshN ? nodes.g(w, i, N, slab) : 0.0, 0.0, 0.0, mu1, mc, a.x, a.dt, a.E,
+                                                   lo, di, up, R);
                             } else
                             rom_assemble_row(i, N, um, u0, (i + 1 < N) ? ur : 0.0, nodes.g(w, i, N, slab), 0.0, 0.0, mu1, mc,
                                              a.nonuniform, a.x, a.dt, a.E, lo, di, up, R);

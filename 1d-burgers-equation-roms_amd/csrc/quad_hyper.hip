@@ -4,9 +4,9 @@
 // (Galerkin) or y_j (LSPG), so a pass streams the H3 rows of the at most 3 m stencil nodes of those rows whatever the
 // mesh, and the kernel never touches a vector of mesh length.
 //
-// The loop is quad_device.hpp's own body (read its header first; it describes the hyper-reduced form) on the compacted mesh
-// of the stencil nodes: tangent stream, decode, projection, the pivoted solve and the stopping test are unchanged.  This
-// file keeps the two descriptions and the entry points:
+// The loop is quad_device.hpp's own body (read its header first; rom_hyper_table_device.hpp describes the hyper-reduced
+// form) on the compacted mesh of the stencil nodes: tangent stream, decode, projection, the pivoted solve and the stopping
+// test are unchanged.  This file keeps the two descriptions and the entry points:
 //   nodes <= 512   per-node arrays g, dt F in LDS as bg_quad_rom_run holds them; mesh row and factor of the table nodes
 //                  (12 B per node) in the 8 KB that layout leaves free: 161 840 B of the compute unit's 163 840
 //   nodes <= 768   g, dt F in the owning wave's registers as bg_quad_rom_run_long holds them (12 doubles each)

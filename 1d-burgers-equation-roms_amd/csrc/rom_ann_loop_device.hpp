@@ -4,21 +4,10 @@
 // rom_ann_fused.hip; this file holds the sweep and its table s_dN, the input set-up (s_qlast), pivoted_gj8, the LDS overlay
 // and the loop.  The closure MLP is rom_ann_device.hpp's.
 //
-// The hyper-reduced form (Args = HyperAnnRunArgs).  Both projections are sums over mesh rows, Ar = sum_i w_i^T y_i and
-// br = sum_i w_i^T R_i, and row i needs the state, the tangent and the coordinates at nodes i - 1, i, i + 1 only.  The caller
-// packs the sorted distinct stencil nodes of the m sampled rows (node[k], k < nodes <= 3 m) with their coordinates and the
-// rows of [U_p | U_s] at them; the three stencil nodes of a sampled row are consecutive integers and therefore consecutive
-// table entries, so the table is a mesh on which a sampled row's neighbours are its table neighbours, and the whole body
-// runs on it with `nodes` for N: the sweep forms tangent and decode at the table nodes, forcing and mass row read the table
-// coordinates as a non-uniform mesh x.  What differs:
-//   - a table node that is only a neighbour assembles as a row outside the mesh (an identity row) and every coefficient is
-//     multiplied by the row's weight xi (Galerkin) or sqrt(xi) (LSPG), 0 there -- its row vanishes from both sums; whether a
-//     sampled row is the Dirichlet row or the last row is decided by node[k] (a sampled row 0 is table node 0 and a sampled
-//     row N - 1 the last table node, so forcing and mass row may ask the table index);
-//   - the run starts from q_p = q0 and u0 gathered at the table nodes, and q_p carries over from step to step: there is no
-//     U_p^T u^n (equal to q_p for orthonormal [U_p U_s]), so the first pass of a step always meets the float32 input of the
-//     previous evaluation and reuses its tangent;
-//   - the outputs are q_p and the closure value q_s = N(q_p) of every step's decode; no vector of mesh length is touched.
+// The hyper-reduced form (Args = HyperAnnRunArgs) is described in rom_hyper_table_device.hpp, which holds its table side; the
+// blocks under `if constexpr (HYPER)` call it.  Here the sweep forms tangent and decode at the table nodes, mesh row and
+// factor of this thread's table nodes stay in registers, and since q_p carries over from step to step the first pass of a
+// step always meets the float32 input of the previous evaluation and reuses its tangent.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,20 +16,14 @@
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
 #include "rom_ann_device.hpp"
+#include "rom_hyper_table_device.hpp"
 
 namespace bg {
 namespace fused {
 
 // bg_hyper_ann_rom_run: x, UT, u0 are the table's xn [nodes], UTn [m8][nodes], u0n [B][nodes]; hist is qhist [B][nsteps+1][n];
 // N is the mesh's node count (it decides the last row), nonuniform is not read (the table is a non-uniform mesh)
-struct HyperAnnRunArgs : AnnRunArgs {
-    const int32_t* node;    // [nodes] ascending mesh nodes of the table
-    const int32_t* pos;     // [nrows] table position of every sampled row
-    const double* xi;       // [nrows] weights
-    const double* q0;       // [B][n]
-    double* qshist;         // [B][nsteps+1][nbar]
-    int nodes, nrows;
-};
+struct HyperAnnRunArgs : AnnRunArgs, HyperClosureTableArgs {};
 
 // rows of the mesh the body works on
 __device__ __forceinline__ int ann_loop_rows(const AnnRunArgs& a) { return a.N; }
@@ -308,23 +291,11 @@ __global__ __launch_bounds__(256, WG) void ann_loop_kernel(Args a)
     if constexpr (HYPER) {
         int* s_smp = reinterpret_cast<int*>(s_shared);          // [NPAD]: 1 + the sampled row at this table node, or 0
         static_assert(NPAD * 4 <= sizeof(s_shared), "the scatter table fits the shared block");
-        for (int k = tid; k < NPAD; k += 256) s_smp[k] = 0;
-        __syncthreads();
-        for (int j = tid; j < a.nrows; j += 256) {
-            const int p = a.pos[j];
-            if ((unsigned)p < (unsigned)N) s_smp[p] = j + 1;
-        }
-        __syncthreads();
+        hyper_scatter_rows<256>(s_smp, NPAD, a.pos, a.nrows, N, tid);
 #pragma unroll
         for (int ii = 0; ii < S / 4; ++ii) {
             const int k = tid + 256 * ii;
-            int j = s_smp[k];
-            const int ir = j ? a.node[k] : a.N;
-            // (a sampled row whose neighbour the table does not hold -- not a table the contract allows -- is left out)
-            if ((unsigned)ir >= (unsigned)a.N || (ir > 0 && k == 0) || (ir < a.N - 1 && k == N - 1)) j = 0;
-            const double xi = j ? a.xi[j - 1] : 0.0;
-            hnode[ii] = j ? ir : a.N;
-            hmul[ii] = GAL ? xi : sqrt(xi);
+            hyper_table_node<GAL>(s_smp[k], k, a.node, a.xi, a.N, N, hnode[ii], hmul[ii]);
         }
     }
 #if BG_ANN_PRIO
@@ -354,15 +325,8 @@ __global__ __launch_bounds__(256, WG) void ann_loop_kernel(Args a)
             s_h[i] = hf;
             s_u[i + 2] = u;
         }
-        if constexpr (HYPER) {                      // q_p = q0 (the caller's U_p^T u0); no closure value belongs to u0
-            const HyperAnnRunArgs& ha = a;
-            if (tid < RW) {
-                const double q = tid < n ? ha.q0[(size_t)smp * n + tid] : 0.0;
-                s_q[tid] = q;
-                if (tid < n) hist[tid] = q;
-            }
-            for (int j = tid; j < nbar; j += 256) ha.qshist[(size_t)smp * (size_t)(a.nsteps + 1) * (size_t)nbar + j] = 0.0;
-        }
+        if constexpr (HYPER)                        // q_p = q0 (the caller's U_p^T u0); no closure value belongs to u0
+            hyper_sample_start<256, RW>(a.q0, s_q, hist, a.qshist, smp, a.nsteps, n, nbar, tid, 0.0);
         __syncthreads();
 
         int flags = 0, info_out = 0;
@@ -442,19 +406,16 @@ __global__ __launch_bounds__(256, WG) void ann_loop_kernel(Args a)
                 decode = true;
                 // ---- assembly: A(u_k), R(u_k) per row into LDS ----------------------------------------------------
                 if constexpr (HYPER) {
-                    // table node i as mesh row hnode (a.N where the node is only a neighbour: an identity row, weight 0), the
-                    // table coordinates as the x[ir - 1], x[ir], x[ir + 1] of the row routine, the weight in the coefficients
+                    // this thread's table nodes, as mesh rows hnode.  No guards on the reads of s_g and s_h: both are written
+                    // for every i < NPAD, and the row routine ignores them where the row lacks the term
 #pragma unroll
                     for (int ii = 0; ii < S / 4; ++ii) {
-                        const int i = tid + 256 * ii, ir = hnode[ii];
+                        const int i = tid + 256 * ii;
                         double lo, di, up, R;
-                        const bool in = ir < a.N;
                         const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-                        rom_assemble_row(ir, a.N, s_u[i + 1], s_u[i + 2], s_u[i + 3], in ? s_g[i] : 0.0,
-                                         (in && ir > 0) ? s_h[i - 1] : 0.0, (in && ir < a.N - 1) ? s_h[i] : 0.0, mu1, mc,
-                                         ann_loop_nonuniform(a), a.x + (in ? i - ir : 0), a.dt, a.E, lo, di, up, R);
-                        const double wm = hmul[ii];
-                        s_coef[i][0] = wm * lo; s_coef[i][1] = wm * di; s_coef[i][2] = wm * up; s_coef[i][3] = wm * R;
+                        hyper_assemble_row(i, hnode[ii], a.N, hmul[ii], s_u[i + 1], s_u[i + 2], s_u[i + 3], s_g[i],
+                                           s_h[i > 0 ? i - 1 : 0], s_h[i], mu1, mc, a.x, a.dt, a.E, lo, di, up, R);
+                        s_coef[i][0] = lo; s_coef[i][1] = di; s_coef[i][2] = up; s_coef[i][3] = R;
                     }
                 } else
                 for (int i = tid; i < (skip(16) ? 0 : NPAD); i += 256) {
@@ -515,9 +476,7 @@ __global__ __launch_bounds__(256, WG) void ann_loop_kernel(Args a)
                 __syncthreads();
             }
             if constexpr (HYPER) {                  // q_p and the closure value of the decode: s_dN is the last evaluation's
-                if (tid < n) hist[(size_t)(step + 1) * n + tid] = s_q[tid];
-                double* qs = a.qshist + ((size_t)smp * (size_t)(a.nsteps + 1) + (size_t)(step + 1)) * (size_t)nbar;
-                for (int j = tid; j < nbar; j += 256) qs[j] = s_dN[n + j][n];
+                hyper_write_step<256, kBS>(hist, a.qshist, smp, a.nsteps, step, s_q, &s_dN[n][n], n, nbar, tid);
             } else {
                 double* hrow = hist + (size_t)(step + 1) * N;
                 for (int i = tid; i < N; i += 256) hrow[i] = s_u[i + 2];

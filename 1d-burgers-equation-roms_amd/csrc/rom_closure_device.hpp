@@ -1,7 +1,10 @@
 // rom_closure_device.hpp -- the mesh side of the closure ROM time loops (one workgroup per sample): what a reduced
 // coordinate q_p and the nbar x 4 NB closure table s_J in LDS drive, whatever closure filled them.
 // Used by rom_rbf_loop_device.hpp (POD-RBF: bg_rbf_rom_run, bg_rbf_rom_run_long, bg_hyper_rbf_rom_run) and
-// rom_ann_wide_loop_device.hpp (POD-ANN: bg_ann_rom_run_wide, bg_hyper_ann_rom_run_wide).
+// rom_ann_wide_loop_device.hpp (POD-ANN: bg_ann_rom_run_wide, bg_hyper_ann_rom_run_wide).  What only their hyper-reduced forms
+// need -- the table side, which describes that form -- is rom_hyper_table_device.hpp's, included here; the narrow POD-ANN loop
+// (rom_ann_loop_device.hpp: its tangent and decode are one MFMA sweep, its dt F is in registers) and quad_device.hpp take that
+// header alone.
 // The pieces take LDS arrays and scalars, not a kernel-args struct.  NT: threads of the workgroup, NW = NT / 64 its waves,
 // NIT: rows per thread of the strided loops, UT_LD: row stride of UT ([n + nbar][UT_LD]: U_p^T, then U_s^T, zero from N).
 // The per-row loops are kept rolled (#pragma unroll 1): unrolled they take registers from the projection.
@@ -9,6 +12,7 @@
 // phases, mfma_passes, pivoted_solve and the issue priorities.
 #pragma once
 #include "rom_fused_device.hpp"
+#include "rom_hyper_table_device.hpp"
 
 namespace bg {
 namespace fused {
@@ -34,9 +38,10 @@ struct HaloEdges {
 };
 
 // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state, row i: dt F into
-// s_fdt, the SUPG term's element loads hf into s_h, u0 into s_u (offset 2) and into row 0 of the sample's history.  The
-// rolled loop over a thread's rows stays in the kernels: inside this function it moved the SGPR spills of rom_rbf_fused's
-// S = 4 instantiations (213 -> 242).
+// s_fdt, the SUPG term's element loads hf into s_h, u0 into s_u (offset 2) and, HIST, into row 0 of the sample's history
+// (the hyper-reduced forms keep no history of u: hist is not read).  The rolled loop over a thread's rows stays in the
+// kernels: inside this function it moved the SGPR spills of rom_rbf_fused's S = 4 instantiations (213 -> 242).
+template <bool HIST = true>
 __device__ __forceinline__ void sample_setup_row(int i, const double* x, const double* u0, int smp, double* hist, int N,
                                                  double mu2, double h, int nonuniform, double dt, double* s_u, double* s_fdt,
                                                  double* s_h)
@@ -45,7 +50,7 @@ __device__ __forceinline__ void sample_setup_row(int i, const double* x, const d
     if (i < N) {
         rom_nodal_forcing(x, i, N, mu2, h, nonuniform, frPrev, fl, hf);
         u = u0[(size_t)smp * N + i];
-        hist[i] = u;
+        if constexpr (HIST) hist[i] = u;
     }
     s_fdt[i] = dt * (frPrev + fl);
     s_h[i] = hf;

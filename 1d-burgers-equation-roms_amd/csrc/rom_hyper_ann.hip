@@ -4,9 +4,9 @@
 // y_j = (A W)[i_j] and w_j = W[i_j] (Galerkin) or y_j (LSPG), so an iteration costs what the at most 3 m stencil nodes of
 // those rows cost whatever the mesh size, and the kernel never touches a vector of mesh length.
 //
-// The loop is bg_ann_rom_run's own body (rom_ann_loop_device.hpp, which describes the hyper-reduced form) on the compacted
-// mesh of the stencil nodes: the closure MLP, the sweep over [U_p | U_s] restricted to the table, mfma_pass and pivoted_gj8
-// are unchanged.  This file keeps the three instantiations and the entry points:
+// The loop is bg_ann_rom_run's own body (rom_ann_loop_device.hpp; rom_hyper_table_device.hpp describes the hyper-reduced
+// form) on the compacted mesh of the stencil nodes: the closure MLP, the sweep over [U_p | U_s] restricted to the table,
+// mfma_pass and pivoted_gj8 are unchanged.  This file keeps the three instantiations and the entry points:
 //   nodes <= 256   S = 4   two workgroups per CU
 //   nodes <= 512   S = 8   two workgroups per CU
 //   nodes <= 768   S = 12  one workgroup per CU (the tangent rows alone are 49 KB of LDS)

@@ -6,10 +6,10 @@
 // costs what the at most 3 m stencil nodes of those rows cost whatever the mesh size; the closure evaluation is the full
 // loop's.  The kernel never touches a vector of mesh length.  bg_hyper_ann_rom_run (rom_hyper_ann.hip) stops at n <= 8.
 //
-// The loop is bg_ann_rom_run_wide's own body (rom_ann_wide_loop_device.hpp, which describes the hyper-reduced form) on the
-// compacted mesh of the stencil nodes: the closure MLP, tangent_fragments, mfma_passes, pivoted_solve and decode_u are
-// unchanged.  This file keeps the three instantiations and the entry points, all on four waves (ann_layers is written for
-// 256 threads):
+// The loop is bg_ann_rom_run_wide's own body (rom_ann_wide_loop_device.hpp; rom_hyper_table_device.hpp describes the
+// hyper-reduced form) on the compacted mesh of the stencil nodes: the closure MLP, tangent_fragments, mfma_passes,
+// pivoted_solve and decode_u are unchanged.  This file keeps the three instantiations and the entry points, all on four
+// waves (ann_layers is written for 256 threads):
 //   nodes <= 256   S = 4    two workgroups per CU   UTn row stride 512
 //   nodes <= 512   S = 8    two workgroups per CU   UTn row stride 512
 //   nodes <= 768   S = 12   one workgroup per CU    UTn row stride 768 (the 512-register budget, 96 KB of LDS)

@@ -5,9 +5,9 @@
 // costs what the at most 3 m stencil nodes of those rows cost whatever the mesh size; the closure evaluation (Ns nbar n) is
 // the full loop's.  The kernel never touches a vector of mesh length.
 //
-// The loop is bg_rbf_rom_run's own body (rom_rbf_loop_device.hpp, which describes the hyper-reduced form) on the compacted
-// mesh of the stencil nodes: the in-kernel fp64 closure, tangent_fragments, mfma_passes, pivoted_solve and decode_u are
-// unchanged.  This file keeps the three instantiations and the entry points:
+// The loop is bg_rbf_rom_run's own body (rom_rbf_loop_device.hpp; rom_hyper_table_device.hpp describes the hyper-reduced
+// form) on the compacted mesh of the stencil nodes: the in-kernel fp64 closure, tangent_fragments, mfma_passes,
+// pivoted_solve and decode_u are unchanged.  This file keeps the three instantiations and the entry points:
 //   nodes <= 256   S = 4   four waves    two workgroups per CU   UTn row stride 512
 //   nodes <= 512   S = 8   four waves    two workgroups per CU   UTn row stride 512
 //   nodes <= 768   S = 8   eight waves   one workgroup per CU    UTn row stride 1024 (the profile of bg_rbf_rom_run_long)

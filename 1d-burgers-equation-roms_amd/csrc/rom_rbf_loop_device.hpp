@@ -4,15 +4,8 @@
 // described in rom_rbf_fused.hip; this file holds the closure (scale, centre, the Jacobian and value tiles), the LDS overlay
 // and the loop; the mesh side is rom_closure_device.hpp's.
 //
-// The hyper-reduced form (Args = HyperRbfRunArgs) is the one rom_ann_loop_device.hpp describes: the body runs on the table
-// of the sorted distinct stencil nodes of the sampled rows with `nodes` for N, the table coordinates read as a non-uniform
-// mesh.  What differs from the full loop:
-//   - a table node that is only a neighbour assembles as an identity row with weight 0, and every coefficient of a sampled
-//     row is multiplied by its weight xi (Galerkin) or sqrt(xi) (LSPG); whether a sampled row is the Dirichlet row or the
-//     last row is decided by node[k]; a sampled row whose neighbour the table does not hold is left out;
-//   - the run starts from q_p = q0 and u0 gathered at the table nodes, and q_p carries over between iterations and steps:
-//     there is no U_p^T U0 (equal to the previous q_new for orthonormal [U_p U_s]);
-//   - the outputs are q_p and the closure value f(q_p) of every step's decode; no vector of mesh length is touched.
+// The hyper-reduced form (Args = HyperRbfRunArgs) is described in rom_hyper_table_device.hpp, which holds its table side; the
+// blocks under `if constexpr (HYPER)` call it.  The closure value of a step's decode is f(q_p), the last evaluation's s_f.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,14 +51,7 @@ struct RbfRunArgs {
 
 // bg_hyper_rbf_rom_run: x, UT, u0 are the table's xn [nodes], UTn [n + nbar][UT_LD] (zero from nodes), u0n [B][nodes]; hist
 // is qhist [B][nsteps+1][n]; N is the mesh's node count (it decides the last row), nonuniform is not read
-struct HyperRbfRunArgs : RbfRunArgs {
-    const int32_t* node;    // [nodes] ascending mesh nodes of the table
-    const int32_t* pos;     // [nrows] table position of every sampled row
-    const double* xi;       // [nrows] weights
-    const double* q0;       // [B][n]
-    double* qshist;         // [B][nsteps+1][nbar]
-    int nodes, nrows;
-};
+struct HyperRbfRunArgs : RbfRunArgs, HyperClosureTableArgs {};
 
 // rows of the mesh the body works on
 __device__ __forceinline__ int rbf_loop_rows(const RbfRunArgs& a) { return a.N; }
@@ -170,22 +156,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(Args a)
     if constexpr (HYPER) {
         int* s_smp = reinterpret_cast<int*>(s_shared);          // [NPAD]: 1 + the sampled row at this table node, or 0
         static_assert(NPAD * 4 <= sizeof(s_shared), "the scatter table fits the shared block");
-        for (int k = tid; k < NPAD; k += NT) s_smp[k] = 0;
-        __syncthreads();
-        for (int j = tid; j < a.nrows; j += NT) {
-            const int p = a.pos[j];
-            if ((unsigned)p < (unsigned)N) s_smp[p] = j + 1;
-        }
-        __syncthreads();
-        for (int k = tid; k < NPAD; k += NT) {
-            int j = s_smp[k];
-            const int ir = j ? a.node[k] : a.N;
-            // (a sampled row whose neighbour the table does not hold -- not a table the contract allows -- is left out)
-            if ((unsigned)ir >= (unsigned)a.N || (ir > 0 && k == 0) || (ir < a.N - 1 && k == N - 1)) j = 0;
-            const double xi = j ? a.xi[j - 1] : 0.0;
-            s_hnode[k] = j ? ir : a.N;
-            s_hmul[k] = GAL ? xi : sqrt(xi);
-        }
+        hyper_scatter_rows<NT>(s_smp, NPAD, a.pos, a.nrows, N, tid);
+        for (int k = tid; k < NPAD; k += NT) hyper_table_node<GAL>(s_smp[k], k, a.node, a.xi, a.N, N, s_hnode[k], s_hmul[k]);
     }
 
     for (int slot = blockIdx.x; slot < a.B; slot += gridDim.x) {
@@ -197,26 +169,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(Args a)
         // ---- per-sample constants (compute_forcing_vector :427-461, f_gp of :556-558) and the initial state ----------
         if constexpr (HYPER) {                      // u0 at the table nodes, q_p = q0 (the caller's U_p^T u0); no closure value belongs to u0
 #pragma unroll 1
-            for (int ii = 0; ii < NIT; ++ii) {
-                const int i = tid + NT * ii;
-                double frPrev = 0.0, fl = 0.0, hf = 0.0, u = 0.0;
-                if (i < N) {
-                    rom_nodal_forcing(a.x, i, N, mu2, h, nonuniform, frPrev, fl, hf);
-                    u = a.u0[(size_t)smp * N + i];
-                }
-                s_fdt[i] = a.dt * (frPrev + fl);
-                s_h[i] = hf;
-                s_u[i + 2] = u;
-            }
+            for (int ii = 0; ii < NIT; ++ii)
+                sample_setup_row<false>(tid + NT * ii, a.x, a.u0, smp, nullptr, N, mu2, h, nonuniform, a.dt, s_u, s_fdt, s_h);
             rederive();
             double zero = 0.0;
             asm volatile("" : "+v"(zero));         // (as a constant it was kept in registers for the whole kernel, and spilled)
-            if (tid < RW) {
-                const double q = tid < n ? a.q0[(size_t)smp * n + tid] : zero;
-                s_q[tid] = q;
-                if (tid < n) hist[tid] = q;
-            }
-            for (int j = tid; j < nbar; j += NT) a.qshist[(size_t)smp * (size_t)(a.nsteps + 1) * (size_t)nbar + j] = zero;
+            hyper_sample_start<NT, RW>(a.q0, s_q, hist, a.qshist, smp, a.nsteps, n, nbar, tid, zero);
         } else {
 #pragma unroll 1
             for (int ii = 0; ii < NIT; ++ii)
@@ -317,22 +275,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(Args a)
                 __syncthreads();                         // s_J consumed: the projection phase reuses its LDS
                 publish_edges<S, NB>(frag, s_elo, s_ehi, owner, t);
                 // ---- assembly: A(u_k), R(u_k) per row into LDS (:1330-1346) ------------------------------------------
-                if constexpr (HYPER) {
-                    // table node i as mesh row s_hnode (a.N where the node is only a neighbour: an identity row, weight 0), the
-                    // table coordinates as the x[ir - 1], x[ir], x[ir + 1] of the row routine, the weight in the coefficients
-#pragma unroll 1
-                    for (int i = tid; i < NPAD; i += NT) {
-                        const int ir = s_hnode[i];
-                        double lo, di, up, R;
-                        const bool in = ir < a.N;
-                        const MeshConst mc = make_mesh_const(h, a.dt, a.E, a.supg);
-                        rom_assemble_row(ir, a.N, s_u[i + 1], s_u[i + 2], s_u[i + 3], in ? s_g[i] : 0.0,
-                                         (in && ir > 0) ? s_h[i - 1] : 0.0, (in && ir < a.N - 1) ? s_h[i] : 0.0, mu1, mc,
-                                         nonuniform, a.x + (in ? i - ir : 0), a.dt, a.E, lo, di, up, R);
-                        const double wm = s_hmul[i];
-                        s_coef[i][0] = wm * lo; s_coef[i][1] = wm * di; s_coef[i][2] = wm * up; s_coef[i][3] = wm * R;
-                    }
-                } else
+                if constexpr (HYPER)
+                    hyper_assemble_rows<NPAD, NT>(s_coef, s_hnode, s_hmul, s_u, s_g, s_h, a.x, a.N, h, a.dt, a.E, a.supg, mu1, tid);
+                else
                     assemble_rows<NPAD, NT>(s_coef, s_u, s_g, s_h, a.x, N, h, a.dt, a.E, a.supg, nonuniform, mu1, tid);
                 __syncthreads();
                 // ---- projection (:1361) ------------------------------------------------------------------------------
@@ -388,9 +333,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void rom_rbf_fused_kernel(Args a)
             }
             if constexpr (HYPER) {                  // q_p and the closure value of the decode
                 rederive();                         // (the per-lane output addresses, hoisted out of the time loop, went to scratch)
-                if (tid < n) hist[(size_t)(step + 1) * n + tid] = s_q[tid];
-                double* qs = a.qshist + ((size_t)smp * (size_t)(a.nsteps + 1) + (size_t)(step + 1)) * (size_t)nbar;
-                for (int j = tid; j < nbar; j += NT) qs[j] = s_f[j];
+                hyper_write_step<NT>(hist, a.qshist, smp, a.nsteps, step, s_q, s_f, n, nbar, tid);
             } else
                 write_hist_row<NT>(hist + (size_t)(step + 1) * N, s_u, N, tid);
             if (tid == 0) a.iters[(size_t)smp * a.nsteps + step] = k;
