@@ -136,6 +136,11 @@ _SIGNATURES = {
     "bg_hyper_rom_wide_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
     "bg_hyper_rom_wide_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "bg_hyper_rom_run_wide": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP + _LOOP_OUT),      # as bg_hyper_rom_run
+    "bg_hyper_rom_blocked_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2),
+    "bg_hyper_rom_blocked_table_elems": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "bg_hyper_rom_blocked_work_elems": (ctypes.c_longlong, [ctypes.c_int]),
+    "bg_hyper_rom_run_blocked": (ctypes.c_int, [ctypes.c_int] * 6 + [c_int_p] + [c_double_p] * 7 + _LOOP_STEP +
+                                 [c_double_p, ctypes.c_int] + _LOOP_OUT),      # as bg_hyper_rom_run, with work and slots before qhist
     # B, n, A, b, x, piv (int32 or null), info (int32), stream
     "bg_wide_solve_pivoted": (ctypes.c_int, [ctypes.c_int] * 2 + [c_double_p] * 3 + [c_int_p] * 2 + [ctypes.c_void_p]),
     "bg_hyper_ann_rom_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 6),

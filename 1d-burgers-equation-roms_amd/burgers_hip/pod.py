@@ -943,6 +943,7 @@ def _limits_accessor(symbol, count, doc):
 for _name, _symbol, _count, _doc in (
         ("hyper_rom_limits", "bg_hyper_rom_limits", 2, "(max_r, max_m) of bg_hyper_rom_run"),
         ("hyper_wide_rom_limits", "bg_hyper_rom_wide_limits", 2, "(max_r, max_m) of bg_hyper_rom_run_wide"),
+        ("hyper_blocked_rom_limits", "bg_hyper_rom_blocked_limits", 2, "(max_r, max_m) of bg_hyper_rom_run_blocked"),
         ("hyper_ann_rom_limits", "bg_hyper_ann_rom_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run"),
         ("hyper_ann_wide_rom_limits", "bg_hyper_ann_rom_wide_limits", 6, "(max_n, max_nbar, max_width, max_layers, max_m, max_nodes) of bg_hyper_ann_rom_run_wide"),
         ("hyper_quad_rom_limits", "bg_hyper_quad_rom_limits", 3, "(max_n, max_m, max_nodes) of bg_hyper_quad_rom_run"),
@@ -976,7 +977,10 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     nnls_rows(G[:, 1:], d - G[:, 0]): stopped at |G xi - d| <= tau |d|, then filled by the same greedy rule up to
     ``min_rows`` rows (default 3 r: fewer rows have diverged at r = 40 even where the training residual was met).
     ``max_rows`` defaults to the limit of the loop that takes r: hyper_rom_limits' (256) up to its r = 40, hyper_wide_rom_limits'
-    (512) above; needing more is a ValueError.  Returns a RowSampling.
+    (512) up to its r = 96, hyper_blocked_rom_limits' (1024) above; needing more is a ValueError.  ``solver="device"`` keeps its
+    own limit: nnls_rows_device holds at most 512 active columns (nnls_limits) and refuses a ``max_rows`` beyond 513 before it
+    launches anything, so with a basis of more than 96 modes it needs an explicit ``max_rows`` <= 513, and a 3 r fill beyond
+    r = 171 is host work.  Returns a RowSampling.
     Two facts about wide bases, from a study at N = 600, r = 96 (3 r = 288 rows): the fill up to 3 r needs enough training
     pairs -- with three runs and stride 20 the greedy rule has no column left to add at 269, and ``min_rows`` must be given
     (200 rows stayed within 4e-11 of the full PROM there); and the NNLS is host work, about a minute at r = 96 with nine runs
@@ -995,8 +999,8 @@ def build_row_sampling(X, Phi, runs, dt, projection, E=0.0, supg=True, tau=1e-4,
     r = Phi.shape[1]
     min_rows = min(3 * r, N) if min_rows is None else int(min_rows)
     if max_rows is None:
-        narrow_r, narrow_m = hyper_rom_limits()
-        max_rows = narrow_m if r <= narrow_r else hyper_wide_rom_limits()[1]
+        (narrow_r, narrow_m), (wide_r, wide_m) = hyper_rom_limits(), hyper_wide_rom_limits()
+        max_rows = narrow_m if r <= narrow_r else wide_m if r <= wide_r else hyper_blocked_rom_limits()[1]
     G, pairs = row_sampling_system(X, Phi, runs, dt, projection, E, supg, stride)
     return _fit_row_sampling(G, pairs, projection, tau, min_rows, int(max_rows), **fit)
 

@@ -65,6 +65,7 @@ _ROUTES = {r.entry: r for r in (
     _Route("bg_rbf_rom_run_long", 1, min_n=513, max_n=1024),
     _Route("bg_hyper_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),
     _Route("bg_hyper_rom_run_wide", 1, min_n=3, max_n="bg_fom_max_n", redo=True),
+    _Route("bg_hyper_rom_run_blocked", 1, min_n=3, max_n="bg_fom_max_n", redo=True),
     _Route("bg_hyper_ann_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # one per CU beyond 512 table nodes (HyperAnnPlan.wg_per_cu)
     _Route("bg_hyper_ann_rom_run_wide", 2, min_n=3, max_n="bg_fom_max_n"), # likewise (HyperAnnWidePlan.wg_per_cu)
     _Route("bg_hyper_rbf_rom_run", 2, min_n=3, max_n="bg_fom_max_n"),      # likewise (HyperRbfPlan.wg_per_cu)
@@ -644,6 +645,7 @@ class HyperPodPlan:
     weights, and the gather index of the stencil nodes.  ``sampling``: a pod.RowSampling.  What the shapes and the sampling
     alone decide is refused before the device is touched; every refusal is a ValueError."""
     entry, limits, table_elems, slab_rows = "bg_hyper_rom_run", "bg_hyper_rom_limits", "bg_hyper_rom_table_elems", 32
+    slots = work = None           # HyperBlockedPodPlan: its workgroups and their workspace, one slot each
 
     def __init__(self, Phi, sampling, X, device):
         shape = tuple(np.shape(Phi))
@@ -680,8 +682,26 @@ class HyperWidePodPlan(HyperPodPlan):
     entry, limits, table_elems, slab_rows = "bg_hyper_rom_run_wide", "bg_hyper_rom_wide_limits", "bg_hyper_rom_wide_table_elems", 16
 
 
+class HyperBlockedPodPlan(HyperPodPlan):
+    """What bg_hyper_rom_run_blocked reads and writes besides the batch: a HyperPodPlan against the blocked loop's limits
+    (r <= 256, m <= 1024, bg_hyper_rom_blocked_limits) with the table PhiS in its layout, r rounded up to 16 doubles per row and
+    m rounded up to 8, and BlockedPodPlan's workspace of ``slots`` slots (one per workgroup; default: one per compute unit,
+    the kernel's LDS admits one workgroup per CU).  The basis, the rows and the weights it keeps also serve the redo of marked
+    samples (_pod_prom_run_hyper_library)."""
+    entry, limits, table_elems, slab_rows = ("bg_hyper_rom_run_blocked", "bg_hyper_rom_blocked_limits",
+                                             "bg_hyper_rom_blocked_table_elems", 8)
+
+    def __init__(self, Phi, sampling, X, device, slots=None):
+        if slots is not None and int(slots) < 1:
+            raise ValueError("slots must be positive")
+        super().__init__(Phi, sampling, X, device)
+        self.slots = int(slots) if slots is not None else _cu_count(self.Phi.device)
+        self.work = torch.empty((self.slots, _lib.load().bg_hyper_rom_blocked_work_elems(self.r)), dtype=torch.float64,
+                                device=self.Phi.device)
+
+
 class HyperRomResult(_HyperResult):
-    """Result of pod_prom_run_hyper (_HyperResult); from the wide loop also ``redone``, the number of samples redone on the
+    """Result of pod_prom_run_hyper (_HyperResult); from the wide and the blocked loop also ``redone``, the number of samples redone on the
     host side.  The decode is U = Phi q as one batched product."""
 
     def _decode(self):
@@ -697,7 +717,7 @@ def _pivot_on_device(pivot):
 
 def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options, balance,
                    pivot="host"):
-    """pod_prom_run_hyper's narrow loop and pod_prom_run_hyper_wide: the plan (or the sampling to build one from) against the
+    """pod_prom_run_hyper's narrow loop, pod_prom_run_hyper_wide and pod_prom_run_hyper_blocked: the plan (or the sampling to build one from) against the
     call, q0 and u0 at the stencil, the launch, and for a route with ``redo`` the marked samples again on the host side, or
     with ``pivot="device"`` by the entry point's own repair kernel (BG_OPT_PIVOT_ON_DEVICE; the narrow loop always has one)."""
     route = _ROUTES[plan_type.entry]
@@ -712,11 +732,12 @@ def _run_hyper_pod(plan_type, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan
     u0d, _, mu2d = _batch_inputs(u0, mu1, mu2, plan.N, device)
     q0 = (u0d @ plan.Phi).contiguous()
     u0s = (u0d[:, plan.stencil] * plan.inside).contiguous()
+    work = () if plan.slots is None else (_lib.ptr(plan.work), plan.slots)
     res = _device_loop(route, Xh, u0d, mu1, mu2, nsteps, device, options, balance,
                        lambda f, N, B, x, inputs, opts, outputs: f(
                            N, B, plan.r, plan.m, int(nsteps), proj, _lib.ptr(plan.rows), _lib.ptr(plan.xi), _lib.ptr(plan.xs),
                            _lib.ptr(plan.PhiS), _lib.ptr(q0), _lib.ptr(u0s), *inputs[1:], float(dt), float(E), float(tol),
-                           int(max_it), opts, *outputs), keep=(plan, q0, u0s), cols=plan.r)
+                           int(max_it), opts, *work, *outputs), keep=(plan, q0, u0s), slots=plan.slots, cols=plan.r)
     out = HyperRomResult(res, plan, u0d)
     if on_device:
         out.redone = 0                          # nothing comes back marked: info is not read, nothing is synchronised
@@ -735,8 +756,12 @@ def pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj,
     for the other projection is refused.  Returns a HyperRomResult.
     A HyperWidePodPlan, or a sampling with a basis of more than bg_hyper_rom_limits' r modes, goes to the wide loop
     (pod_prom_run_hyper_wide: r <= 96, m <= 512, which does synchronise unless ``pivot="device"``; with a narrow plan the
-    keyword is accepted and changes nothing)."""
+    keyword is accepted and changes nothing).  A HyperBlockedPodPlan goes to pod_prom_run_hyper_blocked (r <= 256, m <= 1024);
+    a sampling with a basis of more than 96 modes is refused here and taken there."""
     _pivot_on_device(pivot)
+    if isinstance(sampling_or_plan, HyperBlockedPodPlan):
+        return pod_prom_run_hyper_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device, options,
+                                          balance, pivot)
     if isinstance(sampling_or_plan, HyperWidePodPlan) or (
             not isinstance(sampling_or_plan, HyperPodPlan) and len(np.shape(Phi)) == 2
             and np.shape(Phi)[1] > _lib.limits(HyperPodPlan.limits, 2)[0]):
@@ -759,6 +784,22 @@ def pod_prom_run_hyper_wide(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, 
     singular reduced system is left in ``info`` for check_singular, as by the narrow loop.  Any other value is a ValueError."""
     return _run_hyper_pod(HyperWidePodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device,
                           options, balance, pivot)
+
+
+def pod_prom_run_hyper_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E=0.0, tol=1e-6, max_it=20, device=None,
+                               options=0, balance=True, pivot="host"):
+    """pod_prom_run_hyper for bases of up to 256 modes on up to 1024 sampled rows (bg_hyper_rom_run_blocked,
+    bg_hyper_rom_blocked_limits; meant for r > 96, the thesis' r = 160 and 227): pod_prom_run_blocked's projection and blocked
+    elimination in a per-workgroup workspace slot, driven over the table of sampled rows.  With all rows and unit weights it
+    is the full PROM, on any mesh of up to 1024 nodes.  Samples whose elimination would have needed a row exchange come back
+    marked and are redone by the weighted-row library iteration (_pod_prom_run_hyper_library), so this wrapper reads ``info``
+    back and synchronises the host.  ``sampling_or_plan``: the sampling, or a HyperBlockedPodPlan to reuse across calls
+    (``res.plan``).  Returns a HyperRomResult with ``redone``.  The loop has no repair kernel: ``pivot="device"`` is a
+    ValueError, as is any value but "host"."""
+    if _pivot_on_device(pivot):
+        raise ValueError('bg_hyper_rom_run_blocked has no repair kernel: pivot must be "host"')
+    return _run_hyper_pod(HyperBlockedPodPlan, X, u0, mu1, mu2, dt, nsteps, Phi, sampling_or_plan, proj, E, tol, max_it, device,
+                          options, balance)
 
 
 def _redo_marked_hyper(out, plan, dt, nsteps, proj, E, tol, max_it):
@@ -813,12 +854,19 @@ def pod_prom_run(X, u0, mu1, mu2, dt, nsteps, Phi, projection="Galerkin", E=0.0,
     <= bg_rom_run_long_wide_max_r() take the device-side loop bg_rom_run_long_wide instead of the library path.
     ``hyper`` (opt-in): a pod.RowSampling, a HyperPodPlan or a HyperWidePodPlan sends the call through the hyper-reduced loop
     pod_prom_run_hyper, which assembles the reduced system from the sampled mesh rows only (r <= 40: bg_hyper_rom_run;
-    41 <= r <= 96: bg_hyper_rom_run_wide); sizes it does not cover are refused, not rerouted.
+    41 <= r <= 96: bg_hyper_rom_run_wide); sizes it does not cover are refused, not rerouted.  With ``blocked`` a sampling
+    with a basis of more than 96 modes, and without it a HyperBlockedPodPlan, goes through pod_prom_run_hyper_blocked
+    (97 <= r <= 256, at most 1024 rows: bg_hyper_rom_run_blocked); ``blocked`` with at most 96 modes changes nothing here.
     ``pivot`` (with ``hyper``): "device" has bg_hyper_rom_run_wide redo the samples that need row exchanges in its own repair
-    kernel, where "host" (default) redoes them through the library; the narrow loop always repairs on the device."""
+    kernel, where "host" (default) redoes them through the library; the narrow loop always repairs on the device, the
+    blocked one never does and refuses "device"."""
     proj = _projection(projection, _NOT_AVAILABLE, exact=True)
     _pivot_on_device(pivot)
     if hyper is not None:
+        if (blocked and not isinstance(hyper, HyperPodPlan) and len(np.shape(Phi)) == 2
+                and np.shape(Phi)[1] > _lib.limits(HyperWidePodPlan.limits, 2)[0]):
+            return check_singular(pod_prom_run_hyper_blocked(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device,
+                                                             pivot=pivot))
         return check_singular(pod_prom_run_hyper(X, u0, mu1, mu2, dt, nsteps, Phi, hyper, proj, E, tol, max_it, device, pivot=pivot))
     route = _pod_route(np.shape(Phi)[0], np.shape(Phi)[1], fused, blocked, long_mesh, long_wide)
     if route == "library":
@@ -922,9 +970,10 @@ def _pod_prom_run_library(X, u0, mu1, mu2, dt, nsteps, Phi, proj, E, tol, max_it
 # ------------------------------------------------------------ quadratic manifold
 def _pod_prom_run_hyper_library(plan, u0, mu1, mu2, dt, nsteps, proj, E, tol, max_it):
     """_pod_prom_run_library with the two projections restricted to the rows of ``plan`` (a HyperPodPlan or HyperWidePodPlan)
-    and weighted by its xi -- bg_hyper_rom_run's iteration as library calls: bg_fom_assemble on the full state, the sampled
+    and weighted by its xi (any r) -- bg_hyper_rom_run's iteration as library calls: bg_fom_assemble on the full state, the sampled
     rows gathered, the rows of Y = A Phi from the stencil, rocSOLVER LU, q <- q + dq, the first assembly at u0 itself.  It
-    redoes the samples bg_hyper_rom_run_wide hands back and is the baseline of tools/time_hyper_wide_rom.py.  Returns a
+    redoes the samples bg_hyper_rom_run_wide and bg_hyper_rom_run_blocked hand back and is the baseline of
+    tools/time_hyper_wide_rom.py and tools/time_hyper_blocked_rom.py.  Returns a
     namespace with ``q`` (B, nT+1, r), ``iters``, ``flags`` and ``path``."""
     from . import fom as _fom
     c = _setup(plan.Xh, u0, mu1, mu2, dt, E, plan.Phi.device, max_n=_lib.load().bg_fom_max_n())

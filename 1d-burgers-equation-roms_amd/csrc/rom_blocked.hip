@@ -28,24 +28,18 @@
 
 #include "../../include/burgers_hip.h"
 #include "abi_common.hpp"
-#include "rom_device.hpp"
+#include "rom_blocked_device.hpp"
 
 namespace {
 
 using namespace bg;
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 
-constexpr int BMAX_R = 256;            // largest reduced dimension (16 tiles of 16)
 constexpr int BNMAX = 512;             // largest mesh
-constexpr int BSR = 8;                 // mesh rows per slab (two k-steps of the 16x16x4 instruction)
-constexpr int BSPS = BMAX_R + 16;      // doubles per LDS slab row: RP columns, then the [R, u, 0 ...] block at 256
-constexpr int BSEC = BSR * BSPS;       // one section (Phi or Y) of a slab buffer
-constexpr int BBUF = 2 * BSEC;         // one slab buffer: Phi rows, then Y rows
-constexpr int BT = 38;                 // accumulator tiles per wave and sweep (304 registers)
-constexpr int BMAXITEMS = 16 * 16 + 16;
-constexpr int BLS = 17;                // row stride of the multiplier panel in LDS
-constexpr int BUS = BMAX_R + 16;       // row stride of the U12 panel in LDS
-constexpr int BREGION = 2 * BBUF > BMAX_R * BLS + 16 * BUS + 16 * BLS ? 2 * BBUF : BMAX_R * BLS + 16 * BUS + 16 * BLS;
+// The slab, panel and item sizes and tile_ptr are rom_blocked_device.hpp's, shared with rom_hyper_blocked.hip.  The item table,
+// the matrix steps, the tile store and the solve below are also there as routines (blocked_fill_items, blocked_slab_steps,
+// blocked_store_tiles, blocked_solve), word for word, and this kernel does not call them: with any one of the four called
+// from here the register allocation of the whole kernel changed (228 AGPRs became 174 .. 177 with one or two spilled VGPRs),
+// and the kernel is meant to stay exactly what it was.  A change to one copy belongs in the other.
 
 struct BlockedRunArgs {
     const double* x;        // [N]
@@ -63,12 +57,6 @@ struct BlockedRunArgs {
     long long work_elems;
     int N, NPAD, B, r, RP, nsteps, max_it, supg, nonuniform, force_handback;
 };
-
-// the 16 x 16 tile (ta, tb) of the workspace: lane's four entries (row (lane >> 4) + 4 i, column lane & 15)
-__device__ __forceinline__ double* tile_ptr(double* M, int MW, int ta, int tb, int lane)
-{
-    return M + (size_t)(16 * ta + (lane >> 4)) * MW + 16 * tb + (lane & 15);
-}
 
 template <bool GAL>
 __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
@@ -424,8 +412,6 @@ __global__ __launch_bounds__(256, 1) void rom_blocked_kernel(BlockedRunArgs a)
         }
     }
 }
-
-inline int blocked_rp(int r) { return ((r + 15) / 16) * 16; }
 
 }  // namespace
 

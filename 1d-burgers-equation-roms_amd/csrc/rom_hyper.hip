@@ -432,7 +432,7 @@ inline int hyper_run_args(HyperRunArgs& a, int r_max, int m_max, int N, int B, i
 
 }  // namespace
 
-#if !defined(BG_ROM_HYPER_LOCAL_TU) && !defined(BG_ROM_HYPER_WIDE_TU)
+#if !defined(BG_ROM_HYPER_LOCAL_TU) && !defined(BG_ROM_HYPER_WIDE_TU) && !defined(BG_ROM_HYPER_BLOCKED_TU)
 extern "C" {
 
 int bg_hyper_rom_limits(int* max_r, int* max_m)
@@ -468,4 +468,4 @@ int bg_hyper_rom_run(int N, int B, int r, int m, int nsteps, int projection, con
 }
 
 }  // extern "C"
-#endif  // neither BG_ROM_HYPER_LOCAL_TU nor BG_ROM_HYPER_WIDE_TU
+#endif  // none of BG_ROM_HYPER_LOCAL_TU, BG_ROM_HYPER_WIDE_TU, BG_ROM_HYPER_BLOCKED_TU

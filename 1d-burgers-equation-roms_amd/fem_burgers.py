@@ -106,9 +106,11 @@ class FEMBurgers:
         loop bg_rom_run_long_wide instead of the library path.  ``hyper``: a row sampling (burgers_hip.pod.build_row_sampling)
         or a rom.HyperPodPlan sends the call through the hyper-reduced device-side loop bg_hyper_rom_run, which assembles the
         reduced system from the sampled mesh rows only (any mesh the FOM takes, at most 40 modes and 256 rows); with a basis
-        of 41 .. 96 modes (or a rom.HyperWidePodPlan) through bg_hyper_rom_run_wide, at most 512 rows.  ``pivot`` (with
-        ``hyper``): "device" has that loop redo the samples that need row exchanges in its own repair kernel, where "host"
-        (default) redoes them through the library; anything else raises ValueError."""
+        of 41 .. 96 modes (or a rom.HyperWidePodPlan) through bg_hyper_rom_run_wide, at most 512 rows; with ``blocked`` and a
+        basis of 97 .. 256 modes (or a rom.HyperBlockedPodPlan) through bg_hyper_rom_run_blocked, at most 1024 rows -- without
+        ``blocked`` such a sampling is refused.  ``pivot`` (with ``hyper``): "device" has the wide loop redo the samples that
+        need row exchanges in its own repair kernel, where "host" (default) redoes them through the library; the blocked loop
+        has no repair kernel and refuses "device"; anything else raises ValueError."""
         batched = self._batched(mu1, mu2, u0)
         res = _rom.pod_prom_run(self.X, np.asarray(u0, dtype=np.float64), mu1, mu2, At, int(nTimeSteps),
                                 np.asarray(Phi, dtype=np.float64), projection=projection, E=E, blocked=blocked,

@@ -413,6 +413,37 @@ int bg_hyper_rom_run_wide(int N, int B, int r, int m, int nsteps, int projection
                           const double *mu2, double dt, double E, double tol, int max_it, int options, double *qhist,
                           int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order, void *stream);
 
+/* bg_hyper_rom_run_blocked -- bg_hyper_rom_run for the thesis' finest bases: r <= 256 (meant for r > 96, where
+ *   bg_hyper_rom_run_wide ends), m <= 1024 (bg_hyper_rom_blocked_limits), 3 <= N <= bg_fom_max_n().  reference:
+ *   FEM/fem_burgers.py:709-785 with the sums over mesh rows restricted and weighted; with all rows and unit weights the loop is
+ *   the reference's, so it is also the exact device-side route of these bases on meshes of up to 1024 nodes.
+ *   Opt-in: burgers_hip/rom.py, pod_prom_run_hyper_blocked; the facade's hyper= with blocked=True.
+ *   rows, xi, xs, q0, u0s, qhist, iters, flags, order: as bg_hyper_rom_run.  The differences:
+ *   PhiS   [MPAD][3][RP], MPAD = m rounded up to 8, RP = r rounded up to 16 (bg_hyper_rom_blocked_table_elems(m, r) doubles,
+ *          16-byte aligned; 0 for an m or r the kernel does not cover): rows Phi[i-1], Phi[i], Phi[i+1] of sampled row j at row
+ *          indices 3 j .. 3 j + 2, zero rows outside the mesh and beyond m, zero columns beyond r;
+ *   work   `slots` slots of bg_hyper_rom_blocked_work_elems(r) = RP (RP + 16) doubles, one per workgroup, as bg_rom_run_blocked's
+ *          (no initialisation needed, garbage afterwards): the padded system Ar | -br, eliminated in place.  Workgroup k of
+ *          G = min(B, slots) takes the slots k, k + G, ... of `order` and only ever touches slot k of `work`;
+ *   info   0; k + 1 when the pivot of column k is exactly zero together with the rest of its column (LAPACK's info; the sample
+ *          stops there); BG_INFO_NEEDS_PIVOTING for a sample whose guarded pivot-free elimination met a multiplier above 1 below
+ *          the diagonal: its qhist and iters are then undefined and the caller redoes it (rom.py: the weighted-row library
+ *          iteration).  BG_OPT_FORCE_PIVOTED (tests) marks every sample after its first solve.  There is no repair kernel:
+ *          BG_OPT_PIVOT_ON_DEVICE is refused with BG_ERR_BAD_ARG.
+ *   Errors: as bg_hyper_rom_run_wide, with r > 256 or m > 1024: BG_ERR_UNSUPPORTED_R, and work NULL or slots < 1 with B > 0:
+ *   BG_ERR_WORKSPACE; B = 0: BG_OK with nothing launched.
+ *   One workgroup of four waves per slot, one per compute unit (148 KB of LDS at any m); the sampled rows pass through LDS in
+ *   slabs of 8, 16x16x4 fp64 matrix instructions for the projection and the elimination (csrc/rom_hyper_blocked.hip, sharing
+ *   csrc/rom_blocked_device.hpp with bg_rom_run_blocked).  options: BG_OPT_SUPG | BG_OPT_NONUNIFORM | BG_OPT_FORCE_PIVOTED. */
+int bg_hyper_rom_blocked_limits(int *max_r, int *max_m);
+long long bg_hyper_rom_blocked_table_elems(int m, int r);
+long long bg_hyper_rom_blocked_work_elems(int r);
+int bg_hyper_rom_run_blocked(int N, int B, int r, int m, int nsteps, int projection, const int32_t *rows, const double *xi,
+                             const double *xs, const double *PhiS, const double *q0, const double *u0s, const double *mu1,
+                             const double *mu2, double dt, double E, double tol, int max_it, int options, double *work,
+                             int slots, double *qhist, int32_t *iters, int32_t *flags, int32_t *info, const int32_t *order,
+                             void *stream);
+
 /* bg_wide_solve_pivoted -- x[b] = solve(A[b], b[b]) for a batch of dense systems of 1 <= n <= 96 unknowns by Gauss-Jordan
  *   elimination with partial pivoting, one workgroup of four waves per system on a persistent grid (one per compute unit;
  *   csrc/wide_solve.hip).  The routine is the repair solve of bg_hyper_rom_run_wide (rom_wide_device.hpp, wide_solve_pivoted).
